@@ -15,9 +15,13 @@ its own shard of the batch (weak scaling, no data-path collective); each step en
 RCCL all-gather of the per-pair flow vectors.
 
 Prints ONE JSON line on rank 0. `roofline.achieved` = algorithmic bytes per launch / average kernel
-duration measured with HIP events on the launch stream inside the timed region; `cpu_baseline` = the
-CPU oracle (a port of the reference's useOCL=false path; the reference itself cannot be built here)
-timed on this box's host cores over a bounded sample of the same workload (rank 0, N=1 only).
+duration measured with HIP events on the launch stream inside the timed region.
+
+A plain run sets up, settles the clocks (the sustained leg, --sustain-s), warms up, times exactly --steps steps,
+writes the last step's outputs if --dump-outputs is given, and prints the line. --full adds the records that take
+runs of their own: the cold burst, `cpu_baseline` (the CPU oracle, a port of the reference's useOCL=false path,
+timed on the host cores over a bounded sample of the same workload; rank 0, N=1 only), and at c2 the native shard
+group, the other workloads and the host entries.
 """
 from __future__ import annotations
 
@@ -545,10 +549,12 @@ def build_workload(wl, dev, local_rank: int, rank: int, graph: bool = False):
             cur3, prev3 = colour(cur), colour(prev)
 
             def launch():
-                return eng.process_batch_device_bgr(cur3, prev3)[2]
+                state["bm"] = eng.process_batch_device_bgr(cur3, prev3)
+                return state["bm"][2]
         else:
             def launch():
-                return eng.process_batch_device(cur, prev)[2]
+                state["bm"] = eng.process_batch_device(cur, prev)
+                return state["bm"][2]
 
     if graph:
         eager_launch = launch
@@ -565,6 +571,45 @@ def build_workload(wl, dev, local_rank: int, rank: int, graph: bool = False):
             return graph_result
 
     return launch, eng, state
+
+
+def output_arrays(wl, res, state, eng):
+    """The arrays a caller of the timed path receives from one step (`res`: what that step's launch() returned), by name."""
+    if wl["kind"] == "bm":
+        dx, dy, mode = state["bm"]
+        return {"dx": dx, "dy": dy, "mode": mode}
+    if wl["kind"] in ("fft+sr", "fft+srseq"):  # launch() returns [shifts | scale, rot, pt.x, pt.y] per pair
+        k = eng.n_patches * 2
+        return {"shifts": res[:, :k].reshape(-1, eng.n_patches, 2), "scale_rotation": res[:, k:]}
+    if wl["kind"] == "fft+rt":
+        return {"get_rt": res}
+    if wl["kind"] == "fft+2dt":
+        return {"get_2dt": res}
+    return {"shifts": res}
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(arrays, out_dir: str, suffix: str = "") -> None:
+    """--dump-outputs: every array as <out_dir>/<name><suffix>.npy, float64 where the result is float64 (or a wide integer),
+    float32 otherwise. Above DUMP_LIMIT_BYTES in all, the same fixed, seeded sample of rows (frame pairs) is kept of every array."""
+    import numpy as np
+
+    host = {}
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        host[name] = a.astype(np.float64 if a.dtype == np.float64 or (a.dtype.kind in "iu" and a.itemsize >= 4) else np.float32)
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_LIMIT_BYTES:
+        rows = min(a.shape[0] for a in host.values())
+        keep = max(1, rows * DUMP_LIMIT_BYTES // total)
+        idx = np.sort(np.random.default_rng(0).choice(rows, keep, replace=False))
+        host = {name: a[idx] for name, a in host.items()}
+        print(f"bench.py: --dump-outputs keeps {keep} of {rows} rows (seeded sample, 64 MB limit)", file=sys.stderr)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), a)
 
 
 def timed_steps(step, steps: int, world: int, dev):
@@ -865,6 +910,8 @@ def emit(line) -> None:
 
 def main_native(args) -> None:
     """`bench.py --native --gpus N`: the contract's JSON line, measured through the native shard group (no torch.distributed)."""
+    if args.dump_outputs:
+        raise SystemExit("--dump-outputs writes the outputs of the plain path; --native does not support it")
     quiet_stdout()
     import torch
 
@@ -913,6 +960,12 @@ def main() -> None:
     ap.add_argument("--native-sync-per-step", action="store_true", help="--native: mof_shard_*_sync after every step instead of at the end")
     ap.add_argument("--graph", action="store_true",
                     help="capture one step into a HIP graph and replay it (helps the multi-launch c5 pipeline)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the records that take runs of their own: the cold burst, the CPU baselines and, at c2, the native shard "
+                         "group, the other workloads and the host entries (a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64, "
+                         "at most 64 MB: a fixed, seeded sample of the pairs beyond that); rank r > 0 of N writes <name>_rank<r>.npy")
     args = ap.parse_args()
 
     if args.native:
@@ -967,6 +1020,8 @@ def main() -> None:
             gather = ("blocking all_gather_into_tensor (RCCL)" if args.backend == "nccl"
                       else "blocking all_gather (gloo rehearsal, host staging)")
 
+    last = {}
+
     def step(i=None, drain=False):
         if drain:
             if ag is not None:
@@ -977,6 +1032,7 @@ def main() -> None:
         if i is not None and i < len(ev0):
             ev0[i].record()
         res = launch()
+        last["res"] = res
         if i is not None and i < len(ev1):
             ev1[i].record()
         if ag is not None:
@@ -993,8 +1049,9 @@ def main() -> None:
     # (r06) BOTH regimes are reported: `cold_burst` = exactly the W warm-up + K timed steps the command line asks for, started on a GPU
     # that has idled for a second (what a reader of `--steps 20 --warmup 5` would expect; it reads the clock ramp), then the sustained leg,
     # then the contract's W + K steps on settled clocks (`value`). No headline moves by protocol alone: both numbers are in every line.
+    # The cold burst is a record of its own: --full only. The sustained leg settles the clocks `value` is measured on: every run.
     cold = None
-    if args.sustain_s > 0:
+    if args.full and args.sustain_s > 0:
         torch.cuda.synchronize()
         time.sleep(1.0)
         for _ in range(args.warmup):
@@ -1023,6 +1080,8 @@ def main() -> None:
     step(None, drain=True)
     elapsed = timed_steps(step, args.steps, world, dev)
     kern_ms = sum(a.elapsed_time(b) for a, b in zip(ev0, ev1)) / args.steps  # HIP events on the launch stream
+    if args.dump_outputs:
+        dump_outputs(output_arrays(wl, last["res"], state, eng), args.dump_outputs, f"_rank{rank}" if rank else "")
 
     if rank == 0:
         pairs = B * world * args.steps
@@ -1051,13 +1110,15 @@ def main() -> None:
         }
         if cold is not None:
             line["cold_burst"] = cold
-            line["value_regime"] = "settled clocks: the W + K steps run after the sustained leg (cold_burst = the same W + K steps from an idle GPU)"
         if sustained is not None:
+            line["value_regime"] = "settled clocks: the W + K steps run after the sustained leg" + (
+                " (cold_burst = the same W + K steps from an idle GPU)" if cold is not None else "")
             line["sustained"] = sustained
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(wl)
-        if world == 1 and not args.no_others and args.workload == "c2" and not args.batch:
+        if world == 1 and args.full and not args.no_others and args.workload == "c2" and not args.batch:
             del launch, eng, state, step
+            last.clear()
             torch.cuda.empty_cache()
             # driver-visible records of the other BASELINE configurations (same protocol, fewer steps)
             # the same workload through the NATIVE shard group (C++ host, RCCL inside the library) on this one device: a 1-rank gather

@@ -15,7 +15,7 @@ def pytest_configure(config):
     need = [os.path.join(ROOT, "mrs_optic_flow_amd", "libmof_hip.so"), os.path.join(ROOT, "oracle", "liboracle.so"),
             os.path.join(ROOT, "tests", "cpp", "test_processors")]
     if os.path.exists("/root/reference/include/OpticFlowCalc.h"):  # the adapter compile test needs the reference's header
-        need.append(os.path.join(ROOT, "tests", "cpp", "test_adapter"))
+        need.append(os.path.join(ROOT, "oracle", "_ref", "test_adapter"))
     if not all(os.path.exists(p) for p in need):
         import __graft_entry__
 

@@ -30,7 +30,7 @@ def test_bench_two_rank_rehearsal(gpu):
                    MASTER_PORT=str(port), HSA_ENABLE_IPC_MODE_LEGACY="0")
         procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo",
                                        "--share-gpu", "--workload", "c4", "--batch", "8", "--steps", "3", "--warmup", "1",
-                                       "--sustain-s", "0.2", "--no-cpu-baseline"],  # (> 0: the cold-burst and sustained legs run with two ranks too)
+                                       "--sustain-s", "0.2", "--no-cpu-baseline", "--full"],  # (> 0: the cold-burst and sustained legs run with two ranks too)
                                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env))
     outs = [p.communicate(timeout=600) for p in procs]
     assert all(p.returncode == 0 for p in procs), [o[1][-1500:] for o in outs]
@@ -78,7 +78,7 @@ def test_bench_native_shard_group_on_one_device(gpu):
     The line records what RCCL formed (`rccl_ranks`, ncclCommCount), the per-device step time by HIP events on the shard's stream, that the
     gathered slab equals the plain engine's result bit for bit, and a rate within 5 % of the plain single-engine run in the same process
     regime (the 1-rank gather is a device-local copy of 1 MB per step). Same for c3 through mof_shard_bm_*."""
-    plain = _bench("--workload", "c2", "--steps", "100", "--warmup", "10", "--sustain-s", "0.5", "--no-cpu-baseline", "--no-others")
+    plain = _bench("--workload", "c2", "--steps", "100", "--warmup", "10", "--sustain-s", "0.5", "--no-cpu-baseline", "--no-others", "--full")
     nat = _bench("--native", "--gpus", "1", "--workload", "c2", "--steps", "100", "--warmup", "10")
     assert nat["n_gpus"] == 1 and nat["rccl_ranks"] == 1 and nat["config"]["parallelism"] == "native shard group x1"
     g = nat["native_shard_group"]
@@ -98,3 +98,31 @@ def test_bench_native_shard_group_rehearsal_with_two_shards(gpu):
     g = line["native_shard_group"]
     assert line["n_gpus"] == 2 and line["rccl_ranks"] == 0 and g["gather"].startswith("none") and g["devices"] == [0, 0]
     assert g["shard_results_equal_plain_engine"] is True and len(g["per_device_step_ms"]) == 2 and "roofline" not in line
+
+
+def test_bench_plain_run_times_the_headline_and_dumps_its_outputs(gpu, tmp_path):
+    """A plain run (no --full) carries the headline fields and none of the --full records; --dump-outputs writes what the last timed
+    step computed: for c2 the shifts, equal bit for bit to the engine on the same synthetic batch; for c3 dx / dy / mode."""
+    import numpy as np
+
+    from mrs_optic_flow_amd import FastSpacedBMMethod, FftMethod, synth
+
+    out = tmp_path / "c2"
+    line = _bench("--workload", "c2", "--batch", "16", "--steps", "3", "--warmup", "1", "--sustain-s", "0", "--dump-outputs", str(out))
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["value"] > 0 and line["higher_is_better"] is True
+    assert line["metric"] == "frame_pairs_per_s_fft_phase_corr" and line["dtype"] == "f32" and line["unit"] == "frame-pairs/s"
+    assert not {"cold_burst", "cpu_baseline", "other_workloads", "native_shard_group", "host_entries"} & set(line)
+    got = np.load(out / "shifts.npy")
+    assert got.dtype == np.float64 and got.shape == (16, 64, 2)
+    cur, prev, _, _ = synth.batch_torch(16, 480, 752, 8, gpu, k0=0)
+    fm = FftMethod(sample_point_size=64, frame_shape=(480, 752), grid=(8, 8), origin=(1, 1), stride=(98, 59))
+    assert np.array_equal(fm.process_batch_device(cur, prev).cpu().numpy(), got, equal_nan=True)
+
+    out = tmp_path / "c3"
+    line = _bench("--workload", "c3", "--batch", "8", "--steps", "2", "--warmup", "1", "--sustain-s", "0", "--dump-outputs", str(out))
+    assert line["steps"] == 2 and line["dtype"] == "u8"
+    cur, prev, _, _ = synth.batch_torch(8, 480, 752, 12, gpu, k0=0)
+    want = FastSpacedBMMethod(16, 16, 8, (480, 752)).process_batch_device(cur, prev)
+    for name, w in zip(("dx", "dy", "mode"), want):
+        a = np.load(out / f"{name}.npy")
+        assert a.dtype == np.float32 and np.array_equal(a, w.cpu().numpy().astype(np.float32)), name

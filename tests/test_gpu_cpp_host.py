@@ -82,10 +82,10 @@ def test_drop_in_adapter_against_the_reference_interface_header(gpu, tmp_path):
     """tests/cpp/test_adapter.cpp: `MofFftMethod : OpticFlowCalc` compiled against /root/reference/include/OpticFlowCalc.h
     (with type-check stand-ins for the OpenCV headers, tests/stubs/) and driven exactly like the node drives its
     FftMethod (optic_flow.cpp:1001-1002, :1016-1018, :1685-1690): setImPrev(zeros), processImage through the abstract
-    interface, processImageLongRange on the concrete type. The binary is built where the reference exists (the build
-    container) and travels with the snapshot."""
-    binary = os.path.join(os.path.dirname(__file__), "cpp", "test_adapter")
-    assert os.path.exists(binary), "tests/cpp/test_adapter missing: run __graft_entry__.build() where /root/reference exists"
+    interface, processImageLongRange on the concrete type. The binary is built by oracle/Makefile (target `ref`, part
+    of the `all` that __graft_entry__.build() makes) into oracle/_ref/ where the reference checkout exists, and travels from there."""
+    binary = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref", "test_adapter")
+    assert os.path.exists(binary), "oracle/_ref/test_adapter missing: run __graft_entry__.build() where the reference checkout exists"
     fs, sps, n = 256, 64, 5   # sqNum 4 -> long-range grid 1 x 1
     frames = np.stack([synth.pair_np(37, fs, fs, 4 * t, -2 * t)[0] for t in range(n)])
     path = tmp_path / "frames.raw"
