@@ -23,17 +23,7 @@
 #include "mof_kernels.h"
 
 namespace {
-
 thread_local char g_err[512] = "";
-
-int fail(int code, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
-  va_end(ap);
-  return code;
-}
-
 }  // namespace
 
 namespace mof {
@@ -44,6 +34,23 @@ int capi_fail(int code, const char* fmt, ...) {
   vsnprintf(g_err, sizeof(g_err), fmt, ap);
   va_end(ap);
   return code;
+}
+
+// twiddles W_n^k = exp(-2 pi i k / n), k < n, as (re, im) float pairs: computed in double, the axis values exact
+std::vector<float> twiddle_table(int n) {
+  std::vector<float> tw(2 * (size_t)n);
+  for (int k = 0; k < n; ++k) {
+    double ang = -2.0 * 3.14159265358979323846 * (double)k / (double)n;
+    double c = std::cos(ang), s = std::sin(ang);
+    if ((4 * k) % n == 0) {
+      const int q = (4 * k) / n;
+      c = (q == 0) ? 1.0 : (q == 2) ? -1.0 : 0.0;
+      s = (q == 1) ? -1.0 : (q == 3) ? 1.0 : 0.0;
+    }
+    tw[2 * (size_t)k] = (float)c;
+    tw[2 * (size_t)k + 1] = (float)s;
+  }
+  return tw;
 }
 
 namespace {
@@ -78,6 +85,8 @@ int parked_count() {
 
 namespace {
 
+constexpr auto& fail = mof::capi_fail;
+
 #define HIP_TRY(expr)                                                                          \
   do {                                                                                         \
     hipError_t _e = (expr);                                                                    \
@@ -105,6 +114,105 @@ int select_device(int device) {
   return MOF_OK;
 }
 
+// Which kernels an engine launches, decided once at create (fft_route)
+struct FftRoute {
+  enum Family { TUNED, PLANNED, LARGE };
+  enum Video { PAIRS, SEQ, SEQ_HALF, HALF_SEQ };
+  Family family = TUNED;    // what every launch can run: the hand-tuned K1 of the patch size, the planned LDS kernel
+                            // (pc_kernel_generic.hip), or -- padded patch too large for a CU -- the planned pipeline through HBM (pc_large_kernel.hip)
+  int m = 0;                // transform size: the patch size (TUNED) or the size cv::phaseCorrelate pads it to
+  int half_m = 0;           // > 0: full-resolution pair launches run the fused half-tile kernel of this size instead (pc_half_kernel.hip;
+                            //      cv::phaseCorrelate model only)
+  int pair_half_wgs = 0;    // != 0: full-resolution pair launches run the pair kernel on the half tile (pc_seq_half.hip), this many
+                            //       workgroups per CU
+  Video video = PAIRS;      // a video: the pair form on consecutive frames, K1s (pc_seq_kernel.hip), pc_seq_half.hip, or the half-tile
+  int video_m = 0;          // kernel's sequence form at transform size video_m
+  bool large_tuned = false; // LARGE, full resolution: the estimator's tuned K5s / K6s / K7 instead of L5 / L6 / L7
+  bool odd_tail = false;    // ... on a size whose Nyquist bins are not exact (the rows kernel's exact sums stand in)
+  bool large_video = false; // ... and a video transforms every frame once per pass
+};
+
+// The MOF_FFT_* knobs that select kernels (README), read once per process
+struct FftKnobs {
+  int half, pair_half_wgs;  // MOF_FFT_HALF: -1 unset
+  bool force_planned, force_large, pair_half, seq_pairs, seq_half64, seq_half128, half_seq_off, large_tuned, large_video;
+};
+
+// The route of a configuration (validated by validate_fft); *plan receives the plan of the planned families. False: no plan.
+bool fft_route(const mof_fft_config& c, mof::PcPlan* plan, FftRoute* r) {
+  static const FftKnobs k = [] {
+    FftKnobs r{};
+    const char* v;
+    r.half = (v = getenv("MOF_FFT_HALF")) ? atoi(v) : -1;
+    r.force_planned = getenv("MOF_FFT_FORCE_PLANNED") != nullptr;
+    r.force_large = getenv("MOF_FFT_FORCE_LARGE") != nullptr;
+    r.pair_half = (v = getenv("MOF_FFT_PAIR_HALF")) && atoi(v) != 0;
+    r.pair_half_wgs = (v = getenv("MOF_FFT_PAIR_HALF_WGS")) ? atoi(v) : 2;
+    r.seq_pairs = getenv("MOF_FFT_SEQ_PAIRS") != nullptr;
+    r.seq_half64 = getenv("MOF_FFT_SEQ_HALF64") != nullptr;
+    r.seq_half128 = getenv("MOF_FFT_SEQ_HALF128") != nullptr;
+    r.half_seq_off = (v = getenv("MOF_FFT_HALF_SEQ")) && atoi(v) == 0;
+    r.large_tuned = !(v = getenv("MOF_FFT_LARGE_TUNED")) || atoi(v) != 0;
+    r.large_video = !(v = getenv("MOF_FFT_LARGE_VIDEO")) || atoi(v) != 0;
+    return r;
+  }();
+  const bool ocv = c.peak_model == MOF_PEAK_OPENCV;
+  *r = FftRoute{};
+  if (mof::pc_patch_size_supported(c.patch_size) && !k.force_planned && !k.force_large)
+    r->family = FftRoute::TUNED;
+  else if (!(k.force_large && ocv) && mof::pc_build_plan(c.patch_size, plan))  // (MOF_FFT_FORCE_LARGE with MOF_PEAK_OCL: the planned kernel)
+    r->family = FftRoute::PLANNED;
+  else if (mof::pc_build_line_plan(c.patch_size, plan))
+    r->family = FftRoute::LARGE;
+  else
+    return false;
+  const bool tuned = r->family == FftRoute::TUNED, planned = r->family == FftRoute::PLANNED;
+  const int m = r->m = tuned ? c.patch_size : plan->m;
+  // The fused half-tile kernel: the default for large patches whose half tile fits a CU (even padded size <= 192); MOF_FFT_HALF=0 keeps
+  // them on the pipeline through HBM scratch, MOF_FFT_HALF=1 also routes the tuned / planned sizes it is instantiated for through it.
+  // r05: N = 120 -- the reference's default samplePointSize -- takes it by default too: two workgroups per CU and every phase on all
+  // waves beat the tuned one-workgroup kernel there (1.14 M against 1.10 M pairs/s same-box, profiles/r05_half_raw_pairsrc_ab.txt).
+  // ... and the planned sizes where it beats the full-tile planned kernel on the box (transform sizes 60, 96, 100: p60 1.10 -> 1.38 M,
+  // p96 757 -> 855 k pairs/s, profiles/r05_half_vs_planned_bench_ab.txt, r05_half_vs_planned_rates.txt; 72, 90: +3 % on pairs, and the
+  // video form: profiles/r05_half_vs_planned_final.txt; on patches padded to 64 it loses 4 %, p62); the tuned N = 64 / 128 pair kernels
+  // stay faster than it and keep their sizes. Patches of 109 .. 119 pixels pad to 120 and follow N = 120 itself (the planned kernel at
+  // 120: 869 k against 1.30 M pairs/s). Long-range launches stay on the family's kernel (launch_field).
+  const bool half_ok = ocv && k.half != 0 && !k.force_large && !k.force_planned;
+  if (half_ok && mof::pc_half_supported(m) &&
+      (r->family == FftRoute::LARGE || k.half == 1 || (tuned && m == 120) ||
+       (planned && (m == 60 || m == 72 || m == 90 || m == 96 || m == 100 || m == 120))))
+    r->half_m = m;
+  // A/B (r05): independent pairs of 128 x 128 patches through the pair kernel on the HALF tile, two workgroups per CU (it has
+  // MOF_PEAK_OCL instantiations too)
+  if (tuned && r->half_m == 0 && k.pair_half && mof::pc_pair_half_supported(m)) r->pair_half_wgs = k.pair_half_wgs;
+  // The video form. The half-tile kernel's sequence form: every size it serves by default but 162 (MOF_FFT_HALF_SEQ=0 keeps the pair form);
+  // 128 x 128 patches, whose pair form stays on the tuned kernel -- there it beats the older half-tile sequence kernel (pc_seq_half.hip: one
+  // 8-wave workgroup per CU, 192 VGPRs), c4seq 93.3 k -> 112 k pairs/s, MOF_FFT_SEQ_HALF128=1 keeps that one; and the planned sizes where only
+  // the video form wins (50, 54, 108: pc_half_kernel.hip, MOF_HALF_SEQ_SIZES).
+  int kh_m = r->half_m;
+  if (kh_m == 0 && tuned && m == 128 && !k.seq_half128) kh_m = 128;
+  if (kh_m == 0 && planned && half_ok && !mof::pc_half_supported(m)) kh_m = m;
+  if (kh_m > 0 && ocv && !k.seq_pairs && !k.half_seq_off && mof::pc_half_sequence_supported(kh_m)) {
+    r->video = FftRoute::HALF_SEQ;
+    r->video_m = kh_m;
+  } else if (tuned && !k.seq_pairs && mof::pc_sequence_half_supported(m) && (m != 64 || k.seq_half64)) {
+    r->video = FftRoute::SEQ_HALF;
+  } else if (tuned && !k.seq_pairs && mof::pc_sequence_supported(m)) {
+    r->video = FftRoute::SEQ;
+  }
+  if (r->family == FftRoute::LARGE) {
+    // r06: the tuned transform sizes from 200 on (sr_transform_size_tuned; 96 .. 192 keep L5 / L6 / L7 under MOF_FFT_HALF=0 and
+    // MOF_FFT_FORCE_LARGE=1), and patches that PAD to one of them: the row kernel zero-pads, the column kernel applies the box-zero rule
+    // of padded constant patches from the row kernel's flags. Unpadded patches of 240 / 256 / 480 pixels (the reference's whole-frame
+    // fallback among them, FftMethod.cpp:1709-1716) run them 2.5 x faster than the planned kernels, same Zh / Dt / candidate formats.
+    bool exact = true;
+    r->large_tuned = k.large_tuned && m >= 200 && mof::sr_transform_size_tuned(m, &exact);
+    r->odd_tail = r->large_tuned && !exact;
+    r->large_video = r->large_tuned && k.large_video;
+  }
+  return true;
+}
+
 }  // namespace
 
 struct mof_fft_engine {
@@ -118,14 +226,10 @@ struct mof_fft_engine {
   double* h_out = nullptr;       // pinned
   uint8_t* h_stage = nullptr;    // pinned upload staging (tightly packed frame)
   bool first = true;             // FftMethod.cpp:1761
-  bool generic = false;          // patch sizes without a hand-tuned instantiation run the planned kernel (pc_kernel_generic.hip)
-  bool large = false;            // ... or, when the padded patch does not fit a CU's LDS, the planned pipeline through HBM
-  mof::PcPlan plan{};            //     scratch (pc_large_kernel.hip)
-  float* d_pair_slabs = nullptr; // MOF_FFT_PAIR_HALF=1 (N = 128): slabs of the pair kernel on the half tile (pc_seq_half.hip), two per CU
+  FftRoute route;
+  mof::PcPlan plan{};            // route.family PLANNED / LARGE
+  float* d_pair_slabs = nullptr; // route.pair_half_wgs: slabs of the pair kernel on the half tile, one per workgroup
   int n_pair_slabs = 0;
-  int half_m = 0;                // > 0: cv::phaseCorrelate-model batches on full-resolution frames run the fused half-tile kernel of that
-                                 //      transform size instead (pc_half_kernel.hip: even padded sizes in (135, 192]; MOF_FFT_HALF=1: tuned sizes too)
-  int seq_half_m = 0;            // > 0: a planned size whose VIDEO entry runs the half-tile kernel's sequence form (its pair entries stay on the planned kernel)
   // scratch of the large-patch pipeline, for `cap` patch pairs per pass: row half-spectra of 2 cap patches, Dt, peak
   // candidates, constant-patch flags, C_dc. Grown by a batch that needs more (never under a graph capture, never while pinned).
   float *d_zh = nullptr, *d_dt = nullptr, *d_cdc = nullptr;
@@ -202,121 +306,80 @@ static int launch_large(mof_fft_engine* e, const mof::PcArgs& a, int n_pairs, hi
   }
   if (e->scratch_used && e->scratch_stream != s && !capturing) HIP_TRY(hipStreamWaitEvent(s, e->scratch_ev, 0));
   const size_t zhf = mof::pcl_zh_floats(e->plan);
-  // Unpadded patches of 240 / 256 / 480 pixels (the reference's whole-frame fallback among them, FftMethod.cpp:1709-1716) are the
-  // scale / rotation estimator's transform sizes: its tuned K5s / K6s / K7 (sr_seq_kernel.hip, sr_kernel.hip) run instead of the planned
-  // L5 / L6 / L7 -- same Zh / Dt / candidate formats, 2.5 x faster; L8 (the FftMethod tail) stays. Gray and BGR8 frames alike (the
-  // latter promise the gray path's bits); the long-range mode keeps the planned kernels. MOF_FFT_LARGE_TUNED=0: planned kernels (A/B).
-  static const bool tuned_on = [] { const char* v = getenv("MOF_FFT_LARGE_TUNED"); return !v || atoi(v) != 0; }();
-  // r06: 200, 216, 270, 288, 300, 320, 360, 384, 450 too, and patches that PAD to one of these sizes (193 .. 216, 226 .. 240, 251 .. 256, 271 .. 288, 301 .. 320, 325 .. 360, 376 .. 384,
-  // 451 .. 480): the row kernel
-  // zero-pads, the column kernel applies the box-zero rule of padded constant patches from the row kernel's flags
-  static const int tuned_sizes[] = {225, 243, 375, 405, 625, 675, 729,  // (r06: the odd sizes too)
-                                    200, 216, 240, 250, 256, 270, 288, 300, 320, 324, 360, 384, 400, 432, 450, 480, 486, 500, 512,
-                                    540, 576, 600, 640, 648, 720, 750, 768, 800, 810, 864, 900, 960};  // (r06: 324, 486, 500 and every even size above 512 -- first radix up to 32)
-  bool tuned = false;
-  for (int t : tuned_sizes) tuned = tuned || e->plan.m == t;
-  tuned = tuned && tuned_on && a.downscale == 1;
-  // (250 = 10 x 25, 400 = 16 x 25, 432 = 16 x 27: no plan of theirs ends in an even radix, so the Nyquist bins of their transforms are not exact
-  //  -- the row kernel accumulates each image's four exact integer sums and the column kernel takes the real-only slots from those)
-  const bool odd_tail = e->plan.m == 250 || e->plan.m == 400 || e->plan.m == 432;
+  const FftRoute& r = e->route;
+  const bool tuned = r.large_tuned && a.downscale == 1;  // (the long-range mode keeps the planned kernels)
   // r06, a VIDEO on the tuned transforms (pair k = (frame k + 1, frame k): mof_fft_process_sequence_device, or any caller whose cur = prev + one frame):
   // every frame's row spectra are formed ONCE per pass -- Zh slot = frame * patches + patch, so pair q = k * patches + patch finds its previous
   // image at slot q and its current one at slot q + patches, which is exactly what the column kernel's (zh_prev, zh_cur, stride) takes; the
-  // kernels and their arithmetic are the pair form's, so are the bits. MOF_FFT_LARGE_VIDEO=0 keeps the pair form (A/B and its tests).
-  static const bool video_on = [] { const char* v = getenv("MOF_FFT_LARGE_VIDEO"); return !v || atoi(v) != 0; }();
-  const bool video = video_on && tuned && n_pairs >= 2 && a.cur == a.prev + a.prev_stride && a.cur_stride == a.prev_stride;
+  // kernels and their arithmetic are the pair form's, so are the bits. Otherwise image 2 q + which (0 cur, 1 prev) of every pair q.
+  const bool video = r.large_video && tuned && n_pairs >= 2 && a.cur == a.prev + a.prev_stride && a.cur_stride == a.prev_stride;
+  mof::PclSrc src{};
+  src.base[0] = video ? a.prev : a.cur;  // one unit of images: a frame of the video, or a frame pair
+  src.stride[0] = video ? a.prev_stride : a.cur_stride;
+  if (!video) {
+    src.base[1] = a.prev;
+    src.stride[1] = a.prev_stride;
+  }
+  src.pitch = a.pitch;
+  src.paired = video ? 2 : 1;
+  src.grid_x = a.grid_x;
+  src.grid_y = a.grid_y;
+  src.origin_x = a.origin_x;
+  src.origin_y = a.origin_y;
+  src.stride_x = a.stride_x;
+  src.stride_y = a.stride_y;
+  auto units_on = [&src](int k) {  // the source from unit k on
+    mof::PclSrc u = src;
+    u.base[0] += (size_t)k * src.stride[0];
+    if (src.paired == 1) u.base[1] += (size_t)k * src.stride[1];
+    return u;
+  };
+  const int per_unit = video ? patches : 2 * patches;  // images
+  int* flags = e->d_flags + (video ? (size_t)2 * e->cap : 0);  // per image of a pass (the video's are spread to pairs by launch_pcl_seq_flags)
+  int* sums = e->d_flags + (size_t)4 * e->cap;  // four ints per image (r->odd_tail)
+  const float* zh_prev = e->d_zh + (video ? 0 : zhf);
+  const float* zh_cur = e->d_zh + (video ? (size_t)patches * zhf : 0);
+  const size_t zh_stride = video ? zhf : 2 * zhf;
+  const int* sums_prev = sums + (video ? 0 : 4);
+  const int* sums_cur = sums + (video ? 4 * patches : 0);
+  const int sums_stride = video ? 4 : 8;
+  mof::PclFinal f{};
+  f.Dt = e->d_dt;
+  f.cand = e->d_cand;
+  f.twiddles = e->d_twiddles;
+  f.mode = 1;
+  f.max_px_speed_sq = a.max_px_speed_sq;
+  f.flags = e->d_flags;
+  f.cdc = e->d_cdc;
   const int per_pass = e->cap / patches;
   for (int k0 = 0; k0 < n_pairs; k0 += per_pass) {
     const int np = n_pairs - k0 < per_pass ? n_pairs - k0 : per_pass, nq = np * patches;
-    if (video) {
-      mof::PclSrc src{};
-      src.base[0] = a.prev + (size_t)k0 * a.prev_stride;  // frame k0 of the video
-      src.stride[0] = a.prev_stride;
-      src.pitch = a.pitch;
-      src.paired = 2;
-      src.grid_x = a.grid_x;
-      src.grid_y = a.grid_y;
-      src.origin_x = a.origin_x;
-      src.origin_y = a.origin_y;
-      src.stride_x = a.stride_x;
-      src.stride_y = a.stride_y;
-      int* fs = e->d_flags + (size_t)2 * e->cap;  // per image of this pass: (np + 1) * patches <= 2 cap
-      int* sums = e->d_flags + (size_t)4 * e->cap;  // four ints per image slot
-      HIP_TRY(hipMemsetAsync(fs, 0, (size_t)(nq + patches) * sizeof(int), s));
-      if (odd_tail) HIP_TRY(hipMemsetAsync(sums, 0, (size_t)4 * (nq + patches) * sizeof(int), s));
-      const int frames_per_launch = 65534 / patches > 0 ? 65534 / patches : 1;
-      for (int j0 = 0; j0 < np + 1; j0 += frames_per_launch) {
-        const int nj = np + 1 - j0 < frames_per_launch ? np + 1 - j0 : frames_per_launch;
-        mof::PclSrc sj = src;
-        sj.base[0] += (size_t)j0 * a.prev_stride;
-        HIP_TRY(mof::launch_sr_rows_real_src(sj, e->d_twiddles, e->d_zh + (size_t)j0 * patches * zhf, zhf, fs + (size_t)j0 * patches, e->plan.m,
-                                             nj * patches, a.channels, e->plan.n, s, sums + (size_t)4 * j0 * patches));
-      }
-      HIP_TRY(mof::launch_pcl_seq_flags(fs, e->d_flags, patches, nq, s));
-      const float* zp = e->d_zh;
-      const float* zc = e->d_zh + (size_t)patches * zhf;
-      HIP_TRY(mof::launch_sr_cols_seq(zp, zc, zhf, e->d_twiddles, e->d_dt, e->plan.m, nq, 1, s, e->d_flags, e->plan.n, sums, sums + (size_t)4 * patches, 4));
-      HIP_TRY(mof::launch_pcl_cdc(zp, zc, zhf, e->plan.m, e->d_cdc, nq, s));
-      HIP_TRY(mof::launch_sr_rows_inv(e->d_dt, e->d_twiddles, e->d_cand, e->plan.m, nq, s));
-      mof::PclFinal f{};
-      f.Dt = e->d_dt;
-      f.cand = e->d_cand;
-      f.twiddles = e->d_twiddles;
-      f.mode = 1;
-      f.max_px_speed_sq = a.max_px_speed_sq;
-      f.out = a.out + (size_t)k0 * patches * 2;
-      f.flags = e->d_flags;
-      f.cdc = e->d_cdc;
-      HIP_TRY(mof::launch_pcl_peak(f, e->plan, nq, s, true));
-      continue;
-    }
-    mof::PclSrc src{};
-    src.base[0] = a.cur + (size_t)k0 * a.cur_stride;
-    src.base[1] = a.prev + (size_t)k0 * a.prev_stride;
-    src.stride[0] = a.cur_stride;
-    src.stride[1] = a.prev_stride;
-    src.pitch = a.pitch;
-    src.paired = 1;
-    src.grid_x = a.grid_x;
-    src.grid_y = a.grid_y;
-    src.origin_x = a.origin_x;
-    src.origin_y = a.origin_y;
-    src.stride_x = a.stride_x;
-    src.stride_y = a.stride_y;
-    HIP_TRY(hipMemsetAsync(e->d_flags, 0, (size_t)2 * nq * sizeof(int), s));
-    int* sums = e->d_flags + (size_t)4 * e->cap;  // four ints per image 2 q + which
-    if (tuned && odd_tail) HIP_TRY(hipMemsetAsync(sums, 0, (size_t)8 * nq * sizeof(int), s));
-    // (launch_pcl_rows splits at 65534 images on pair boundaries: keep a pass's image count a multiple of 2 * patches below that)
-    const int pairs_per_launch = 65534 / (2 * patches) > 0 ? 65534 / (2 * patches) : 1;
-    for (int j0 = 0; j0 < np; j0 += pairs_per_launch) {
-      const int nj = np - j0 < pairs_per_launch ? np - j0 : pairs_per_launch;
-      mof::PclSrc sj = src;
-      sj.base[0] += (size_t)j0 * a.cur_stride;
-      sj.base[1] += (size_t)j0 * a.prev_stride;
+    const int units = video ? np + 1 : np;
+    HIP_TRY(hipMemsetAsync(flags, 0, (size_t)units * per_unit * sizeof(int), s));
+    if (tuned && r.odd_tail) HIP_TRY(hipMemsetAsync(sums, 0, (size_t)4 * units * per_unit * sizeof(int), s));
+    // (the row launchers split at 65534 images, a pair form on pair boundaries: keep a launch's image count a multiple of a unit below that)
+    const int units_per_launch = 65534 / per_unit > 0 ? 65534 / per_unit : 1;
+    for (int j0 = 0; j0 < units; j0 += units_per_launch) {
+      const int nj = units - j0 < units_per_launch ? units - j0 : units_per_launch;
+      const mof::PclSrc sj = units_on(k0 + j0);
+      float* zh = e->d_zh + (size_t)j0 * per_unit * zhf;
       if (tuned)
-        HIP_TRY(mof::launch_sr_rows_real_src(sj, e->d_twiddles, e->d_zh + (size_t)2 * j0 * patches * zhf, zhf,
-                                             e->d_flags + (size_t)2 * j0 * patches, e->plan.m, 2 * nj * patches, a.channels, e->plan.n, s,
-                                             sums + (size_t)8 * j0 * patches));
+        HIP_TRY(mof::launch_sr_rows_real_src(sj, e->d_twiddles, zh, zhf, flags + (size_t)j0 * per_unit, e->plan.m, nj * per_unit, a.channels,
+                                             e->plan.n, s, sums + (size_t)4 * j0 * per_unit));
       else
-        HIP_TRY(mof::launch_pcl_rows(sj, e->plan, e->d_twiddles, e->d_zh + (size_t)2 * j0 * patches * zhf, zhf,
-                                     e->d_flags + (size_t)2 * j0 * patches, 2 * nj * patches, a.channels, a.downscale, s));
+        HIP_TRY(mof::launch_pcl_rows(sj, e->plan, e->d_twiddles, zh, zhf, flags + (size_t)j0 * per_unit, nj * per_unit, a.channels,
+                                     a.downscale, s));
     }
+    if (video) HIP_TRY(mof::launch_pcl_seq_flags(flags, e->d_flags, patches, nq, s));
     if (tuned) {
-      HIP_TRY(mof::launch_sr_cols_seq(e->d_zh + zhf, e->d_zh, 2 * zhf, e->d_twiddles, e->d_dt, e->plan.m, nq, 1, s, e->d_flags, e->plan.n, sums + 4, sums, 8));
-      HIP_TRY(mof::launch_pcl_cdc(e->d_zh + zhf, e->d_zh, 2 * zhf, e->plan.m, e->d_cdc, nq, s));
+      HIP_TRY(mof::launch_sr_cols_seq(zh_prev, zh_cur, zh_stride, e->d_twiddles, e->d_dt, e->plan.m, nq, 1, s, e->d_flags, e->plan.n,
+                                      sums_prev, sums_cur, sums_stride));
+      HIP_TRY(mof::launch_pcl_cdc(zh_prev, zh_cur, zh_stride, e->plan.m, e->d_cdc, nq, s));
       HIP_TRY(mof::launch_sr_rows_inv(e->d_dt, e->d_twiddles, e->d_cand, e->plan.m, nq, s));
     } else {
-      HIP_TRY(mof::launch_pcl_cols(e->d_zh + zhf, e->d_zh, 2 * zhf, e->plan, e->d_twiddles, e->d_dt, e->d_cdc, e->d_flags, nq, s));
+      HIP_TRY(mof::launch_pcl_cols(zh_prev, zh_cur, zh_stride, e->plan, e->d_twiddles, e->d_dt, e->d_cdc, e->d_flags, nq, s));
     }
-    mof::PclFinal f{};
-    f.Dt = e->d_dt;
-    f.cand = e->d_cand;
-    f.twiddles = e->d_twiddles;
-    f.mode = 1;
-    f.max_px_speed_sq = a.max_px_speed_sq;
     f.out = a.out + (size_t)k0 * patches * 2;
-    f.flags = e->d_flags;
-    f.cdc = e->d_cdc;
     HIP_TRY(mof::launch_pcl_peak(f, e->plan, nq, s, tuned));
   }
   if (!capturing) {
@@ -330,16 +393,18 @@ static int launch_large(mof_fft_engine* e, const mof::PcArgs& a, int n_pairs, hi
 // every K1 launch of an engine: the hand-tuned instantiation of its patch size, the planned general kernel, or -- for patches
 // too large for a CU -- the planned pipeline through HBM scratch. Returns a MOF status.
 static int launch_field(mof_fft_engine* e, const mof::PcArgs& a, int n_pairs, hipStream_t stream) {
-  if (e->half_m > 0 && a.downscale == 1 && a.peak_model == 0) {  // (no scratch, nothing engine-owned but the twiddles)
-    HIP_TRY(mof::launch_pc_half(a, e->half_m, e->cfg.patch_size, n_pairs, stream));
+  const FftRoute& r = e->route;
+  if (r.half_m > 0 && a.downscale == 1) {  // (no scratch, nothing engine-owned but the twiddles)
+    HIP_TRY(mof::launch_pc_half(a, r.half_m, e->cfg.patch_size, n_pairs, stream));
     return MOF_OK;
   }
-  if (e->large) return launch_large(e, a, n_pairs, stream);
-  if (e->d_pair_slabs && a.downscale == 1) {
+  if (r.family == FftRoute::LARGE) return launch_large(e, a, n_pairs, stream);
+  if (r.pair_half_wgs != 0 && a.downscale == 1) {
     HIP_TRY(mof::launch_pc_pair_half(a, e->cfg.patch_size, n_pairs, e->d_pair_slabs, e->n_pair_slabs, stream));
     return MOF_OK;
   }
-  HIP_TRY(e->generic ? mof::launch_pc_generic(a, e->plan, n_pairs, stream) : mof::launch_pc_field(a, e->cfg.patch_size, n_pairs, stream));
+  HIP_TRY(r.family == FftRoute::PLANNED ? mof::launch_pc_generic(a, e->plan, n_pairs, stream)
+                                        : mof::launch_pc_field(a, e->cfg.patch_size, n_pairs, stream));
   return MOF_OK;
 }
 #define FIELD_TRY(expr)       \
@@ -455,52 +520,13 @@ int mof_fft_create(const mof_fft_config* cfg, mof_fft_engine** out) try {
   if (!e) return fail(MOF_ERR_NO_MEMORY, "out of host memory");
   e->cfg = *cfg;
   e->frame_bytes = (size_t)cfg->frame_width * cfg->frame_height;
-  // diagnostics (A/B of the kernel families on one size, and their parity tests against each other):
-  // MOF_FFT_FORCE_PLANNED=1 runs the planned LDS kernel also where a tuned instantiation exists, MOF_FFT_FORCE_LARGE=1 the
-  // planned pipeline through HBM scratch at any size (cv::phaseCorrelate model only)
-  static const bool force_planned = getenv("MOF_FFT_FORCE_PLANNED") != nullptr, force_large = getenv("MOF_FFT_FORCE_LARGE") != nullptr;
-  e->generic = !mof::pc_patch_size_supported(cfg->patch_size) || force_planned || force_large;
-  if (e->generic && (force_large && cfg->peak_model == MOF_PEAK_OPENCV ? true : !mof::pc_build_plan(cfg->patch_size, &e->plan))) {
-    e->generic = false;
-    e->large = true;
-    if (!mof::pc_build_line_plan(cfg->patch_size, &e->plan)) {  // (validate_fft has checked it)
-      delete e;
-      return fail(MOF_ERR_UNSUPPORTED, "no plan for patch_size %d", cfg->patch_size);
-    }
+  if (!fft_route(*cfg, &e->plan, &e->route)) {  // (validate_fft has checked that a plan exists)
+    delete e;
+    return fail(MOF_ERR_UNSUPPORTED, "no plan for patch_size %d", cfg->patch_size);
   }
-  const int n = (e->generic || e->large) ? e->plan.m : cfg->patch_size;  // transform size: the planned kernels work on the padded patch
-  {
-    // the fused half-tile kernel: the default for large patches whose half tile fits a CU (even padded size <= 192); MOF_FFT_HALF=0
-    // keeps them on the pipeline through HBM scratch, MOF_FFT_HALF=1 also routes the tuned / planned sizes it is instantiated for
-    // (64, 96, 120, 128) through it -- A/B and the parity tests of the formulation
-    static const int half_knob = [] { const char* v = getenv("MOF_FFT_HALF"); return v ? atoi(v) : -1; }();
-    // r05: N = 120 -- the reference's default samplePointSize -- takes it by default too: two workgroups per CU and every phase on all
-    // waves beat the tuned one-workgroup kernel there (1.14 M against 1.10 M pairs/s same-box, profiles/r05_half_raw_pairsrc_ab.txt);
-    // its long-range mode and OpenCL peak model stay on the tuned kernel (launch_field)
-    const bool tuned_size_default = n == 120 && !e->generic && !e->large;
-    // ... and the planned sizes where it beats the full-tile planned kernel on the box (transform sizes 60, 96, 100: p60 1.10 -> 1.38 M,
-    // p96 757 -> 855 k pairs/s, profiles/r05_half_vs_planned_bench_ab.txt, r05_half_vs_planned_rates.txt; on patches padded to 64 it
-    // loses 4 %, p62); the tuned N = 64 / 128 pair kernels stay faster than it and keep their sizes. Patches of 109 .. 119 pixels pad to
-    // 120 and follow N = 120 itself (the planned kernel at 120: 869 k against 1.30 M pairs/s)
-    const bool planned_size_default = e->generic && !force_planned && (n == 60 || n == 72 || n == 90 || n == 96 || n == 100 || n == 120);  // (72, 90: +3 % on pairs, and the video form: profiles/r05_half_vs_planned_final.txt)
-    if (cfg->peak_model == MOF_PEAK_OPENCV && mof::pc_half_supported(n) && half_knob != 0 && !force_large && !force_planned &&
-        (e->large || half_knob == 1 || tuned_size_default || planned_size_default))
-      e->half_m = n;
-  }
-  // twiddles W_n^k = exp(-2 pi i k / n), double -> float, axis values exact
-  std::vector<float> tw(2 * (size_t)n);
-  for (int k = 0; k < n; ++k) {
-    double ang = -2.0 * 3.14159265358979323846 * (double)k / (double)n;
-    double c = std::cos(ang), s = std::sin(ang);
-    if ((4 * k) % n == 0) {
-      const int q = (4 * k) / n;
-      c = (q == 0) ? 1.0 : (q == 2) ? -1.0 : 0.0;
-      s = (q == 1) ? -1.0 : (q == 3) ? 1.0 : 0.0;
-    }
-    tw[2 * k] = (float)c;
-    tw[2 * k + 1] = (float)s;
-  }
-  if (!e->generic && !e->large && n == 64) {  // the tuned N = 64 kernel's matrix-core stage reads its DFT-16 fragments from behind the twiddles
+  const FftRoute& r = e->route;
+  std::vector<float> tw = mof::twiddle_table(r.m);
+  if (r.family == FftRoute::TUNED && r.m == 64) {  // the tuned N = 64 kernel's matrix-core stage reads its DFT-16 fragments from behind the twiddles
     std::vector<uint32_t> frag(1024, 0u);
     mof::pc_mfma_s1_fragments(frag.data());
     tw.resize(128 + 1024);
@@ -525,38 +551,25 @@ int mof_fft_create(const mof_fft_config* cfg, mof_fft_engine** out) try {
   CREATE_TRY(hipMalloc(&e->d_out, res * sizeof(double)));
   CREATE_TRY(hipHostMalloc(&e->h_out, res * sizeof(double), hipHostMallocDefault));
   CREATE_TRY(hipHostMalloc(&e->h_stage, e->frame_bytes, hipHostMallocDefault));
-  if (e->half_m > 0) CREATE_TRY(mof::pc_configure_half(e->half_m));
-  {
-    // the planned sizes whose VIDEO form is the half-tile kernel's although their pair form is not (fft_sequence)
-    static const int half_knob2 = [] { const char* v = getenv("MOF_FFT_HALF"); return v ? atoi(v) : -1; }();
-    static const bool force_planned2 = getenv("MOF_FFT_FORCE_PLANNED") != nullptr, force_large2 = getenv("MOF_FFT_FORCE_LARGE") != nullptr;
-    if (e->generic && e->half_m == 0 && half_knob2 != 0 && !force_planned2 && !force_large2 && cfg->peak_model == MOF_PEAK_OPENCV &&
-        !mof::pc_half_supported(n) && mof::pc_half_sequence_supported(n)) {
-      e->seq_half_m = n;
-      CREATE_TRY(mof::pc_configure_half(n));
-    }
-  }
-  if (e->large) {
+  // the kernels the route can launch (a video's half-tile form runs at half_m whenever that is set)
+  if (r.half_m > 0 || r.video == FftRoute::HALF_SEQ) CREATE_TRY(mof::pc_configure_half(r.half_m > 0 ? r.half_m : r.video_m));
+  if (r.family == FftRoute::LARGE) {
     CREATE_TRY(hipEventCreateWithFlags(&e->scratch_ev, hipEventDisableTiming));
     CREATE_TRY(large_alloc(e, cfg->grid_x * cfg->grid_y));  // one frame pair; a batch grows it to a whole pass
-  } else if (e->generic) {
+  } else if (r.family == FftRoute::PLANNED) {
     CREATE_TRY(mof::pc_configure_generic());
   } else {
-    CREATE_TRY(mof::pc_configure(n));
-    if (mof::pc_sequence_supported(n)) CREATE_TRY(mof::pc_configure_sequence());
-    if (mof::pc_sequence_half_supported(n)) CREATE_TRY(mof::pc_configure_sequence_half(n));
-    if (n == 128 && cfg->peak_model == MOF_PEAK_OPENCV && mof::pc_half_sequence_supported(n)) CREATE_TRY(mof::pc_configure_half(n));  // (its video form serves 128 x 128, fft_sequence)
-    // A/B knob (r05): independent pairs of 128 x 128 patches through the pair kernel on the HALF tile, two workgroups per CU
-    static const bool pair_half = [] { const char* v = getenv("MOF_FFT_PAIR_HALF"); return v && atoi(v) != 0; }();
-    if (pair_half && mof::pc_pair_half_supported(n)) {
-      int dev = 0, cus = 256;
-      hipDeviceProp_t prop;
-      if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-      static const int per_cu = [] { const char* v = getenv("MOF_FFT_PAIR_HALF_WGS"); return v ? atoi(v) : 2; }();
-      e->n_pair_slabs = per_cu * cus;
-      CREATE_TRY(mof::pc_configure_pair_half(n));
-      CREATE_TRY(hipMalloc(&e->d_pair_slabs, (size_t)e->n_pair_slabs * mof::pc_pair_half_slab_floats(n) * sizeof(float)));
-    }
+    CREATE_TRY(mof::pc_configure(r.m));
+  }
+  if (r.video == FftRoute::SEQ) CREATE_TRY(mof::pc_configure_sequence());
+  if (r.video == FftRoute::SEQ_HALF) CREATE_TRY(mof::pc_configure_sequence_half(r.m));
+  if (r.pair_half_wgs != 0) {
+    int dev = 0, cus = 256;
+    hipDeviceProp_t prop;
+    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
+    e->n_pair_slabs = r.pair_half_wgs * cus;
+    CREATE_TRY(mof::pc_configure_pair_half(r.m));
+    CREATE_TRY(hipMalloc(&e->d_pair_slabs, (size_t)e->n_pair_slabs * mof::pc_pair_half_slab_floats(r.m) * sizeof(float)));
   }
 #undef CREATE_TRY
   *out = e;
@@ -566,7 +579,11 @@ int mof_fft_create(const mof_fft_config* cfg, mof_fft_engine** out) try {
 }
 
 const char* mof_fft_kernel_variant(const mof_fft_engine* e) {
-  return !e ? "" : (e->half_m > 0 ? "planned-half" : (e->large ? "planned-large" : (e->generic ? "planned" : mof::pc_kernel_variant(e->cfg.patch_size))));
+  if (!e) return "";
+  const FftRoute& r = e->route;
+  return r.half_m > 0 ? "planned-half"
+                      : (r.family == FftRoute::LARGE ? "planned-large"
+                                                     : (r.family == FftRoute::PLANNED ? "planned" : mof::pc_kernel_variant(e->cfg.patch_size)));
 }
 
 static void fft_destroy_now(void* p) {
@@ -657,34 +674,6 @@ int mof_fft_reset(mof_fft_engine* e) {
   return MOF_OK;
 }
 
-int mof_fft_process(mof_fft_engine* e, const uint8_t* frame, size_t pitch, double* out_xy, int* n_invalid) {
-  if (!e) return fail(MOF_ERR_NOT_INIT, "null engine");
-  if (!frame || !out_xy || pitch < (size_t)e->cfg.frame_width) return fail(MOF_ERR_BAD_ARG, "bad frame/pitch/out");
-  BusyGuard g(e->busy);
-  if (!g.owned) return fail(MOF_ERR_BUSY, "engine busy");  // reference: returns an empty vector
-  HIP_TRY(hipSetDevice(e->cfg.device));
-  const int cur_slot = 1 - e->prev_slot;
-  pack_frame(e->h_stage, frame, pitch, e->cfg.frame_width, e->cfg.frame_height);
-  HIP_TRY(hipMemcpyAsync(e->d_frames[cur_slot], e->h_stage, e->frame_bytes, hipMemcpyHostToDevice, e->stream));
-  // `first`: the frame is correlated with itself (FftMethod.cpp:1791-1793)
-  const uint8_t* prev = e->first ? e->d_frames[cur_slot] : e->d_frames[e->prev_slot];
-  mof::PcArgs a = fft_args(e, e->d_frames[cur_slot], 0, prev, 0, (size_t)e->cfg.frame_width, e->d_out);
-  FIELD_TRY(launch_field(e, a, 1, e->stream));
-  const size_t res = (size_t)e->cfg.grid_x * e->cfg.grid_y * 2;
-  HIP_TRY(hipMemcpyAsync(e->h_out, e->d_out, res * sizeof(double), hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  int bad = 0;
-  for (size_t i = 0; i < res; i += 2) {
-    out_xy[i] = e->h_out[i];
-    out_xy[i + 1] = e->h_out[i + 1];
-    if (std::isnan(e->h_out[i])) ++bad;
-  }
-  if (n_invalid) *n_invalid = bad;
-  e->prev_slot = cur_slot;  // imPrev = imCurr.clone(), FftMethod.cpp:1872
-  e->first = false;         // :1900
-  return MOF_OK;
-}
-
 // Long-range geometry (FftMethod.cpp:1685, :1720): same patch size on the quarter-resolution frame,
 // sqNum_lr = sqNum / 4 patches per side. Only defined for the reference's own tiling.
 static int long_range_args(const mof_fft_engine* e, mof::PcArgs* a) {
@@ -710,19 +699,23 @@ int mof_fft_long_range_patches(const mof_fft_engine* e) {
   return rc ? rc : a.grid_x * a.grid_y;
 }
 
-int mof_fft_process_long_range(mof_fft_engine* e, const uint8_t* frame, size_t pitch, double* out_xy, int* n_invalid) {
+// processImage / processImageLongRange (FftMethod.cpp:1775-1900 / :1905-2004): one host frame against the engine's previous one
+static int fft_process_frame(mof_fft_engine* e, const uint8_t* frame, size_t pitch, double* out_xy, int* n_invalid, bool long_range) {
   if (!e) return fail(MOF_ERR_NOT_INIT, "null engine");
   if (!frame || !out_xy || pitch < (size_t)e->cfg.frame_width) return fail(MOF_ERR_BAD_ARG, "bad frame/pitch/out");
   BusyGuard g(e->busy);
-  if (!g.owned) return fail(MOF_ERR_BUSY, "engine busy");
+  if (!g.owned) return fail(MOF_ERR_BUSY, "engine busy");  // reference: returns an empty vector
   HIP_TRY(hipSetDevice(e->cfg.device));
   const int cur_slot = 1 - e->prev_slot;
   pack_frame(e->h_stage, frame, pitch, e->cfg.frame_width, e->cfg.frame_height);
   HIP_TRY(hipMemcpyAsync(e->d_frames[cur_slot], e->h_stage, e->frame_bytes, hipMemcpyHostToDevice, e->stream));
-  const uint8_t* prev = e->first ? e->d_frames[cur_slot] : e->d_frames[e->prev_slot];  // FftMethod.cpp:1920-1922
+  // `first`: the frame is correlated with itself (FftMethod.cpp:1791-1793, :1920-1922)
+  const uint8_t* prev = e->first ? e->d_frames[cur_slot] : e->d_frames[e->prev_slot];
   mof::PcArgs a = fft_args(e, e->d_frames[cur_slot], 0, prev, 0, (size_t)e->cfg.frame_width, e->d_out);
-  int rc = long_range_args(e, &a);
-  if (rc) return rc;
+  if (long_range) {
+    int rc = long_range_args(e, &a);
+    if (rc) return rc;
+  }
   FIELD_TRY(launch_field(e, a, 1, e->stream));
   const size_t res = (size_t)a.grid_x * a.grid_y * 2;
   HIP_TRY(hipMemcpyAsync(e->h_out, e->d_out, res * sizeof(double), hipMemcpyDeviceToHost, e->stream));
@@ -734,17 +727,25 @@ int mof_fft_process_long_range(mof_fft_engine* e, const uint8_t* frame, size_t p
     if (std::isnan(e->h_out[i])) ++bad;
   }
   if (n_invalid) *n_invalid = bad;
-  e->prev_slot = cur_slot;  // imPrev = imCurr.clone(), FftMethod.cpp:1992
-  e->first = false;         // :2004
+  e->prev_slot = cur_slot;  // imPrev = imCurr.clone(), FftMethod.cpp:1872, :1992
+  e->first = false;         // :1900, :2004
   return MOF_OK;
 }
 
-int mof_fft_process_long_range_batch_device(mof_fft_engine* e, const uint8_t* d_cur, size_t cur_stride,
-                                            const uint8_t* d_prev, size_t prev_stride, size_t pitch, int n_pairs,
-                                            double* d_out_xy, void* stream) {
+int mof_fft_process(mof_fft_engine* e, const uint8_t* frame, size_t pitch, double* out_xy, int* n_invalid) {
+  return fft_process_frame(e, frame, pitch, out_xy, n_invalid, false);
+}
+
+int mof_fft_process_long_range(mof_fft_engine* e, const uint8_t* frame, size_t pitch, double* out_xy, int* n_invalid) {
+  return fft_process_frame(e, frame, pitch, out_xy, n_invalid, true);
+}
+
+// The device batch entries: n_pairs frame pairs of `channels` interleaved channels (1 gray, 3 BGR8)
+static int fft_batch(mof_fft_engine* e, const uint8_t* d_cur, size_t cur_stride, const uint8_t* d_prev, size_t prev_stride, size_t pitch,
+                     int n_pairs, double* d_out_xy, void* stream, int channels, bool long_range) {
   if (!e) return fail(MOF_ERR_NOT_INIT, "null engine");
   if (n_pairs == 0) return MOF_OK;  // an empty batch carries no pointers to check
-  if (!d_cur || !d_prev || !d_out_xy || n_pairs < 0 || pitch < (size_t)e->cfg.frame_width)
+  if (!d_cur || !d_prev || !d_out_xy || n_pairs < 0 || pitch < (size_t)channels * (size_t)e->cfg.frame_width)
     return fail(MOF_ERR_BAD_ARG, "bad batch arguments");
   if ((unsigned long long)n_pairs * (unsigned long long)(e->cfg.grid_x * e->cfg.grid_y) > 0x7fffffffull)
     return fail(MOF_ERR_BAD_ARG, "batch too large for one launch");
@@ -752,8 +753,11 @@ int mof_fft_process_long_range_batch_device(mof_fft_engine* e, const uint8_t* d_
   if (!g.owned) return fail(MOF_ERR_BUSY, "engine busy");
   HIP_TRY(hipSetDevice(e->cfg.device));
   mof::PcArgs a = fft_args(e, d_cur, cur_stride, d_prev, prev_stride, pitch, d_out_xy);
-  int rc = long_range_args(e, &a);
-  if (rc) return rc;
+  a.channels = channels;
+  if (long_range) {
+    int rc = long_range_args(e, &a);
+    if (rc) return rc;
+  }
   if (mof::stream_capturing((hipStream_t)stream)) e->graph_pinned.store(true);
   FIELD_TRY(launch_field(e, a, n_pairs, (hipStream_t)stream));
   return MOF_OK;
@@ -761,23 +765,22 @@ int mof_fft_process_long_range_batch_device(mof_fft_engine* e, const uint8_t* d_
 
 int mof_fft_process_batch_device(mof_fft_engine* e, const uint8_t* d_cur, size_t cur_stride, const uint8_t* d_prev,
                                  size_t prev_stride, size_t pitch, int n_pairs, double* d_out_xy, void* stream) {
-  if (!e) return fail(MOF_ERR_NOT_INIT, "null engine");
-  if (n_pairs == 0) return MOF_OK;  // an empty batch carries no pointers to check
-  if (!d_cur || !d_prev || !d_out_xy || n_pairs < 0 || pitch < (size_t)e->cfg.frame_width)
-    return fail(MOF_ERR_BAD_ARG, "bad batch arguments");
-  if ((unsigned long long)n_pairs * (unsigned long long)(e->cfg.grid_x * e->cfg.grid_y) > 0x7fffffffull)
-    return fail(MOF_ERR_BAD_ARG, "batch too large for one launch");
-  BusyGuard g(e->busy);
-  if (!g.owned) return fail(MOF_ERR_BUSY, "engine busy");
-  HIP_TRY(hipSetDevice(e->cfg.device));
-  mof::PcArgs a = fft_args(e, d_cur, cur_stride, d_prev, prev_stride, pitch, d_out_xy);
-  if (mof::stream_capturing((hipStream_t)stream)) e->graph_pinned.store(true);
-  FIELD_TRY(launch_field(e, a, n_pairs, (hipStream_t)stream));
-  return MOF_OK;
+  return fft_batch(e, d_cur, cur_stride, d_prev, prev_stride, pitch, n_pairs, d_out_xy, stream, 1, false);
 }
 
-// A video: pair k = (frame k + 1, frame k). 64 x 64 patches run the sequence kernel (one real transform per frame and
-// patch, pc_seq_kernel.hip); the other sizes run the pair kernel on cur = frames + 1, prev = frames (no copy either).
+int mof_fft_process_batch_device_bgr(mof_fft_engine* e, const uint8_t* d_cur, size_t cur_stride, const uint8_t* d_prev,
+                                     size_t prev_stride, size_t pitch, int n_pairs, double* d_out_xy, void* stream) {
+  return fft_batch(e, d_cur, cur_stride, d_prev, prev_stride, pitch, n_pairs, d_out_xy, stream, 3, false);
+}
+
+int mof_fft_process_long_range_batch_device(mof_fft_engine* e, const uint8_t* d_cur, size_t cur_stride,
+                                            const uint8_t* d_prev, size_t prev_stride, size_t pitch, int n_pairs,
+                                            double* d_out_xy, void* stream) {
+  return fft_batch(e, d_cur, cur_stride, d_prev, prev_stride, pitch, n_pairs, d_out_xy, stream, 1, true);
+}
+
+// A video: pair k = (frame k + 1, frame k), in the route's video form (fft_route); the pair form runs the engine's pair kernels on
+// cur = frames + 1, prev = frames (no copy either).
 static int fft_sequence(mof_fft_engine* e, const uint8_t* d_frames, size_t frame_stride, size_t pitch, int n_frames,
                         double* d_out_xy, void* stream, int channels) {
   if (!e) return fail(MOF_ERR_NOT_INIT, "null engine");
@@ -793,36 +796,24 @@ static int fft_sequence(mof_fft_engine* e, const uint8_t* d_frames, size_t frame
   mof::PcArgs a = fft_args(e, d_frames + frame_stride, frame_stride, d_frames, frame_stride, pitch, d_out_xy);
   a.channels = channels;
   if (mof::stream_capturing((hipStream_t)stream)) e->graph_pinned.store(true);
-  static const int run = [] { const char* v = getenv("MOF_FFT_SEQ_RUN"); const int r = v ? atoi(v) : 0; return r >= 1 ? r : 16; }();
-  static const bool run_set = [] { const char* v = getenv("MOF_FFT_SEQ_RUN"); return v && atoi(v) >= 1; }();
-  static const bool pairs_only = getenv("MOF_FFT_SEQ_PAIRS") != nullptr, half64 = getenv("MOF_FFT_SEQ_HALF64") != nullptr;
-  const int n = e->cfg.patch_size;
-  const bool half = !e->generic && !e->large && !pairs_only && mof::pc_sequence_half_supported(n) && (n != 64 || half64);
-  const bool full = !e->generic && !e->large && !pairs_only && !half && mof::pc_sequence_supported(n);
-  // the half-tile kernel's video form (r05): every size it serves by default but 162; MOF_FFT_HALF_SEQ=0 keeps the pair form on consecutive frames
-  static const bool half_seq_off = [] { const char* v = getenv("MOF_FFT_HALF_SEQ"); return v && atoi(v) == 0; }();
-  // ... and 128 x 128 patches, whose pair form stays on the tuned kernel: on a video the half-tile kernel's sequence form beats the older
-  // half-tile sequence kernel (pc_seq_half.hip: one 8-wave workgroup per CU, 192 VGPRs) -- c4seq 93.3 k -> 112 k pairs/s; MOF_FFT_SEQ_HALF128=1 keeps that one
-  static const bool old128 = getenv("MOF_FFT_SEQ_HALF128") != nullptr;
-  // ... and the planned sizes where only the video form wins (50, 54, 108: pc_half_kernel.hip, MOF_HALF_SEQ_SIZES)
-  const int kh_m = e->half_m > 0 ? e->half_m
-                                 : ((!e->generic && !e->large && n == 128 && !old128) ? 128 : ((e->generic && e->seq_half_m > 0) ? e->seq_half_m : 0));
-  const bool khalf = kh_m > 0 && !pairs_only && !half_seq_off && e->cfg.peak_model == MOF_PEAK_OPENCV && mof::pc_half_sequence_supported(kh_m);
-  if (!half && !full && !khalf) {
+  const FftRoute& r = e->route;
+  if (r.video == FftRoute::PAIRS) {
     FIELD_TRY(launch_field(e, a, n_pairs, (hipStream_t)stream));
     return MOF_OK;
   }
+  // MOF_FFT_SEQ_RUN: pairs a workgroup walks in time (0: the launchers pick the run length; pc_seq_half.hip takes 16)
+  static const int run_knob = [] { const char* v = getenv("MOF_FFT_SEQ_RUN"); const int r = v ? atoi(v) : 0; return r >= 1 ? r : 0; }();
   // the run index rides gridDim.z (at most 65535 per launch): a very long video goes out in several launches
   const size_t per_pair = (size_t)e->cfg.grid_x * e->cfg.grid_y * 2;
-  const int max_pairs = 65535 * (run_set ? run : (khalf ? 4 : (full ? 2 : run)));  // (the launchers' own run lengths are at least 4 / 2)
+  const int max_pairs = 65535 * (run_knob ? run_knob : (r.video == FftRoute::HALF_SEQ ? 4 : (r.video == FftRoute::SEQ ? 2 : 16)));  // (the launchers' own run lengths are at least 4 / 2)
   for (int k0 = 0; k0 < n_pairs; k0 += max_pairs) {
     const int nk = n_pairs - k0 < max_pairs ? n_pairs - k0 : max_pairs;
     mof::PcArgs c = a;
     c.cur = d_frames + (size_t)k0 * frame_stride;  // the sequence kernels index frames, not pairs
     c.out = d_out_xy + (size_t)k0 * per_pair;
-    if (khalf) HIP_TRY(mof::launch_pc_half_sequence(c, kh_m, n, nk, run_set ? run : 0, (hipStream_t)stream));  // (0: the launcher picks the run length)
-    else if (half) HIP_TRY(mof::launch_pc_sequence_half(c, n, nk, run, (hipStream_t)stream));
-    else HIP_TRY(mof::launch_pc_sequence(c, nk, run_set ? run : 0, (hipStream_t)stream));  // (0: the launcher picks the run length)
+    if (r.video == FftRoute::HALF_SEQ) HIP_TRY(mof::launch_pc_half_sequence(c, r.video_m, e->cfg.patch_size, nk, run_knob, (hipStream_t)stream));
+    else if (r.video == FftRoute::SEQ_HALF) HIP_TRY(mof::launch_pc_sequence_half(c, e->cfg.patch_size, nk, run_knob ? run_knob : 16, (hipStream_t)stream));
+    else HIP_TRY(mof::launch_pc_sequence(c, nk, run_knob, (hipStream_t)stream));
   }
   return MOF_OK;
 }
@@ -835,24 +826,6 @@ int mof_fft_process_sequence_device(mof_fft_engine* e, const uint8_t* d_frames, 
 int mof_fft_process_sequence_device_bgr(mof_fft_engine* e, const uint8_t* d_frames, size_t frame_stride, size_t pitch, int n_frames,
                                         double* d_out_xy, void* stream) {
   return fft_sequence(e, d_frames, frame_stride, pitch, n_frames, d_out_xy, stream, 3);
-}
-
-int mof_fft_process_batch_device_bgr(mof_fft_engine* e, const uint8_t* d_cur, size_t cur_stride, const uint8_t* d_prev,
-                                     size_t prev_stride, size_t pitch, int n_pairs, double* d_out_xy, void* stream) {
-  if (!e) return fail(MOF_ERR_NOT_INIT, "null engine");
-  if (n_pairs == 0) return MOF_OK;  // an empty batch carries no pointers to check
-  if (!d_cur || !d_prev || !d_out_xy || n_pairs < 0 || pitch < 3 * (size_t)e->cfg.frame_width)
-    return fail(MOF_ERR_BAD_ARG, "bad batch arguments");
-  if ((unsigned long long)n_pairs * (unsigned long long)(e->cfg.grid_x * e->cfg.grid_y) > 0x7fffffffull)
-    return fail(MOF_ERR_BAD_ARG, "batch too large for one launch");
-  BusyGuard g(e->busy);
-  if (!g.owned) return fail(MOF_ERR_BUSY, "engine busy");
-  HIP_TRY(hipSetDevice(e->cfg.device));
-  mof::PcArgs a = fft_args(e, d_cur, cur_stride, d_prev, prev_stride, pitch, d_out_xy);
-  a.channels = 3;
-  if (mof::stream_capturing((hipStream_t)stream)) e->graph_pinned.store(true);
-  FIELD_TRY(launch_field(e, a, n_pairs, (hipStream_t)stream));
-  return MOF_OK;
 }
 
 int mof_fft_process_batch_host(mof_fft_engine* e, const uint8_t* cur, size_t cur_stride, const uint8_t* prev,

@@ -33,6 +33,8 @@ struct PcArgs {
 // 1024 dwords behind the 64 twiddles of an N = 64 engine: the f16 hi / lo fragments of the radix-16 DFT matrix, in the lane order
 // of v_mfma_f32_32x32x16_f16's A operand (pc_passes3.hpp, fwd3_rows_mfma)
 void pc_mfma_s1_fragments(uint32_t* out);
+// twiddles W_n^k = exp(-2 pi i k / n), k < n, as (re, im) float pairs (mof_capi.hip; both engines' d_twiddles)
+std::vector<float> twiddle_table(int n);
 
 // Run-time plan of the general K1 (pc_kernel_generic.hip): any samplePointSize n whose padded transform size
 // m = cv::getOptimalDFTSize(n) gives an m x m complex tile that fits one CU's LDS (m <= 135)
@@ -206,8 +208,8 @@ std::vector<uint32_t> sr_weight_planes(const std::vector<int16_t>& weights, int 
 std::vector<SrTileBox> sr_tile_boxes(const std::vector<SrMapEntry>& map, int res, int ksize, int* lds_per_wave, int tile_px);
 
 bool sr_resolution_supported(int res);      // tuned transforms (K5s / K6s / K7) exist for this resolution
-bool sr_pair_kernels_supported(int res);
-bool sr_transform_size_tuned(int m, bool* exact_nyquist);  // the tuned transforms exist for transform size m (the FFT engine's list)   // ... and the packed pair kernels K5 / K6 (240, 256, 480)
+bool sr_pair_kernels_supported(int res);    // ... and the packed pair kernels K5 / K6 (240, 256, 480)
+bool sr_transform_size_tuned(int m, bool* exact_nyquist);  // the tuned transforms exist for transform size m (the one list of them)
 int sr_candidates(int res);
 hipError_t launch_sr_logpolar(const SrLpArgs& a, int interp /*2 cubic, 4 lanczos4*/, int n_images, hipStream_t stream);
 hipError_t launch_sr_phase_correlate(const SrPcArgs& a, int res, int n_pairs, hipStream_t stream);
@@ -234,6 +236,7 @@ hipError_t launch_pcl_seq_flags(const int* fs, int* f2, int patches, int n_pairs
 hipError_t launch_sr_cols_seq(const float* zh_prev, const float* zh_cur, size_t zh_stride, const float* twiddles, float* Dt, int res,
                               int n_pairs, int run, hipStream_t stream, const int* flags = nullptr, int n = 0,  // flags + n < res: the box-zero rule of padded constant patches (run = 1)
                               const int* sums_prev = nullptr, const int* sums_cur = nullptr, int sums_stride = 0);  // the rows kernel's exact sums, pair p at p * sums_stride ints
+int sr_seq_columns_per_wave(int res);  // K6s's columns per wave at transform size res; 0: no K6s there
 // K56 (sr_fused_kernel.hip): K5s + K6s in one kernel, the row transforms as a dense product on the matrix cores -- reads the u8
 // log-polar images instead of Zh. `frags` = sr_fused_fragments(res) on the device. Same pair / run semantics as K6s.
 bool sr_fused_supported(int res);

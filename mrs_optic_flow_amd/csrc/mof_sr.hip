@@ -357,7 +357,8 @@ int seq_run_for(const mof_sr_engine* e, int m) {
   int cus = 0;
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, e->cfg.device) != hipSuccess || cus <= 0) cus = 256;
   const int tn = e->generic ? e->plan.m : e->cfg.resolution;
-  const int cw = (tn >= 540 || tn == 324 || tn == 486 || tn == 500) ? 2 : 4;  // columns per wave (sr_seq_kernel.hip: seq_cw -- first radix above 16)
+  const int cw = mof::sr_seq_columns_per_wave(tn);  // columns per wave
+  if (cw == 0) return 16;  // (no K6s at this size: the planned L6 walks no runs)
   const long groups = (tn / 2 + 1 + cw - 1) / cw, slots = (long)cus * 8;  // one-wave workgroups, two per SIMD
   auto cost = [&](int r) {
     const long wgs = groups * ((m + r - 1) / r), rounds = (wgs + slots - 1) / slots;
@@ -575,7 +576,7 @@ int mof_sr_create(const mof_sr_config* cfg, mof_sr_engine** out) try {
     sbl = mof::sr_tile_boxes(map, res, 8, &slds_l, 16);
   }
   const int tn = generic ? plan.m : res;  // transform size: the planned pipeline works on the padded image
-  std::vector<float> tw(2 * (size_t)tn);
+  const std::vector<float> tw = mof::twiddle_table(tn);
   mof_sr_engine* e = new (std::nothrow) mof_sr_engine();
   if (!e) return mof::capi_fail(MOF_ERR_NO_MEMORY, "out of host memory");
   e->cfg = *cfg;
@@ -592,17 +593,6 @@ int mof_sr_create(const mof_sr_config* cfg, mof_sr_engine** out) try {
   }
   e->chunk = chunk_pairs(cfg->batch_chunk);
   e->two_lanes = two_lane_default(cfg->pipeline_lanes);
-  for (int k = 0; k < tn; ++k) {
-    double ang = -2.0 * 3.14159265358979323846 * (double)k / (double)tn;
-    double c = std::cos(ang), s = std::sin(ang);
-    if ((4 * k) % tn == 0) {
-      const int q = (4 * k) / tn;
-      c = (q == 0) ? 1.0 : (q == 2) ? -1.0 : 0.0;
-      s = (q == 1) ? -1.0 : (q == 3) ? 1.0 : 0.0;
-    }
-    tw[2 * (size_t)k] = (float)c;
-    tw[2 * (size_t)k + 1] = (float)s;
-  }
 #define CREATE_TRY(expr)                                                                  \
   do {                                                                                    \
     hipError_t _e = (expr);                                                               \

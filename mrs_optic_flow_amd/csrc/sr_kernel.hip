@@ -776,32 +776,28 @@ __global__ void __launch_bounds__(64) sr_final_kernel(SrPcArgs a) {
   }
 }
 
-// Resolutions whose transforms are the tuned in-register ones (K5s / K6s / K7): the estimator's own three, and (r06) every transform size the
-// FFT engine's large patches brought along whose Nyquist bin is exact (250 / 400 / 432 would need the exact-sums form of the row kernel: they stay
-// on the planned pipeline, like every resolution that is not itself one of these sizes). MOF_SR_TUNED_ALL=0: the three only (A/B, tests).
+// The transform sizes with tuned in-register transforms (K5s / K6s / K7) -- the only list of them: the estimator's own three, and (r06) every
+// transform size the FFT engine's large patches brought along. 250 = 10 x 25, 400 = 16 x 25, 432 = 16 x 27 (*exact_nyquist = false): no plan
+// of theirs ends in an even radix, so their Nyquist bins are not exact -- the row kernel accumulates each image's four exact integer sums and
+// the column kernel takes the real-only slots from those (the FFT engine's large-patch pipeline and the estimator's padded resolutions).
 bool sr_transform_size_tuned(int m, bool* exact_nyquist) {
-  static const int exact[] = {225, 243, 375, 405, 625, 675, 729,  // (odd: no Nyquist bin to keep exact)
-                              96, 100, 108, 120, 150, 162, 128, 144, 160, 180, 192, 200, 216, 240, 256, 270, 288, 300, 320, 324, 360, 384, 450, 480, 486, 500, 512, 540, 576, 600, 640, 648, 720, 750, 768, 800, 810, 864, 900, 960};
-  for (int t : exact)
+  static const int sizes[] = {225, 243, 375, 405, 625, 675, 729,  // (odd: no Nyquist bin to keep exact)
+                              96, 100, 108, 120, 150, 162, 128, 144, 160, 180, 192, 200, 216, 240, 250, 256, 270, 288, 300, 320, 324, 360, 384,
+                              400, 432, 450, 480, 486, 500, 512, 540, 576, 600, 640, 648, 720, 750, 768, 800, 810, 864, 900, 960};
+  for (int t : sizes)
     if (m == t) {
-      if (exact_nyquist) *exact_nyquist = true;
+      if (exact_nyquist) *exact_nyquist = m != 250 && m != 400 && m != 432;
       return true;
     }
-  if (m == 250 || m == 400 || m == 432) {  // odd last radix: the real-only slots come from the images' exact integer sums
-    if (exact_nyquist) *exact_nyquist = false;
-    return true;
-  }
   return false;
 }
 bool sr_pair_kernels_supported(int res) { return res == 240 || res == 256 || res == 480; }  // K5 / K6 (packed pairs), K56, K6p
+// Resolutions the estimator runs unpadded on the tuned transforms: 240 / 256 / 480, and every even tuned size with an exact Nyquist bin
+// (MOF_SR_TUNED_ALL=0: the three only, A/B and tests). Any other resolution runs on the size it pads to (mof_sr.hip: tuned there too).
 bool sr_resolution_supported(int res) {
   static const bool all = [] { const char* v = getenv("MOF_SR_TUNED_ALL"); return !v || atoi(v) != 0; }();
-  if (sr_pair_kernels_supported(res)) return true;
-  if (!all) return false;
-  static const int sizes[] = {96, 100, 108, 120, 150, 162, 128, 144, 160, 180, 192, 200, 216, 270, 288, 300, 320, 324, 360, 384, 450, 486, 500, 512, 540, 576, 600, 640, 648, 720, 750, 768, 800, 810, 864, 900, 960};
-  for (int t : sizes)
-    if (res == t) return true;
-  return false;
+  bool exact = false;
+  return sr_pair_kernels_supported(res) || (all && res % 2 == 0 && sr_transform_size_tuned(res, &exact) && exact);
 }
 
 template <int K>

@@ -684,6 +684,11 @@ hipError_t launch_sr_rows_real_src(const PclSrc& src, const float* twiddles, flo
   }
 }
 
+// the transform sizes K6s is instantiated for: every size of sr_transform_size_tuned (sr_kernel.hip)
+#define MOF_SR_SEQ_SIZES(X) X(96) X(100) X(108) X(120) X(128) X(144) X(150) X(160) X(162) X(180) X(192) X(200) X(216) X(225) X(240) X(243) \
+  X(250) X(256) X(270) X(288) X(300) X(320) X(324) X(360) X(375) X(384) X(400) X(405) X(432) X(450) X(480) X(486) X(500) X(512) X(540) \
+  X(576) X(600) X(625) X(640) X(648) X(675) X(720) X(729) X(750) X(768) X(800) X(810) X(864) X(900) X(960)
+
 hipError_t launch_sr_cols_seq(const float* zh_prev, const float* zh_cur, size_t zh_stride, const float* twiddles, float* Dt, int res,
                               int n_pairs, int run, hipStream_t stream, const int* flags, int n, const int* sums_prev, const int* sums_cur, int sums_stride) {
   if (n_pairs <= 0) return hipSuccess;
@@ -693,57 +698,22 @@ hipError_t launch_sr_cols_seq(const float* zh_prev, const float* zh_cur, size_t 
   // a run longer than one pair walks cur(p) as prev(p + 1): only valid for a contiguous sequence
   if (run > 1 && zh_cur != zh_prev + zh_stride) return hipErrorInvalidValue;
   switch (res) {
-    case 200: return launch_cols_seq_n<200>(zh_prev, zh_cur, zh_stride, twiddles, Dt, n_pairs, run, flags, n, sums_prev, sums_cur, sums_stride, stream);
-    case 216: return launch_cols_seq_n<216>(zh_prev, zh_cur, zh_stride, twiddles, Dt, n_pairs, run, flags, n, sums_prev, sums_cur, sums_stride, stream);
-    case 240: return launch_cols_seq_n<240>(zh_prev, zh_cur, zh_stride, twiddles, Dt, n_pairs, run, flags, n, sums_prev, sums_cur, sums_stride, stream);
-    case 256: return launch_cols_seq_n<256>(zh_prev, zh_cur, zh_stride, twiddles, Dt, n_pairs, run, flags, n, sums_prev, sums_cur, sums_stride, stream);
-    case 250: return launch_cols_seq_n<250>(zh_prev, zh_cur, zh_stride, twiddles, Dt, n_pairs, run, flags, n, sums_prev, sums_cur, sums_stride, stream);
-    case 400: return launch_cols_seq_n<400>(zh_prev, zh_cur, zh_stride, twiddles, Dt, n_pairs, run, flags, n, sums_prev, sums_cur, sums_stride, stream);
-    case 432: return launch_cols_seq_n<432>(zh_prev, zh_cur, zh_stride, twiddles, Dt, n_pairs, run, flags, n, sums_prev, sums_cur, sums_stride, stream);
-    case 270: return launch_cols_seq_n<270>(zh_prev, zh_cur, zh_stride, twiddles, Dt, n_pairs, run, flags, n, sums_prev, sums_cur, sums_stride, stream);
-    case 300: return launch_cols_seq_n<300>(zh_prev, zh_cur, zh_stride, twiddles, Dt, n_pairs, run, flags, n, sums_prev, sums_cur, sums_stride, stream);
-    case 450: return launch_cols_seq_n<450>(zh_prev, zh_cur, zh_stride, twiddles, Dt, n_pairs, run, flags, n, sums_prev, sums_cur, sums_stride, stream);
-    case 288: return launch_cols_seq_n<288>(zh_prev, zh_cur, zh_stride, twiddles, Dt, n_pairs, run, flags, n, sums_prev, sums_cur, sums_stride, stream);
-    case 320: return launch_cols_seq_n<320>(zh_prev, zh_cur, zh_stride, twiddles, Dt, n_pairs, run, flags, n, sums_prev, sums_cur, sums_stride, stream);
-    case 360: return launch_cols_seq_n<360>(zh_prev, zh_cur, zh_stride, twiddles, Dt, n_pairs, run, flags, n, sums_prev, sums_cur, sums_stride, stream);
-    case 384: return launch_cols_seq_n<384>(zh_prev, zh_cur, zh_stride, twiddles, Dt, n_pairs, run, flags, n, sums_prev, sums_cur, sums_stride, stream);
-    case 480: return launch_cols_seq_n<480>(zh_prev, zh_cur, zh_stride, twiddles, Dt, n_pairs, run, flags, n, sums_prev, sums_cur, sums_stride, stream);
-    case 512: return launch_cols_seq_n<512>(zh_prev, zh_cur, zh_stride, twiddles, Dt, n_pairs, run, flags, n, sums_prev, sums_cur, sums_stride, stream);
-    case 225: return launch_cols_seq_n<225>(zh_prev, zh_cur, zh_stride, twiddles, Dt, n_pairs, run, flags, n, sums_prev, sums_cur, sums_stride, stream);
-    case 243: return launch_cols_seq_n<243>(zh_prev, zh_cur, zh_stride, twiddles, Dt, n_pairs, run, flags, n, sums_prev, sums_cur, sums_stride, stream);
-    case 375: return launch_cols_seq_n<375>(zh_prev, zh_cur, zh_stride, twiddles, Dt, n_pairs, run, flags, n, sums_prev, sums_cur, sums_stride, stream);
-    case 405: return launch_cols_seq_n<405>(zh_prev, zh_cur, zh_stride, twiddles, Dt, n_pairs, run, flags, n, sums_prev, sums_cur, sums_stride, stream);
-    case 625: return launch_cols_seq_n<625>(zh_prev, zh_cur, zh_stride, twiddles, Dt, n_pairs, run, flags, n, sums_prev, sums_cur, sums_stride, stream);
-    case 675: return launch_cols_seq_n<675>(zh_prev, zh_cur, zh_stride, twiddles, Dt, n_pairs, run, flags, n, sums_prev, sums_cur, sums_stride, stream);
-    case 729: return launch_cols_seq_n<729>(zh_prev, zh_cur, zh_stride, twiddles, Dt, n_pairs, run, flags, n, sums_prev, sums_cur, sums_stride, stream);
-    case 128: return launch_cols_seq_n<128>(zh_prev, zh_cur, zh_stride, twiddles, Dt, n_pairs, run, flags, n, sums_prev, sums_cur, sums_stride, stream);
-    case 96: return launch_cols_seq_n<96>(zh_prev, zh_cur, zh_stride, twiddles, Dt, n_pairs, run, flags, n, sums_prev, sums_cur, sums_stride, stream);
-    case 100: return launch_cols_seq_n<100>(zh_prev, zh_cur, zh_stride, twiddles, Dt, n_pairs, run, flags, n, sums_prev, sums_cur, sums_stride, stream);
-    case 108: return launch_cols_seq_n<108>(zh_prev, zh_cur, zh_stride, twiddles, Dt, n_pairs, run, flags, n, sums_prev, sums_cur, sums_stride, stream);
-    case 120: return launch_cols_seq_n<120>(zh_prev, zh_cur, zh_stride, twiddles, Dt, n_pairs, run, flags, n, sums_prev, sums_cur, sums_stride, stream);
-    case 150: return launch_cols_seq_n<150>(zh_prev, zh_cur, zh_stride, twiddles, Dt, n_pairs, run, flags, n, sums_prev, sums_cur, sums_stride, stream);
-    case 162: return launch_cols_seq_n<162>(zh_prev, zh_cur, zh_stride, twiddles, Dt, n_pairs, run, flags, n, sums_prev, sums_cur, sums_stride, stream);
-    case 144: return launch_cols_seq_n<144>(zh_prev, zh_cur, zh_stride, twiddles, Dt, n_pairs, run, flags, n, sums_prev, sums_cur, sums_stride, stream);
-    case 160: return launch_cols_seq_n<160>(zh_prev, zh_cur, zh_stride, twiddles, Dt, n_pairs, run, flags, n, sums_prev, sums_cur, sums_stride, stream);
-    case 180: return launch_cols_seq_n<180>(zh_prev, zh_cur, zh_stride, twiddles, Dt, n_pairs, run, flags, n, sums_prev, sums_cur, sums_stride, stream);
-    case 192: return launch_cols_seq_n<192>(zh_prev, zh_cur, zh_stride, twiddles, Dt, n_pairs, run, flags, n, sums_prev, sums_cur, sums_stride, stream);
-    case 324: return launch_cols_seq_n<324>(zh_prev, zh_cur, zh_stride, twiddles, Dt, n_pairs, run, flags, n, sums_prev, sums_cur, sums_stride, stream);
-    case 486: return launch_cols_seq_n<486>(zh_prev, zh_cur, zh_stride, twiddles, Dt, n_pairs, run, flags, n, sums_prev, sums_cur, sums_stride, stream);
-    case 500: return launch_cols_seq_n<500>(zh_prev, zh_cur, zh_stride, twiddles, Dt, n_pairs, run, flags, n, sums_prev, sums_cur, sums_stride, stream);
-    case 540: return launch_cols_seq_n<540>(zh_prev, zh_cur, zh_stride, twiddles, Dt, n_pairs, run, flags, n, sums_prev, sums_cur, sums_stride, stream);
-    case 576: return launch_cols_seq_n<576>(zh_prev, zh_cur, zh_stride, twiddles, Dt, n_pairs, run, flags, n, sums_prev, sums_cur, sums_stride, stream);
-    case 600: return launch_cols_seq_n<600>(zh_prev, zh_cur, zh_stride, twiddles, Dt, n_pairs, run, flags, n, sums_prev, sums_cur, sums_stride, stream);
-    case 640: return launch_cols_seq_n<640>(zh_prev, zh_cur, zh_stride, twiddles, Dt, n_pairs, run, flags, n, sums_prev, sums_cur, sums_stride, stream);
-    case 648: return launch_cols_seq_n<648>(zh_prev, zh_cur, zh_stride, twiddles, Dt, n_pairs, run, flags, n, sums_prev, sums_cur, sums_stride, stream);
-    case 720: return launch_cols_seq_n<720>(zh_prev, zh_cur, zh_stride, twiddles, Dt, n_pairs, run, flags, n, sums_prev, sums_cur, sums_stride, stream);
-    case 750: return launch_cols_seq_n<750>(zh_prev, zh_cur, zh_stride, twiddles, Dt, n_pairs, run, flags, n, sums_prev, sums_cur, sums_stride, stream);
-    case 768: return launch_cols_seq_n<768>(zh_prev, zh_cur, zh_stride, twiddles, Dt, n_pairs, run, flags, n, sums_prev, sums_cur, sums_stride, stream);
-    case 800: return launch_cols_seq_n<800>(zh_prev, zh_cur, zh_stride, twiddles, Dt, n_pairs, run, flags, n, sums_prev, sums_cur, sums_stride, stream);
-    case 810: return launch_cols_seq_n<810>(zh_prev, zh_cur, zh_stride, twiddles, Dt, n_pairs, run, flags, n, sums_prev, sums_cur, sums_stride, stream);
-    case 864: return launch_cols_seq_n<864>(zh_prev, zh_cur, zh_stride, twiddles, Dt, n_pairs, run, flags, n, sums_prev, sums_cur, sums_stride, stream);
-    case 900: return launch_cols_seq_n<900>(zh_prev, zh_cur, zh_stride, twiddles, Dt, n_pairs, run, flags, n, sums_prev, sums_cur, sums_stride, stream);
-    case 960: return launch_cols_seq_n<960>(zh_prev, zh_cur, zh_stride, twiddles, Dt, n_pairs, run, flags, n, sums_prev, sums_cur, sums_stride, stream);
+#define X(N) \
+  case N: return launch_cols_seq_n<N>(zh_prev, zh_cur, zh_stride, twiddles, Dt, n_pairs, run, flags, n, sums_prev, sums_cur, sums_stride, stream);
+    MOF_SR_SEQ_SIZES(X)
+#undef X
     default: return hipErrorInvalidValue;
+  }
+}
+
+// K6s's columns per wave at transform size res (seq_cw), 0 where it has no instantiation
+int sr_seq_columns_per_wave(int res) {
+  switch (res) {
+#define X(N) \
+  case N: return seq_cw<N>();
+    MOF_SR_SEQ_SIZES(X)
+#undef X
+    default: return 0;
   }
 }
 
