@@ -452,6 +452,47 @@ int mof_sr_logpolar_batch_device(mof_sr_engine* e, const uint8_t* d_src, size_t 
                                  int interpolation, uint8_t* d_dst, void* stream);
 
 /* ------------------------------------------------------------------------------------------ */
+/* Camera front end: scale_factor downscale, crop, gray (optic_flow.cpp:1603-1622)            */
+/* ------------------------------------------------------------------------------------------ */
+/* What the node does to every camera frame before processImage: cv::resize of the whole frame by the integer scale_factor
+ * (:1603-1607, INTER_LINEAR), the crop of :1609-1618 and cv::cvtColor(.., CV_RGB2GRAY) applied to BGR data (:1622). One streaming
+ * kernel (csrc/fe_kernel.hip) turns a batch of camera frames into gray crops that any entry taking gray frames consumes: the
+ * estimator, the long-range mode and the block matchers at any factor, the FFT engine at s > 1. (FFT-only callers at s = 1 keep the
+ * fused *_bgr entries, which convert inside the transform's own load and are faster.)
+ * Arithmetic: at an EXACT ratio (both camera sides divisible by s) OpenCV's 8-bit fixed-point resize reduces to closed forms,
+ * per channel -- odd s (1 included): the single tap src(s y + (s-1)/2, s x + (s-1)/2); even s: (a + b + c + d + 2) >> 2 over the
+ * 2 x 2 block at rows and columns s y + s/2 - 1 .. s y + s/2 (s = 2 is OpenCV's INTER_AREA fast path, the same formula) -- and
+ * 3-channel frames then go through gray = (c0*4899 + c1*9617 + c2*1868 + 8192) >> 14, byte 0 with the R weight, as the node
+ * applies CV_RGB2GRAY to BGR8 data. A mono8 camera needs no gray step. [published OpenCV algorithm, unpinned]. Non-integral
+ * ratios go through OpenCV's general bilinear path (float coefficients, a SIMD / scalar rounding split) and are not restated:
+ * MOF_ERR_UNSUPPORTED. */
+typedef struct mof_frontend_config {
+  int src_width, src_height;                   /* camera frame, pixels                                             */
+  int channels;                                /* 1 = mono8, 3 = BGR8 (CV_RGB2GRAY as the node applies it)         */
+  int scale;                                   /* integer scale_factor >= 1; src sides divisible by it when > 1     */
+  int crop_x, crop_y, crop_width, crop_height; /* in the downscaled image                                          */
+} mof_frontend_config;
+
+/* The node's own rectangle, with its integer truncations: fs' = frame_size / s (:867-869), dsize = (W / s, H / s) (:1604),
+ * xi = (int)cx - fs'/2, yi = (H / s)/2 - fs'/2 (:1611-1614), crop (xi, yi, fs', fs'). MOF_ERR_UNSUPPORTED at a non-integral
+ * ratio (checked first), MOF_ERR_BAD_ARG where the node throws: the crop leaves the scaled image. Note that the node centres
+ * the crop of the SCALED image on the UNSCALED principal point cx_ = K[2] (:1502, :1611), so at s >= 2 the crop leaves the
+ * image unless the principal point lies far left; callers who want a downscaled crop fill crop_* themselves, e.g. centred on
+ * cx / s. The processors' geometry stays the caller's: mof_fft_config_reference(&f, fs', sample_point_size / s, ..) (:871-874). */
+int mof_frontend_config_reference(mof_frontend_config* cfg, int cam_width, int cam_height, int channels, int scale_factor,
+                                  int frame_size, double cx);
+/* MOF_OK, MOF_ERR_BAD_ARG (channels not 1 / 3, scale < 1, an empty or outside crop) or MOF_ERR_UNSUPPORTED (non-integral ratio). */
+int mof_frontend_validate(const mof_frontend_config* cfg);
+/* n camera frames (frame i at d_src + i*src_stride, rows src_pitch >= channels * src_width bytes apart, any alignment) -> n
+ * crop_width x crop_height gray crops (crop i at d_dst + i*dst_stride, rows dst_pitch >= crop_width bytes apart). Stateless and
+ * asynchronous on `stream`; launches on the caller's CURRENT device and never changes it; allocates nothing, so it can be
+ * captured into a HIP graph. n = 0 is a no-op. MOF_ERR_BAD_ARG (nothing launched) for a bad config, null pointers, a pitch
+ * too small, output crops that overlap each other, or source and destination ranges that overlap; MOF_ERR_NO_DEVICE without a
+ * device. */
+int mof_frontend_batch_device(const mof_frontend_config* cfg, const uint8_t* d_src, size_t src_stride, size_t src_pitch, int n,
+                              uint8_t* d_dst, size_t dst_stride, size_t dst_pitch, void* stream);
+
+/* ------------------------------------------------------------------------------------------ */
 /* Geometry tail: per-patch shifts -> camera-frame velocity (OpticFlow::getRT / get2DT)       */
 /* ------------------------------------------------------------------------------------------ */
 /* The consumers of processImage / processImageLongRange in the node (optic_flow.cpp:1719 -> :515-774 getRT,

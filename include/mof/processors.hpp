@@ -378,6 +378,35 @@ class scaleRotationEstimator {
   int res_ = 0;
 };
 
+// The node's camera front end (optic_flow.cpp:1603-1622; include/mof.h, mof_frontend_*): cv::resize by the integer scale_factor,
+// the crop, CV_RGB2GRAY on BGR8 data -- camera frames on the device in, gray crops on the device out, for any processor that takes
+// gray frames. Stateless; launches on the caller's current device.
+class CameraFrontEnd {
+ public:
+  explicit CameraFrontEnd(const mof_frontend_config& cfg) : cfg_(cfg) { detail::check(mof_frontend_validate(&cfg_), "mof_frontend_validate"); }
+  // The node's own rectangle (:1611-1618, integer truncations included); throws where the node does (the crop leaves the scaled
+  // image: at s >= 2 it is centred on the UNSCALED cx_) and at a non-integral ratio.
+  static CameraFrontEnd reference(int cam_width, int cam_height, int channels, int scale_factor, int frame_size, double cx) {
+    mof_frontend_config c{};
+    detail::check(mof_frontend_config_reference(&c, cam_width, cam_height, channels, scale_factor, frame_size, cx),
+                  "mof_frontend_config_reference");
+    return CameraFrontEnd(c);
+  }
+  int outWidth() const { return cfg_.crop_width; }
+  int outHeight() const { return cfg_.crop_height; }
+  // n camera frames (d_src + i * src_stride, rows src_pitch bytes apart) -> n gray crops (d_dst + i * dst_stride, rows dst_pitch
+  // bytes apart). Asynchronous on `stream`.
+  void processBatchDevice(const uint8_t* d_src, size_t src_stride, size_t src_pitch, int n, uint8_t* d_dst, size_t dst_stride,
+                          size_t dst_pitch, void* stream = nullptr) const {
+    detail::check(mof_frontend_batch_device(&cfg_, d_src, src_stride, src_pitch, n, d_dst, dst_stride, dst_pitch, stream),
+                  "mof_frontend_batch_device");
+  }
+  const mof_frontend_config& config() const { return cfg_; }
+
+ private:
+  mof_frontend_config cfg_{};
+};
+
 }  // namespace mof
 
 // ------------------------------------------------------------------------------------------------

@@ -52,6 +52,11 @@ class BmConfig(C.Structure):
                 ("low_contrast_rule", C.c_int), ("device", C.c_int)]
 
 
+class FrontendConfig(C.Structure):
+    _fields_ = [("src_width", C.c_int), ("src_height", C.c_int), ("channels", C.c_int), ("scale", C.c_int),
+                ("crop_x", C.c_int), ("crop_y", C.c_int), ("crop_width", C.c_int), ("crop_height", C.c_int)]
+
+
 # every symbol include/mof.h declares: (name, restype, argtypes)
 _VP, _SZ, _I = C.c_void_p, C.c_size_t, C.c_int
 SYMBOLS = {
@@ -129,6 +134,9 @@ SYMBOLS = {
     "mof_sr_process_sequence_device": (_I, [_VP, _VP, _SZ, _SZ, _I, _VP, _VP, C.POINTER(_I)]),
     "mof_sr_process_sequence_host": (_I, [_VP, _VP, _SZ, _SZ, _I, _VP, C.POINTER(_I)]),
     "mof_sr_logpolar_batch_device": (_I, [_VP, _VP, _SZ, _SZ, _I, _I, _VP, _VP]),
+    "mof_frontend_config_reference": (_I, [C.POINTER(FrontendConfig), _I, _I, _I, _I, _I, C.c_double]),
+    "mof_frontend_validate": (_I, [C.POINTER(FrontendConfig)]),
+    "mof_frontend_batch_device": (_I, [C.POINTER(FrontendConfig), _VP, _SZ, _SZ, _I, _VP, _SZ, _SZ, _VP]),
     "mof_geom_layout_reference": (_I, [_VP, _I, _I]),
     "mof_geom_undistort_points": (_I, [_VP, C.c_double, _VP, _I, _VP]),
     "mof_geom_find_homography": (_I, [_VP, _VP, _I, _VP, _VP, C.POINTER(_I)]),

@@ -244,4 +244,18 @@ std::vector<uint32_t> sr_fused_fragments(int res);
 hipError_t launch_sr_cols_fused(const uint8_t* lp_prev, const uint8_t* lp_cur, size_t lp_stride, const uint32_t* frags,
                                 const float* twiddles, float* Dt, int res, int n_pairs, int run, hipStream_t stream);
 
+// ---- the camera front end (fe_kernel.hip): cv::resize by an exact integer factor, crop, CV_RGB2GRAY -> gray crops ----
+struct FeArgs {
+  const uint8_t* src;      // device, frame f at src + f * src_stride, rows src_pitch bytes apart, CH bytes per pixel
+  size_t src_stride, src_pitch;
+  uint8_t* dst;            // device, frame f at dst + f * dst_stride, rows dst_pitch bytes apart
+  size_t dst_stride, dst_pitch;
+  int scale;               // integer downscale factor s >= 1 (the source sides divisible by it)
+  int crop_x, crop_y, crop_w, crop_h;  // in the downscaled image
+  unsigned total;          // lanes of one launch (set by the launcher)
+};
+int frontend_run_pixels(int channels, int scale);  // output pixels per lane
+// channels 1 or 3; lanes per frame = crop_h * ceil(crop_w / frontend_run_pixels) must stay <= 2^31
+hipError_t launch_frontend(const FeArgs& a, int channels, int n_frames, hipStream_t stream);
+
 }  // namespace mof

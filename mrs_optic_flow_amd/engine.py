@@ -16,7 +16,7 @@ import ctypes as C
 import numpy as np
 
 from . import _capi
-from ._capi import BmConfig, FftConfig, SrConfig, check
+from ._capi import BmConfig, FftConfig, FrontendConfig, SrConfig, check
 
 
 def _np_u8(frame) -> np.ndarray:
@@ -565,3 +565,61 @@ class ScaleRotationEstimator:
             self.close()
         except Exception:
             pass
+
+
+class CameraFrontEnd:
+    """The node's camera front end (/root/reference/src/optic_flow.cpp:1603-1622): cv::resize of the whole camera frame by the
+    integer ``scale`` (INTER_LINEAR, exact ratios only), the ``crop`` = (x, y, width, height) of the downscaled image and, for
+    3-channel frames, CV_RGB2GRAY as the node applies it to BGR8 data (include/mof.h, mof_frontend_*). ``camera_shape`` = (H, W);
+    ``crop=None`` keeps the whole downscaled image. The output feeds any processor that takes gray frames. Stateless."""
+
+    def __init__(self, camera_shape: tuple[int, int], channels: int = 3, scale: int = 1,
+                 crop: tuple[int, int, int, int] | None = None):
+        h, w = camera_shape
+        s = int(scale)
+        if crop is None:
+            crop = (0, 0, w // s if s > 0 else 0, h // s if s > 0 else 0)
+        self._lib = _capi.load()
+        self.cfg = FrontendConfig(int(w), int(h), int(channels), s, *(int(v) for v in crop))
+        check(self._lib.mof_frontend_validate(C.byref(self.cfg)))
+
+    @classmethod
+    def reference(cls, camera_shape: tuple[int, int], channels: int, scale_factor: int, frame_size: int, cx: float) -> "CameraFrontEnd":
+        """The node's own rectangle (mof_frontend_config_reference): crop (int(cx) - fs'/2, (H/s)/2 - fs'/2, fs', fs'), fs' =
+        frame_size / s. Raises MofError(MOF_ERR_BAD_ARG) where the node throws -- at s >= 2 it centres the crop on the UNSCALED
+        principal point -- and MofError(MOF_ERR_UNSUPPORTED) at a non-integral ratio."""
+        h, w = camera_shape
+        cfg = FrontendConfig()
+        check(_capi.load().mof_frontend_config_reference(C.byref(cfg), int(w), int(h), int(channels), int(scale_factor),
+                                                          int(frame_size), float(cx)))
+        return cls((h, w), cfg.channels, cfg.scale, (cfg.crop_x, cfg.crop_y, cfg.crop_width, cfg.crop_height))
+
+    @property
+    def crop(self) -> tuple[int, int, int, int]:
+        return (self.cfg.crop_x, self.cfg.crop_y, self.cfg.crop_width, self.cfg.crop_height)
+
+    @property
+    def out_shape(self) -> tuple[int, int]:
+        return (self.cfg.crop_height, self.cfg.crop_width)
+
+    def process_batch_device(self, frames, out=None, stream=None):
+        """frames: torch uint8 [n, H, W] (mono8) or [n, H, W, 3] (BGR8, pixel stride 3) on a GPU, any row pitch and frame stride
+        -> uint8 [n, crop_height, crop_width] on the same device (``out``: any such tensor with dense rows). Asynchronous on the
+        device's current stream (or ``stream``), run under that device's context."""
+        import torch
+
+        dev = frames.device if isinstance(frames, torch.Tensor) else None
+        _check_device_batch(frames, frames, (self.cfg.src_height, self.cfg.src_width), dev.index if dev is not None else -1,
+                            channels=self.cfg.channels)
+        n = frames.shape[0]
+        ch, cw = self.out_shape
+        if out is None:
+            out = torch.empty((n, ch, cw), dtype=torch.uint8, device=dev)
+        if not (isinstance(out, torch.Tensor) and out.is_cuda and out.device == dev and out.dtype == torch.uint8
+                and tuple(out.shape) == (n, ch, cw) and out.stride(2) == 1 and out.stride(1) >= cw and out.stride(0) >= 0):
+            raise ValueError(f"out must be a uint8 [{n}, {ch}, {cw}] tensor with dense rows on {dev}")
+        with torch.cuda.device(dev):
+            s = stream if stream is not None else torch.cuda.current_stream(dev)
+            check(self._lib.mof_frontend_batch_device(C.byref(self.cfg), frames.data_ptr(), frames.stride(0), frames.stride(1), n,
+                                                      out.data_ptr(), out.stride(0), out.stride(1), _stream_ptr(s)))
+        return out
