@@ -119,13 +119,17 @@ typedef struct mof_fft_engine mof_fft_engine;
  * every other N with M <= 135 ("planned", csrc/pc_kernel_generic.hip); a planned pipeline through HBM scratch for larger patches up to
  * M = 960 ("planned-large", csrc/pc_large_kernel.hip; r06: at every M from 200 to 960, even or odd, the transforms inside it are the
  * scale / rotation estimator's tuned in-register ones (csrc/sr_seq_kernel.hip: the row kernel zero-pads, 250 / 400 / 432 take their
- * real-only spectrum slots from exact integer pixel sums); the planned transforms remain for the long-range mode and as the A/B form). mof_fft_create fails with MOF_ERR_UNSUPPORTED
- * only beyond that, and for MOF_PEAK_OCL on sizes the reference's OpenCL branch cannot plan either (odd, not 5-smooth) or M > 135.
+ * real-only spectrum slots from exact integer pixel sums); the planned transforms remain for the long-range mode and as the A/B form).
+ * MOF_PEAK_OCL serves every even 2^a 3^b 5^c patch size up to 960 -- what the reference's OpenCL branch plans, never padded
+ * (FftMethod.cpp:481-539, :787-816) --, from 136 on through the planned transforms of "planned-large". mof_fft_create fails with
+ * MOF_ERR_UNSUPPORTED only beyond M = 960, and for MOF_PEAK_OCL on sizes the reference's OpenCL branch cannot plan either (odd, not
+ * 5-smooth).
  * The large-patch pipeline owns scratch (three half-spectrum planes per patch pair of a pass); it grows with the first batch
  * that needs more -- never inside a HIP graph capture: run the largest batch once before capturing. */
 int mof_fft_create(const mof_fft_config* cfg, mof_fft_engine** out);
 /* Diagnostics: name of the kernel formulation the engine launches for cv::phaseCorrelate-model batches on full-resolution frames:
  * "stockham" (pc_kernel.hip / pc_kernel_mixed.hip), "planned-half", "planned" or "planned-large" (above) in the product library;
+ * MOF_PEAK_OCL engines name theirs the same way ("planned-large" for every patch size from 136 on);
  * "quad" only in the A/B build csrc/ab/libmof_hip_quad.so with MOF_PC_QUAD=1 (pc_kernel_quad.hip, a measured-slower alternative kept
  * for comparison, not shipped). MOF_FFT_HALF=0 / 1 (environment, read once) keeps every size off / forces the instantiated sizes
  * onto the half-tile kernel (A/B and the tests of either family). */

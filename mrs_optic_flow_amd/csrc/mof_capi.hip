@@ -206,7 +206,8 @@ bool fft_route(const mof_fft_config& c, mof::PcPlan* plan, FftRoute* r) {
     // of padded constant patches from the row kernel's flags. Unpadded patches of 240 / 256 / 480 pixels (the reference's whole-frame
     // fallback among them, FftMethod.cpp:1709-1716) run them 2.5 x faster than the planned kernels, same Zh / Dt / candidate formats.
     bool exact = true;
-    r->large_tuned = k.large_tuned && m >= 200 && mof::sr_transform_size_tuned(m, &exact);
+    // MOF_PEAK_OCL (never padded) keeps L5 - L8, whose PK = 1 forms carry its model (the tuned K6s / K7 have cv::phaseCorrelate's only)
+    r->large_tuned = ocv && k.large_tuned && m >= 200 && mof::sr_transform_size_tuned(m, &exact);
     r->odd_tail = r->large_tuned && !exact;
     r->large_video = r->large_tuned && k.large_video;
   }
@@ -351,6 +352,8 @@ static int launch_large(mof_fft_engine* e, const mof::PcArgs& a, int n_pairs, hi
   f.max_px_speed_sq = a.max_px_speed_sq;
   f.flags = e->d_flags;
   f.cdc = e->d_cdc;
+  f.peak_model = e->cfg.peak_model;
+  f.search_radius = e->cfg.search_radius;
   const int per_pass = e->cap / patches;
   for (int k0 = 0; k0 < n_pairs; k0 += per_pass) {
     const int np = n_pairs - k0 < per_pass ? n_pairs - k0 : per_pass, nq = np * patches;
@@ -377,7 +380,7 @@ static int launch_large(mof_fft_engine* e, const mof::PcArgs& a, int n_pairs, hi
       HIP_TRY(mof::launch_pcl_cdc(zh_prev, zh_cur, zh_stride, e->plan.m, e->d_cdc, nq, s));
       HIP_TRY(mof::launch_sr_rows_inv(e->d_dt, e->d_twiddles, e->d_cand, e->plan.m, nq, s));
     } else {
-      HIP_TRY(mof::launch_pcl_cols(zh_prev, zh_cur, zh_stride, e->plan, e->d_twiddles, e->d_dt, e->d_cdc, e->d_flags, nq, s));
+      HIP_TRY(mof::launch_pcl_cols(zh_prev, zh_cur, zh_stride, e->plan, e->d_twiddles, e->d_dt, e->d_cdc, e->d_flags, nq, s, e->cfg.peak_model));
     }
     f.out = a.out + (size_t)k0 * patches * 2;
     HIP_TRY(mof::launch_pcl_peak(f, e->plan, nq, s, tuned));
@@ -482,19 +485,17 @@ static int validate_fft(const mof_fft_config* c) {
     // cv::phaseCorrelate pads to, M = getOptimalDFTSize(N)
     mof::PcPlan plan;
     if (!mof::pc_build_plan(c->patch_size, &plan)) {
-      // the padded patch does not fit one CU's LDS (M > 135): the planned pipeline through HBM scratch (pc_large_kernel.hip)
+      // the padded patch does not fit one CU's LDS (M > 135): the planned pipeline through HBM scratch (pc_large_kernel.hip), both
+      // peak models
       if (!mof::pc_build_line_plan(c->patch_size, &plan))
         return fail(MOF_ERR_UNSUPPORTED, "patch_size %d pads to %d: beyond the planned transforms (<= 960)", c->patch_size,
                     mof::pc_optimal_dft_size(c->patch_size));
-      if (c->peak_model == MOF_PEAK_OCL)
-        return fail(MOF_ERR_UNSUPPORTED, "peak_model MOF_PEAK_OCL is available for patches that fit one CU (padded size <= 135); "
-                    "patch_size %d runs the cv::phaseCorrelate model only", c->patch_size);
     }
     // useOCL=true plans radix-{2,3,4,5,8} passes for the patch size itself and never pads (FftMethod.cpp:481-539, :787-816):
     // sizes with another prime factor have no OpenCL plan in the reference either; its CCS packing assumes an even size
     if (c->peak_model == MOF_PEAK_OCL && (plan.m != plan.n || (plan.n & 1)))
-      return fail(MOF_ERR_UNSUPPORTED, "peak_model MOF_PEAK_OCL needs an even patch_size of the form 2^a 3^b 5^c (the reference's "
-                  "OpenCL branch cannot plan %d either)", c->patch_size);
+      return fail(MOF_ERR_UNSUPPORTED, "peak_model MOF_PEAK_OCL needs an even patch_size of the form 2^a 3^b 5^c, up to 960 (the "
+                  "reference's OpenCL branch cannot plan %d either)", c->patch_size);
   }
   if (c->origin_x + (long)(c->grid_x - 1) * c->stride_x + c->patch_size > c->frame_width ||
       c->origin_y + (long)(c->grid_y - 1) * c->stride_y + c->patch_size > c->frame_height)

@@ -79,16 +79,18 @@ struct PclFinal {
   double* out;
   const int* flags;        // mode 1, nullable: [2 pairs] constant-patch flags written by pcl_rows (bit 0: not constant, bit 1: pixel 0 != 0)
   const float* cdc;        // mode 1, with flags: [pairs] DC bin of the cross-power spectrum
+  int peak_model;          // mode 1: 0 = cv::phaseCorrelate, 1 = the OpenCL kernel's model (m == n; L7 + L8 of the planned pipeline only)
+  int search_radius;       // peak_model 1
 };
 size_t pcl_zh_floats(const PcPlan& pl);  // floats of one image's row half-spectra Zh: (m/2 + 1) * m complex
 int pcl_candidates(const PcPlan& pl);    // peak candidates per pair
 // L5: images -> Zh (image f at zh + f * zh_stride floats); flags (nullable, ZEROED by the caller): 1 int per image
 hipError_t launch_pcl_rows(const PclSrc& src, const PcPlan& pl, const float* twiddles, float* zh, size_t zh_stride, int* flags,
                            int n_images, int channels, int downscale, hipStream_t stream);
-// L6: pair p = (cur: zh_cur + p * zh_stride, prev: zh_prev + p * zh_stride) -> Dt[p]; cdc nullable
+// L6: pair p = (cur: zh_cur + p * zh_stride, prev: zh_prev + p * zh_stride) -> Dt[p]; cdc nullable; peak_model as PclFinal
 hipError_t launch_pcl_cols(const float* zh_prev, const float* zh_cur, size_t zh_stride, const PcPlan& pl, const float* twiddles,
-                           float* Dt, float* cdc, const int* flags, int n_pairs, hipStream_t stream);
-// L7 + L8 (a.Dt, a.cand, a.twiddles, a.mode, a.out [, a.M_log | a.max_px_speed_sq, a.flags, a.cdc])
+                           float* Dt, float* cdc, const int* flags, int n_pairs, hipStream_t stream, int peak_model = 0);
+// L7 + L8 (a.Dt, a.cand, a.twiddles, a.mode, a.out [, a.M_log | a.max_px_speed_sq, a.flags, a.cdc, a.peak_model, a.search_radius])
 hipError_t launch_pcl_peak(const PclFinal& a, const PcPlan& pl, int n_pairs, hipStream_t stream, bool candidates_done = false);
 // C_dc of every pair from its row spectra (for pipelines whose column kernel does not hand it out)
 hipError_t launch_pcl_cdc(const float* zh_prev, const float* zh_cur, size_t zh_stride, int m, float* cdc, int n_pairs, hipStream_t stream);

@@ -467,6 +467,11 @@ __device__ __forceinline__ float ocl_scale_mask(float v, int y, int x, int sr) {
   const bool masked = (y > sr && y < N - sr) || (x > sr && x < N - sr);
   return masked ? 0.f : v * (1.0f / (float)(N * N));
 }
+// ... at a run-time size m (the large-patch pipeline, pc_large_kernel.hip); scale = 1.0f / (float)(m * m), hoisted by the caller
+__device__ __forceinline__ float ocl_scale_mask(float v, int y, int x, int sr, int m, float scale) {
+  const bool masked = (y > sr && y < m - sr) || (x > sr && x < m - sr);
+  return masked ? 0.f : v * scale;
+}
 
 }  // namespace
 }  // namespace mof

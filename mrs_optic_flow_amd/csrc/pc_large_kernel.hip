@@ -18,6 +18,8 @@
 //   L8 pcl_final    : first-maximum reduction, the 5 x 5 window re-evaluated from Dt in fp64 (as K8, sr_kernel.hip), centroid;
 //                     then EITHER pt -> (scale, rot) with the estimator's gate (scaleRotationEstimator.cpp:119-124) OR
 //                     shift = -pt with FftMethod's gate (FftMethod.cpp:1838-1856, against samplePointSize / 2 -- unpadded).
+// FftMethod under useOCL=true (MOF_PEAK_OCL: even 5-smooth patches, never padded) runs the PK = 1 forms of L6 - L8: the OpenCL kernel's
+// normalisation, its scaled and +-search_radius-masked surface in L7's scan and L8's 7 x 7 positive-only window (pc_common.hpp).
 // Scratch per image: Zh = NU M complex; per pair: Dt = NU M complex (HBM; the caller owns and sizes it).
 
 #include <hip/hip_runtime.h>
@@ -185,7 +187,7 @@ __global__ void __launch_bounds__(PCL_T) pcl_rows_kernel(PclSrc src, PcPlan pl, 
 }
 
 // ---- L6 ------------------------------------------------------------------------------------------------------------------
-template <bool EXACT>
+template <bool EXACT, int PK>
 __global__ void __launch_bounds__(PCL_T) pcl_cols_kernel(const float* __restrict__ zh_prev, const float* __restrict__ zh_cur,
                                                          size_t zh_stride, PcPlan pl, const float* __restrict__ twiddles,
                                                          float* __restrict__ Dt, float* __restrict__ cdc, const int* __restrict__ flags,
@@ -236,12 +238,13 @@ __global__ void __launch_bounds__(PCL_T) pcl_cols_kernel(const float* __restrict
   // the in-LDS planned kernel (pc_kernel_generic.hip, box_zeros).
   // r05: the box's exact zeros are ALL the lines k != 0 with k n = 0 (mod m) -- the multiples of zq (pc_common.hpp, box_zero_period) --, the
   // Nyquist line alone for most sizes but e.g. every multiple of 50 for 196 in 200
-  const bool box_zeros = flags && m > pl.n && (((flags[2 * pair] & 1) == 0) || ((flags[2 * pair + 1] & 1) == 0));
+  // (PK = 1: the OpenCL model never pads, m == n, and a constant patch is NaN in L8 whatever its bins hold)
+  const bool box_zeros = PK == 0 && flags && m > pl.n && (((flags[2 * pair] & 1) == 0) || ((flags[2 * pair + 1] & 1) == 0));
   const int zq = box_zero_period(pl.n, m);
   for (int v0 = 0; v0 < m; v0 += 64) {
     const int v = v0 + lane, vv = v < m ? v : m - 1;  // (lanes past the line repeat its last bin: cross_power_ab's wave-uniform
     const cf a = lds_read(&z[sk(vv)]), b = lds_read(&z[line + sk(vv)]);  //  branch wants every lane to take part)
-    cf C = cross_power_ab(a, b, u_edge && (vv == 0 || (even && vv == hu)));
+    cf C = cross_power_ab<PK>(a, b, u_edge && (vv == 0 || (even && vv == hu)));
     if (box_zeros && (box_zero_line(u, zq) || box_zero_line(vv, zq))) C = {0.f, 0.f};
     if (v < m) z[sk(v)] = {C.x, -C.y};
     if (cdc && u == 0 && v == 0) cdc[pair] = C.x;  // C_dc: all that is left of a degenerate pair's spectrum (pc_common.hpp)
@@ -273,9 +276,9 @@ __global__ void __launch_bounds__(64) pcl_cdc_kernel(const float* __restrict__ z
 }
 
 // ---- L7 ------------------------------------------------------------------------------------------------------------------
-template <bool EXACT>
+template <bool EXACT, int PK>
 __global__ void __launch_bounds__(PCL_T) pcl_rows_inv_kernel(const float* __restrict__ Dt, PcPlan pl, const float* __restrict__ twiddles,
-                                                             float2* __restrict__ cand, int n_cand, int line) {
+                                                             float2* __restrict__ cand, int n_cand, int line, int search_radius) {
   extern __shared__ __attribute__((aligned(16))) unsigned char pcl_lds[];
   cf* z = reinterpret_cast<cf*>(pcl_lds);  // [PCL_LINES][line]
   cf* tw = z + PCL_LINES * line;
@@ -314,14 +317,17 @@ __global__ void __launch_bounds__(PCL_T) pcl_rows_inv_kernel(const float* __rest
     if (2 * (p0 + 2 * wave + ll) < m) ++nl;
   const Walk w = {line, 1, 0, ~0, 0};
   if (nl > 0) pass_lines<EXACT>(z, tw, pl, w, 2 * wave, nl, lane, false);
-  // first maximum of the fft-shifted surface (fftShift: index i -> (i + (m >> 1)) mod m for even and odd m; minMaxLoc)
+  // first maximum of the fft-shifted surface (fftShift: index i -> (i + (m >> 1)) mod m for even and odd m; minMaxLoc); PK = 1 scans the
+  // OpenCL kernel's surface: scaled by 1 / m^2, masked values read as 0 and take part (pc_common.hpp, ocl_scale_mask; as pc_kernel_generic.hip)
+  const float ocl_scale = 1.0f / (float)(m * m);
   Best best = {-__builtin_huge_valf(), 0x7fffffff};
   for (int ll = 0; ll < nl; ++ll) {
     const int l = 2 * wave + ll, y1 = 2 * (p0 + l), y2 = y1 + 1;
     const int r1 = (y1 + H >= m ? y1 + H - m : y1 + H) * m, r2 = (y2 + H >= m ? y2 + H - m : y2 + H) * m;
     for (int x = lane; x < m; x += 64) {
       const int xs = x + H >= m ? x + H - m : x + H;
-      const cf v = z[l * line + sk(x)];
+      cf v = z[l * line + sk(x)];
+      if constexpr (PK == 1) v = {ocl_scale_mask(v.x, y1, x, search_radius, m, ocl_scale), ocl_scale_mask(v.y, y2, x, search_radius, m, ocl_scale)};
       best = better(best, Best{v.x, r1 + xs});
       if (y2 < m) best = better(best, Best{v.y, r2 + xs});
     }
@@ -340,10 +346,14 @@ __global__ void __launch_bounds__(PCL_T) pcl_rows_inv_kernel(const float* __rest
 }
 
 // ---- L8 ------------------------------------------------------------------------------------------------------------------
-// The 25 window values are re-evaluated from the half spectrum of their rows (Dt), in double, as K8 (sr_kernel.hip) does:
+// The W x W window values (W = 5, PK = 1: 7) are re-evaluated from the half spectrum of their rows (Dt), in double, as K8 (sr_kernel.hip) does:
 //   S[y][x] = Re G[y][0] + [M even: (-1)^x Re G[y][M/2]] + 2 sum_{u=1}^{(M-1)/2} Re(G[y][u] W^{ux})
+// PK = 1 (mode 1 only): each value cast to float, scaled and masked as L7 scanned it, values <= 0 dropped, the sum seeded with FLT_EPSILON
+// (pc_common.hpp, PeakModel / centroid_gate_store); a constant patch has no finite surface (1 / 0 in a real-only slot) and gives NaN.
+template <int PK>
 __global__ void __launch_bounds__(64) pcl_final_kernel(PclFinal a) {
-  __shared__ double part[25][65];
+  constexpr int RAD = PeakModel<PK>::RAD, W = PeakModel<PK>::W, WW = W * W;
+  __shared__ double part[WW][65];
   const int m = a.m, H = m >> 1;
   const bool even = (m & 1) == 0;
   const int umax = even ? H - 1 : H;
@@ -361,52 +371,56 @@ __global__ void __launch_bounds__(64) pcl_final_kernel(PclFinal a) {
   const cf* Dt = reinterpret_cast<const cf*>(a.Dt) + (size_t)pair * (H + 1) * m;
   const bool have = best.idx != 0x7fffffff;
   const int px = have ? best.idx % m : 0, py = have ? best.idx / m : 0;
-  int wy[5], wx[5];  // window rows / columns in un-shifted coordinates
+  int wy[W], wx[W];  // window rows / columns in un-shifted coordinates
 #pragma unroll
-  for (int k = 0; k < 5; ++k) {
-    wy[k] = ((((py - 2 + k) % m) + m) % m - H + m) % m;
-    wx[k] = ((((px - 2 + k) % m) + m) % m - H + m) % m;
+  for (int k = 0; k < W; ++k) {
+    wy[k] = ((((py - RAD + k) % m) + m) % m - H + m) % m;
+    wx[k] = ((((px - RAD + k) % m) + m) % m - H + m) % m;
   }
-  double acc[25];
+  double acc[WW];
 #pragma unroll
-  for (int k = 0; k < 25; ++k) acc[k] = 0.0;
+  for (int k = 0; k < WW; ++k) acc[k] = 0.0;
   for (int u = 1 + lane; u <= umax; u += 64) {
-    cf f[5];
+    cf f[W];
 #pragma unroll
-    for (int r = 0; r < 5; ++r) f[r] = Dt[(size_t)u * m + wy[r]];
+    for (int r = 0; r < W; ++r) f[r] = Dt[(size_t)u * m + wy[r]];
 #pragma unroll
-    for (int c = 0; c < 5; ++c) {
+    for (int c = 0; c < W; ++c) {
       const float2 w = *reinterpret_cast<const float2*>(a.twiddles + 2 * (int)(((long)u * wx[c]) % m));  // (cos, -sin)
 #pragma unroll
-      for (int r = 0; r < 5; ++r) acc[r * 5 + c] += (double)f[r].x * (double)w.x - (double)f[r].y * (double)w.y;
+      for (int r = 0; r < W; ++r) acc[r * W + c] += (double)f[r].x * (double)w.x - (double)f[r].y * (double)w.y;
     }
   }
 #pragma unroll
-  for (int k = 0; k < 25; ++k) part[k][lane] = acc[k];
+  for (int k = 0; k < WW; ++k) part[k][lane] = acc[k];
   __syncthreads();
-  const int ys = py - 2 + lane / 5, xs = px - 2 + lane % 5;
+  const int ys = py - RAD + lane / W, xs = px - RAD + lane % W;
   double cx = 0.0, cy = 0.0, sum = 0.0;
-  if (have && lane < 25 && ys >= 0 && ys <= m - 1 && xs >= 0 && xs <= m - 1) {  // window clamped to the (padded) image
-    const int y = wy[lane / 5], x = wx[lane % 5];
+  if (have && lane < WW && ys >= 0 && ys <= m - 1 && xs >= 0 && xs <= m - 1) {  // window clamped to the (padded) image
+    const int y = wy[lane / W], x = wx[lane % W];
     double s2 = 0.0;
     for (int l = 0; l < 64; ++l) s2 += part[lane][l];
     double s0 = (double)Dt[y].x;
     if (even) s0 += ((x & 1) ? -1.0 : 1.0) * (double)Dt[(size_t)H * m + y].x;
-    const double val = (double)(float)(s0 + 2.0 * s2);  // the surface is CV_32F
+    double val = (double)(float)(s0 + 2.0 * s2);  // the surface is CV_32F
+    if constexpr (PK == 1) {
+      const float v = ocl_scale_mask((float)val, y, x, a.search_radius, m, 1.0f / (float)(m * m));
+      val = v > 0.f ? (double)v : 0.0;
+    }
     cx = (double)xs * val;
     cy = (double)ys * val;
     sum = val;
   }
 #pragma unroll
-  for (int off = 16; off > 0; off >>= 1) {
+  for (int off = WW > 32 ? 32 : 16; off > 0; off >>= 1) {
     cx += __shfl_xor(cx, off, 64);
     cy += __shfl_xor(cy, off, 64);
     sum += __shfl_xor(sum, off, 64);
   }
   if (lane != 0) return;
-  sum += 2.220446049250313e-16;  // DBL_EPSILON, FftMethod.cpp:1378
+  sum += PK == 1 ? 1.1920928955078125e-07 : 2.220446049250313e-16;  // FLT_EPSILON cl:1342 / DBL_EPSILON, FftMethod.cpp:1378
   const double half_m = (double)m / 2.0;  // cv::phaseCorrelate's centre: that of the PADDED image
-  if (a.mode == 0) {
+  if (PK == 0 && a.mode == 0) {
     // scaleRotationEstimator: pt = center - t, NOT negated (:117); |pt.x| > resolution / 2 (int division) -> (1, 0) (:119-121)
     const double ptx = half_m - cx / sum, pty = half_m - cy / sum;
     double scale = 1.0, rot = 0.0;
@@ -420,7 +434,8 @@ __global__ void __launch_bounds__(64) pcl_final_kernel(PclFinal a) {
     o[2] = ptx;
     o[3] = pty;
   } else {
-    // FftMethod: shift = -cv::phaseCorrelate(cur, prev) = t - M/2 (:1836), gate against samplePointSize / 2 (:1838-1856)
+    // FftMethod: shift = -cv::phaseCorrelate(cur, prev) = t - M/2 (:1836); the OpenCL branch returns t - M/2 un-negated (:1833) -- the
+    // same number; gate against samplePointSize / 2 (:1838-1856)
     double sx = cx / sum - half_m, sy = cy / sum - half_m;
     bool degenerate = false;
     if (a.flags) {  // a constant patch (pc_common.hpp, degenerate pairs); padded, only the all-zero patch stays constant
@@ -429,8 +444,12 @@ __global__ void __launch_bounds__(64) pcl_final_kernel(PclFinal a) {
       degenerate = m == a.n ? (cc || pc) : ((cc && (fc & 2) == 0) || (pc && (fp & 2) == 0));
     }
     if (degenerate) {
-      const double c9 = 9.0 * (double)a.cdc[pair];
-      sx = sy = (c9 > 0.0 ? c9 / (c9 + 2.220446049250313e-16) : 0.0) - half_m;
+      if constexpr (PK == 1) {
+        sx = sy = __builtin_nan("");  // 1 / (a b) with b = 0 in the other real-only slots (cl:1029): no finite surface
+      } else {
+        const double c9 = 9.0 * (double)a.cdc[pair];
+        sx = sy = (c9 > 0.0 ? c9 / (c9 + 2.220446049250313e-16) : 0.0) - half_m;
+      }
     }
     const double half_n = (double)a.n / 2.0;
     const bool bad = (sx * sx + sy * sy > a.max_px_speed_sq) || (fabs(sx) > half_n) || (fabs(sy) > half_n) || (sx != sx) ||
@@ -531,23 +550,21 @@ hipError_t launch_pcl_rows(const PclSrc& src, const PcPlan& pl, const float* twi
 }
 
 hipError_t launch_pcl_cols(const float* zh_prev, const float* zh_cur, size_t zh_stride, const PcPlan& pl, const float* twiddles,
-                           float* Dt, float* cdc, const int* flags, int n_pairs, hipStream_t stream) {
+                           float* Dt, float* cdc, const int* flags, int n_pairs, hipStream_t stream, int peak_model) {
   if (n_pairs <= 0) return hipSuccess;
+  if (peak_model != 0 && peak_model != 1) return hipErrorInvalidValue;
   const int line = pcl_line(pl.m), NU = (pl.m >> 1) + 1;
   const size_t lds = pcl_lds_bytes(pl.m);
   const bool ex = needs_exact(pl);
-  hipError_t e = ex ? allow_lds(&pcl_cols_kernel<true>, lds) : allow_lds(&pcl_cols_kernel<false>, lds);
+  auto kernel = peak_model == 1 ? (ex ? &pcl_cols_kernel<true, 1> : &pcl_cols_kernel<false, 1>)
+                                : (ex ? &pcl_cols_kernel<true, 0> : &pcl_cols_kernel<false, 0>);
+  hipError_t e = allow_lds(kernel, lds);
   if (e != hipSuccess) return e;
   for (int p0 = 0; p0 < n_pairs; p0 += 65535) {
     const int np = n_pairs - p0 < 65535 ? n_pairs - p0 : 65535;
-    if (ex)
-      hipLaunchKernelGGL(pcl_cols_kernel<true>, dim3((unsigned)((NU + 3) / 4), (unsigned)np), dim3(PCL_T), lds, stream,
-                         zh_prev + (size_t)p0 * zh_stride, zh_cur + (size_t)p0 * zh_stride, zh_stride, pl, twiddles,
-                         Dt + (size_t)p0 * NU * pl.m * 2, cdc ? cdc + p0 : nullptr, flags ? flags + 2 * (size_t)p0 : nullptr, line);
-    else
-      hipLaunchKernelGGL(pcl_cols_kernel<false>, dim3((unsigned)((NU + 3) / 4), (unsigned)np), dim3(PCL_T), lds, stream,
-                         zh_prev + (size_t)p0 * zh_stride, zh_cur + (size_t)p0 * zh_stride, zh_stride, pl, twiddles,
-                         Dt + (size_t)p0 * NU * pl.m * 2, cdc ? cdc + p0 : nullptr, flags ? flags + 2 * (size_t)p0 : nullptr, line);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((NU + 3) / 4), (unsigned)np), dim3(PCL_T), lds, stream, zh_prev + (size_t)p0 * zh_stride,
+                       zh_cur + (size_t)p0 * zh_stride, zh_stride, pl, twiddles, Dt + (size_t)p0 * NU * pl.m * 2, cdc ? cdc + p0 : nullptr,
+                       flags ? flags + 2 * (size_t)p0 : nullptr, line);
   }
   return hipGetLastError();
 }
@@ -563,10 +580,16 @@ hipError_t launch_pcl_cdc(const float* zh_prev, const float* zh_cur, size_t zh_s
 
 hipError_t launch_pcl_peak(const PclFinal& a_in, const PcPlan& pl, int n_pairs, hipStream_t stream, bool candidates_done) {
   if (n_pairs <= 0) return hipSuccess;
+  const int pk = a_in.mode == 1 ? a_in.peak_model : 0;  // (the estimator, mode 0, has cv::phaseCorrelate's model only)
+  // (candidates from the tuned K7 are those of cv::phaseCorrelate's surface)
+  if ((pk != 0 && pk != 1) || (pk == 1 && (candidates_done || pl.m != pl.n))) return hipErrorInvalidValue;
   const int line = pcl_line(pl.m), NU = (pl.m >> 1) + 1, n_cand = pcl_candidates(pl);
   const size_t lds = pcl_lds_bytes(pl.m);
   const bool ex = needs_exact(pl);
-  hipError_t e = ex ? allow_lds(&pcl_rows_inv_kernel<true>, lds) : allow_lds(&pcl_rows_inv_kernel<false>, lds);
+  auto inv = pk == 1 ? (ex ? &pcl_rows_inv_kernel<true, 1> : &pcl_rows_inv_kernel<false, 1>)
+                     : (ex ? &pcl_rows_inv_kernel<true, 0> : &pcl_rows_inv_kernel<false, 0>);
+  auto fin = pk == 1 ? &pcl_final_kernel<1> : &pcl_final_kernel<0>;
+  hipError_t e = allow_lds(inv, lds);
   if (e != hipSuccess) return e;
   for (int p0 = 0; p0 < n_pairs; p0 += 65535) {
     const int np = n_pairs - p0 < 65535 ? n_pairs - p0 : 65535;
@@ -579,15 +602,10 @@ hipError_t launch_pcl_peak(const PclFinal& a_in, const PcPlan& pl, int n_pairs, 
     a.out = a_in.out + (size_t)p0 * (a.mode == 0 ? 4 : 2);
     if (a.flags) a.flags = a_in.flags + 2 * (size_t)p0;
     if (a.cdc) a.cdc = a_in.cdc + p0;
-    if (candidates_done) {
-      // (L7 was run by somebody else: the tuned K7 for patches of 240 / 256 / 480 pixels)
-    } else if (ex)
-      hipLaunchKernelGGL(pcl_rows_inv_kernel<true>, dim3((unsigned)n_cand, (unsigned)np), dim3(PCL_T), lds, stream, a.Dt, pl, a.twiddles,
-                         const_cast<float2*>(a.cand), n_cand, line);
-    else
-      hipLaunchKernelGGL(pcl_rows_inv_kernel<false>, dim3((unsigned)n_cand, (unsigned)np), dim3(PCL_T), lds, stream, a.Dt, pl, a.twiddles,
-                         const_cast<float2*>(a.cand), n_cand, line);
-    hipLaunchKernelGGL(pcl_final_kernel, dim3((unsigned)np), dim3(64), 0, stream, a);
+    if (!candidates_done)  // (else L7 was run by somebody else: the tuned K7 for patches of 240 / 256 / 480 pixels)
+      hipLaunchKernelGGL(inv, dim3((unsigned)n_cand, (unsigned)np), dim3(PCL_T), lds, stream, a.Dt, pl, a.twiddles, const_cast<float2*>(a.cand),
+                         n_cand, line, a.search_radius);
+    hipLaunchKernelGGL(fin, dim3((unsigned)np), dim3(64), 0, stream, a);
   }
   return hipGetLastError();
 }
