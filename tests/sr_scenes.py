@@ -1,4 +1,7 @@
-"""Synthetic similarity-transformed views for the scale/rotation estimator tests (test helper)."""
+"""Synthetic similarity-transformed views for the scale/rotation estimator tests (test helper).
+
+These images are low-passed twice (synth.canvas_np(blur=True), then a Gaussian of sigma 1.5): neighbouring pixels differ by a few grey levels
+and no interpolation sum leaves [0, 255] from below. Full-range, impulse and saturating content lives in hard_content.py."""
 import numpy as np
 from scipy import ndimage
 

@@ -222,3 +222,190 @@ def test_fast_16x16_scan_at_every_even_radius(gpu, radius):
         for k in range(3):
             wdx, wdy, wmode = O.bm_process(cur[k], prev[k], cfg)
             assert (dx[k] == wdx).all() and (dy[k] == wdy).all() and tuple(mode[k, :2]) == wmode, (radius, step, gx, gy, k)
+
+
+# ---- saturated content: every 16-bit field of a packed SAD above 2^15 (tests/hard_content.py) --------------------------------------------
+# v_qsad_pk_u16_u8 accumulates into four 16-bit fields; "255 * 256 < 65536" is why that is exact. Noise against noise stays near 85 per pixel
+# (about 21,850 per 256 pixels, sigma about 960: bit 15 is never set), so the flush interval of the generic scan, the packed (sad << 16 | index)
+# key of the 16 x 16 scan and the centre - best difference of the low-contrast rule only ever saw the lower half of their range.
+SATURATED_GEOMETRIES = [
+    (16, 0, 2), (16, 8, 2), (16, 0, 8), (16, 8, 8), (16, 0, 16), (16, 8, 16),  # the 16 x 16 form
+    (8, 0, 2), (8, 4, 5),      # generic form, eight blocks per workgroup (64-pixel blocks: their sums cannot reach 2^15)
+    (32, 0, 8),
+    (36, 4, 7), (44, 0, 9),    # ragged row tails
+    (64, 0, 3), (100, 4, 13),  # packed sums flushed every 4 and 2 rows
+    (120, 24, 21), (128, 0, 24),
+]
+
+
+def _low_contrast_gap(radius):
+    return int(np.floor(0.2 * radius * radius))  # the largest centre - best that FastSpacedBMMethod.cl:77-82 still zeroes
+
+
+def _saturated_frames(block, step, radius):
+    """(names, cur[n, h, w], prev[n, h, w], planted shift) for a 3 x 2 grid of blocks (and some slack, so the frame is wider than high)."""
+    import hard_content as H
+
+    S, r = block + step, radius
+    h, w = 2 * S + 2 * r + 1, 3 * S + 2 * r + 5 + (6 * S if block == 8 else 0)  # (block 8: nine blocks a row, more than one workgroup takes)
+    seed = 1000 * block + 10 * radius + step
+    names, cur, prev = [], [], []
+    c, p = H.band_pair(seed, (h, w), 40)
+    names += ["band_pair(40)", "band_pair(40) swapped"]
+    cur += [c, p]
+    prev += [p, c]
+    black, white = np.zeros((h, w), np.uint8), np.full((h, w), 255, np.uint8)
+    names += ["0 against 255", "255 against 0"]
+    cur += [black, white]
+    prev += [white, black]
+    # binary noise with a planted shift: cur[y, x] = prev[y - sy, x - sx] -> SAD 0 at candidate (-sx, -sy), multiples of 255 elsewhere
+    sx, sy = min(r, 3) - (r > 1), -(min(r, 5) // 2)
+    pn = H.binary_noise(seed, (h, w))
+    names.append("binary noise, planted shift")
+    cur.append(np.roll(pn, (sy, sx), axis=(0, 1)))
+    prev.append(pn)
+    # 0 / 255 noise of density q against black, q chosen so that the sums over TWICE the pixels of one 16-bit field (two flush intervals of
+    # the generic scan; 512 pixels where a block is one field) lie around 2^16: mean 65536, sigma about 2800. The fields themselves then
+    # lie around 2^15 and are exact; summed over any longer interval about half the candidates would wrap and half would not. (On the other
+    # frames of this list every candidate's sum over two intervals lies in [2^16, 2^17): a 16-bit wrap takes the same 65536 off all of
+    # them and leaves every answer as it was -- these frames are what a flush interval that is too long cannot survive.)
+    field_px = block * (block if block <= 16 else max(256 // block, 1))
+    names.append("noise around 2^16 per two fields")
+    cur.append(black)
+    prev.append(H.bernoulli_noise(seed, (h, w), 65536.0 / (255.0 * 2 * field_px) if field_px >= 188 else 0.5))
+    # the low-contrast threshold straddled at saturated magnitude: from 0 against 255, ONE pixel per block -- a corner of its window, which
+    # only the corner candidate of that block covers -- is lowered, so that candidate beats the centre by exactly that much: by `gap` in
+    # the first block row (top-left corners: no window of the second row reaches them) and by gap + 1 in the second (bottom-right corners,
+    # below every window of the first row). The planted pixels of a row are a whole block pitch apart: no candidate covers two.
+    gap = _low_contrast_gap(r)
+    assert gap + 1 <= 255
+    pl = white.copy()
+    gx, gy = (w - 2 * r) // S, (h - 2 * r) // S
+    W = block + 2 * r
+    assert gy == 2
+    for bx in range(gx):
+        pl[0, bx * S] = 255 - gap
+        pl[S + W - 1, bx * S + W - 1] = 255 - (gap + 1)
+    names.append("threshold straddled")
+    cur.append(black)
+    prev.append(pl)
+    return names, np.stack(cur), np.stack(prev), (sx, sy)
+
+
+def _check_saturated(gpu, block, step, radius, bgr=True):
+    """The body of test_saturated_sads_bit_exact (a child process runs it too, under MOF_BM_GENERIC=1)."""
+    names, cur, prev, (sx, sy) = _saturated_frames(block, step, radius)
+    n, h, w = cur.shape
+    S, r, D = block + step, radius, 2 * radius + 1
+    # the derivation, on one block with numpy: every candidate's SAD over the pixels the kernels keep in one 16-bit field (the whole 16 x 16
+    # block; 256 // block rows of a larger one) lies in [175 n, 255 n] -- [44800, 65280] for 256 pixels: bit 15 set, 16 bits kept
+    rows = block if block <= 16 else max(256 // block, 1)
+    c0 = cur[0, r:r + block, r:r + block].astype(np.int64)
+    full = np.zeros((D, D), np.int64)
+    for ys in range(D):
+        for xs in range(D):
+            d = np.abs(c0 - prev[0, ys:ys + block, xs:xs + block].astype(np.int64))
+            full[ys, xs] = d.sum()
+            for j0 in range(0, block - rows + 1, rows):
+                f, npx = int(d[j0:j0 + rows].sum()), rows * block
+                assert 175 * npx <= f <= 255 * npx and f < 1 << 16, (block, ys, xs, j0, f)
+                assert npx < 188 or f & 0x8000, (block, ys, xs, j0, f)
+    assert block == 8 or rows * block >= 188  # (only the 64-pixel blocks stay below 2^15)
+    srt = np.sort(full.ravel())
+    assert srt[0] < srt[1], "the minimum of a band_pair block is not unique"
+
+    tc, tp = torch.from_numpy(cur).to(gpu), torch.from_numpy(prev).to(gpu)
+    engines = [("fast", FastSpacedBMMethod(block, radius, step, (h, w)), O.bm_config_fast_spaced(w, h, block, step, radius), slice(0, w))]
+    if step == 0:  # BlockMethod: square frames, no low-contrast rule
+        engines.append(("block", BlockMethod(h, block, radius), O.bm_config_block_method(h, block, radius), slice(0, h)))
+    checked = 0
+    for kind, eng, cfg, cols in engines:
+        assert (eng.cfg.grid_x, eng.cfg.grid_y) == (cfg.grid_x, cfg.grid_y)
+        dx, dy, mode = (v.cpu().numpy() for v in eng.process_batch_device(tc[:, :, cols], tp[:, :, cols]))
+        zeroed = kept = 0
+        for k in range(n):
+            ck, pk = np.ascontiguousarray(cur[k][:, cols]), np.ascontiguousarray(prev[k][:, cols])
+            wdx, wdy, wmode = O.bm_process(ck, pk, cfg)
+            wdx, wdy = wdx.reshape(dx[k].shape), wdy.reshape(dy[k].shape)
+            bad = np.argwhere((dx[k] != wdx) | (dy[k] != wdy))
+            if bad.size:
+                b0 = tuple(int(v) for v in bad[0])
+                raise AssertionError((kind, names[k], (block, step, radius), f"{len(bad)} blocks differ; first (by, bx) {b0}: got "
+                                      f"{(int(dx[k][b0]), int(dy[k][b0]))}, want {(int(wdx[b0]), int(wdy[b0]))}"))
+            assert tuple(mode[k, :2]) == wmode, (kind, names[k])
+            assert list(mode[k, 0:6:2]) == list(O.bm_histogram_top(wdx, radius, 3)), (kind, names[k])
+            assert list(mode[k, 1:6:2]) == list(O.bm_histogram_top(wdy, radius, 3)), (kind, names[k])
+            checked += 1
+            # what the answers must be, oracle or not
+            if names[k] in ("0 against 255", "255 against 0"):  # every SAD = 255 block^2: all ties
+                want = 0 if kind == "fast" else -r              # the low-contrast rule / the first minimum (BlockMethod.cpp:63)
+                assert (dx[k] == want).all() and (dy[k] == want).all(), (kind, names[k])
+            elif names[k].startswith("binary noise"):
+                assert (dx[k] == -sx).all() and (dy[k] == -sy).all(), (kind, names[k], sx, sy)
+            elif names[k] == "threshold straddled" and kind == "fast":
+                zeroed, kept = int(((dx[k] == 0) & (dy[k] == 0)).sum()), int(((dx[k] != 0) | (dy[k] != 0)).sum())
+        if kind == "fast":
+            assert zeroed == kept == cfg.grid_x, (zeroed, kept)  # first block row zeroed, second kept: both sides of the threshold
+    # the threshold on ONE block, each corner of its window in turn (first and last x-shift, first and last y-shift): lowered by gap ->
+    # zeroed; by gap + 1 -> the corner candidate is kept
+    size, gap = block + 2 * r, _low_contrast_gap(r)
+    one = FastSpacedBMMethod(block, radius, 0, (size, size))
+    cz = np.zeros((size, size), np.uint8)
+    for oy, ox in ((0, 0), (0, size - 1), (size - 1, 0), (size - 1, size - 1)):
+        for g in (gap, gap + 1):
+            pv = np.full((size, size), 255, np.uint8)
+            pv[oy, ox] = 255 - g
+            assert block == 8 or 255 * block * block - g > 1 << 15
+            want = (0, 0) if g == gap else (r if ox else -r, r if oy else -r)
+            dx, dy, _ = (v.cpu().numpy() for v in one.process_batch_device(torch.from_numpy(cz[None]).to(gpu), torch.from_numpy(pv[None]).to(gpu)))
+            wdx, wdy, _ = O.bm_process(cz, pv, O.bm_config_fast_spaced(size, size, block, 0, r))
+            assert (int(dx.ravel()[0]), int(dy.ravel()[0])) == want == (int(wdx.ravel()[0]), int(wdy.ravel()[0])), (g, oy, ox, dx, dy, wdx, wdy)
+    # the BGR8 entry: white BGR must give gray 255 (and black 0), then the same bits as the gray entry
+    if bgr:
+        assert (O.rgb2gray(np.full((4, 8, 3), 255, np.uint8)) == 255).all() and (O.rgb2gray(np.zeros((4, 8, 3), np.uint8)) == 0).all()
+        kind, eng, cfg, cols = engines[0]
+        bc, bp = (np.ascontiguousarray(np.repeat(a[..., None], 3, axis=-1)) for a in (cur, prev))
+        gdx, gdy, gmode = (v.cpu().numpy() for v in eng.process_batch_device(tc, tp))
+        dx, dy, mode = (v.cpu().numpy() for v in eng.process_batch_device_bgr(torch.from_numpy(bc).to(gpu), torch.from_numpy(bp).to(gpu)))
+        for k in range(n):
+            assert np.array_equal(O.rgb2gray(bc[k]), cur[k]) and np.array_equal(O.rgb2gray(bp[k]), prev[k]), names[k]
+            assert np.array_equal(dx[k], gdx[k]) and np.array_equal(dy[k], gdy[k]) and np.array_equal(mode[k], gmode[k]), ("bgr", names[k])
+    return checked
+
+
+@pytest.mark.parametrize("block,step,radius", SATURATED_GEOMETRIES)
+def test_saturated_sads_bit_exact(gpu, block, step, radius):
+    """Both scans on frames whose partial sums fill their 16-bit fields (band_pair(40): every 256-pixel SAD in [44800, 65280], asserted with
+    numpy on one block), on the extremes (0 against 255 and back: every SAD = 255 block^2, all ties -> BlockMethod's first minimum (-r, -r),
+    FastSpacedBMMethod's (0, 0) by the low-contrast rule), on binary noise with a planted shift (SAD 0 there, multiples of 255 elsewhere), on 0 / 255
+    noise whose sums over two flush intervals lie around 2^16 (a longer interval would wrap half the candidates) and on the low-contrast threshold straddled at that magnitude (centre - best = floor(0.2 r^2) and one more, both sums above 2^15): bit-exact
+    against the oracle, gray and BGR8."""
+    assert _check_saturated(gpu, block, step, radius) >= 7
+
+
+_GENERIC16_SCRIPT = r"""
+import sys
+sys.path[:0] = [{root!r}, {tests!r}]
+import torch
+import test_gpu_bm as T
+dev = torch.device("cuda", 0)
+checked = 0
+for block, step, radius in T.SATURATED_GEOMETRIES:
+    if block == 16:
+        checked += T._check_saturated(dev, block, step, radius)
+print("generic16 ok", checked)
+"""
+
+
+def test_block_16_on_the_generic_scan_with_saturated_sads(gpu):
+    """MOF_BM_GENERIC=1 sends 16 x 16 blocks through the generic scan (the knob is read in the launch path): the saturated cases of the
+    16 x 16 geometries once more in a child process with the knob set; MOF_BM_VERBOSE shows that the generic form really ran."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    script = _GENERIC16_SCRIPT.format(root=root, tests=os.path.join(root, "tests"))
+    r = subprocess.run([sys.executable, "-c", script], capture_output=True, text=True, timeout=600,
+                       env=dict(os.environ, MOF_BM_GENERIC="1", MOF_BM_VERBOSE="1"))
+    n16 = sum(1 for g in SATURATED_GEOMETRIES if g[0] == 16)
+    assert r.returncode == 0 and f"generic16 ok {n16 * 7 + 3 * 7}" in r.stdout, (r.stdout[-1500:], r.stderr[-1500:])
+    assert "block scan plan" in r.stderr, r.stderr[-500:]

@@ -32,18 +32,38 @@ for res, M in ((480, 49.9), (256, 45.0)):
             assert np.array_equal(got[k], want), (res, interp, k, int((got[k] != want).sum()))
             checked += 1
 print("remap ok", checked)
+# the same forms on full-range, saturating and impulse images (tests/hard_content.py): both clamps, every tap a byte of its own
+import hard_content as H
+hard = 0
+for res, M in ((480, 49.9), (256, 45.0)):
+    names, frames = H.remap_batch(500 + res, res, 2 * len(H.REMAP_CLASSES))
+    est = ScaleRotationEstimator(res, M)
+    t = torch.from_numpy(frames).to(dev)
+    for interp in (INTER_CUBIC, INTER_LANCZOS4):
+        dst = torch.full(tuple(t.shape), 37, dtype=torch.uint8, device=dev)
+        got = est.logpolar_batch_device(t, interp, dst=dst).cpu().numpy()
+        for k in range(len(frames)):
+            want = O.logpolar(frames[k], M, interp, dst=np.full((res, res), 37, np.uint8))
+            if not np.array_equal(got[k], want):
+                phi, rho = (int(v) for v in np.argwhere(got[k] != want)[0])
+                raise AssertionError((res, interp, names[k], int((got[k] != want).sum()), "first (phi, rho, got, want)", phi, rho,
+                                      int(got[k, phi, rho]), int(want[phi, rho])))
+            hard += 1
+print("hard remap ok", hard)
 """
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-@pytest.mark.parametrize("env", [{"MOF_SR_LP_RING": "16"}, {"MOF_SR_LP_SUPER": "0"}, {"MOF_SR_LP_STAGED": "0"}])
+@pytest.mark.parametrize("env", [{"MOF_SR_LP_RING": "16"}, {"MOF_SR_LP_SUPER": "0"}, {"MOF_SR_LP_STAGED": "0"}, {"MOF_SR_LP_GLOBAL": "1"}])
 def test_remap_other_kernel_forms_are_byte_exact(gpu, env):
     """K4's 16-deep ring (maps whose largest super-tile box exceeds 3072 dwords), its one-box-per-wave form (resolutions that
-    are not a multiple of 16, boxes beyond 4096 dwords) and the table-in-LDS kernel (unaligned layouts), forced by their
-    knobs on maps that would take the 12-deep super-tile form: every byte against the oracle."""
+    are not a multiple of 16, boxes beyond 4096 dwords), the table-in-LDS kernel (unaligned layouts) and the per-pixel kernel on
+    batches (MOF_SR_LP_GLOBAL=1), forced by their knobs on maps that would take the 12-deep super-tile form: every byte against
+    the oracle, on the smooth scenes and on a batch of hard_content's classes (a second count line)."""
     script = _REMAP_SCRIPT.format(root=ROOT, tests=os.path.join(ROOT, "tests"))
     r = subprocess.run([sys.executable, "-c", script], capture_output=True, text=True, timeout=600, env=dict(os.environ, **env))
     assert r.returncode == 0 and "remap ok 36" in r.stdout, (env, r.stdout[-1500:], r.stderr[-1500:])
+    assert "hard remap ok 104" in r.stdout, (env, r.stdout[-1500:], r.stderr[-1500:])
 
 
 @pytest.mark.parametrize("env,target,select", [
