@@ -13,7 +13,19 @@
 
 #include <hip/hip_runtime.h>
 
+#include <atomic>
+
 namespace mof {
+
+// Non-re-entrancy flag of the reference (`running`, FftMethod.cpp:1775-1777), made atomic.
+struct BusyGuard {
+  std::atomic<bool>& flag;
+  bool owned;
+  explicit BusyGuard(std::atomic<bool>& f) : flag(f), owned(!f.exchange(true)) {}
+  ~BusyGuard() {
+    if (owned) flag.store(false);
+  }
+};
 
 struct RelaxedCapture {
   hipStreamCaptureMode mode = hipStreamCaptureModeRelaxed;
@@ -39,6 +51,44 @@ inline hipError_t fill_on(hipStream_t s, void* dst, int value, size_t bytes) {
   const hipError_t e = hipMemsetAsync(dst, value, bytes, s);
   return e != hipSuccess ? e : hipStreamSynchronize(s);
 }
+
+// Ordering of engine-owned scratch across streams: every call that touches the scratch records the event behind its last kernel
+// (release); a later call on a DIFFERENT stream first makes its stream wait for it (acquire; same-stream calls are ordered by the
+// stream itself). Called with the engine's busy flag held.
+struct ScratchFence {
+  hipEvent_t ev = nullptr;
+  hipStream_t stream = nullptr;  // stream of the last user
+  bool scratch_used = false;
+  hipError_t create() { return hipEventCreateWithFlags(&ev, hipEventDisableTiming); }
+  void destroy() {
+    if (ev) (void)hipEventDestroy(ev);
+  }
+  // before the first launch that reads or writes the scratch
+  hipError_t acquire(hipStream_t s) {
+    if (!scratch_used || stream == s) return hipSuccess;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    const hipError_t err = hipStreamIsCapturing(s, &cap);
+    if (err != hipSuccess) return err;
+    // a capturing stream must not take a dependency on work outside its graph: the caller orders graph replays
+    return cap == hipStreamCaptureStatusNone ? hipStreamWaitEvent(s, ev, 0) : hipSuccess;
+  }
+  // behind the last launch of the call
+  hipError_t release(hipStream_t s) {
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    hipError_t err = hipStreamIsCapturing(s, &cap);
+    if (err != hipSuccess) return err;
+    if (cap != hipStreamCaptureStatusNone) return hipSuccess;  // events recorded while capturing belong to the graph
+    err = hipEventRecord(ev, s);
+    if (err != hipSuccess) return err;
+    stream = s;
+    scratch_used = true;
+    return hipSuccess;
+  }
+  // before the scratch is re-allocated or freed: a batch on a caller's stream may still use it
+  void wait_idle() {
+    if (ev && scratch_used) (void)hipEventSynchronize(ev);
+  }
+};
 
 // engines whose destroy was deferred because a captured graph may still use their device memory
 void park_engine(void (*destroy_now)(void*), void* engine);  // mof_capi.hip

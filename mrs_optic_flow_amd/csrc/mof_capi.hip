@@ -93,15 +93,7 @@ constexpr auto& fail = mof::capi_fail;
     if (_e != hipSuccess) return fail(MOF_ERR_HIP, "%s: %s", #expr, hipGetErrorString(_e));    \
   } while (0)
 
-// Non-re-entrancy flag of the reference (`running`, FftMethod.cpp:1775-1777), made atomic.
-struct BusyGuard {
-  std::atomic<bool>& flag;
-  bool owned;
-  explicit BusyGuard(std::atomic<bool>& f) : flag(f), owned(!f.exchange(true)) {}
-  ~BusyGuard() {
-    if (owned) flag.store(false);
-  }
-};
+using mof::BusyGuard;
 
 int select_device(int device) {
   int n = 0;
@@ -237,9 +229,7 @@ struct mof_fft_engine {
   float2* d_cand = nullptr;
   int* d_flags = nullptr;
   int cap = 0;
-  hipEvent_t scratch_ev = nullptr;       // behind the last kernel that used the scratch (cross-stream ordering, as mof_sr)
-  hipStream_t scratch_stream = nullptr;
-  bool scratch_used = false;
+  mof::ScratchFence fence;                // cross-stream ordering of that scratch
   std::atomic<bool> busy{false};
   std::atomic<bool> graph_pinned{false};  // a batch call was captured into a HIP graph (capi_graph.hpp)
   std::mutex host_mu;                     // mof_fft_process_batch_host: upload / run / download pipeline (host_pipe.hpp), made by its first call
@@ -296,7 +286,7 @@ static int launch_large(mof_fft_engine* e, const mof::PcArgs& a, int n_pairs, hi
     if (capturing)
       return fail(MOF_ERR_BAD_ARG, "the large-patch scratch must grow to %d patch pairs, which cannot happen inside a graph capture: "
                                    "run one batch of this size before capturing", want_pairs * patches);
-    if (e->scratch_used) (void)hipEventSynchronize(e->scratch_ev);
+    e->fence.wait_idle();
     (void)hipStreamSynchronize(e->stream);
     const hipError_t err = large_alloc(e, want_pairs * patches);
     if (err != hipSuccess) {
@@ -305,7 +295,7 @@ static int launch_large(mof_fft_engine* e, const mof::PcArgs& a, int n_pairs, hi
                   want_pairs * patches, hipGetErrorString(err));
     }
   }
-  if (e->scratch_used && e->scratch_stream != s && !capturing) HIP_TRY(hipStreamWaitEvent(s, e->scratch_ev, 0));
+  HIP_TRY(e->fence.acquire(s));
   const size_t zhf = mof::pcl_zh_floats(e->plan);
   const FftRoute& r = e->route;
   const bool tuned = r.large_tuned && a.downscale == 1;  // (the long-range mode keeps the planned kernels)
@@ -367,16 +357,16 @@ static int launch_large(mof_fft_engine* e, const mof::PcArgs& a, int n_pairs, hi
       const mof::PclSrc sj = units_on(k0 + j0);
       float* zh = e->d_zh + (size_t)j0 * per_unit * zhf;
       if (tuned)
-        HIP_TRY(mof::launch_sr_rows_real_src(sj, e->d_twiddles, zh, zhf, flags + (size_t)j0 * per_unit, e->plan.m, nj * per_unit, a.channels,
-                                             e->plan.n, s, sums + (size_t)4 * j0 * per_unit));
+        HIP_TRY(mof::launch_sr_rows_real_src(mof::SrRowsSrc{sj, e->d_twiddles, zh, zhf, flags + (size_t)j0 * per_unit, e->plan.m, a.channels, e->plan.n,
+                                                            sums + (size_t)4 * j0 * per_unit}, nj * per_unit, s));
       else
         HIP_TRY(mof::launch_pcl_rows(sj, e->plan, e->d_twiddles, zh, zhf, flags + (size_t)j0 * per_unit, nj * per_unit, a.channels,
                                      a.downscale, s));
     }
     if (video) HIP_TRY(mof::launch_pcl_seq_flags(flags, e->d_flags, patches, nq, s));
     if (tuned) {
-      HIP_TRY(mof::launch_sr_cols_seq(zh_prev, zh_cur, zh_stride, e->d_twiddles, e->d_dt, e->plan.m, nq, 1, s, e->d_flags, e->plan.n,
-                                      sums_prev, sums_cur, sums_stride));
+      HIP_TRY(mof::launch_sr_cols_seq(mof::SrColsSeq{zh_prev, zh_cur, zh_stride, e->d_twiddles, e->d_dt, e->plan.m, 1, e->d_flags, e->plan.n,
+                                                     sums_prev, sums_cur, sums_stride}, nq, s));
       HIP_TRY(mof::launch_pcl_cdc(zh_prev, zh_cur, zh_stride, e->plan.m, e->d_cdc, nq, s));
       HIP_TRY(mof::launch_sr_rows_inv(e->d_dt, e->d_twiddles, e->d_cand, e->plan.m, nq, s));
     } else {
@@ -385,11 +375,7 @@ static int launch_large(mof_fft_engine* e, const mof::PcArgs& a, int n_pairs, hi
     f.out = a.out + (size_t)k0 * patches * 2;
     HIP_TRY(mof::launch_pcl_peak(f, e->plan, nq, s, tuned));
   }
-  if (!capturing) {
-    HIP_TRY(hipEventRecord(e->scratch_ev, s));
-    e->scratch_stream = s;
-    e->scratch_used = true;
-  }
+  HIP_TRY(e->fence.release(s));
   return MOF_OK;
 }
 
@@ -555,7 +541,7 @@ int mof_fft_create(const mof_fft_config* cfg, mof_fft_engine** out) try {
   // the kernels the route can launch (a video's half-tile form runs at half_m whenever that is set)
   if (r.half_m > 0 || r.video == FftRoute::HALF_SEQ) CREATE_TRY(mof::pc_configure_half(r.half_m > 0 ? r.half_m : r.video_m));
   if (r.family == FftRoute::LARGE) {
-    CREATE_TRY(hipEventCreateWithFlags(&e->scratch_ev, hipEventDisableTiming));
+    CREATE_TRY(e->fence.create());
     CREATE_TRY(large_alloc(e, cfg->grid_x * cfg->grid_y));  // one frame pair; a batch grows it to a whole pass
   } else if (r.family == FftRoute::PLANNED) {
     CREATE_TRY(mof::pc_configure_generic());
@@ -592,10 +578,10 @@ static void fft_destroy_now(void* p) {
   mof::RelaxedCapture relaxed;  // frees must not invalidate a capture running on another thread
   (void)hipSetDevice(e->cfg.device);
   if (e->stream) (void)hipStreamSynchronize(e->stream);
-  if (e->scratch_ev && e->scratch_used) (void)hipEventSynchronize(e->scratch_ev);  // a batch on a caller's stream may still use the scratch
+  e->fence.wait_idle();
   delete e->host_pipe;
   large_free(e);
-  if (e->scratch_ev) (void)hipEventDestroy(e->scratch_ev);
+  e->fence.destroy();
   if (e->d_twiddles) (void)hipFree(e->d_twiddles);
   if (e->d_pair_slabs) (void)hipFree(e->d_pair_slabs);
   if (e->d_frames[0]) (void)hipFree(e->d_frames[0]);

@@ -209,9 +209,36 @@ std::vector<uint32_t> sr_weight_planes(const std::vector<int16_t>& weights, int 
 // tile = 8 (per-wave boxes) or 16 (super-tile boxes shared by a workgroup)
 std::vector<SrTileBox> sr_tile_boxes(const std::vector<SrMapEntry>& map, int res, int ksize, int* lds_per_wave, int tile_px);
 
-bool sr_resolution_supported(int res);      // tuned transforms (K5s / K6s / K7) exist for this resolution
-bool sr_pair_kernels_supported(int res);    // ... and the packed pair kernels K5 / K6 (240, 256, 480)
-bool sr_transform_size_tuned(int m, bool* exact_nyquist);  // the tuned transforms exist for transform size m (the one list of them)
+bool sr_pair_kernels_supported(int res);    // the packed pair kernels K5 / K6 (and K6p) exist for this resolution: 240, 256, 480
+bool sr_transform_size_tuned(int m, bool* exact_nyquist);  // the tuned transforms K5s / K6s / K7 exist for transform size m (sr_common.hpp: MOF_SR_TUNED_SIZES)
+
+// The MOF_SR_* knobs of the estimator's engine (README), read once per process (mof_sr.hip: sr_knobs)
+struct SrKnobs {
+  bool tuned_all = true;  // MOF_SR_TUNED_ALL=0: tuned transforms at 240 / 256 / 480 only, every other resolution on the planned pipeline
+  bool pair_seq = true;   // MOF_SR_PAIR_SEQ=0: independent pairs of 240 / 256 / 480 through the packed pair kernels K5 / K6
+  bool fused = false;     // MOF_SR_FUSED=1: K56 for the independent pairs of the resolutions it is built for
+  bool verbose = false;   // MOF_SR_VERBOSE
+  int seq_run = 0;        // MOF_SR_SEQ_RUN in 1 .. 4096: the fixed run of K6s; 0: chosen per pass
+  int chunk = 0;          // MOF_SR_CHUNK: pairs per pass over mof_sr_config.batch_chunk (a value outside 1 .. 4096: the default); 0: unset
+  int overlap = -1;       // MOF_SR_OVERLAP: 0 / 1 over mof_sr_config.pipeline_lanes; -1: unset
+};
+// Which kernels an estimator launches and how large its buffers are, decided once at create (sr_route)
+struct SrRoute {
+  enum Family { TUNED, TUNED_PAD, PLANNED };
+  enum Pairs { FRAMES, PACKED, FUSED };
+  Family family = TUNED;  // TUNED: K5s / K6s / K7 + K8 on the resolution itself; the resolution padded to m = getOptimalDFTSize: TUNED_PAD, the
+                          // zero-padding frame form of K5s, K6s, K7 and the planned pipeline's final kernel -- or PLANNED, L5 - L8 (pc_large_kernel.hip)
+  int m = 0;              // transform size
+  bool sums = false;      // TUNED_PAD at 250 / 400 / 432: a frame's four exact pixel sums sit `sums_off` floats into its Zh slot (the slack
+  size_t sums_off = 0;    // behind the padded rows), so they travel wherever the slot is copied
+  size_t zh_floats = 0;   // floats of one image's row half-spectra (Dt has the same shape)
+  int candidates = 0;     // peak candidates per pair
+  Pairs pairs = FRAMES;   // the batch entry's independent pairs: the frame kernels, the packed K5 / K6, or the fused K56
+  int seq_run = 0;        // pairs one wave of K6s walks in time: 0 = chosen per pass, MOF_SR_SEQ_RUN fixes it (r05: 16)
+};
+// Pure host code (no HIP call): the route of an even resolution >= 16; *plan receives the line plan of the padded families. False: the
+// resolution pads beyond the planned transforms.
+bool sr_route(int resolution, const SrKnobs& k, PcPlan* plan, SrRoute* r);
 int sr_candidates(int res);
 hipError_t launch_sr_logpolar(const SrLpArgs& a, int interp /*2 cubic, 4 lanczos4*/, int n_images, hipStream_t stream);
 hipError_t launch_sr_phase_correlate(const SrPcArgs& a, int res, int n_pairs, hipStream_t stream);
@@ -224,20 +251,41 @@ hipError_t launch_sr_identity(double* out4, hipStream_t stream);  // (1, 0, 0, 0
 // K5s: images lp + f * lp_stride (res * res u8, tightly packed rows) -> zh + f * zh_stride (strides: bytes / floats)
 hipError_t launch_sr_rows_real(const uint8_t* lp, size_t lp_stride, const float* twiddles, float* zh, size_t zh_stride, int res,
                                int n_frames, hipStream_t stream);
-// K6s: pair p = (cur: zh_cur + p * zh_stride, prev: zh_prev + p * zh_stride) -> Dt[p]; `run` > 1 lets one wave walk that
-// many consecutive pairs re-using cur(p) as prev(p + 1) -- only valid when zh_cur == zh_prev + zh_stride (a sequence)
-// K5s on patches of frames (FftMethod patches of 240 / 256 / 480 pixels) and K7 alone: the tuned transforms under the FFT engine's
-// large-patch pipeline; flags as launch_pcl_rows
-hipError_t launch_sr_rows_real_src(const PclSrc& src, const float* twiddles, float* zh, size_t zh_stride, int* flags, int res, int n_images,
-                                   int channels, int n, hipStream_t stream, int* sums = nullptr);  // n <= res: the unpadded patch size (zeros beyond n x n);
-                                   // sums: 4 ints per image (zeroed), the exact sums sum (+-1)^y (+-1)^x p -- filled by the plans whose Nyquist bin is not exact (250, 400, 432)
+// K5s on patches of frames and K7 alone: the tuned transforms under the FFT engine's large-patch pipeline and the estimator's padded resolutions
+struct SrRowsSrc {
+  PclSrc src;
+  const float* twiddles;  // res (cos, -sin) pairs
+  float* zh;              // image f -> zh + f * zh_stride floats
+  size_t zh_stride;
+  int* flags;             // as launch_pcl_rows (nullable)
+  int res;                // transform size
+  int channels;           // 1 or 3
+  int n;                  // n <= res: the unpadded patch size (zeros beyond n x n)
+  int* sums;              // nullable: 4 ints per image (zeroed; src.sums_stride apart), the exact sums sum (+-1)^y (+-1)^x p -- filled by the plans
+                          // whose Nyquist bin is not exact (250, 400, 432)
+};
+hipError_t launch_sr_rows_real_src(const SrRowsSrc& a, int n_images, hipStream_t stream);
 hipError_t launch_sr_rows_inv(const float* Dt, const float* twiddles, float2* cand, int res, int n_pairs, hipStream_t stream);
 // a video's per-image flags fs[frame * patches + patch] -> the per-pair layout the column kernel and the tail read: f2[2 q] = cur = fs[q + patches],
 // f2[2 q + 1] = prev = fs[q] (pair q = k * patches + patch of frames k + 1, k)
 hipError_t launch_pcl_seq_flags(const int* fs, int* f2, int patches, int n_pairs, hipStream_t stream);
-hipError_t launch_sr_cols_seq(const float* zh_prev, const float* zh_cur, size_t zh_stride, const float* twiddles, float* Dt, int res,
-                              int n_pairs, int run, hipStream_t stream, const int* flags = nullptr, int n = 0,  // flags + n < res: the box-zero rule of padded constant patches (run = 1)
-                              const int* sums_prev = nullptr, const int* sums_cur = nullptr, int sums_stride = 0);  // the rows kernel's exact sums, pair p at p * sums_stride ints
+// K6s: pair p = (cur: zh_cur + p * zh_stride, prev: zh_prev + p * zh_stride) -> Dt[p]
+struct SrColsSeq {
+  const float* zh_prev;
+  const float* zh_cur;
+  size_t zh_stride;
+  const float* twiddles;
+  float* Dt;
+  int res;                // transform size
+  int run;                // > 1 lets one wave walk that many consecutive pairs re-using cur(p) as prev(p + 1) -- only valid when
+                          // zh_cur == zh_prev + zh_stride (a sequence)
+  const int* flags;       // nullable; flags + n < res: the box-zero rule of padded constant patches (run = 1)
+  int n;                  // the unpadded size; 0: res
+  const int* sums_prev;   // the rows kernel's exact sums (nullable where the plan's Nyquist bin is exact), pair p at p * sums_stride ints
+  const int* sums_cur;
+  int sums_stride;
+};
+hipError_t launch_sr_cols_seq(const SrColsSeq& a, int n_pairs, hipStream_t stream);
 int sr_seq_columns_per_wave(int res);  // K6s's columns per wave at transform size res; 0: no K6s there
 // K56 (sr_fused_kernel.hip): K5s + K6s in one kernel, the row transforms as a dense product on the matrix cores -- reads the u8
 // log-polar images instead of Zh. `frags` = sr_fused_fragments(res) on the device. Same pair / run semantics as K6s.

@@ -46,17 +46,28 @@ constexpr int kCoefScale = 1 << 15; // INTER_REMAP_COEF_SCALE
 // so the DEFAULT stays 512 pairs = 1.9 GB (r04, advisor); a caller that has the memory opts in through
 // mof_sr_config.batch_chunk (bench.py does for c5 / c5seq).
 constexpr int kChunkDefault = MOF_SR_CHUNK;
-// mof_sr_config.batch_chunk / .pipeline_lanes; MOF_SR_CHUNK / MOF_SR_OVERLAP in the environment override both at
-// create() (sweeps)
+// The MOF_SR_* knobs of the engine (README), read once per process. MOF_SR_CHUNK / MOF_SR_OVERLAP override mof_sr_config.batch_chunk /
+// .pipeline_lanes at create() (sweeps)
+const mof::SrKnobs& sr_knobs() {
+  static const mof::SrKnobs k = [] {
+    mof::SrKnobs r;
+    const char* v;
+    r.tuned_all = !(v = getenv("MOF_SR_TUNED_ALL")) || atoi(v) != 0;
+    r.pair_seq = !(v = getenv("MOF_SR_PAIR_SEQ")) || atoi(v) != 0;
+    r.fused = (v = getenv("MOF_SR_FUSED")) && atoi(v) != 0;
+    r.verbose = (v = getenv("MOF_SR_VERBOSE")) && atoi(v) != 0;
+    if ((v = getenv("MOF_SR_SEQ_RUN")) && atoi(v) >= 1 && atoi(v) <= 4096) r.seq_run = atoi(v);
+    if ((v = getenv("MOF_SR_CHUNK"))) r.chunk = atoi(v) >= 1 && atoi(v) <= 4096 ? atoi(v) : kChunkDefault;
+    if ((v = getenv("MOF_SR_OVERLAP"))) r.overlap = atoi(v) != 0;
+    return r;
+  }();
+  return k;
+}
 int chunk_pairs(int cfg_chunk) {
-  const char* e = getenv("MOF_SR_CHUNK");
-  const int n = e ? atoi(e) : cfg_chunk;
-  return n >= 1 && n <= 4096 ? n : kChunkDefault;
+  if (sr_knobs().chunk) return sr_knobs().chunk;
+  return cfg_chunk >= 1 && cfg_chunk <= 4096 ? cfg_chunk : kChunkDefault;
 }
-bool two_lane_default(int cfg_lanes) {
-  const char* v = getenv("MOF_SR_OVERLAP");
-  return v ? atoi(v) != 0 : cfg_lanes == 2;
-}
+bool two_lane_default(int cfg_lanes) { return sr_knobs().overlap >= 0 ? sr_knobs().overlap != 0 : cfg_lanes == 2; }
 
 #define SR_TRY(expr)                                                                                  \
   do {                                                                                                \
@@ -236,20 +247,43 @@ std::vector<SrTileBox> sr_tile_boxes(const std::vector<SrMapEntry>& map, int res
   return boxes;
 }
 
+// Resolutions on the tuned transforms unpadded: 240 / 256 / 480, and every even tuned size with an exact Nyquist bin (MOF_SR_TUNED_ALL=0: the
+// three only, A/B and tests). Any other resolution runs on the size cv::phaseCorrelate pads it to, plan.m = getOptimalDFTSize(resolution):
+// where that size has tuned transforms, on the zero-padding frame form of K5s, K6s, K7 and only the final kernel of the planned pipeline (r06).
+bool sr_route(int res, const SrKnobs& k, PcPlan* plan, SrRoute* r) {
+  *r = SrRoute{};
+  bool exact = false;
+  if (sr_pair_kernels_supported(res) || (k.tuned_all && res % 2 == 0 && sr_transform_size_tuned(res, &exact) && exact)) {
+    r->m = res;
+    r->zh_floats = sr_zh_floats(res);
+    r->candidates = sr_candidates(res);
+    // Independent pairs run the FRAME kernels too (sr_seq_kernel.hip): each of the 2n log-polar images gets its own real row transform, K6s
+    // correlates slot 2p against 2p + 1, one pair per wave-run. Same-box c5: 360 k pairs/s against 354 k for the packed pair kernels (K5 / K6
+    // of sr_kernel.hip, MOF_SR_PAIR_SEQ=0; 240 / 256 / 480 only), and the batch entry computes exactly what the stateful entry computes for a
+    // fresh estimator fed (prev, cur): same bits. MOF_SR_FUSED: K56, K5s + K6s in one kernel.
+    if (!k.pair_seq && sr_pair_kernels_supported(res)) r->pairs = SrRoute::PACKED;
+    else if (k.fused && sr_fused_supported(res)) r->pairs = SrRoute::FUSED;
+  } else {
+    if (!pc_build_line_plan(res, plan)) return false;
+    r->family = SrRoute::PLANNED;
+    r->m = plan->m;
+    r->zh_floats = pcl_zh_floats(*plan);
+    r->candidates = pcl_candidates(*plan);
+    exact = true;
+    if (k.tuned_all && sr_transform_size_tuned(plan->m, &exact)) {
+      r->family = SrRoute::TUNED_PAD;
+      r->sums = !exact;
+      if (r->sums) r->sums_off = (size_t)((plan->m >> 1) + 1) * ((plan->m + 7) & ~7) * 2;  // behind the padded rows; pcl_zh_floats leaves 16 floats per row of slack
+    }
+  }
+  r->seq_run = k.seq_run;
+  return true;
+}
+
 }  // namespace mof
 
-namespace {
-
-struct BusyGuard {
-  std::atomic<bool>& flag;
-  bool owned;
-  explicit BusyGuard(std::atomic<bool>& f) : flag(f), owned(!f.exchange(true)) {}
-  ~BusyGuard() {
-    if (owned) flag.store(false);
-  }
-};
-
-}  // namespace
+using mof::BusyGuard;
+using mof::SrRoute;
 
 struct mof_sr_engine {
   mof_sr_config cfg{};
@@ -276,32 +310,19 @@ struct mof_sr_engine {
   uint8_t* h_stage = nullptr;
   double* h_out = nullptr;
   double* h_seq = nullptr;       // pinned [chunk][4]: a pass's results, read back when a sequence call resolves the gate
-  int seq_run = 0;               // pairs one wave of K6s walks in time: 0 = chosen per pass (seq_run_for), MOF_SR_SEQ_RUN fixes it (r05: 16)
   int chunk = 0;                 // frame pairs per pipeline pass
   int scratch_pairs = 0;         // pairs per pass the scratch holds now (1 after create, `chunk` after the first batch)
   bool two_lanes = false;        // remap of pass k+1 beside the transforms of pass k (mof_sr_config.pipeline_lanes == 2)
   bool first = true;             // :31
-  // resolutions without hand-tuned transforms (anything but 240 / 256 / 480) run the planned pipeline of
-  // pc_large_kernel.hip on the size cv::phaseCorrelate pads to, plan.m = getOptimalDFTSize(resolution)
-  bool generic = false;
-  mof::PcPlan plan{};
-  // r06: a generic resolution whose PADDED size plan.m has tuned transforms runs K5s (the zero-padding frame form of the row kernel) / K6s /
-  // K7 and only the final kernel of the planned pipeline. pad_sums: plan.m is 250 / 400 / 432 (odd last radix) -- the four exact pixel sums of
-  // a frame sit `sums_off` floats into its Zh slot (the slack behind the padded rows), so they travel wherever the slot is copied
-  bool tuned_pad = false, pad_sums = false;
-  size_t sums_off = 0;
+  SrRoute route;                 // which transforms every launch runs (sr_route)
+  mof::PcPlan plan{};            // route.family TUNED_PAD / PLANNED: the line plan of the padded size route.m
   std::atomic<bool> busy{false};
   std::mutex host_mu;  // mof_sr_process_sequence_host: the upload pipeline (host_pipe.hpp), made by its first call
   mof::HostPipe* host_pipe = nullptr;
   // a batch call was captured into a HIP graph: the graph's kernel nodes hold raw pointers into the scratch below, so
   // from then on the scratch neither grows nor is freed until mof_sr_release_graphs (capi_graph.hpp)
   std::atomic<bool> graph_pinned{false};
-  // Ordering of the engine-owned scratch (d_lp, d_Zt, d_Dt, d_cand, d_out) across streams: every call that
-  // touches it records `scratch_ev` behind its last kernel; a later call on a DIFFERENT stream first makes its
-  // stream wait for that event (same-stream calls are ordered by the stream itself).
-  hipEvent_t scratch_ev = nullptr;
-  hipStream_t scratch_stream = nullptr;  // stream of the last user
-  bool scratch_used = false;
+  mof::ScratchFence fence;  // ordering of the engine-owned scratch (d_lp, d_Zt, d_Dt, d_cand, d_out) across streams
   // Two-lane batch pipeline: the log-polar remaps of chunk k+1 (bound by LDS / L1 latency, little HBM traffic) run on
   // `remap_stream` while the transforms of chunk k (bound by HBM) run on the caller's stream; the log-polar images are
   // double-buffered and handed over with events.
@@ -313,38 +334,30 @@ struct mof_sr_engine {
 
 namespace {
 
-// sizes of the transform scratch and the three transform steps, tuned or planned
-size_t zh_floats(const mof_sr_engine* e) { return e->generic ? mof::pcl_zh_floats(e->plan) : mof::sr_zh_floats(e->cfg.resolution); }
-int peak_candidates(const mof_sr_engine* e) { return e->generic ? mof::pcl_candidates(e->plan) : mof::sr_candidates(e->cfg.resolution); }
+// the three transform steps, by the engine's route
 hipError_t rows_real(const mof_sr_engine* e, const uint8_t* lp, size_t lp_stride, float* zh, size_t zh_stride, int n_frames, hipStream_t s) {
   const int res = e->cfg.resolution;
-  if (!e->generic) return mof::launch_sr_rows_real(lp, lp_stride, e->d_twiddles, zh, zh_stride, res, n_frames, s);
+  const SrRoute& r = e->route;
+  if (r.family == SrRoute::TUNED) return mof::launch_sr_rows_real(lp, lp_stride, e->d_twiddles, zh, zh_stride, res, n_frames, s);
   mof::PclSrc src{};
   src.base[0] = lp;
   src.stride[0] = lp_stride;
   src.pitch = (size_t)res;  // log-polar images are tightly packed
-  if (e->tuned_pad) {
-    src.paired = 2;  // "a video whose one patch is the whole image": image f = base[0] + f * stride[0]
-    src.grid_x = src.grid_y = 1;
-    src.stride_x = src.stride_y = res;
-    int* sums = nullptr;
-    if (e->pad_sums) {
-      sums = reinterpret_cast<int*>(zh + e->sums_off);
-      src.sums_stride = (int)zh_stride;
-      const hipError_t err = n_frames == 1 ? hipMemsetAsync(sums, 0, 4 * sizeof(int), s)  // (the row kernel adds into them; the stateful call passes no stride)
-                                           : hipMemset2DAsync(sums, zh_stride * sizeof(float), 0, 4 * sizeof(int), (size_t)n_frames, s);
-      if (err != hipSuccess) return err;
-    }
-    return mof::launch_sr_rows_real_src(src, e->d_twiddles, zh, zh_stride, nullptr, e->plan.m, n_frames, 1, res, s, sums);
+  if (r.family == SrRoute::PLANNED) return mof::launch_pcl_rows(src, e->plan, e->d_twiddles, zh, zh_stride, nullptr, n_frames, 1, 1, s);
+  src.paired = 2;  // "a video whose one patch is the whole image": image f = base[0] + f * stride[0]
+  src.grid_x = src.grid_y = 1;
+  src.stride_x = src.stride_y = res;
+  int* sums = nullptr;
+  if (r.sums) {
+    sums = reinterpret_cast<int*>(zh + r.sums_off);
+    src.sums_stride = (int)zh_stride;
+    const hipError_t err = n_frames == 1 ? hipMemsetAsync(sums, 0, 4 * sizeof(int), s)  // (the row kernel adds into them; the stateful call passes no stride)
+                                         : hipMemset2DAsync(sums, zh_stride * sizeof(float), 0, 4 * sizeof(int), (size_t)n_frames, s);
+    if (err != hipSuccess) return err;
   }
-  return mof::launch_pcl_rows(src, e->plan, e->d_twiddles, zh, zh_stride, nullptr, n_frames, 1, 1, s);
+  return mof::launch_sr_rows_real_src(mof::SrRowsSrc{src, e->d_twiddles, zh, zh_stride, nullptr, r.m, 1, res, sums}, n_frames, s);
 }
-// K56: K5s + K6s in one kernel on the u8 log-polar images (MOF_SR_FUSED, tuned resolutions)
-bool fused_requested() {
-  static const bool on = [] { const char* v = getenv("MOF_SR_FUSED"); return v && atoi(v) != 0; }();
-  return on;
-}
-bool use_fused(const mof_sr_engine* e) { return e->d_wfrag != nullptr; }  // (the fragments exist only when the knob was set at create)
+// K56: K5s + K6s in one kernel on the u8 log-polar images (route.pairs FUSED; the fragments exist only then)
 hipError_t cols_fused(const mof_sr_engine* e, const uint8_t* lp_prev, const uint8_t* lp_cur, size_t lp_stride, int n_pairs, int run, hipStream_t s) {
   return mof::launch_sr_cols_fused(lp_prev, lp_cur, lp_stride, e->d_wfrag, e->d_twiddles, e->d_Dt, e->cfg.resolution, n_pairs, run, s);
 }
@@ -353,10 +366,10 @@ hipError_t cols_fused(const mof_sr_engine* e, const uint8_t* lp_prev, const uint
 // groups x 4 runs = 244 one-wave workgroups on 2048 slots. Workgroups last run + ~0.6 column transforms (the first pair's previous spectra
 // are transformed too), the launch lasts ceil(workgroups / slots) rounds: the shortest run within 3 % of the least product.
 int seq_run_for(const mof_sr_engine* e, int m) {
-  if (e->seq_run > 0) return e->seq_run;
+  if (e->route.seq_run > 0) return e->route.seq_run;
   int cus = 0;
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, e->cfg.device) != hipSuccess || cus <= 0) cus = 256;
-  const int tn = e->generic ? e->plan.m : e->cfg.resolution;
+  const int tn = e->route.m;
   const int cw = mof::sr_seq_columns_per_wave(tn);  // columns per wave
   if (cw == 0) return 16;  // (no K6s at this size: the planned L6 walks no runs)
   const long groups = (tn / 2 + 1 + cw - 1) / cw, slots = (long)cus * 8;  // one-wave workgroups, two per SIMD
@@ -371,15 +384,19 @@ int seq_run_for(const mof_sr_engine* e, int m) {
   return 16;
 }
 hipError_t cols_seq(const mof_sr_engine* e, const float* zh_prev, const float* zh_cur, size_t zh_stride, int n_pairs, int run, hipStream_t s) {
-  if (!e->generic) return mof::launch_sr_cols_seq(zh_prev, zh_cur, zh_stride, e->d_twiddles, e->d_Dt, e->cfg.resolution, n_pairs, run, s);
-  if (e->tuned_pad)
-    return mof::launch_sr_cols_seq(zh_prev, zh_cur, zh_stride, e->d_twiddles, e->d_Dt, e->plan.m, n_pairs, run, s, nullptr, e->cfg.resolution,
-                                   e->pad_sums ? reinterpret_cast<const int*>(zh_prev + e->sums_off) : nullptr,
-                                   e->pad_sums ? reinterpret_cast<const int*>(zh_cur + e->sums_off) : nullptr, (int)zh_stride);
-  return mof::launch_pcl_cols(zh_prev, zh_cur, zh_stride, e->plan, e->d_twiddles, e->d_Dt, nullptr, nullptr, n_pairs, s);
+  const SrRoute& r = e->route;
+  if (r.family == SrRoute::PLANNED) return mof::launch_pcl_cols(zh_prev, zh_cur, zh_stride, e->plan, e->d_twiddles, e->d_Dt, nullptr, nullptr, n_pairs, s);
+  mof::SrColsSeq a{zh_prev, zh_cur, zh_stride, e->d_twiddles, e->d_Dt, r.m, run, nullptr, e->cfg.resolution, nullptr, nullptr, 0};
+  if (r.sums) {
+    a.sums_prev = reinterpret_cast<const int*>(zh_prev + r.sums_off);
+    a.sums_cur = reinterpret_cast<const int*>(zh_cur + r.sums_off);
+    a.sums_stride = (int)zh_stride;
+  }
+  return mof::launch_sr_cols_seq(a, n_pairs, s);
 }
 hipError_t peak(const mof_sr_engine* e, const mof::SrPcArgs& a, int n_pairs, hipStream_t s) {
-  if (!e->generic) return mof::launch_sr_peak(a, e->cfg.resolution, n_pairs, s);
+  const SrRoute& r = e->route;
+  if (r.family == SrRoute::TUNED) return mof::launch_sr_peak(a, r.m, n_pairs, s);
   mof::PclFinal f{};
   f.Dt = a.Dt;
   f.cand = a.cand;
@@ -387,40 +404,10 @@ hipError_t peak(const mof_sr_engine* e, const mof::SrPcArgs& a, int n_pairs, hip
   f.mode = 0;
   f.M_log = a.M;
   f.out = a.out;
-  if (e->tuned_pad) {  // K7 forms the candidates; L8 (the planned pipeline's final kernel: it knows the padded geometry) reads them
-    const hipError_t err = mof::launch_sr_rows_inv(a.Dt, a.twiddles, a.cand, e->plan.m, n_pairs, s);
-    if (err != hipSuccess) return err;
-    return mof::launch_pcl_peak(f, e->plan, n_pairs, s, true);
-  }
-  return mof::launch_pcl_peak(f, e->plan, n_pairs, s);
-}
-
-// Called with the busy flag held, before the first launch that reads or writes the scratch.
-hipError_t scratch_acquire(mof_sr_engine* e, hipStream_t s) {
-  if (e->scratch_used && e->scratch_stream != s) {
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    hipError_t err = hipStreamIsCapturing(s, &cap);
-    if (err != hipSuccess) return err;
-    // a capturing stream must not take a dependency on work outside its graph: the caller orders graph replays
-    if (cap == hipStreamCaptureStatusNone) {
-      err = hipStreamWaitEvent(s, e->scratch_ev, 0);
-      if (err != hipSuccess) return err;
-    }
-  }
-  return hipSuccess;
-}
-
-// Called behind the last launch of the call.
-hipError_t scratch_release(mof_sr_engine* e, hipStream_t s) {
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  hipError_t err = hipStreamIsCapturing(s, &cap);
-  if (err != hipSuccess) return err;
-  if (cap != hipStreamCaptureStatusNone) return hipSuccess;  // events recorded while capturing belong to the graph
-  err = hipEventRecord(e->scratch_ev, s);
-  if (err != hipSuccess) return err;
-  e->scratch_stream = s;
-  e->scratch_used = true;
-  return hipSuccess;
+  if (r.family == SrRoute::PLANNED) return mof::launch_pcl_peak(f, e->plan, n_pairs, s);
+  // K7 forms the candidates; L8 (the planned pipeline's final kernel: it knows the padded geometry) reads them
+  const hipError_t err = mof::launch_sr_rows_inv(a.Dt, a.twiddles, a.cand, r.m, n_pairs, s);
+  return err != hipSuccess ? err : mof::launch_pcl_peak(f, e->plan, n_pairs, s, true);
 }
 
 // The pipeline scratch (log-polar images of two passes, Zt, Dt, peak candidates, results) for `pairs` pairs per pass.
@@ -439,12 +426,12 @@ hipError_t scratch_alloc(mof_sr_engine* e, int pairs) {
   {
     // pair pipeline: packed row spectra Zt, nn complex per pair; sequence pipeline: (pairs + 1) frames of half spectra
     // (or, pairs through the frame kernels: 2 * pairs frames of half spectra)
-    const size_t zt = e->generic ? 0 : (size_t)pairs * nn * 2 * sizeof(float), zh1 = (size_t)(pairs + 1) * zh_floats(e) * sizeof(float),
-                 zh2 = (size_t)2 * pairs * zh_floats(e) * sizeof(float), zh = zh1 > zh2 ? zh1 : zh2;
+    const size_t zhf = e->route.zh_floats, zt = e->route.family == SrRoute::TUNED ? (size_t)pairs * nn * 2 * sizeof(float) : 0,
+                 zh1 = (size_t)(pairs + 1) * zhf * sizeof(float), zh2 = (size_t)2 * pairs * zhf * sizeof(float), zh = zh1 > zh2 ? zh1 : zh2;
     if ((err = hipMalloc(&e->d_Zt, zt > zh ? zt : zh)) != hipSuccess) return err;
   }
-  if ((err = hipMalloc(&e->d_Dt, (size_t)pairs * zh_floats(e) * sizeof(float))) != hipSuccess) return err;  // Dt has Zh's shape
-  if ((err = hipMalloc(&e->d_cand, (size_t)pairs * peak_candidates(e) * sizeof(float2))) != hipSuccess) return err;
+  if ((err = hipMalloc(&e->d_Dt, (size_t)pairs * e->route.zh_floats * sizeof(float))) != hipSuccess) return err;  // Dt has Zh's shape
+  if ((err = hipMalloc(&e->d_cand, (size_t)pairs * e->route.candidates * sizeof(float2))) != hipSuccess) return err;
   if ((err = hipMalloc(&e->d_out, (size_t)pairs * 4 * sizeof(double))) != hipSuccess) return err;
   if ((err = hipMalloc(&e->d_degen, (size_t)pairs * sizeof(int))) != hipSuccess) return err;
   e->scratch_pairs = pairs;
@@ -472,7 +459,7 @@ int scratch_reserve(mof_sr_engine* e, int pairs, hipStream_t s) {
   if (hipStreamIsCapturing(s, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone)
     return mof::capi_fail(MOF_ERR_BAD_ARG, "the estimator's scratch must grow to %d pairs per pass, which cannot happen inside a graph capture: "
                                             "call mof_sr_reserve (or run one batch) before capturing", pairs);
-  if (e->scratch_used) (void)hipEventSynchronize(e->scratch_ev);
+  e->fence.wait_idle();
   (void)hipStreamSynchronize(e->stream);
   (void)hipStreamSynchronize(e->remap_stream);
   const hipError_t err = scratch_alloc(e, pairs);
@@ -502,7 +489,7 @@ static void sr_destroy_now(void* p) {
   mof::RelaxedCapture relaxed;
   (void)hipSetDevice(e->cfg.device);
   if (e->stream) (void)hipStreamSynchronize(e->stream);
-  if (e->scratch_ev && e->scratch_used) (void)hipEventSynchronize(e->scratch_ev);  // a batch on a caller's stream may still use the scratch
+  e->fence.wait_idle();
   delete e->host_pipe;
   void* dev[] = {e->d_boxes[0], e->d_boxes[1], e->d_sboxes[0], e->d_sboxes[1], e->d_map, e->d_w_cubic, e->d_w_lanczos, e->d_wp[0], e->d_wp[1], e->d_twiddles, e->d_frame, e->d_temp_im, e->d_zh_prev, e->d_wfrag,
                  e->d_lp,  e->d_Zt,      e->d_Dt,        e->d_cand,     e->d_out, e->d_degen};
@@ -511,7 +498,7 @@ static void sr_destroy_now(void* p) {
   if (e->h_stage) (void)hipHostFree(e->h_stage);
   if (e->h_out) (void)hipHostFree(e->h_out);
   if (e->h_seq) (void)hipHostFree(e->h_seq);
-  if (e->scratch_ev) (void)hipEventDestroy(e->scratch_ev);
+  e->fence.destroy();
   if (e->remap_stream) (void)hipStreamSynchronize(e->remap_stream);
   for (hipEvent_t ev : {e->ev_fork, e->ev_lp[0], e->ev_lp[1], e->ev_fft[0], e->ev_fft[1]})
     if (ev) (void)hipEventDestroy(ev);
@@ -545,13 +532,12 @@ int mof_sr_create(const mof_sr_config* cfg, mof_sr_engine** out) try {
     return mof::capi_fail(MOF_ERR_BAD_ARG, "logpolar_variant must be MOF_LOGPOLAR_CV4 (0) or MOF_LOGPOLAR_CV3 (1)");
   if (cfg->batch_chunk < 0 || cfg->batch_chunk > 4096 || cfg->pipeline_lanes < 0 || cfg->pipeline_lanes > 2)
     return mof::capi_fail(MOF_ERR_BAD_ARG, "batch_chunk must be 0..4096 and pipeline_lanes 0..2");
-  // any even resolution: scaleRotationEstimator takes `res` from a parameter (scaleRotationEstimator.cpp:3-5); 240 / 256 / 480
-  // have hand-tuned transforms, the rest run the planned pipeline on the size cv::phaseCorrelate pads to
+  // any even resolution: scaleRotationEstimator takes `res` from a parameter (scaleRotationEstimator.cpp:3-5)
   if (cfg->resolution < 16 || (cfg->resolution & 1))
     return mof::capi_fail(MOF_ERR_BAD_ARG, "resolution %d: an even resolution >= 16 is required", cfg->resolution);
   mof::PcPlan plan{};
-  const bool generic = !mof::sr_resolution_supported(cfg->resolution);
-  if (generic && !mof::pc_build_line_plan(cfg->resolution, &plan))
+  SrRoute route;
+  if (!mof::sr_route(cfg->resolution, sr_knobs(), &plan, &route))
     return mof::capi_fail(MOF_ERR_UNSUPPORTED, "resolution %d pads to %d: beyond the planned transforms (<= 960)", cfg->resolution,
                           mof::pc_optimal_dft_size(cfg->resolution));
   int ndev = 0;
@@ -575,22 +561,12 @@ int mof_sr_create(const mof_sr_config* cfg, mof_sr_engine** out) try {
     sbc = mof::sr_tile_boxes(map, res, 4, &slds_c, 16);
     sbl = mof::sr_tile_boxes(map, res, 8, &slds_l, 16);
   }
-  const int tn = generic ? plan.m : res;  // transform size: the planned pipeline works on the padded image
-  const std::vector<float> tw = mof::twiddle_table(tn);
+  const std::vector<float> tw = mof::twiddle_table(route.m);
   mof_sr_engine* e = new (std::nothrow) mof_sr_engine();
   if (!e) return mof::capi_fail(MOF_ERR_NO_MEMORY, "out of host memory");
   e->cfg = *cfg;
-  e->generic = generic;
+  e->route = route;
   e->plan = plan;
-  if (generic) {
-    static const bool all = [] { const char* v = getenv("MOF_SR_TUNED_ALL"); return !v || atoi(v) != 0; }();
-    bool exact = true;
-    if (all && mof::sr_transform_size_tuned(plan.m, &exact)) {
-      e->tuned_pad = true;
-      e->pad_sums = !exact;
-      e->sums_off = (size_t)((plan.m >> 1) + 1) * ((plan.m + 7) & ~7) * 2;  // behind the padded rows; pcl_zh_floats leaves 16 floats per row of slack
-    }
-  }
   e->chunk = chunk_pairs(cfg->batch_chunk);
   e->two_lanes = two_lane_default(cfg->pipeline_lanes);
 #define CREATE_TRY(expr)                                                                  \
@@ -603,7 +579,7 @@ int mof_sr_create(const mof_sr_config* cfg, mof_sr_engine** out) try {
     }                                                                                     \
   } while (0)
   CREATE_TRY(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
-  CREATE_TRY(hipEventCreateWithFlags(&e->scratch_ev, hipEventDisableTiming));
+  CREATE_TRY(e->fence.create());
   CREATE_TRY(hipStreamCreateWithFlags(&e->remap_stream, hipStreamNonBlocking));
   CREATE_TRY(hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming));
   for (int b = 0; b < 2; ++b) {
@@ -621,7 +597,7 @@ int mof_sr_create(const mof_sr_config* cfg, mof_sr_engine** out) try {
   if (!sbc.empty()) {
     e->sbox_dwords[0] = slds_c / 4;
     e->sbox_dwords[1] = slds_l / 4;
-    if (const char* v = getenv("MOF_SR_VERBOSE"); v && atoi(v) != 0)  // diagnostics: the staged remap's largest boxes (dwords)
+    if (sr_knobs().verbose)  // diagnostics: the staged remap's largest boxes (dwords)
       fprintf(stderr, "mof_sr: res %d: largest super-tile box cubic %d, lanczos4 %d dwords; per-wave boxes %d / %d bytes\n", res, e->sbox_dwords[0],
               e->sbox_dwords[1], lds_c, lds_l);
     CREATE_TRY(hipMalloc(&e->d_sboxes[0], sbc.size() * sizeof(mof::SrTileBox)));
@@ -642,24 +618,20 @@ int mof_sr_create(const mof_sr_config* cfg, mof_sr_engine** out) try {
   }
   CREATE_TRY(hipMalloc(&e->d_twiddles, tw.size() * sizeof(float)));
   CREATE_TRY(mof::copy_on(e->stream, e->d_twiddles, tw.data(), tw.size() * sizeof(float), hipMemcpyHostToDevice));
-  if (!e->generic && fused_requested() && mof::sr_fused_supported(res)) {  // (1 MB of f16 matrix fragments at 480: only for the opt-in path)
+  if (route.pairs == SrRoute::FUSED) {  // (1 MB of f16 matrix fragments at 480: only for the opt-in path)
     const std::vector<uint32_t> fr = mof::sr_fused_fragments(res);
     CREATE_TRY(hipMalloc(&e->d_wfrag, fr.size() * sizeof(uint32_t)));
     CREATE_TRY(mof::copy_on(e->stream, e->d_wfrag, fr.data(), fr.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
   }
   CREATE_TRY(hipMalloc(&e->d_frame, nn));
   CREATE_TRY(hipMalloc(&e->d_temp_im, nn));
-  CREATE_TRY(hipMalloc(&e->d_zh_prev, zh_floats(e) * sizeof(float)));
+  CREATE_TRY(hipMalloc(&e->d_zh_prev, route.zh_floats * sizeof(float)));
   CREATE_TRY(mof::fill_on(e->stream, e->d_temp_im, 0, nn));  // tempIm = cv::Mat::zeros, :27
-  CREATE_TRY(mof::fill_on(e->stream, e->d_zh_prev, 0, zh_floats(e) * sizeof(float)));
+  CREATE_TRY(mof::fill_on(e->stream, e->d_zh_prev, 0, route.zh_floats * sizeof(float)));
   CREATE_TRY(scratch_alloc(e, 1));  // the stateful call needs one pair; a batch grows it to a whole pass (scratch_reserve)
   CREATE_TRY(hipHostMalloc(&e->h_stage, nn, hipHostMallocDefault));
   CREATE_TRY(hipHostMalloc(&e->h_out, 4 * sizeof(double), hipHostMallocDefault));
   CREATE_TRY(hipHostMalloc(&e->h_seq, (size_t)e->chunk * 4 * sizeof(double), hipHostMallocDefault));
-  {
-    const char* v = getenv("MOF_SR_SEQ_RUN");
-    if (v && atoi(v) >= 1 && atoi(v) <= 4096) e->seq_run = atoi(v);
-  }
 #undef CREATE_TRY
   *out = e;
   return MOF_OK;
@@ -699,7 +671,7 @@ static mof::SrPcArgs pc_args(const mof_sr_engine* e, const uint8_t* lp_cur, cons
   a.Zt = e->d_Zt;
   a.Dt = e->d_Dt;
   a.cand = e->d_cand;
-  a.n_cand = peak_candidates(e);
+  a.n_cand = e->route.candidates;
   a.M = e->cfg.magnitude;
   a.out = out;
   return a;
@@ -720,7 +692,7 @@ int mof_sr_process(mof_sr_engine* e, const uint8_t* frame, size_t pitch, double*
   BusyGuard g(e->busy);
   if (!g.owned) return mof::capi_fail(MOF_ERR_BUSY, "engine busy");
   SR_TRY(hipSetDevice(e->cfg.device));
-  const size_t nn = (size_t)res * res, zh_bytes = zh_floats(e) * sizeof(float);
+  const size_t nn = (size_t)res * res, zh_bytes = e->route.zh_floats * sizeof(float);
   for (int y = 0; y < res; ++y) std::memcpy(e->h_stage + (size_t)y * res, frame + (size_t)y * pitch, (size_t)res);
   SR_TRY(hipMemcpyAsync(e->d_frame, e->h_stage, nn, hipMemcpyHostToDevice, e->stream));
   mof::SrLpArgs lp{};
@@ -734,12 +706,12 @@ int mof_sr_process(mof_sr_engine* e, const uint8_t* frame, size_t pitch, double*
   const int interp = e->first ? 2 : 4;  // INTER_CUBIC for the very first frame (:45), INTER_LANCZOS4 from then on (:112)
   lp_tables(e, interp, &lp);
   SR_TRY(mof::launch_sr_logpolar(lp, interp, 1, e->stream));
-  SR_TRY(scratch_acquire(e, e->stream));
+  SR_TRY(e->fence.acquire(e->stream));
   // tempIm.convertTo(CV_32FC1) (:47, :115) + the row half of the forward DFT of cv::phaseCorrelate (:117): K5s
   SR_TRY(rows_real(e, e->d_temp_im, 0, e->d_Zt, 0, 1, e->stream));
   if (e->first) {
     SR_TRY(hipMemcpyAsync(e->d_zh_prev, e->d_Zt, zh_bytes, hipMemcpyDeviceToDevice, e->stream));  // prevIm_F32 = .., :48
-    SR_TRY(scratch_release(e, e->stream));
+    SR_TRY(e->fence.release(e->stream));
     SR_TRY(hipStreamSynchronize(e->stream));
     e->first = false;  // :73
     out_scale_rot[0] = 1.0;
@@ -754,7 +726,7 @@ int mof_sr_process(mof_sr_engine* e, const uint8_t* frame, size_t pitch, double*
   // the reference returns early on the gate, BEFORE prevIm_F32 = tempIm_F32.clone() (:119-121 vs :128)
   if (!(std::fabs(e->h_out[2]) > (double)(res / 2)))
     SR_TRY(hipMemcpyAsync(e->d_zh_prev, e->d_Zt, zh_bytes, hipMemcpyDeviceToDevice, e->stream));
-  SR_TRY(scratch_release(e, e->stream));
+  SR_TRY(e->fence.release(e->stream));
   SR_TRY(hipStreamSynchronize(e->stream));
   return MOF_OK;
 }
@@ -775,7 +747,7 @@ int mof_sr_process_sequence_device(mof_sr_engine* e, const uint8_t* d_frames, si
   const bool capturing = mof::stream_capturing(s);
   if (capturing && n_gated)
     return mof::capi_fail(MOF_ERR_BAD_ARG, "resolving the gate reads results back on the host: pass n_gated = NULL while capturing");
-  const size_t nn = (size_t)res * res, zhf = zh_floats(e), zh_bytes = zhf * sizeof(float);
+  const size_t nn = (size_t)res * res, zhf = e->route.zh_floats, zh_bytes = zhf * sizeof(float);
   {
     const int rc = scratch_reserve(e, scratch_want(e, n_frames), s);
     if (rc != MOF_OK) return rc;
@@ -785,7 +757,7 @@ int mof_sr_process_sequence_device(mof_sr_engine* e, const uint8_t* d_frames, si
   if (capturing && e->first)
     return mof::capi_fail(MOF_ERR_BAD_ARG, "capturing a sequence on a fresh estimator would bake its one-off first-frame branch "
                                             "(INTER_CUBIC, scaleRotationEstimator.cpp:45) into the graph: process one frame first");
-  SR_TRY(scratch_acquire(e, s));
+  SR_TRY(e->fence.acquire(s));
   if (capturing) e->graph_pinned.store(true);
   const int C = e->scratch_pairs < e->chunk ? e->scratch_pairs : e->chunk;  // new frames per pass
   float* zh = e->d_Zt;
@@ -860,11 +832,11 @@ int mof_sr_process_sequence_device(mof_sr_engine* e, const uint8_t* d_frames, si
     return MOF_OK;
   }();
   if (rc != MOF_OK) {
-    (void)scratch_release(e, s);  // (the error text of the failing launch stays the thread's last error)
+    (void)e->fence.release(s);  // (the error text of the failing launch stays the thread's last error)
     return rc;
   }
   e->first = first;
-  SR_TRY(scratch_release(e, s));
+  SR_TRY(e->fence.release(s));
   if (n_gated) {
     SR_TRY(hipStreamSynchronize(s));
     *n_gated = gated_total;
@@ -922,7 +894,7 @@ int mof_sr_process_batch_device(mof_sr_engine* e, const uint8_t* d_cur, size_t c
     const int rc = scratch_reserve(e, scratch_want(e, n_pairs), s);
     if (rc != MOF_OK) return rc;
   }
-  SR_TRY(scratch_acquire(e, s));
+  SR_TRY(e->fence.acquire(s));
   if (mof::stream_capturing(s)) e->graph_pinned.store(true);
   const int kChunk = e->chunk;
   // Under graph capture the fork / join below pulls the engine's stream into the caller's capture (event record on the
@@ -963,27 +935,22 @@ int mof_sr_process_batch_device(mof_sr_engine* e, const uint8_t* d_cur, size_t c
       SR_TRY(hipStreamWaitEvent(s, e->ev_lp[b], 0));  // also the join: every remap precedes a wait on the caller's stream
     }
     mof::SrPcArgs a = pc_args(e, lp_buf, lp_buf + nn, 2 * nn, d_out + 4 * (size_t)k0);
-    // Independent pairs go through the FRAME kernels too (sr_seq_kernel.hip): each of the 2n log-polar images gets its own real
-    // row transform (image 2p = cur of pair p, 2p + 1 = prev), K6s correlates slot 2p against 2p + 1, one pair per wave-run.
-    // Same-box c5: 360 k pairs/s against 354 k for the packed pair kernels (K5 / K6 of sr_kernel.hip, MOF_SR_PAIR_SEQ=0), and
-    // the batch entry now computes exactly what the stateful entry computes for a fresh estimator fed (prev, cur): same bits.
-    static const bool via_frames = [] { const char* v = getenv("MOF_SR_PAIR_SEQ"); return !v || atoi(v) != 0; }();
-    if (via_frames || e->generic || !mof::sr_pair_kernels_supported(res)) {  // (the packed pair kernels exist for 240 / 256 / 480 only)
-      const size_t zhf = zh_floats(e);
-      if (use_fused(e)) {
+    if (e->route.pairs == SrRoute::PACKED) {
+      a.degen = e->d_degen;
+      SR_TRY(mof::launch_sr_phase_correlate(a, res, n, s));
+    } else {
+      const size_t zhf = e->route.zh_floats;
+      if (e->route.pairs == SrRoute::FUSED) {
         SR_TRY(cols_fused(e, lp_buf + nn, lp_buf, 2 * nn, n, 1, s));
-      } else {
+      } else {  // the frame kernels: image 2p = cur of pair p, 2p + 1 = prev
         SR_TRY(rows_real(e, lp_buf, nn, e->d_Zt, zhf, 2 * n, s));
         SR_TRY(cols_seq(e, e->d_Zt + zhf, e->d_Zt, 2 * zhf, n, 1, s));
       }
       SR_TRY(peak(e, a, n, s));
-    } else {
-      a.degen = e->d_degen;
-      SR_TRY(mof::launch_sr_phase_correlate(a, res, n, s));
     }
     if (two_lanes) SR_TRY(hipEventRecord(e->ev_fft[b], s));
   }
-  SR_TRY(scratch_release(e, s));
+  SR_TRY(e->fence.release(s));
   return MOF_OK;
 }
 

@@ -1,5 +1,5 @@
 // sr_common.hpp -- the in-register two-stage 1-D transform shared by the scale/rotation kernels (sr_kernel.hip: independent
-// pairs; sr_seq_kernel.hip: video sequences). Device code only.
+// pairs; sr_seq_kernel.hip: video sequences), the list of the sizes it is planned for and the launchers' way from a run-time size to one of them.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -260,6 +260,25 @@ template <>
 struct SrPlan<216> {  // 12 x 18: three lines per stage-1 pass (54 of 64 lanes), twelve of sixteen lanes per line in stage 2
   static constexpr int R1 = 12, R2 = 18, Y2 = 19, LINE = 229;
 };
+
+// The transform sizes with tuned in-register transforms (K5s / K6s / K7) -- the ONE list of them; a new size is an SrPlan<N> above and an entry here.
+// The estimator's own three (240 / 256 / 480) and (r06) every transform size the FFT engine's large patches brought along. 250 / 400 / 432
+// (SrNyqExact false) take the exact-sums form of the row and column kernels: the row kernel accumulates each image's four exact integer sums and
+// the column kernel takes the real-only slots from those (the FFT engine's large-patch pipeline and the estimator's padded resolutions).
+#define MOF_SR_TUNED_SIZES(X) X(96) X(100) X(108) X(120) X(128) X(144) X(150) X(160) X(162) X(180) X(192) X(200) X(216) X(225) X(240) X(243) \
+  X(250) X(256) X(270) X(288) X(300) X(320) X(324) X(360) X(375) X(384) X(400) X(405) X(432) X(450) X(480) X(486) X(500) X(512) X(540) \
+  X(576) X(600) X(625) X(640) X(648) X(675) X(720) X(729) X(750) X(768) X(800) X(810) X(864) X(900) X(960)
+// Host side: a run-time transform size to a compile-time one -- f(std::integral_constant<int, N>{}) for a listed m, hipErrorInvalidValue otherwise
+template <class F>
+hipError_t sr_dispatch_size(int m, F&& f) {
+  switch (m) {
+#define X(N) \
+  case N: return f(std::integral_constant<int, N>{});
+    MOF_SR_TUNED_SIZES(X)
+#undef X
+    default: return hipErrorInvalidValue;
+  }
+}
 
 // Zt / Zh / Dt (and the log-polar images) are STREAMS: written once by one kernel, read once by the next, hundreds of MB per
 // pass. Marking those accesses non-temporal keeps them from displacing each other's lines on their way through the caches:

@@ -776,29 +776,14 @@ __global__ void __launch_bounds__(64) sr_final_kernel(SrPcArgs a) {
   }
 }
 
-// The transform sizes with tuned in-register transforms (K5s / K6s / K7) -- the only list of them: the estimator's own three, and (r06) every
-// transform size the FFT engine's large patches brought along. 250 = 10 x 25, 400 = 16 x 25, 432 = 16 x 27 (*exact_nyquist = false): no plan
-// of theirs ends in an even radix, so their Nyquist bins are not exact -- the row kernel accumulates each image's four exact integer sums and
-// the column kernel takes the real-only slots from those (the FFT engine's large-patch pipeline and the estimator's padded resolutions).
+// (the list: MOF_SR_TUNED_SIZES, sr_common.hpp)
 bool sr_transform_size_tuned(int m, bool* exact_nyquist) {
-  static const int sizes[] = {225, 243, 375, 405, 625, 675, 729,  // (odd: no Nyquist bin to keep exact)
-                              96, 100, 108, 120, 150, 162, 128, 144, 160, 180, 192, 200, 216, 240, 250, 256, 270, 288, 300, 320, 324, 360, 384,
-                              400, 432, 450, 480, 486, 500, 512, 540, 576, 600, 640, 648, 720, 750, 768, 800, 810, 864, 900, 960};
-  for (int t : sizes)
-    if (m == t) {
-      if (exact_nyquist) *exact_nyquist = m != 250 && m != 400 && m != 432;
-      return true;
-    }
-  return false;
+  return sr_dispatch_size(m, [&](auto n) {
+    if (exact_nyquist) *exact_nyquist = SrNyqExact<SrPlan<decltype(n)::value>>::value;
+    return hipSuccess;
+  }) == hipSuccess;
 }
 bool sr_pair_kernels_supported(int res) { return res == 240 || res == 256 || res == 480; }  // K5 / K6 (packed pairs), K56, K6p
-// Resolutions the estimator runs unpadded on the tuned transforms: 240 / 256 / 480, and every even tuned size with an exact Nyquist bin
-// (MOF_SR_TUNED_ALL=0: the three only, A/B and tests). Any other resolution runs on the size it pads to (mof_sr.hip: tuned there too).
-bool sr_resolution_supported(int res) {
-  static const bool all = [] { const char* v = getenv("MOF_SR_TUNED_ALL"); return !v || atoi(v) != 0; }();
-  bool exact = false;
-  return sr_pair_kernels_supported(res) || (all && res % 2 == 0 && sr_transform_size_tuned(res, &exact) && exact);
-}
 
 template <int K>
 static hipError_t launch_lp_lds(const SrLpArgs& a, int n_images, hipStream_t stream) {
@@ -915,51 +900,14 @@ static hipError_t launch_sr_peak_n(const SrPcArgs& a, int n_pairs, hipStream_t s
   return hipGetLastError();
 }
 
+// (the even sizes with an exact Nyquist bin: K8 = sr_final_kernel knows no odd size and no exact sums; the others have no instantiation)
 hipError_t launch_sr_peak(const SrPcArgs& a, int res, int n_pairs, hipStream_t stream) {
   if (n_pairs <= 0) return hipSuccess;
-  switch (res) {
-    case 240: return launch_sr_peak_n<240>(a, n_pairs, stream);
-    case 256: return launch_sr_peak_n<256>(a, n_pairs, stream);
-    case 480: return launch_sr_peak_n<480>(a, n_pairs, stream);
-    case 128: return launch_sr_peak_n<128>(a, n_pairs, stream);
-    case 96: return launch_sr_peak_n<96>(a, n_pairs, stream);
-    case 100: return launch_sr_peak_n<100>(a, n_pairs, stream);
-    case 108: return launch_sr_peak_n<108>(a, n_pairs, stream);
-    case 120: return launch_sr_peak_n<120>(a, n_pairs, stream);
-    case 150: return launch_sr_peak_n<150>(a, n_pairs, stream);
-    case 162: return launch_sr_peak_n<162>(a, n_pairs, stream);
-    case 144: return launch_sr_peak_n<144>(a, n_pairs, stream);
-    case 160: return launch_sr_peak_n<160>(a, n_pairs, stream);
-    case 180: return launch_sr_peak_n<180>(a, n_pairs, stream);
-    case 192: return launch_sr_peak_n<192>(a, n_pairs, stream);
-    case 200: return launch_sr_peak_n<200>(a, n_pairs, stream);
-    case 216: return launch_sr_peak_n<216>(a, n_pairs, stream);
-    case 270: return launch_sr_peak_n<270>(a, n_pairs, stream);
-    case 288: return launch_sr_peak_n<288>(a, n_pairs, stream);
-    case 300: return launch_sr_peak_n<300>(a, n_pairs, stream);
-    case 320: return launch_sr_peak_n<320>(a, n_pairs, stream);
-    case 324: return launch_sr_peak_n<324>(a, n_pairs, stream);
-    case 360: return launch_sr_peak_n<360>(a, n_pairs, stream);
-    case 384: return launch_sr_peak_n<384>(a, n_pairs, stream);
-    case 450: return launch_sr_peak_n<450>(a, n_pairs, stream);
-    case 486: return launch_sr_peak_n<486>(a, n_pairs, stream);
-    case 500: return launch_sr_peak_n<500>(a, n_pairs, stream);
-    case 512: return launch_sr_peak_n<512>(a, n_pairs, stream);
-    case 540: return launch_sr_peak_n<540>(a, n_pairs, stream);
-    case 576: return launch_sr_peak_n<576>(a, n_pairs, stream);
-    case 600: return launch_sr_peak_n<600>(a, n_pairs, stream);
-    case 640: return launch_sr_peak_n<640>(a, n_pairs, stream);
-    case 648: return launch_sr_peak_n<648>(a, n_pairs, stream);
-    case 720: return launch_sr_peak_n<720>(a, n_pairs, stream);
-    case 750: return launch_sr_peak_n<750>(a, n_pairs, stream);
-    case 768: return launch_sr_peak_n<768>(a, n_pairs, stream);
-    case 800: return launch_sr_peak_n<800>(a, n_pairs, stream);
-    case 810: return launch_sr_peak_n<810>(a, n_pairs, stream);
-    case 864: return launch_sr_peak_n<864>(a, n_pairs, stream);
-    case 900: return launch_sr_peak_n<900>(a, n_pairs, stream);
-    case 960: return launch_sr_peak_n<960>(a, n_pairs, stream);
-    default: return hipErrorInvalidValue;
-  }
+  return sr_dispatch_size(res, [&](auto n) {
+    constexpr int N = decltype(n)::value;
+    if constexpr (N % 2 == 0 && SrNyqExact<SrPlan<N>>::value) return launch_sr_peak_n<N>(a, n_pairs, stream);
+    else return hipErrorInvalidValue;
+  });
 }
 
 // K7 alone (r04): Dt -> peak candidates, for the FFT engine's large patches of 240 / 256 / 480 pixels (pc_large_kernel.hip's L8 follows)
@@ -981,59 +929,7 @@ hipError_t launch_sr_rows_inv(const float* Dt, const float* twiddles, float2* ca
   a.twiddles = twiddles;
   a.cand = cand;
   a.n_cand = sr_candidates(res);
-  switch (res) {
-    case 200: return launch_sr_rows_inv_n<200>(a, n_pairs, stream);
-    case 216: return launch_sr_rows_inv_n<216>(a, n_pairs, stream);
-    case 240: return launch_sr_rows_inv_n<240>(a, n_pairs, stream);
-    case 256: return launch_sr_rows_inv_n<256>(a, n_pairs, stream);
-    case 250: return launch_sr_rows_inv_n<250>(a, n_pairs, stream);
-    case 400: return launch_sr_rows_inv_n<400>(a, n_pairs, stream);
-    case 432: return launch_sr_rows_inv_n<432>(a, n_pairs, stream);
-    case 270: return launch_sr_rows_inv_n<270>(a, n_pairs, stream);
-    case 300: return launch_sr_rows_inv_n<300>(a, n_pairs, stream);
-    case 450: return launch_sr_rows_inv_n<450>(a, n_pairs, stream);
-    case 288: return launch_sr_rows_inv_n<288>(a, n_pairs, stream);
-    case 320: return launch_sr_rows_inv_n<320>(a, n_pairs, stream);
-    case 360: return launch_sr_rows_inv_n<360>(a, n_pairs, stream);
-    case 384: return launch_sr_rows_inv_n<384>(a, n_pairs, stream);
-    case 480: return launch_sr_rows_inv_n<480>(a, n_pairs, stream);
-    case 512: return launch_sr_rows_inv_n<512>(a, n_pairs, stream);
-    case 225: return launch_sr_rows_inv_n<225>(a, n_pairs, stream);
-    case 243: return launch_sr_rows_inv_n<243>(a, n_pairs, stream);
-    case 375: return launch_sr_rows_inv_n<375>(a, n_pairs, stream);
-    case 405: return launch_sr_rows_inv_n<405>(a, n_pairs, stream);
-    case 625: return launch_sr_rows_inv_n<625>(a, n_pairs, stream);
-    case 675: return launch_sr_rows_inv_n<675>(a, n_pairs, stream);
-    case 729: return launch_sr_rows_inv_n<729>(a, n_pairs, stream);
-    case 128: return launch_sr_rows_inv_n<128>(a, n_pairs, stream);
-    case 96: return launch_sr_rows_inv_n<96>(a, n_pairs, stream);
-    case 100: return launch_sr_rows_inv_n<100>(a, n_pairs, stream);
-    case 108: return launch_sr_rows_inv_n<108>(a, n_pairs, stream);
-    case 120: return launch_sr_rows_inv_n<120>(a, n_pairs, stream);
-    case 150: return launch_sr_rows_inv_n<150>(a, n_pairs, stream);
-    case 162: return launch_sr_rows_inv_n<162>(a, n_pairs, stream);
-    case 144: return launch_sr_rows_inv_n<144>(a, n_pairs, stream);
-    case 160: return launch_sr_rows_inv_n<160>(a, n_pairs, stream);
-    case 180: return launch_sr_rows_inv_n<180>(a, n_pairs, stream);
-    case 192: return launch_sr_rows_inv_n<192>(a, n_pairs, stream);
-    case 324: return launch_sr_rows_inv_n<324>(a, n_pairs, stream);
-    case 486: return launch_sr_rows_inv_n<486>(a, n_pairs, stream);
-    case 500: return launch_sr_rows_inv_n<500>(a, n_pairs, stream);
-    case 540: return launch_sr_rows_inv_n<540>(a, n_pairs, stream);
-    case 576: return launch_sr_rows_inv_n<576>(a, n_pairs, stream);
-    case 600: return launch_sr_rows_inv_n<600>(a, n_pairs, stream);
-    case 640: return launch_sr_rows_inv_n<640>(a, n_pairs, stream);
-    case 648: return launch_sr_rows_inv_n<648>(a, n_pairs, stream);
-    case 720: return launch_sr_rows_inv_n<720>(a, n_pairs, stream);
-    case 750: return launch_sr_rows_inv_n<750>(a, n_pairs, stream);
-    case 768: return launch_sr_rows_inv_n<768>(a, n_pairs, stream);
-    case 800: return launch_sr_rows_inv_n<800>(a, n_pairs, stream);
-    case 810: return launch_sr_rows_inv_n<810>(a, n_pairs, stream);
-    case 864: return launch_sr_rows_inv_n<864>(a, n_pairs, stream);
-    case 900: return launch_sr_rows_inv_n<900>(a, n_pairs, stream);
-    case 960: return launch_sr_rows_inv_n<960>(a, n_pairs, stream);
-    default: return hipErrorInvalidValue;
-  }
+  return sr_dispatch_size(res, [&](auto n) { return launch_sr_rows_inv_n<decltype(n)::value>(a, n_pairs, stream); });
 }
 
 hipError_t launch_sr_phase_correlate(const SrPcArgs& a, int res, int n_pairs, hipStream_t stream) {

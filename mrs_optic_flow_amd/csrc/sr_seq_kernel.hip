@@ -620,101 +620,39 @@ hipError_t launch_sr_rows_real(const uint8_t* lp, size_t lp_stride, const float*
       src.paired = 2;
       src.grid_x = src.grid_y = 1;
       src.stride_x = src.stride_y = res;
-      return launch_sr_rows_real_src(src, twiddles, zh, zh_stride, nullptr, res, n_frames, 1, res, stream, nullptr);
+      return launch_sr_rows_real_src(SrRowsSrc{src, twiddles, zh, zh_stride, nullptr, res, 1, res, nullptr}, n_frames, stream);
     }
   }
 }
 
-hipError_t launch_sr_rows_real_src(const PclSrc& src, const float* twiddles, float* zh, size_t zh_stride, int* flags, int res, int n_images,
-                                   int channels, int n, hipStream_t stream, int* sums) {
+hipError_t launch_sr_rows_real_src(const SrRowsSrc& a, int n_images, hipStream_t stream) {
   if (n_images <= 0) return hipSuccess;
-  if ((src.paired != 1 && src.paired != 2) || (channels != 1 && channels != 3) || n < 2 || n > res) return hipErrorInvalidValue;
-  switch (res) {
-    case 200: return launch_rows_real_src_n<200>(src, twiddles, zh, zh_stride, flags, n_images, channels, n, sums, stream);
-    case 216: return launch_rows_real_src_n<216>(src, twiddles, zh, zh_stride, flags, n_images, channels, n, sums, stream);
-    case 240: return launch_rows_real_src_n<240>(src, twiddles, zh, zh_stride, flags, n_images, channels, n, sums, stream);
-    case 256: return launch_rows_real_src_n<256>(src, twiddles, zh, zh_stride, flags, n_images, channels, n, sums, stream);
-    case 250: return launch_rows_real_src_n<250>(src, twiddles, zh, zh_stride, flags, n_images, channels, n, sums, stream);
-    case 400: return launch_rows_real_src_n<400>(src, twiddles, zh, zh_stride, flags, n_images, channels, n, sums, stream);
-    case 432: return launch_rows_real_src_n<432>(src, twiddles, zh, zh_stride, flags, n_images, channels, n, sums, stream);
-    case 270: return launch_rows_real_src_n<270>(src, twiddles, zh, zh_stride, flags, n_images, channels, n, sums, stream);
-    case 300: return launch_rows_real_src_n<300>(src, twiddles, zh, zh_stride, flags, n_images, channels, n, sums, stream);
-    case 450: return launch_rows_real_src_n<450>(src, twiddles, zh, zh_stride, flags, n_images, channels, n, sums, stream);
-    case 288: return launch_rows_real_src_n<288>(src, twiddles, zh, zh_stride, flags, n_images, channels, n, sums, stream);
-    case 320: return launch_rows_real_src_n<320>(src, twiddles, zh, zh_stride, flags, n_images, channels, n, sums, stream);
-    case 360: return launch_rows_real_src_n<360>(src, twiddles, zh, zh_stride, flags, n_images, channels, n, sums, stream);
-    case 384: return launch_rows_real_src_n<384>(src, twiddles, zh, zh_stride, flags, n_images, channels, n, sums, stream);
-    case 480: return launch_rows_real_src_n<480>(src, twiddles, zh, zh_stride, flags, n_images, channels, n, sums, stream);
-    case 512: return launch_rows_real_src_n<512>(src, twiddles, zh, zh_stride, flags, n_images, channels, n, sums, stream);
-    case 225: return launch_rows_real_src_n<225>(src, twiddles, zh, zh_stride, flags, n_images, channels, n, sums, stream);
-    case 243: return launch_rows_real_src_n<243>(src, twiddles, zh, zh_stride, flags, n_images, channels, n, sums, stream);
-    case 375: return launch_rows_real_src_n<375>(src, twiddles, zh, zh_stride, flags, n_images, channels, n, sums, stream);
-    case 405: return launch_rows_real_src_n<405>(src, twiddles, zh, zh_stride, flags, n_images, channels, n, sums, stream);
-    case 625: return launch_rows_real_src_n<625>(src, twiddles, zh, zh_stride, flags, n_images, channels, n, sums, stream);
-    case 675: return launch_rows_real_src_n<675>(src, twiddles, zh, zh_stride, flags, n_images, channels, n, sums, stream);
-    case 729: return launch_rows_real_src_n<729>(src, twiddles, zh, zh_stride, flags, n_images, channels, n, sums, stream);
-    case 128: return launch_rows_real_src_n<128>(src, twiddles, zh, zh_stride, flags, n_images, channels, n, sums, stream);
-    case 96: return launch_rows_real_src_n<96>(src, twiddles, zh, zh_stride, flags, n_images, channels, n, sums, stream);
-    case 100: return launch_rows_real_src_n<100>(src, twiddles, zh, zh_stride, flags, n_images, channels, n, sums, stream);
-    case 108: return launch_rows_real_src_n<108>(src, twiddles, zh, zh_stride, flags, n_images, channels, n, sums, stream);
-    case 120: return launch_rows_real_src_n<120>(src, twiddles, zh, zh_stride, flags, n_images, channels, n, sums, stream);
-    case 150: return launch_rows_real_src_n<150>(src, twiddles, zh, zh_stride, flags, n_images, channels, n, sums, stream);
-    case 162: return launch_rows_real_src_n<162>(src, twiddles, zh, zh_stride, flags, n_images, channels, n, sums, stream);
-    case 144: return launch_rows_real_src_n<144>(src, twiddles, zh, zh_stride, flags, n_images, channels, n, sums, stream);
-    case 160: return launch_rows_real_src_n<160>(src, twiddles, zh, zh_stride, flags, n_images, channels, n, sums, stream);
-    case 180: return launch_rows_real_src_n<180>(src, twiddles, zh, zh_stride, flags, n_images, channels, n, sums, stream);
-    case 192: return launch_rows_real_src_n<192>(src, twiddles, zh, zh_stride, flags, n_images, channels, n, sums, stream);
-    case 324: return launch_rows_real_src_n<324>(src, twiddles, zh, zh_stride, flags, n_images, channels, n, sums, stream);
-    case 486: return launch_rows_real_src_n<486>(src, twiddles, zh, zh_stride, flags, n_images, channels, n, sums, stream);
-    case 500: return launch_rows_real_src_n<500>(src, twiddles, zh, zh_stride, flags, n_images, channels, n, sums, stream);
-    case 540: return launch_rows_real_src_n<540>(src, twiddles, zh, zh_stride, flags, n_images, channels, n, sums, stream);
-    case 576: return launch_rows_real_src_n<576>(src, twiddles, zh, zh_stride, flags, n_images, channels, n, sums, stream);
-    case 600: return launch_rows_real_src_n<600>(src, twiddles, zh, zh_stride, flags, n_images, channels, n, sums, stream);
-    case 640: return launch_rows_real_src_n<640>(src, twiddles, zh, zh_stride, flags, n_images, channels, n, sums, stream);
-    case 648: return launch_rows_real_src_n<648>(src, twiddles, zh, zh_stride, flags, n_images, channels, n, sums, stream);
-    case 720: return launch_rows_real_src_n<720>(src, twiddles, zh, zh_stride, flags, n_images, channels, n, sums, stream);
-    case 750: return launch_rows_real_src_n<750>(src, twiddles, zh, zh_stride, flags, n_images, channels, n, sums, stream);
-    case 768: return launch_rows_real_src_n<768>(src, twiddles, zh, zh_stride, flags, n_images, channels, n, sums, stream);
-    case 800: return launch_rows_real_src_n<800>(src, twiddles, zh, zh_stride, flags, n_images, channels, n, sums, stream);
-    case 810: return launch_rows_real_src_n<810>(src, twiddles, zh, zh_stride, flags, n_images, channels, n, sums, stream);
-    case 864: return launch_rows_real_src_n<864>(src, twiddles, zh, zh_stride, flags, n_images, channels, n, sums, stream);
-    case 900: return launch_rows_real_src_n<900>(src, twiddles, zh, zh_stride, flags, n_images, channels, n, sums, stream);
-    case 960: return launch_rows_real_src_n<960>(src, twiddles, zh, zh_stride, flags, n_images, channels, n, sums, stream);
-    default: return hipErrorInvalidValue;
-  }
+  if ((a.src.paired != 1 && a.src.paired != 2) || (a.channels != 1 && a.channels != 3) || a.n < 2 || a.n > a.res) return hipErrorInvalidValue;
+  return sr_dispatch_size(a.res, [&](auto n) {
+    return launch_rows_real_src_n<decltype(n)::value>(a.src, a.twiddles, a.zh, a.zh_stride, a.flags, n_images, a.channels, a.n, a.sums, stream);
+  });
 }
 
-// the transform sizes K6s is instantiated for: every size of sr_transform_size_tuned (sr_kernel.hip)
-#define MOF_SR_SEQ_SIZES(X) X(96) X(100) X(108) X(120) X(128) X(144) X(150) X(160) X(162) X(180) X(192) X(200) X(216) X(225) X(240) X(243) \
-  X(250) X(256) X(270) X(288) X(300) X(320) X(324) X(360) X(375) X(384) X(400) X(405) X(432) X(450) X(480) X(486) X(500) X(512) X(540) \
-  X(576) X(600) X(625) X(640) X(648) X(675) X(720) X(729) X(750) X(768) X(800) X(810) X(864) X(900) X(960)
-
-hipError_t launch_sr_cols_seq(const float* zh_prev, const float* zh_cur, size_t zh_stride, const float* twiddles, float* Dt, int res,
-                              int n_pairs, int run, hipStream_t stream, const int* flags, int n, const int* sums_prev, const int* sums_cur, int sums_stride) {
+hipError_t launch_sr_cols_seq(const SrColsSeq& a, int n_pairs, hipStream_t stream) {
   if (n_pairs <= 0) return hipSuccess;
-  if (run < 1) run = 1;
-  if (flags && run != 1) return hipErrorInvalidValue;  // (the box-zero flags are per independent pair: image 2 p = cur, 2 p + 1 = prev)
-  if (n <= 0) n = res;
+  const int run = a.run < 1 ? 1 : a.run;
+  if (a.flags && run != 1) return hipErrorInvalidValue;  // (the box-zero flags are per independent pair: image 2 p = cur, 2 p + 1 = prev)
   // a run longer than one pair walks cur(p) as prev(p + 1): only valid for a contiguous sequence
-  if (run > 1 && zh_cur != zh_prev + zh_stride) return hipErrorInvalidValue;
-  switch (res) {
-#define X(N) \
-  case N: return launch_cols_seq_n<N>(zh_prev, zh_cur, zh_stride, twiddles, Dt, n_pairs, run, flags, n, sums_prev, sums_cur, sums_stride, stream);
-    MOF_SR_SEQ_SIZES(X)
-#undef X
-    default: return hipErrorInvalidValue;
-  }
+  if (run > 1 && a.zh_cur != a.zh_prev + a.zh_stride) return hipErrorInvalidValue;
+  return sr_dispatch_size(a.res, [&](auto n) {
+    return launch_cols_seq_n<decltype(n)::value>(a.zh_prev, a.zh_cur, a.zh_stride, a.twiddles, a.Dt, n_pairs, run, a.flags, a.n <= 0 ? a.res : a.n,
+                                                 a.sums_prev, a.sums_cur, a.sums_stride, stream);
+  });
 }
 
 // K6s's columns per wave at transform size res (seq_cw), 0 where it has no instantiation
 int sr_seq_columns_per_wave(int res) {
-  switch (res) {
-#define X(N) \
-  case N: return seq_cw<N>();
-    MOF_SR_SEQ_SIZES(X)
-#undef X
-    default: return 0;
-  }
+  int cw = 0;
+  (void)sr_dispatch_size(res, [&](auto n) {
+    cw = seq_cw<decltype(n)::value>();
+    return hipSuccess;
+  });
+  return cw;
 }
 
 }  // namespace mof

@@ -4,7 +4,9 @@
 //   * every entry point on a null engine,
 //   * the scale/rotation estimator's host-built tables (cv::logPolar maps in remap's fixed point, cubic / Lanczos4
 //     weight tables), compared entry by entry with the oracle's tables,
-//   * the geometry tail's host forms (getRT / get2DT and their stages).
+//   * the geometry tail's host forms (getRT / get2DT and their stages),
+//   * the estimator's create-time route (sr_route) for every even resolution against tests/golden/sr_route_table.txt, recorded from the
+//     code before SrRoute existed, and the one list of tuned transform sizes seen through each of its three users.
 // Where a device IS present the create() calls succeed and the engines are destroyed again.
 #include <cmath>
 #include <cstdio>
@@ -13,6 +15,7 @@
 
 #include "mof.h"
 #include "mof_kernels.h"
+#include "sr_common.hpp"
 extern "C" {
 #include "oracle.h"
 }
@@ -138,6 +141,62 @@ int main() {
         CHECK(sum == 1 << 15);
       }
     }
+  }
+  // ---- the estimator's route, decided without a device ----
+  {
+    std::FILE* f = std::fopen(MOF_GOLDEN_DIR "/sr_route_table.txt", "r");
+    CHECK(f != nullptr);
+    static const char* const families[] = {"TUNED", "TUNED_PAD", "PLANNED"};
+    char line[256], fam[16];
+    int rows = 0;
+    while (std::fgets(line, sizeof line, f)) {
+      if (line[0] == '#') continue;
+      int all, res, m, sums, cand;
+      size_t off, zh;
+      const int got = std::sscanf(line, "%d %d %15s %d %d %zu %zu %d", &all, &res, fam, &m, &sums, &off, &zh, &cand);
+      CHECK(got == 3 || got == 8);
+      mof::SrKnobs k;
+      k.tuned_all = all != 0;
+      mof::PcPlan plan{};
+      mof::SrRoute r;
+      const bool ok = mof::sr_route(res, k, &plan, &r);
+      if (got == 3) {
+        CHECK(std::strcmp(fam, "unsupported") == 0 && !ok);
+      } else {
+        CHECK(ok && std::strcmp(fam, families[r.family]) == 0 && r.m == m && r.sums == (sums != 0) && r.sums_off == off);
+        CHECK(r.zh_floats == zh && r.candidates == cand && r.pairs == mof::SrRoute::FRAMES && r.seq_run == 0);
+        CHECK(r.family == mof::SrRoute::TUNED || (plan.n == res && plan.m == m));
+      }
+      ++rows;
+    }
+    std::fclose(f);
+    CHECK(rows == 2 * 493);  // even resolutions 16 .. 1000, MOF_SR_TUNED_ALL unset and 0
+    // the pair form of the batch entry and the fixed K6s run follow their knobs
+    for (int res = 16; res <= 1000; res += 2) {
+      mof::SrKnobs k;
+      mof::PcPlan plan{};
+      mof::SrRoute r;
+      k.pair_seq = false;
+      k.fused = true;
+      k.seq_run = 7;
+      if (!mof::sr_route(res, k, &plan, &r)) continue;
+      const bool tuned = r.family == mof::SrRoute::TUNED;
+      const mof::SrRoute::Pairs want = mof::sr_pair_kernels_supported(res) ? mof::SrRoute::PACKED
+                                       : tuned && mof::sr_fused_supported(res) ? mof::SrRoute::FUSED : mof::SrRoute::FRAMES;
+      CHECK(r.pairs == want && r.seq_run == 7);
+      k.pair_seq = true;
+      CHECK(mof::sr_route(res, k, &plan, &r) && r.pairs == (tuned && mof::sr_fused_supported(res) ? mof::SrRoute::FUSED : mof::SrRoute::FRAMES));
+    }
+    // one list of tuned transform sizes, whoever is asked
+    int listed = 0;
+    for (int m = 2; m <= 1000; ++m) {
+      bool exact = false;
+      const bool tuned = mof::sr_transform_size_tuned(m, &exact);
+      const bool in_list = mof::sr_dispatch_size(m, [](auto) { return hipSuccess; }) == hipSuccess;
+      CHECK(tuned == in_list && tuned == (mof::sr_seq_columns_per_wave(m) != 0));
+      listed += tuned;
+    }
+    CHECK(listed == 50);
   }
   // ---- geometry tail, host forms ----
   {

@@ -353,6 +353,49 @@ def test_video_form_of_the_tuned_large_patch_path(gpu):
         assert r.returncode == 0 and "large video ok 26" in r.stdout, (env, r.stdout[-1500:], r.stderr[-2500:])
 
 
+@pytest.mark.parametrize("n", [200, 250])
+def test_large_patch_engine_on_two_streams(gpu, n):
+    """The FFT engine's large-patch pipeline runs through engine-owned scratch (row spectra, Dt, candidates, flags -- and at 250, whose
+    Nyquist bin is not exact, the images' exact pixel sums): batches issued back to back on two different streams must not corrupt each other
+    (the second stream waits for the first batch's last kernel, capi_graph.hpp: ScratchFence), nor may the stateful entry on the engine's
+    own stream right behind a batch. 200 is the smallest patch on the tuned large route; 48 pairs of one patch each keep a batch on the GPU
+    long enough to overlap with the next. A regression guard for the ordering, not a proof of it: a missing wait CAN go unnoticed."""
+    B = 48
+    cur, prev, _, _ = synth.batch_np(B, n, n, 6, classes=False, k0=n)
+    ta, tb = torch.from_numpy(cur).to(gpu), torch.from_numpy(prev).to(gpu)
+    fm = FftMethod(n, n, 80.0)
+    assert fm.kernel_variant == "planned-large" and fm.n_patches == 1
+    fm.processImage(prev[0])  # (an engine's very first frame is correlated with itself, FftMethod.cpp:1791-1793)
+    want_one = fm.processImage(cur[0])
+    want1 = fm.process_batch_device(ta, tb).clone()
+    want2 = fm.process_batch_device(tb, ta).clone()
+    torch.cuda.synchronize()
+    assert torch.isfinite(want1).sum() > B and not torch.equal(torch.nan_to_num(want1), torch.nan_to_num(want2))
+    assert np.abs(want_one).max() > 1  # (a real pair, not the first frame's self-correlation)
+
+    def same(a, b):
+        return torch.equal(torch.nan_to_num(a, nan=-1e9), torch.nan_to_num(b, nan=-1e9))
+
+    s1, s2 = torch.cuda.Stream(), torch.cuda.Stream()
+    for _ in range(4):
+        with torch.cuda.stream(s1):
+            got1 = fm.process_batch_device(ta, tb)
+        with torch.cuda.stream(s2):
+            got2 = fm.process_batch_device(tb, ta)
+        with torch.cuda.stream(s1):
+            got3 = fm.process_batch_device(ta, tb)
+        torch.cuda.synchronize()
+        assert same(got1, want1) and same(got2, want2) and same(got3, want1)
+    # the stateful entry (engine's own stream) right behind a batch on another stream
+    fm.processImage(prev[0])
+    with torch.cuda.stream(s2):
+        got2 = fm.process_batch_device(tb, ta)
+    one = fm.processImage(cur[0])
+    torch.cuda.synchronize()
+    assert same(got2, want2)
+    assert np.array_equal(one, want_one, equal_nan=True)
+
+
 # ---- scaleRotationEstimator at any even resolution (scaleRotationEstimator.cpp:3-32) ----
 @pytest.mark.parametrize("res,M", [(320, 45.0), (360, 49.9), (400, 49.9), (128, 25.0), (200, 35.0), (250, 40.0), (300, 49.9),
                                     (350, 49.9), (500, 60.0), (192, 30.0), (640, 70.0), (720, 75.0), (270, 40.0), (208, 35.0), (336, 49.9), (416, 55.0), (432, 55.0), (496, 60.0), (160, 30.0), (180, 30.0), (144, 28.0), (220, 35.0), (370, 50.0), (100, 22.0), (120, 25.0), (150, 28.0), (104, 22.0)])
