@@ -561,9 +561,7 @@ __global__ void __launch_bounds__(256) bm_refine_sad_kernel(const uint8_t* __res
   }
 #pragma unroll
   for (int k = 0; k < 9; ++k) {
-    unsigned int v = acc[k];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += (unsigned int)__shfl_xor((int)v, off, 64);
+    const unsigned int v = wave_sum(acc[k]);
     if ((tid & 63) == 0) red[tid >> 6][k] = v;
   }
   __syncthreads();

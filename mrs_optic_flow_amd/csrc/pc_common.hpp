@@ -242,6 +242,92 @@ __device__ __forceinline__ Best better(Best a, Best b) {
   return (b.v > a.v || (b.v == a.v && b.idx < a.idx)) ? b : a;
 }
 
+// ---- cross-lane exchange on the VALU -------------------------------------------------------------------------------
+// lane_xor<OFF>(x) = the x of lane (lane ^ OFF), OFF in {32, 16, 8, 4, 2, 1}: what __shfl_xor(x, OFF, 64) returns, without
+// the trip through the wave's in-order LDS queue that ds_bpermute_b32 takes (the peak tails are chains of 12 - 14
+// dependent exchanges at the end of every patch, on a CU whose LDS pipe is busy with the other workgroups' tiles):
+//   32: v_permlane32_swap   16: v_permlane16_swap   8: DPP row_ror:8   4: DPP row_shl:4 | row_shr:4 under complementary
+//   bank masks   2, 1: DPP quad_perm
+// CONTRACT: ALL 64 LANES ACTIVE. DPP and the swaps keep the old value where the source lane is inactive, ds_bpermute
+// returns 0 there: a call site inside lane-divergent control flow stays on __shfl_xor.
+__device__ __forceinline__ int wave_lane() { return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
+
+template <int OFF>
+__device__ __forceinline__ uint32_t lane_xor(uint32_t x) {
+  static_assert(OFF == 32 || OFF == 16 || OFF == 8 || OFF == 4 || OFF == 2 || OFF == 1, "one butterfly level");
+  if constexpr (OFF == 32) {
+    // (x, x) -> r[0] = {x[0..31], x[0..31]}, r[1] = {x[32..63], x[32..63]}: the partner is picked explicitly (better() is
+    // not symmetric in its operands when one is NaN, so "op(r[0], r[1])" would not be the same butterfly)
+    const auto r = __builtin_amdgcn_permlane32_swap(x, x, false, false);
+    return (wave_lane() & 32) ? r[0] : r[1];
+  } else if constexpr (OFF == 16) {
+    const auto r = __builtin_amdgcn_permlane16_swap(x, x, false, false);  // the same, by bit 4 of the lane
+    return (wave_lane() & 16) ? r[0] : r[1];
+  } else if constexpr (OFF == 8) {
+    return (uint32_t)__builtin_amdgcn_update_dpp((int)x, (int)x, 0x128, 0xf, 0xf, false);  // row_ror:8
+  } else if constexpr (OFF == 4) {
+    const int lo = __builtin_amdgcn_update_dpp((int)x, (int)x, 0x104, 0xf, 0x5, false);  // row_shl:4 -> lanes 0-3, 8-11 of a row
+    return (uint32_t)__builtin_amdgcn_update_dpp(lo, (int)x, 0x114, 0xf, 0xa, false);    // row_shr:4 -> lanes 4-7, 12-15
+  } else if constexpr (OFF == 2) {
+    return (uint32_t)__builtin_amdgcn_update_dpp((int)x, (int)x, 0x4e, 0xf, 0xf, false);  // quad_perm:[2,3,0,1]
+  } else {
+    return (uint32_t)__builtin_amdgcn_update_dpp((int)x, (int)x, 0xb1, 0xf, 0xf, false);  // quad_perm:[1,0,3,2]
+  }
+}
+template <int OFF>
+__device__ __forceinline__ int lane_xor(int x) { return (int)lane_xor<OFF>((uint32_t)x); }
+template <int OFF>
+__device__ __forceinline__ float lane_xor(float x) { return __uint_as_float(lane_xor<OFF>(__float_as_uint(x))); }
+template <int OFF>
+__device__ __forceinline__ double lane_xor(double x) {
+  const uint64_t u = (uint64_t)__double_as_longlong(x);
+  const uint32_t lo = lane_xor<OFF>((uint32_t)u), hi = lane_xor<OFF>((uint32_t)(u >> 32));
+  return __longlong_as_double((long long)((uint64_t)hi << 32 | lo));
+}
+
+// The butterflies of the peak tails, levels TOP, TOP/2 .. 1 with the partners and the operand order of the __shfl_xor
+// loops they replace (same bits). TOP < 32 where only the first 2 TOP lanes hold non-zero terms.
+template <int TOP = 32, class T>
+__device__ __forceinline__ T wave_sum(T v) {
+  if constexpr (TOP >= 32) v += lane_xor<32>(v);
+  if constexpr (TOP >= 16) v += lane_xor<16>(v);
+  v += lane_xor<8>(v);
+  v += lane_xor<4>(v);
+  v += lane_xor<2>(v);
+  v += lane_xor<1>(v);
+  return v;
+}
+template <int OFF>
+__device__ __forceinline__ void wave_sum3_level(double& a, double& b, double& c) {
+  const double oa = lane_xor<OFF>(a), ob = lane_xor<OFF>(b), oc = lane_xor<OFF>(c);
+  a += oa;
+  b += ob;
+  c += oc;
+}
+template <int TOP = 32>
+__device__ __forceinline__ void wave_sum3(double& a, double& b, double& c) {
+  if constexpr (TOP >= 32) wave_sum3_level<32>(a, b, c);
+  if constexpr (TOP >= 16) wave_sum3_level<16>(a, b, c);
+  wave_sum3_level<8>(a, b, c);
+  wave_sum3_level<4>(a, b, c);
+  wave_sum3_level<2>(a, b, c);
+  wave_sum3_level<1>(a, b, c);
+}
+template <int OFF>
+__device__ __forceinline__ Best wave_best_level(Best b) {
+  const Best o = {lane_xor<OFF>(b.v), lane_xor<OFF>(b.idx)};
+  return better(b, o);
+}
+// every lane ends with the wave's first maximum (better())
+__device__ __forceinline__ Best wave_best(Best b) {
+  b = wave_best_level<32>(b);
+  b = wave_best_level<16>(b);
+  b = wave_best_level<8>(b);
+  b = wave_best_level<4>(b);
+  b = wave_best_level<2>(b);
+  return wave_best_level<1>(b);
+}
+
 
 // cv::cvtColor(.., CV_RGB2GRAY) on 8-bit data (fixed point, yuv_shift 14): gray = (c0*R2Y + c1*G2Y + c2*B2Y + 2^13) >> 14
 // with R2Y 4899, G2Y 9617, B2Y 1868. The node feeds it BGR8 data (optic_flow.cpp:1465 toCvCopy(BGR8), :1622
@@ -431,12 +517,7 @@ __device__ __forceinline__ void centroid_gate_store(Best best, float wval, int l
   const int ys = py - RAD + lane / W, xs = px - RAD + lane % W;
   const double val = (double)wval;  // 0 for lanes outside the window
   double cx = (double)xs * val, cy = (double)ys * val, sum = val;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    cx += __shfl_xor(cx, off, 64);
-    cy += __shfl_xor(cy, off, 64);
-    sum += __shfl_xor(sum, off, 64);
-  }
+  wave_sum3(cx, cy, sum);
   if (lane == 0) {
     sum += PK == 1 ? 1.1920928955078125e-07 : 2.220446049250313e-16;  // FLT_EPSILON cl:1342 / DBL_EPSILON :1378
     // shift = -(center - t) = t - N/2   (:1836); the OpenCL branch returns centroid - N/2 un-negated (cl:1370, :1833)

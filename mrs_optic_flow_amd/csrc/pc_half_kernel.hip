@@ -868,11 +868,7 @@ have_current:
     else
       pass_lines_static<SP, 0, 1, HalfScanSink>(z, tw, rows, l0, nl, lane, false, HalfScanSink{&best, M, H});
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    Best o = {__shfl_xor(best.v, off, 64), __shfl_xor(best.idx, off, 64)};
-    best = better(best, o);
-  }
+  best = wave_best(best);
   if (lane == 0) red[wave] = best;
   __syncthreads();
 
@@ -889,12 +885,7 @@ have_current:
       val = (double)((y & 1) ? s.y : s.x);
     }
     double cx = (double)xs * val, cy = (double)ys * val, sum = val;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      cx += __shfl_xor(cx, off, 64);
-      cy += __shfl_xor(cy, off, 64);
-      sum += __shfl_xor(sum, off, 64);
-    }
+    wave_sum3(cx, cy, sum);
     if (lane == 0) {
       sum += 2.220446049250313e-16;  // DBL_EPSILON :1378
       // shift = -(center - t) = t - M / 2.0 (:1836): cv::phaseCorrelate's centre is that of the PADDED image

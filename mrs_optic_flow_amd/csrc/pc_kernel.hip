@@ -55,6 +55,9 @@ namespace mof {
 #ifndef MOF_K1_MFMA_S1  // S1 of the three-stage forward transform on the matrix cores (pc_passes3.hpp)
 #define MOF_K1_MFMA_S1 0
 #endif
+#ifndef MOF_K1_TAIL_BARRIER  // 0: no barrier between the window read and the centroid where a workgroup runs ONE patch
+#define MOF_K1_TAIL_BARRIER 1
+#endif
 template <int N, int DS, int CH, int PK>
 __global__ void __launch_bounds__(PcTraits<N>::T) pc_field_kernel(PcArgs a) {
   static_assert(CH == 1 || (CH == 3 && DS == 1), "BGR front end only for the full-resolution path");
@@ -325,11 +328,7 @@ __global__ void __launch_bounds__(PcTraits<N>::T) pc_field_kernel(PcArgs a) {
 #else
   best = Best{z[zaddr<N>(lane, wave)].x, lane * N + wave};
 #endif
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    Best o = {__shfl_xor(best.v, off, 64), __shfl_xor(best.idx, off, 64)};
-    best = better(best, o);
-  }
+  best = wave_best(best);
   if (lane == 0) red[wave] = best;
   __syncthreads();
 
@@ -351,7 +350,8 @@ __global__ void __launch_bounds__(PcTraits<N>::T) pc_field_kernel(PcArgs a) {
     });
     degenerate = const_codes_degenerate<P::WAVES>(my_code, lane);
   }
-  __syncthreads();  // (needed by the persistent form only; dropping it for one-workgroup-per-patch sizes measured -1 %)
+  // (needed by the persistent form only; -DMOF_K1_TAIL_BARRIER=0 drops it where a workgroup runs one patch: A/B in DESIGN 8)
+  if constexpr (PERSIST || MOF_K1_TAIL_BARRIER) __syncthreads();
   if (wave == 0)
     centroid_gate_store<N, PK>(best, wval, lane, a.max_px_speed_sq, a.out + 2 * (size_t)p, degenerate,
                                degenerate ? *reinterpret_cast<const float*>(const_code + 16) : 0.f);

@@ -471,11 +471,7 @@ __global__ void __launch_bounds__(StaticPlanOf<MS>::T, StaticPlanOf<MS>::WPE) pc
       best = better(best, Best{surf(y, x), ys * m + xs});
     }
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    Best o = {__shfl_xor(best.v, off, 64), __shfl_xor(best.idx, off, 64)};
-    best = better(best, o);
-  }
+  best = wave_best(best);
   if (lane == 0) red[wave] = best;
   __syncthreads();
 
@@ -494,12 +490,7 @@ __global__ void __launch_bounds__(StaticPlanOf<MS>::T, StaticPlanOf<MS>::WPE) pc
       val = (double)((PK == 1 && !(v > 0.f)) ? 0.f : v);
     }
     double cx = (double)xs * val, cy = (double)ys * val, sum = val;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      cx += __shfl_xor(cx, off, 64);
-      cy += __shfl_xor(cy, off, 64);
-      sum += __shfl_xor(sum, off, 64);
-    }
+    wave_sum3(cx, cy, sum);
     if (lane == 0) {
       sum += PK == 1 ? 1.1920928955078125e-07 : 2.220446049250313e-16;  // FLT_EPSILON cl:1342 / DBL_EPSILON :1378
       // shift = -(center - t) = t - M / 2.0 (:1836): cv::phaseCorrelate's centre is that of the PADDED image

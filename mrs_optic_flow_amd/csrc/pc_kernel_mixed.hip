@@ -419,11 +419,7 @@ __global__ void __launch_bounds__(T) pc_field_kernel_120(PcArgs a) {
   __syncthreads();
   Best best = {-__builtin_huge_valf(), 0x7fffffff};
   if (wave * LPW < H) best = col_pass_inv<PK>(z, wave * LPW, lane, tw, a.search_radius);
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    Best o = {__shfl_xor(best.v, off, 64), __shfl_xor(best.idx, off, 64)};
-    best = better(best, o);
-  }
+  best = wave_best(best);
   if (lane == 0) red[wave] = best;
   __syncthreads();
 

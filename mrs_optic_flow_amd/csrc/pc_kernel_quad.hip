@@ -362,11 +362,7 @@ __global__ void __launch_bounds__(T, 4) pc_quad64_kernel(PcArgs a) {
       mi = min(mi, v[k].y == m ? y1 * N + xs0 + k : 0x7fffffff);
     }
     best = Best{m, mi};
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      Best o = {__shfl_xor(best.v, off, 64), __shfl_xor(best.idx, off, 64)};
-      best = better(best, o);
-    }
+    best = wave_best(best);
     if (lane == 0) red[wave] = best;
   }
   __syncthreads();

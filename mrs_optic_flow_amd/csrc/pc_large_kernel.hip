@@ -267,11 +267,8 @@ __global__ void __launch_bounds__(64) pcl_cdc_kernel(const float* __restrict__ z
     sc += (double)c[v].x;
     sp += (double)p[v].x;
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    sc += __shfl_xor(sc, off, 64);
-    sp += __shfl_xor(sp, off, 64);
-  }
+  sc = wave_sum(sc);
+  sp = wave_sum(sp);
   if (lane == 0) cdc[pair] = cross_power_ab(cf{(float)sc, 0.f}, cf{(float)sp, 0.f}, true).x;
 }
 
@@ -332,11 +329,7 @@ __global__ void __launch_bounds__(PCL_T) pcl_rows_inv_kernel(const float* __rest
       if (y2 < m) best = better(best, Best{v.y, r2 + xs});
     }
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    Best o = {__shfl_xor(best.v, off, 64), __shfl_xor(best.idx, off, 64)};
-    best = better(best, o);
-  }
+  best = wave_best(best);
   if (lane == 0) red[wave] = best;
   __syncthreads();
   if (tid == 0) {
@@ -363,11 +356,7 @@ __global__ void __launch_bounds__(64) pcl_final_kernel(PclFinal a) {
     const float2 c = a.cand[(size_t)pair * a.n_cand + i];
     best = better(best, Best{c.x, __float_as_int(c.y)});
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    Best o = {__shfl_xor(best.v, off, 64), __shfl_xor(best.idx, off, 64)};
-    best = better(best, o);
-  }
+  best = wave_best(best);
   const cf* Dt = reinterpret_cast<const cf*>(a.Dt) + (size_t)pair * (H + 1) * m;
   const bool have = best.idx != 0x7fffffff;
   const int px = have ? best.idx % m : 0, py = have ? best.idx / m : 0;
@@ -411,12 +400,7 @@ __global__ void __launch_bounds__(64) pcl_final_kernel(PclFinal a) {
     cy = (double)ys * val;
     sum = val;
   }
-#pragma unroll
-  for (int off = WW > 32 ? 32 : 16; off > 0; off >>= 1) {
-    cx += __shfl_xor(cx, off, 64);
-    cy += __shfl_xor(cy, off, 64);
-    sum += __shfl_xor(sum, off, 64);
-  }
+  wave_sum3<(WW > 32 ? 32 : 16)>(cx, cy, sum);
   if (lane != 0) return;
   sum += PK == 1 ? 1.1920928955078125e-07 : 2.220446049250313e-16;  // FLT_EPSILON cl:1342 / DBL_EPSILON, FftMethod.cpp:1378
   const double half_m = (double)m / 2.0;  // cv::phaseCorrelate's centre: that of the PADDED image

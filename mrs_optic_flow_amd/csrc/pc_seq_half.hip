@@ -496,11 +496,7 @@ __global__ void __launch_bounds__(HalfTile<N>::T, (N == 64 ? 4 : 2)) pc_seq_half
     }
     __syncthreads();
     Best best = half_row_pairs<N, PK>(z, 8 * wave, lane, tw, a.search_radius);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      Best o = {__shfl_xor(best.v, off, 64), __shfl_xor(best.idx, off, 64)};
-      best = better(best, o);
-    }
+    best = wave_best(best);
     if (lane == 0) red[wave] = best;
     __syncthreads();
     float wval = 0.f;
@@ -597,11 +593,7 @@ __global__ void __launch_bounds__(HalfTile<N>::T, MOF_PAIR_HALF_WPE) pc_pair_hal
     //  zero spectrum the reference's transforms give it and the flat surface produces the degenerate answer by itself, as in the
     //  sequence kernel above)
     Best best = half_row_pairs<N, PK>(z, 8 * wave, lane, tw, a.search_radius);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      Best o = {__shfl_xor(best.v, off, 64), __shfl_xor(best.idx, off, 64)};
-      best = better(best, o);
-    }
+    best = wave_best(best);
     if (lane == 0) red[wave] = best;
     __syncthreads();
     float wval = 0.f;

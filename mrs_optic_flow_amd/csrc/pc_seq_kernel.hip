@@ -263,11 +263,7 @@ __global__ void __launch_bounds__(256) pc_seq_kernel(PcArgs a, int n_pairs, int 
     __syncthreads();
     // ---- 3. row pairs + arg-max (fftShift :1297-1305, minMaxLoc :1539)
     Best best = row_pass_inv64<PK>(z, 8 * wave, lane, tw_row, a.search_radius);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      Best o = {__shfl_xor(best.v, off, 64), __shfl_xor(best.idx, off, 64)};
-      best = better(best, o);
-    }
+    best = wave_best(best);
     if (lane == 0) red[wave] = best;
     __syncthreads();
     // ---- 4. 5x5 weighted centroid in double + validity gate (:1337-1383, :1838-1856), wave 0

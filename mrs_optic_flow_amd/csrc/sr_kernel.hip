@@ -678,11 +678,7 @@ __global__ void __launch_bounds__(K7Cfg<N>::T) sr_rows_inv_kernel(SrPcArgs a) {
       if (!ODD || y2 < N) best = better(best, Best{v[k2].y, r2 + xs});
     }
   });
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    Best o = {__shfl_xor(best.v, off, 64), __shfl_xor(best.idx, off, 64)};
-    best = better(best, o);
-  }
+  best = wave_best(best);
   if (lane == 0) red[wave] = best;
   __syncthreads();
   if (tid == 0) {
@@ -707,11 +703,7 @@ __global__ void __launch_bounds__(64) sr_final_kernel(SrPcArgs a) {
     const float2 c = a.cand[(size_t)pair * a.n_cand + i];
     best = better(best, Best{c.x, __float_as_int(c.y)});
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    Best o = {__shfl_xor(best.v, off, 64), __shfl_xor(best.idx, off, 64)};
-    best = better(best, o);
-  }
+  best = wave_best(best);
   const cf* Dt = reinterpret_cast<const cf*>(a.Dt) + (size_t)pair * (H + 1) * N;
   const bool have = best.idx != 0x7fffffff;
   const int px = have ? best.idx % N : 0, py = have ? best.idx / N : 0;
@@ -753,12 +745,7 @@ __global__ void __launch_bounds__(64) sr_final_kernel(SrPcArgs a) {
     cy = (double)ys * val;
     sum = val;
   }
-#pragma unroll
-  for (int off = 16; off > 0; off >>= 1) {
-    cx += __shfl_xor(cx, off, 64);
-    cy += __shfl_xor(cy, off, 64);
-    sum += __shfl_xor(sum, off, 64);
-  }
+  wave_sum3<16>(cx, cy, sum);
   if (lane == 0) {
     sum += 2.220446049250313e-16;
     double ptx = (double)N / 2.0 - cx / sum, pty = (double)N / 2.0 - cy / sum;

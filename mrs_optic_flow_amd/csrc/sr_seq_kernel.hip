@@ -205,13 +205,10 @@ __global__ void __launch_bounds__(RowsReal<N>::T) sr_rows_real_src_kernel(PclSrc
     }
   }
   if constexpr (!SrNyqExact<P>::value) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      s00 += __shfl_xor(s00, off, 64);
-      s01 += __shfl_xor(s01, off, 64);
-      s10 += __shfl_xor(s10, off, 64);
-      s11 += __shfl_xor(s11, off, 64);
-    }
+    s00 = wave_sum(s00);
+    s01 = wave_sum(s01);
+    s10 = wave_sum(s10);
+    s11 = wave_sum(s11);
 #ifndef MOF_SR_SUMS_ABLATE  // (diagnostic build: no atomics -- results wrong by design)
     if (lane == 0 && sums) {  // (zeroed by the caller; 255 * 432^2 < 2^31)
       int* q = sums + (size_t)(src.sums_stride ? src.sums_stride : 4) * img;
