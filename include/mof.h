@@ -210,6 +210,33 @@ int mof_fft_process_batch_device_bgr(mof_fft_engine* e, const uint8_t* d_cur, si
 int mof_fft_process_batch_host(mof_fft_engine* e, const uint8_t* cur, size_t cur_stride, const uint8_t* prev,
                                size_t prev_stride, size_t pitch, int n_pairs, double* out_xy);
 
+/* Per-patch correlation quality: the *_q forms of the entries above hand out, beside every shift, two doubles about the correlation
+ * surface the shift was read from -- quality[2 * (pair * patches + patch) + {0, 1}] = (response, peak):
+ *   MOF_PEAK_OPENCV  response = the sum of the surface over the 5 x 5 window (clamped to the padded patch) around its first maximum,
+ *                    taken before DBL_EPSILON is added, divided by M^2, M = getOptimalDFTSize(patch_size) the padded transform side:
+ *                    the `response` output of cv::phaseCorrelate (weightedCentroid, FftMethod.cpp:1337-1383), which the reference
+ *                    never reads. peak = the surface value at that maximum / M^2.
+ *   MOF_PEAK_OCL     response = refine()'s sum: the values > 0 of the clamped 7 x 7 window, seeded with FLT_EPSILON, of the surface the
+ *                    kernel has already scaled by 1 / N^2 and masked (cl/FftMethod.cl:1315-1379); peak = its first maximum, raw.
+ * A matched pair has a response near 1, independent noise about 0.1. The value is OpenCV's response and, like every number of this
+ * engine, held to the CPU oracle, not pinned to a bit pattern. It does not depend on the validity gate: a patch whose shift is NaN
+ * because of max_px_speed or the +- patch_size / 2 rule still reports its response and peak. A surface that is NaN throughout gives
+ * (NaN, NaN). A constant patch: under MOF_PEAK_OPENCV the flat surface's values, peak = C_dc / M^2 and response = 9 peak (the window at
+ * the corner is clamped to 3 x 3; both 0 for an all-zero patch); under MOF_PEAK_OCL (NaN, NaN), as the shift.
+ * quality / d_quality may be null: the call is then the entry without _q (which is this code with a null pointer; every output keeps
+ * its bits either way). The device entries allocate nothing and may be captured into a HIP graph under the rules above. channels:
+ * 1 gray, 3 BGR8 (pitch in bytes); long_range 0 | 1, not together with channels == 3 (MOF_ERR_BAD_ARG). Out of scope: the estimator's
+ * response (mof_sr_*) and the sharded entries. */
+int mof_fft_process_q(mof_fft_engine* e, const uint8_t* frame, size_t pitch, double* out_xy, double* quality, int* n_invalid);
+int mof_fft_process_long_range_q(mof_fft_engine* e, const uint8_t* frame, size_t pitch, double* out_xy, double* quality, int* n_invalid);
+int mof_fft_process_batch_device_q(mof_fft_engine* e, const uint8_t* d_cur, size_t cur_stride, const uint8_t* d_prev, size_t prev_stride,
+                                   size_t pitch, int n_pairs, int channels, int long_range, double* d_out_xy, double* d_quality,
+                                   void* stream);
+int mof_fft_process_sequence_device_q(mof_fft_engine* e, const uint8_t* d_frames, size_t frame_stride, size_t pitch, int n_frames,
+                                      int channels, double* d_out_xy, double* d_quality, void* stream);
+int mof_fft_process_batch_host_q(mof_fft_engine* e, const uint8_t* cur, size_t cur_stride, const uint8_t* prev, size_t prev_stride,
+                                 size_t pitch, int n_pairs, double* out_xy, double* quality);
+
 /* Pinned (page-locked) host memory for callers that do not link HIP themselves: hipHostMalloc / hipHostFree / hipHostRegister /
  * hipHostUnregister behind the C ABI. Frames handed to the *_batch_host entries from such memory skip the staging copy. */
 int mof_host_alloc(size_t bytes, void** out);

@@ -40,6 +40,11 @@ struct Point2f {
 };
 
 // What the engine needs of a CV_8UC1 cv::Mat: data pointer, size, row step in bytes.
+// Per-patch correlation quality (include/mof.h, "Per-patch correlation quality"): cv::phaseCorrelate's `response` and the peak value
+struct PatchQuality {
+  double response, peak;
+};
+
 struct ImageView {
   const uint8_t* data;
   int rows, cols;
@@ -93,9 +98,12 @@ class FftMethod {
     if (imCurr.rows != cfg_.frame_height || imCurr.cols != cfg_.frame_width)
       throw std::runtime_error("processImage: frame size does not match the engine geometry");
     std::vector<Point2d> speeds((size_t)cfg_.grid_x * cfg_.grid_y);
-    const int rc = mof_fft_process(engine_, imCurr.data, imCurr.step, reinterpret_cast<double*>(speeds.data()), &last_invalid_);
+    std::vector<PatchQuality> quality(speeds.size());
+    const int rc = mof_fft_process_q(engine_, imCurr.data, imCurr.step, reinterpret_cast<double*>(speeds.data()),
+                                     reinterpret_cast<double*>(quality.data()), &last_invalid_);
     if (rc == MOF_ERR_BUSY) return {};  // `if (running) return std::vector<cv::Point2d>();`
-    detail::check(rc, "mof_fft_process");
+    detail::check(rc, "mof_fft_process_q");
+    last_quality_.swap(quality);
     return speeds;
   }
 
@@ -111,9 +119,12 @@ class FftMethod {
     const int n = mof_fft_long_range_patches(engine_);
     detail::check(n < 0 ? n : MOF_OK, "mof_fft_long_range_patches");
     std::vector<Point2d> speeds((size_t)n);
-    const int rc = mof_fft_process_long_range(engine_, imCurr.data, imCurr.step, reinterpret_cast<double*>(speeds.data()), &last_invalid_);
+    std::vector<PatchQuality> quality(speeds.size());
+    const int rc = mof_fft_process_long_range_q(engine_, imCurr.data, imCurr.step, reinterpret_cast<double*>(speeds.data()),
+                                                reinterpret_cast<double*>(quality.data()), &last_invalid_);
     if (rc == MOF_ERR_BUSY) return {};
-    detail::check(rc, "mof_fft_process_long_range");
+    detail::check(rc, "mof_fft_process_long_range_q");
+    last_quality_.swap(quality);
     return speeds;
   }
 
@@ -123,6 +134,19 @@ class FftMethod {
                              void* stream = nullptr) {
     detail::check(mof_fft_process_sequence_device(engine_, d_frames, frame_stride, pitch, n_frames, d_out_xy, stream),
                   "mof_fft_process_sequence_device");
+  }
+
+  // The batched entries with the per-patch quality beside the shifts: d_quality as d_out_xy, (response, peak) per patch; either
+  // may be what a node weighs its vectors by. channels: 1 gray, 3 BGR8; long_range as processImageLongRange (gray only).
+  void processBatchDeviceQ(const uint8_t* d_cur, size_t cur_stride, const uint8_t* d_prev, size_t prev_stride, size_t pitch, int n_pairs,
+                           double* d_out_xy, double* d_quality, void* stream = nullptr, int channels = 1, bool long_range = false) {
+    detail::check(mof_fft_process_batch_device_q(engine_, d_cur, cur_stride, d_prev, prev_stride, pitch, n_pairs, channels, long_range ? 1 : 0,
+                                                 d_out_xy, d_quality, stream), "mof_fft_process_batch_device_q");
+  }
+  void processSequenceDeviceQ(const uint8_t* d_frames, size_t frame_stride, size_t pitch, int n_frames, double* d_out_xy, double* d_quality,
+                              void* stream = nullptr, int channels = 1) {
+    detail::check(mof_fft_process_sequence_device_q(engine_, d_frames, frame_stride, pitch, n_frames, channels, d_out_xy, d_quality, stream),
+                  "mof_fft_process_sequence_device_q");
   }
 
   // A video in HOST memory (a replayed camera log): frame i at frames + i * frame_stride, rows `pitch` bytes apart. Returns the vectors the
@@ -139,6 +163,9 @@ class FftMethod {
 
   int sqNum() const { return cfg_.grid_x; }
   int invalidPatches() const { return last_invalid_; }
+  // (response, peak) of every patch of the last processImage / processImageLongRange call, indexed as its vectors; a gated patch
+  // (NaN vector) still carries its quality
+  const std::vector<PatchQuality>& lastQuality() const { return last_quality_; }
   const mof_fft_config& config() const { return cfg_; }
   mof_fft_engine* handle() { return engine_; }
 
@@ -147,6 +174,7 @@ class FftMethod {
   mof_fft_engine* engine_ = nullptr;
   double fx_ = 300, fy_ = 300;
   int last_invalid_ = 0;
+  std::vector<PatchQuality> last_quality_;
 };
 
 // The batched-frames mode across the GPUs of one node (include/mof.h, mof_shard_*): ceil(B / G) contiguous shards, one engine

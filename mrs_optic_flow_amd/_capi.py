@@ -86,6 +86,11 @@ SYMBOLS = {
     "mof_fft_process_sequence_device_bgr": (_I, [_VP, _VP, _SZ, _SZ, _I, _VP, _VP]),
     "mof_fft_process_batch_device_bgr": (_I, [_VP, _VP, _SZ, _VP, _SZ, _SZ, _I, _VP, _VP]),
     "mof_fft_process_batch_host": (_I, [_VP, _VP, _SZ, _VP, _SZ, _SZ, _I, _VP]),
+    "mof_fft_process_q": (_I, [_VP, _VP, _SZ, _VP, _VP, C.POINTER(_I)]),
+    "mof_fft_process_long_range_q": (_I, [_VP, _VP, _SZ, _VP, _VP, C.POINTER(_I)]),
+    "mof_fft_process_batch_device_q": (_I, [_VP, _VP, _SZ, _VP, _SZ, _SZ, _I, _I, _I, _VP, _VP, _VP]),
+    "mof_fft_process_sequence_device_q": (_I, [_VP, _VP, _SZ, _SZ, _I, _I, _VP, _VP, _VP]),
+    "mof_fft_process_batch_host_q": (_I, [_VP, _VP, _SZ, _VP, _SZ, _SZ, _I, _VP, _VP]),
     "mof_host_alloc": (_I, [_SZ, C.POINTER(_VP)]),
     "mof_host_free": (_I, [_VP]),
     "mof_host_register": (_I, [_VP, _SZ]),

@@ -217,6 +217,8 @@ struct mof_fft_engine {
   size_t frame_bytes = 0;
   double* d_out = nullptr;       // one frame's results
   double* h_out = nullptr;       // pinned
+  double* d_quality = nullptr;   // one frame's (response, peak) per patch, beside d_out / h_out (the stateful *_q entries)
+  double* h_quality = nullptr;   // pinned
   uint8_t* h_stage = nullptr;    // pinned upload staging (tightly packed frame)
   bool first = true;             // FftMethod.cpp:1761
   FftRoute route;
@@ -234,6 +236,7 @@ struct mof_fft_engine {
   std::atomic<bool> graph_pinned{false};  // a batch call was captured into a HIP graph (capi_graph.hpp)
   std::mutex host_mu;                     // mof_fft_process_batch_host: upload / run / download pipeline (host_pipe.hpp), made by its first call
   mof::HostPipe* host_pipe = nullptr;
+  mof::HostPipe* host_pipe_q = nullptr;   // mof_fft_process_batch_host_q with a quality output: the same pipeline with a second output
 };
 
 static void large_free(mof_fft_engine* e) {
@@ -373,6 +376,7 @@ static int launch_large(mof_fft_engine* e, const mof::PcArgs& a, int n_pairs, hi
       HIP_TRY(mof::launch_pcl_cols(zh_prev, zh_cur, zh_stride, e->plan, e->d_twiddles, e->d_dt, e->d_cdc, e->d_flags, nq, s, e->cfg.peak_model));
     }
     f.out = a.out + (size_t)k0 * patches * 2;
+    f.quality = a.quality ? a.quality + (size_t)k0 * patches * 2 : nullptr;
     HIP_TRY(mof::launch_pcl_peak(f, e->plan, nq, s, tuned));
   }
   HIP_TRY(e->fence.release(s));
@@ -537,6 +541,8 @@ int mof_fft_create(const mof_fft_config* cfg, mof_fft_engine** out) try {
   CREATE_TRY(mof::fill_on(e->stream, e->d_frames[1], 0, e->frame_bytes));
   CREATE_TRY(hipMalloc(&e->d_out, res * sizeof(double)));
   CREATE_TRY(hipHostMalloc(&e->h_out, res * sizeof(double), hipHostMallocDefault));
+  CREATE_TRY(hipMalloc(&e->d_quality, res * sizeof(double)));
+  CREATE_TRY(hipHostMalloc(&e->h_quality, res * sizeof(double), hipHostMallocDefault));
   CREATE_TRY(hipHostMalloc(&e->h_stage, e->frame_bytes, hipHostMallocDefault));
   // the kernels the route can launch (a video's half-tile form runs at half_m whenever that is set)
   if (r.half_m > 0 || r.video == FftRoute::HALF_SEQ) CREATE_TRY(mof::pc_configure_half(r.half_m > 0 ? r.half_m : r.video_m));
@@ -580,6 +586,7 @@ static void fft_destroy_now(void* p) {
   if (e->stream) (void)hipStreamSynchronize(e->stream);
   e->fence.wait_idle();
   delete e->host_pipe;
+  delete e->host_pipe_q;
   large_free(e);
   e->fence.destroy();
   if (e->d_twiddles) (void)hipFree(e->d_twiddles);
@@ -588,6 +595,8 @@ static void fft_destroy_now(void* p) {
   if (e->d_frames[1]) (void)hipFree(e->d_frames[1]);
   if (e->d_out) (void)hipFree(e->d_out);
   if (e->h_out) (void)hipHostFree(e->h_out);
+  if (e->d_quality) (void)hipFree(e->d_quality);
+  if (e->h_quality) (void)hipHostFree(e->h_quality);
   if (e->h_stage) (void)hipHostFree(e->h_stage);
   if (e->stream) (void)hipStreamDestroy(e->stream);
   delete e;
@@ -618,7 +627,7 @@ static void pack_frame(uint8_t* dst, const uint8_t* src, size_t pitch, int w, in
 }
 
 static mof::PcArgs fft_args(const mof_fft_engine* e, const uint8_t* cur, size_t cs, const uint8_t* prev, size_t ps,
-                            size_t pitch, double* out) {
+                            size_t pitch, double* out, double* quality) {
   mof::PcArgs a{};
   a.cur = cur;
   a.prev = prev;
@@ -638,6 +647,7 @@ static mof::PcArgs fft_args(const mof_fft_engine* e, const uint8_t* cur, size_t 
   a.max_px_speed_sq = e->cfg.max_px_speed * e->cfg.max_px_speed;  // pow(max_px_speed_t, 2), FftMethod.cpp:1686
   a.twiddles = e->d_twiddles;
   a.out = out;
+  a.quality = quality;
   return a;
 }
 
@@ -687,7 +697,8 @@ int mof_fft_long_range_patches(const mof_fft_engine* e) {
 }
 
 // processImage / processImageLongRange (FftMethod.cpp:1775-1900 / :1905-2004): one host frame against the engine's previous one
-static int fft_process_frame(mof_fft_engine* e, const uint8_t* frame, size_t pitch, double* out_xy, int* n_invalid, bool long_range) {
+static int fft_process_frame(mof_fft_engine* e, const uint8_t* frame, size_t pitch, double* out_xy, double* quality, int* n_invalid,
+                             bool long_range) {
   if (!e) return fail(MOF_ERR_NOT_INIT, "null engine");
   if (!frame || !out_xy || pitch < (size_t)e->cfg.frame_width) return fail(MOF_ERR_BAD_ARG, "bad frame/pitch/out");
   BusyGuard g(e->busy);
@@ -698,7 +709,7 @@ static int fft_process_frame(mof_fft_engine* e, const uint8_t* frame, size_t pit
   HIP_TRY(hipMemcpyAsync(e->d_frames[cur_slot], e->h_stage, e->frame_bytes, hipMemcpyHostToDevice, e->stream));
   // `first`: the frame is correlated with itself (FftMethod.cpp:1791-1793, :1920-1922)
   const uint8_t* prev = e->first ? e->d_frames[cur_slot] : e->d_frames[e->prev_slot];
-  mof::PcArgs a = fft_args(e, e->d_frames[cur_slot], 0, prev, 0, (size_t)e->cfg.frame_width, e->d_out);
+  mof::PcArgs a = fft_args(e, e->d_frames[cur_slot], 0, prev, 0, (size_t)e->cfg.frame_width, e->d_out, quality ? e->d_quality : nullptr);
   if (long_range) {
     int rc = long_range_args(e, &a);
     if (rc) return rc;
@@ -706,7 +717,9 @@ static int fft_process_frame(mof_fft_engine* e, const uint8_t* frame, size_t pit
   FIELD_TRY(launch_field(e, a, 1, e->stream));
   const size_t res = (size_t)a.grid_x * a.grid_y * 2;
   HIP_TRY(hipMemcpyAsync(e->h_out, e->d_out, res * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+  if (quality) HIP_TRY(hipMemcpyAsync(e->h_quality, e->d_quality, res * sizeof(double), hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));
+  if (quality) std::memcpy(quality, e->h_quality, res * sizeof(double));
   int bad = 0;
   for (size_t i = 0; i < res; i += 2) {
     out_xy[i] = e->h_out[i];
@@ -720,16 +733,24 @@ static int fft_process_frame(mof_fft_engine* e, const uint8_t* frame, size_t pit
 }
 
 int mof_fft_process(mof_fft_engine* e, const uint8_t* frame, size_t pitch, double* out_xy, int* n_invalid) {
-  return fft_process_frame(e, frame, pitch, out_xy, n_invalid, false);
+  return fft_process_frame(e, frame, pitch, out_xy, nullptr, n_invalid, false);
+}
+
+int mof_fft_process_q(mof_fft_engine* e, const uint8_t* frame, size_t pitch, double* out_xy, double* quality, int* n_invalid) {
+  return fft_process_frame(e, frame, pitch, out_xy, quality, n_invalid, false);
 }
 
 int mof_fft_process_long_range(mof_fft_engine* e, const uint8_t* frame, size_t pitch, double* out_xy, int* n_invalid) {
-  return fft_process_frame(e, frame, pitch, out_xy, n_invalid, true);
+  return fft_process_frame(e, frame, pitch, out_xy, nullptr, n_invalid, true);
+}
+
+int mof_fft_process_long_range_q(mof_fft_engine* e, const uint8_t* frame, size_t pitch, double* out_xy, double* quality, int* n_invalid) {
+  return fft_process_frame(e, frame, pitch, out_xy, quality, n_invalid, true);
 }
 
 // The device batch entries: n_pairs frame pairs of `channels` interleaved channels (1 gray, 3 BGR8)
 static int fft_batch(mof_fft_engine* e, const uint8_t* d_cur, size_t cur_stride, const uint8_t* d_prev, size_t prev_stride, size_t pitch,
-                     int n_pairs, double* d_out_xy, void* stream, int channels, bool long_range) {
+                     int n_pairs, double* d_out_xy, double* d_quality, void* stream, int channels, bool long_range) {
   if (!e) return fail(MOF_ERR_NOT_INIT, "null engine");
   if (n_pairs == 0) return MOF_OK;  // an empty batch carries no pointers to check
   if (!d_cur || !d_prev || !d_out_xy || n_pairs < 0 || pitch < (size_t)channels * (size_t)e->cfg.frame_width)
@@ -739,7 +760,7 @@ static int fft_batch(mof_fft_engine* e, const uint8_t* d_cur, size_t cur_stride,
   BusyGuard g(e->busy);
   if (!g.owned) return fail(MOF_ERR_BUSY, "engine busy");
   HIP_TRY(hipSetDevice(e->cfg.device));
-  mof::PcArgs a = fft_args(e, d_cur, cur_stride, d_prev, prev_stride, pitch, d_out_xy);
+  mof::PcArgs a = fft_args(e, d_cur, cur_stride, d_prev, prev_stride, pitch, d_out_xy, d_quality);
   a.channels = channels;
   if (long_range) {
     int rc = long_range_args(e, &a);
@@ -752,24 +773,34 @@ static int fft_batch(mof_fft_engine* e, const uint8_t* d_cur, size_t cur_stride,
 
 int mof_fft_process_batch_device(mof_fft_engine* e, const uint8_t* d_cur, size_t cur_stride, const uint8_t* d_prev,
                                  size_t prev_stride, size_t pitch, int n_pairs, double* d_out_xy, void* stream) {
-  return fft_batch(e, d_cur, cur_stride, d_prev, prev_stride, pitch, n_pairs, d_out_xy, stream, 1, false);
+  return fft_batch(e, d_cur, cur_stride, d_prev, prev_stride, pitch, n_pairs, d_out_xy, nullptr, stream, 1, false);
+}
+
+int mof_fft_process_batch_device_q(mof_fft_engine* e, const uint8_t* d_cur, size_t cur_stride, const uint8_t* d_prev, size_t prev_stride,
+                                   size_t pitch, int n_pairs, int channels, int long_range, double* d_out_xy, double* d_quality,
+                                   void* stream) {
+  if (!e) return fail(MOF_ERR_NOT_INIT, "null engine");
+  if ((channels != 1 && channels != 3) || (long_range != 0 && long_range != 1))
+    return fail(MOF_ERR_BAD_ARG, "channels must be 1 or 3 and long_range 0 or 1");
+  if (channels == 3 && long_range) return fail(MOF_ERR_BAD_ARG, "the long-range mode takes gray frames only");
+  return fft_batch(e, d_cur, cur_stride, d_prev, prev_stride, pitch, n_pairs, d_out_xy, d_quality, stream, channels, long_range != 0);
 }
 
 int mof_fft_process_batch_device_bgr(mof_fft_engine* e, const uint8_t* d_cur, size_t cur_stride, const uint8_t* d_prev,
                                      size_t prev_stride, size_t pitch, int n_pairs, double* d_out_xy, void* stream) {
-  return fft_batch(e, d_cur, cur_stride, d_prev, prev_stride, pitch, n_pairs, d_out_xy, stream, 3, false);
+  return fft_batch(e, d_cur, cur_stride, d_prev, prev_stride, pitch, n_pairs, d_out_xy, nullptr, stream, 3, false);
 }
 
 int mof_fft_process_long_range_batch_device(mof_fft_engine* e, const uint8_t* d_cur, size_t cur_stride,
                                             const uint8_t* d_prev, size_t prev_stride, size_t pitch, int n_pairs,
                                             double* d_out_xy, void* stream) {
-  return fft_batch(e, d_cur, cur_stride, d_prev, prev_stride, pitch, n_pairs, d_out_xy, stream, 1, true);
+  return fft_batch(e, d_cur, cur_stride, d_prev, prev_stride, pitch, n_pairs, d_out_xy, nullptr, stream, 1, true);
 }
 
 // A video: pair k = (frame k + 1, frame k), in the route's video form (fft_route); the pair form runs the engine's pair kernels on
 // cur = frames + 1, prev = frames (no copy either).
 static int fft_sequence(mof_fft_engine* e, const uint8_t* d_frames, size_t frame_stride, size_t pitch, int n_frames,
-                        double* d_out_xy, void* stream, int channels) {
+                        double* d_out_xy, double* d_quality, void* stream, int channels) {
   if (!e) return fail(MOF_ERR_NOT_INIT, "null engine");
   if (n_frames == 0 || n_frames == 1) return MOF_OK;  // no pair
   if (!d_frames || !d_out_xy || n_frames < 0 || pitch < (size_t)channels * (size_t)e->cfg.frame_width)
@@ -780,7 +811,7 @@ static int fft_sequence(mof_fft_engine* e, const uint8_t* d_frames, size_t frame
   BusyGuard g(e->busy);
   if (!g.owned) return fail(MOF_ERR_BUSY, "engine busy");
   HIP_TRY(hipSetDevice(e->cfg.device));
-  mof::PcArgs a = fft_args(e, d_frames + frame_stride, frame_stride, d_frames, frame_stride, pitch, d_out_xy);
+  mof::PcArgs a = fft_args(e, d_frames + frame_stride, frame_stride, d_frames, frame_stride, pitch, d_out_xy, d_quality);
   a.channels = channels;
   if (mof::stream_capturing((hipStream_t)stream)) e->graph_pinned.store(true);
   const FftRoute& r = e->route;
@@ -798,6 +829,7 @@ static int fft_sequence(mof_fft_engine* e, const uint8_t* d_frames, size_t frame
     mof::PcArgs c = a;
     c.cur = d_frames + (size_t)k0 * frame_stride;  // the sequence kernels index frames, not pairs
     c.out = d_out_xy + (size_t)k0 * per_pair;
+    c.quality = d_quality ? d_quality + (size_t)k0 * per_pair : nullptr;
     if (r.video == FftRoute::HALF_SEQ) HIP_TRY(mof::launch_pc_half_sequence(c, r.video_m, e->cfg.patch_size, nk, run_knob, (hipStream_t)stream));
     else if (r.video == FftRoute::SEQ_HALF) HIP_TRY(mof::launch_pc_sequence_half(c, e->cfg.patch_size, nk, run_knob ? run_knob : 16, (hipStream_t)stream));
     else HIP_TRY(mof::launch_pc_sequence(c, nk, run_knob, (hipStream_t)stream));
@@ -807,16 +839,28 @@ static int fft_sequence(mof_fft_engine* e, const uint8_t* d_frames, size_t frame
 
 int mof_fft_process_sequence_device(mof_fft_engine* e, const uint8_t* d_frames, size_t frame_stride, size_t pitch, int n_frames,
                                     double* d_out_xy, void* stream) {
-  return fft_sequence(e, d_frames, frame_stride, pitch, n_frames, d_out_xy, stream, 1);
+  return fft_sequence(e, d_frames, frame_stride, pitch, n_frames, d_out_xy, nullptr, stream, 1);
+}
+
+int mof_fft_process_sequence_device_q(mof_fft_engine* e, const uint8_t* d_frames, size_t frame_stride, size_t pitch, int n_frames,
+                                      int channels, double* d_out_xy, double* d_quality, void* stream) {
+  if (!e) return fail(MOF_ERR_NOT_INIT, "null engine");
+  if (channels != 1 && channels != 3) return fail(MOF_ERR_BAD_ARG, "channels must be 1 or 3");
+  return fft_sequence(e, d_frames, frame_stride, pitch, n_frames, d_out_xy, d_quality, stream, channels);
 }
 
 int mof_fft_process_sequence_device_bgr(mof_fft_engine* e, const uint8_t* d_frames, size_t frame_stride, size_t pitch, int n_frames,
                                         double* d_out_xy, void* stream) {
-  return fft_sequence(e, d_frames, frame_stride, pitch, n_frames, d_out_xy, stream, 3);
+  return fft_sequence(e, d_frames, frame_stride, pitch, n_frames, d_out_xy, nullptr, stream, 3);
 }
 
 int mof_fft_process_batch_host(mof_fft_engine* e, const uint8_t* cur, size_t cur_stride, const uint8_t* prev,
-                               size_t prev_stride, size_t pitch, int n_pairs, double* out_xy) try {
+                               size_t prev_stride, size_t pitch, int n_pairs, double* out_xy) {
+  return mof_fft_process_batch_host_q(e, cur, cur_stride, prev, prev_stride, pitch, n_pairs, out_xy, nullptr);
+}
+
+int mof_fft_process_batch_host_q(mof_fft_engine* e, const uint8_t* cur, size_t cur_stride, const uint8_t* prev, size_t prev_stride,
+                                 size_t pitch, int n_pairs, double* out_xy, double* quality) try {
   if (!e) return fail(MOF_ERR_NOT_INIT, "null engine");
   if (n_pairs == 0) return MOF_OK;  // an empty batch carries no pointers to check
   if (!cur || !prev || !out_xy || n_pairs < 0 || pitch < (size_t)e->cfg.frame_width)
@@ -827,16 +871,19 @@ int mof_fft_process_batch_host(mof_fft_engine* e, const uint8_t* cur, size_t cur
   {
     std::lock_guard<std::mutex> lock(e->host_mu);
     if (!e->host_pipe) e->host_pipe = new mof::HostPipe(e->frame_bytes, &res, 1);
+    const size_t res2[2] = {res, res};
+    if (quality && !e->host_pipe_q) e->host_pipe_q = new mof::HostPipe(e->frame_bytes, res2, 2);
   }
-  const mof::HostPipe::Out out{out_xy, res};
+  const mof::HostPipe::Out out[2] = {{out_xy, res}, {quality, res}};
+  mof::HostPipe* pipe = quality ? e->host_pipe_q : e->host_pipe;
   hipError_t he = hipSuccess;
   // chunks of frames go up on the pipe's copy stream while the engine's stream runs the previous chunk through the DEVICE batch entry
   // (its kernels, its bits); a video -- cur = prev + one frame -- arrives as the two views of ONE uploaded run
-  const int rc = e->host_pipe->process(
-      cur, cur_stride, prev, prev_stride, pitch, e->cfg.frame_width, e->cfg.frame_height, n_pairs, &out, e->stream,
-      [e](const mof::HostPipe::Chunk& c, hipStream_t s) {
-        return mof_fft_process_batch_device(e, c.d_cur, c.stride, c.d_prev, c.stride, (size_t)e->cfg.frame_width, c.count,
-                                            static_cast<double*>(c.d_out[0]), s);
+  const int rc = pipe->process(
+      cur, cur_stride, prev, prev_stride, pitch, e->cfg.frame_width, e->cfg.frame_height, n_pairs, out, e->stream,
+      [e, quality](const mof::HostPipe::Chunk& c, hipStream_t s) {
+        return fft_batch(e, c.d_cur, c.stride, c.d_prev, c.stride, (size_t)e->cfg.frame_width, c.count, static_cast<double*>(c.d_out[0]),
+                         quality ? static_cast<double*>(c.d_out[1]) : nullptr, s, 1, false);
       },
       &he);
   if (rc == -1) return fail(MOF_ERR_HIP, "host batch pipeline: %s", hipGetErrorString(he));

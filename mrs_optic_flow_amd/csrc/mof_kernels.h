@@ -28,6 +28,7 @@ struct PcArgs {
   double max_px_speed_sq; // FftMethod.cpp:1686
   const float* twiddles;  // device, N (cos, -sin) pairs, computed in double on the host
   double* out;            // device, [pair][patch] (x, y)
+  double* quality;        // device, nullable: [pair][patch] (response, peak) of the correlation surface (pc_common.hpp, quality_store)
 };
 
 // 1024 dwords behind the 64 twiddles of an N = 64 engine: the f16 hi / lo fragments of the radix-16 DFT matrix, in the lane order
@@ -81,6 +82,7 @@ struct PclFinal {
   const float* cdc;        // mode 1, with flags: [pairs] DC bin of the cross-power spectrum
   int peak_model;          // mode 1: 0 = cv::phaseCorrelate, 1 = the OpenCL kernel's model (m == n; L7 + L8 of the planned pipeline only)
   int search_radius;       // peak_model 1
+  double* quality;         // mode 1, nullable: [pairs] (response, peak), as PcArgs::quality
 };
 size_t pcl_zh_floats(const PcPlan& pl);  // floats of one image's row half-spectra Zh: (m/2 + 1) * m complex
 int pcl_candidates(const PcPlan& pl);    // peak candidates per pair

@@ -508,9 +508,35 @@ __device__ __forceinline__ float centroid_window_value(Best best, int lane, Surf
   return 0.f;
 }
 
-// degenerate: one of the two patches is constant; c_dc = the DC bin of the cross-power spectrum (see above)
+// The correlation quality of one patch, stored by lane 0 of a tail beside the shift when the launch asked for it (`q` non-null: a
+// wave-uniform test of a kernarg pointer, no second instantiation). It does not depend on the gate.
+//   PK = 0: q[0] = cv::phaseCorrelate's `response` = window sum (before DBL_EPSILON) / M^2, q[1] = the first maximum / M^2   (:1337-1383)
+//   PK = 1: q[0] = refine()'s sum (seeded with FLT_EPSILON), q[1] = the first maximum, of the surface the kernel has scaled  (cl:1315-1379)
+// `have` = the surface held a maximum (best.idx != 0x7fffffff; else NaN, NaN). A constant patch (`degenerate`): the flat surface c_dc of
+// PK = 0 -- peak c_dc / M^2, nine of them in the clamped 3 x 3 window -- and NaN, NaN under PK = 1, as for the shift.
+template <int PK>
+__device__ __forceinline__ void quality_store(double* q, double window_sum, float peak, double mm, bool have, bool degenerate, float c_dc) {
+  double response = window_sum, pk = (double)peak;
+  if constexpr (PK == 0) {
+    response /= mm;
+    pk /= mm;
+  }
+  if (!have) response = pk = __builtin_nan("");
+  if (degenerate) {
+    if constexpr (PK == 1) {
+      response = pk = __builtin_nan("");
+    } else {
+      pk = (double)c_dc / mm;
+      response = 9.0 * pk;
+    }
+  }
+  q[0] = response;
+  q[1] = pk;
+}
+
+// degenerate: one of the two patches is constant; c_dc = the DC bin of the cross-power spectrum (see above); quality: nullable (quality_store)
 template <int N, int PK = 0>
-__device__ __forceinline__ void centroid_gate_store(Best best, float wval, int lane, double max_px_speed_sq, double* out,
+__device__ __forceinline__ void centroid_gate_store(Best best, float wval, int lane, double max_px_speed_sq, double* out, double* quality,
                                                     bool degenerate = false, float c_dc = 0.f) {
   constexpr int RAD = PeakModel<PK>::RAD, W = PeakModel<PK>::W;
   const int px = best.idx % N, py = best.idx / N;
@@ -519,7 +545,9 @@ __device__ __forceinline__ void centroid_gate_store(Best best, float wval, int l
   double cx = (double)xs * val, cy = (double)ys * val, sum = val;
   wave_sum3(cx, cy, sum);
   if (lane == 0) {
+    const double window_sum = sum;
     sum += PK == 1 ? 1.1920928955078125e-07 : 2.220446049250313e-16;  // FLT_EPSILON cl:1342 / DBL_EPSILON :1378
+    if (quality) quality_store<PK>(quality, PK == 1 ? sum : window_sum, best.v, (double)N * (double)N, best.idx != 0x7fffffff, degenerate, c_dc);
     // shift = -(center - t) = t - N/2   (:1836); the OpenCL branch returns centroid - N/2 un-negated (cl:1370, :1833)
     double sx = cx / sum - (double)N / 2.0;
     double sy = cy / sum - (double)N / 2.0;

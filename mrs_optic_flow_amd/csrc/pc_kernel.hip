@@ -353,7 +353,7 @@ __global__ void __launch_bounds__(PcTraits<N>::T) pc_field_kernel(PcArgs a) {
   // (needed by the persistent form only; -DMOF_K1_TAIL_BARRIER=0 drops it where a workgroup runs one patch: A/B in DESIGN 8)
   if constexpr (PERSIST || MOF_K1_TAIL_BARRIER) __syncthreads();
   if (wave == 0)
-    centroid_gate_store<N, PK>(best, wval, lane, a.max_px_speed_sq, a.out + 2 * (size_t)p, degenerate,
+    centroid_gate_store<N, PK>(best, wval, lane, a.max_px_speed_sq, a.out + 2 * (size_t)p, a.quality ? a.quality + 2 * (size_t)p : nullptr, degenerate,
                                degenerate ? *reinterpret_cast<const float*>(const_code + 16) : 0.f);
   }  // persistent loop
 }
@@ -425,6 +425,7 @@ static hipError_t launch_n(const PcArgs& a_in, int n_pairs, hipStream_t stream) 
       c.cur = a.cur + (size_t)k0 * a.cur_stride;
       c.prev = a.prev + (size_t)k0 * a.prev_stride;
       c.out = a.out + (size_t)k0 * patches * 2;
+      if (a.quality) c.quality = a.quality + (size_t)k0 * patches * 2;
       c.total = nk * patches;
       launch(c, dim3((unsigned)a.grid_x, (unsigned)a.grid_y, (unsigned)nk));
     }

@@ -492,6 +492,7 @@ __global__ void __launch_bounds__(StaticPlanOf<MS>::T, StaticPlanOf<MS>::WPE) pc
     double cx = (double)xs * val, cy = (double)ys * val, sum = val;
     wave_sum3(cx, cy, sum);
     if (lane == 0) {
+      const double window_sum = sum;
       sum += PK == 1 ? 1.1920928955078125e-07 : 2.220446049250313e-16;  // FLT_EPSILON cl:1342 / DBL_EPSILON :1378
       // shift = -(center - t) = t - M / 2.0 (:1836): cv::phaseCorrelate's centre is that of the PADDED image
       const double half_m = (double)m / 2.0, half_n = (double)n / 2.0;
@@ -509,6 +510,9 @@ __global__ void __launch_bounds__(StaticPlanOf<MS>::T, StaticPlanOf<MS>::WPE) pc
           sx = sy = (c9 > 0.0 ? c9 / (c9 + 2.220446049250313e-16) : 0.0) - half_m;
         }
       }
+      if (a.quality)
+        quality_store<PK>(a.quality + 2 * p, PK == 1 ? sum : window_sum, best.v, (double)m * (double)m, have, degenerate,
+                          degenerate ? __int_as_float(flags[2]) : 0.f);
       // the gate compares with samplePointSize / 2 -- the UNPADDED size (:1841-1842)
       const bool bad = (sx * sx + sy * sy > a.max_px_speed_sq) || (fabs(sx) > half_n) || (fabs(sy) > half_n) || (sx != sx) ||
                        (sy != sy) || (!have && !degenerate);
@@ -571,6 +575,7 @@ hipError_t launch_pc_generic(const PcArgs& a_in, const PcPlan& pl, int n_pairs, 
     c.cur = a_in.cur + (size_t)k0 * a_in.cur_stride;
     c.prev = a_in.prev + (size_t)k0 * a_in.prev_stride;
     c.out = a_in.out + (size_t)k0 * patches * 2;
+    if (a_in.quality) c.quality = a_in.quality + (size_t)k0 * patches * 2;
     c.total = nk * patches;
     const dim3 g((unsigned)c.grid_x, (unsigned)c.grid_y, (unsigned)nk);
     if (c.peak_model == 1) {

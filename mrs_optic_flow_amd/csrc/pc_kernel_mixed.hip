@@ -438,7 +438,7 @@ __global__ void __launch_bounds__(T) pc_field_kernel_120(PcArgs a) {
   }
   __syncthreads();
   if (wave == 0)
-    centroid_gate_store<N, PK>(best, wval, lane, a.max_px_speed_sq, a.out + 2 * (size_t)p, degenerate,
+    centroid_gate_store<N, PK>(best, wval, lane, a.max_px_speed_sq, a.out + 2 * (size_t)p, a.quality ? a.quality + 2 * (size_t)p : nullptr, degenerate,
                                degenerate ? *reinterpret_cast<const float*>(const_code + 16) : 0.f);
   }  // persistent loop
 }

@@ -391,7 +391,7 @@ __global__ void __launch_bounds__(T, 4) pc_quad64_kernel(PcArgs a) {
   if (wave == 0) {
     const int lane = lane0;
     const float wval = centroid_window_value<N, PK>(best, lane, [&](int ys, int xs) { return win[(ys - wy0) * N + xs]; });
-    centroid_gate_store<N, PK>(best, wval, lane, a.max_px_speed_sq, a.out + 2 * (size_t)p);
+    centroid_gate_store<N, PK>(best, wval, lane, a.max_px_speed_sq, a.out + 2 * (size_t)p, a.quality ? a.quality + 2 * (size_t)p : nullptr);
   }
 }
 

@@ -402,6 +402,7 @@ __global__ void __launch_bounds__(64) pcl_final_kernel(PclFinal a) {
   }
   wave_sum3<(WW > 32 ? 32 : 16)>(cx, cy, sum);
   if (lane != 0) return;
+  const double window_sum = sum;
   sum += PK == 1 ? 1.1920928955078125e-07 : 2.220446049250313e-16;  // FLT_EPSILON cl:1342 / DBL_EPSILON, FftMethod.cpp:1378
   const double half_m = (double)m / 2.0;  // cv::phaseCorrelate's centre: that of the PADDED image
   if (PK == 0 && a.mode == 0) {
@@ -435,6 +436,9 @@ __global__ void __launch_bounds__(64) pcl_final_kernel(PclFinal a) {
         sx = sy = (c9 > 0.0 ? c9 / (c9 + 2.220446049250313e-16) : 0.0) - half_m;
       }
     }
+    if (a.quality)
+      quality_store<PK>(a.quality + 2 * (size_t)pair, PK == 1 ? sum : window_sum, best.v, (double)m * (double)m, have, degenerate,
+                        (PK == 0 && degenerate) ? a.cdc[pair] : 0.f);
     const double half_n = (double)a.n / 2.0;
     const bool bad = (sx * sx + sy * sy > a.max_px_speed_sq) || (fabs(sx) > half_n) || (fabs(sy) > half_n) || (sx != sx) ||
                      (sy != sy) || (!have && !degenerate);
@@ -584,6 +588,7 @@ hipError_t launch_pcl_peak(const PclFinal& a_in, const PcPlan& pl, int n_pairs, 
     a.Dt = a_in.Dt + (size_t)p0 * NU * pl.m * 2;
     a.cand = a_in.cand + (size_t)p0 * n_cand;
     a.out = a_in.out + (size_t)p0 * (a.mode == 0 ? 4 : 2);
+    a.quality = (a.mode == 1 && a_in.quality) ? a_in.quality + (size_t)p0 * 2 : nullptr;
     if (a.flags) a.flags = a_in.flags + 2 * (size_t)p0;
     if (a.cdc) a.cdc = a_in.cdc + p0;
     if (!candidates_done)  // (else L7 was run by somebody else: the tuned K7 for patches of 240 / 256 / 480 pixels)

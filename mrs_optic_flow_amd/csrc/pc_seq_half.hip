@@ -510,7 +510,8 @@ __global__ void __launch_bounds__(HalfTile<N>::T, (N == 64 ? 4 : 2)) pc_seq_half
     }
     __syncthreads();
     if (wave == 0)
-      centroid_gate_store<N, PK>(best, wval, lane, a.max_px_speed_sq, a.out + 2 * ((size_t)(p0 + f - 1) * patches + patch));
+      centroid_gate_store<N, PK>(best, wval, lane, a.max_px_speed_sq, a.out + 2 * ((size_t)(p0 + f - 1) * patches + patch),
+                                 a.quality ? a.quality + 2 * ((size_t)(p0 + f - 1) * patches + patch) : nullptr);
   }
 }
 
@@ -606,7 +607,7 @@ __global__ void __launch_bounds__(HalfTile<N>::T, MOF_PAIR_HALF_WPE) pc_pair_hal
       });
     }
     __syncthreads();
-    if (wave == 0) centroid_gate_store<N, PK>(best, wval, lane, a.max_px_speed_sq, a.out + 2 * (size_t)p);
+    if (wave == 0) centroid_gate_store<N, PK>(best, wval, lane, a.max_px_speed_sq, a.out + 2 * (size_t)p, a.quality ? a.quality + 2 * (size_t)p : nullptr);
   }
 }
 

@@ -278,7 +278,8 @@ __global__ void __launch_bounds__(256) pc_seq_kernel(PcArgs a, int n_pairs, int 
     }
     __syncthreads();
     if (wave == 0)
-      centroid_gate_store<N, PK>(best, wval, lane, a.max_px_speed_sq, a.out + 2 * ((size_t)(p0 + f - 1) * patches + patch));
+      centroid_gate_store<N, PK>(best, wval, lane, a.max_px_speed_sq, a.out + 2 * ((size_t)(p0 + f - 1) * patches + patch),
+                                 a.quality ? a.quality + 2 * ((size_t)(p0 + f - 1) * patches + patch) : nullptr);
   }
 }
 

@@ -191,9 +191,11 @@ class FftMethod:
         f = _np_u8(imCurr)
         self._check_shape(f)
         out = np.empty((self.n_patches, 2), np.float64)
+        quality = np.empty((self.n_patches, 2), np.float64)
         ninv = C.c_int(0)
-        check(self._lib.mof_fft_process(self._h, f.ctypes.data, f.strides[0], out.ctypes.data, C.byref(ninv)))
+        check(self._lib.mof_fft_process_q(self._h, f.ctypes.data, f.strides[0], out.ctypes.data, quality.ctypes.data, C.byref(ninv)))
         self.last_invalid = ninv.value
+        self.last_quality = quality  # [patches, 2] (response, peak) of this call's correlation surfaces (include/mof.h)
         return out
 
     def processImageLongRange(self, imCurr, gui=False, debug=False, midPoint=None, yaw_angle=0.0, rot_center=None,
@@ -205,12 +207,22 @@ class FftMethod:
         if n < 0:
             check(n)
         out = np.empty((n, 2), np.float64)
+        quality = np.empty((n, 2), np.float64)
         ninv = C.c_int(0)
-        check(self._lib.mof_fft_process_long_range(self._h, f.ctypes.data, f.strides[0], out.ctypes.data, C.byref(ninv)))
+        check(self._lib.mof_fft_process_long_range_q(self._h, f.ctypes.data, f.strides[0], out.ctypes.data, quality.ctypes.data,
+                                                     C.byref(ninv)))
         self.last_invalid = ninv.value
+        self.last_quality = quality
         return out
 
-    def process_long_range_batch_device(self, cur, prev, stream=None):
+    def _quality_like(self, out):
+        """The [pairs, patches, 2] float64 (response, peak) tensor that goes beside the shifts ``out`` of a device entry."""
+        import torch
+
+        return torch.empty(tuple(out.shape), dtype=torch.float64, device=out.device)
+
+    def process_long_range_batch_device(self, cur, prev, stream=None, return_quality=False):
+        """``return_quality``: also return the per-patch correlation quality, (shifts, quality) -- as on every batched entry below."""
         import torch
 
         _check_device_batch(cur, prev, (self.cfg.frame_height, self.cfg.frame_width), self.cfg.device)
@@ -221,24 +233,35 @@ class FftMethod:
         out = torch.empty((n, n_lr, 2), dtype=torch.float64, device=cur.device)
         s = stream if stream is not None else torch.cuda.current_stream(cur.device)
         _pin_if_capturing(self, s)
+        if return_quality:
+            quality = self._quality_like(out)
+            check(self._lib.mof_fft_process_batch_device_q(self._h, cur.data_ptr(), cur.stride(0), prev.data_ptr(), prev.stride(0),
+                                                           cur.stride(1), n, 1, 1, out.data_ptr(), quality.data_ptr(), _stream_ptr(s)))
+            return out, quality
         check(self._lib.mof_fft_process_long_range_batch_device(self._h, cur.data_ptr(), cur.stride(0), prev.data_ptr(),
                                                                 prev.stride(0), cur.stride(1), n, out.data_ptr(),
                                                                 _stream_ptr(s)))
         return out
 
     # -- batched --------------------------------------------------------------------------------
-    def process_batch_host(self, cur: np.ndarray, prev: np.ndarray) -> np.ndarray:
+    def process_batch_host(self, cur: np.ndarray, prev: np.ndarray, return_quality=False):
         cur, prev, cs, ps, pitch = _host_batch_views(cur, prev)
         self._check_shape(cur)
         n = cur.shape[0]
         out = np.empty((n, self.n_patches, 2), np.float64)
+        if return_quality:
+            quality = np.empty((n, self.n_patches, 2), np.float64)
+            check(self._lib.mof_fft_process_batch_host_q(self._h, cur.ctypes.data, cs, prev.ctypes.data, ps, pitch, n, out.ctypes.data,
+                                                         quality.ctypes.data))
+            return out, quality
         check(self._lib.mof_fft_process_batch_host(self._h, cur.ctypes.data, cs, prev.ctypes.data, ps, pitch, n, out.ctypes.data))
         return out
 
-    def process_batch_device(self, cur, prev, out=None, stream=None):
+    def process_batch_device(self, cur, prev, out=None, stream=None, return_quality=False):
         """cur, prev: torch uint8 tensors [n, H, W] on this engine's device (last dim contiguous,
         any row pitch / frame stride). Asynchronous on torch's current stream. Returns a
-        float64 tensor [n, patches, 2]."""
+        float64 tensor [n, patches, 2]; with ``return_quality`` (shifts, quality), quality a float64 tensor [n, patches, 2] of
+        (response, peak) per patch (include/mof.h, "Per-patch correlation quality")."""
         import torch
 
         _check_device_batch(cur, prev, (self.cfg.frame_height, self.cfg.frame_width), self.cfg.device)
@@ -250,11 +273,16 @@ class FftMethod:
             raise ValueError("out must be a dense float64 tensor of n * patches * 2 elements on the engine's device")
         s = stream if stream is not None else torch.cuda.current_stream(cur.device)
         _pin_if_capturing(self, s)
+        if return_quality:
+            quality = self._quality_like(out)
+            check(self._lib.mof_fft_process_batch_device_q(self._h, cur.data_ptr(), cur.stride(0), prev.data_ptr(), prev.stride(0),
+                                                           cur.stride(1), n, 1, 0, out.data_ptr(), quality.data_ptr(), _stream_ptr(s)))
+            return out, quality
         check(self._lib.mof_fft_process_batch_device(self._h, cur.data_ptr(), cur.stride(0), prev.data_ptr(),
                                                      prev.stride(0), cur.stride(1), n, out.data_ptr(), _stream_ptr(s)))
         return out
 
-    def process_sequence_device(self, frames, out=None, stream=None):
+    def process_sequence_device(self, frames, out=None, stream=None, return_quality=False):
         """frames: torch uint8 [n, H, W] video on this engine's device -> float64 [n - 1, patches, 2]: pair k = (frame k + 1,
         frame k), what consecutive processImage calls return after the first (FftMethod.cpp:1872). Asynchronous."""
         import torch
@@ -268,11 +296,16 @@ class FftMethod:
             raise ValueError("out must be a dense float64 tensor of (n - 1) * patches * 2 elements on the engine's device")
         s = stream if stream is not None else torch.cuda.current_stream(frames.device)
         _pin_if_capturing(self, s)
+        if return_quality:
+            quality = self._quality_like(out)
+            check(self._lib.mof_fft_process_sequence_device_q(self._h, frames.data_ptr(), frames.stride(0), frames.stride(1), n, 1,
+                                                              out.data_ptr(), quality.data_ptr(), _stream_ptr(s)))
+            return out, quality
         check(self._lib.mof_fft_process_sequence_device(self._h, frames.data_ptr(), frames.stride(0), frames.stride(1), n,
                                                         out.data_ptr(), _stream_ptr(s)))
         return out
 
-    def process_sequence_device_bgr(self, frames, stream=None):
+    def process_sequence_device_bgr(self, frames, stream=None, return_quality=False):
         """frames: torch uint8 [n, H, W, 3] BGR8 video (W-stride 3, any row pitch) -> float64 [n - 1, patches, 2]; CV_RGB2GRAY
         fused into the sequence kernels' loads, identical bits to process_sequence_device on the converted frames."""
         import torch
@@ -282,11 +315,16 @@ class FftMethod:
         out = torch.empty((max(n - 1, 0), self.n_patches, 2), dtype=torch.float64, device=frames.device)
         s = stream if stream is not None else torch.cuda.current_stream(frames.device)
         _pin_if_capturing(self, s)
+        if return_quality:
+            quality = self._quality_like(out)
+            check(self._lib.mof_fft_process_sequence_device_q(self._h, frames.data_ptr(), frames.stride(0), frames.stride(1), n, 3,
+                                                              out.data_ptr(), quality.data_ptr(), _stream_ptr(s)))
+            return out, quality
         check(self._lib.mof_fft_process_sequence_device_bgr(self._h, frames.data_ptr(), frames.stride(0), frames.stride(1), n,
                                                             out.data_ptr(), _stream_ptr(s)))
         return out
 
-    def process_batch_device_bgr(self, cur, prev, stream=None):
+    def process_batch_device_bgr(self, cur, prev, stream=None, return_quality=False):
         """cur, prev: torch uint8 [n, H, W, 3] BGR8 views (crop of the camera frames; W-stride 3, any row pitch):
         CV_RGB2GRAY (as the node applies it to BGR data) is fused into the kernel's load."""
         import torch
@@ -296,6 +334,11 @@ class FftMethod:
         out = torch.empty((n, self.n_patches, 2), dtype=torch.float64, device=cur.device)
         s = stream if stream is not None else torch.cuda.current_stream(cur.device)
         _pin_if_capturing(self, s)
+        if return_quality:
+            quality = self._quality_like(out)
+            check(self._lib.mof_fft_process_batch_device_q(self._h, cur.data_ptr(), cur.stride(0), prev.data_ptr(), prev.stride(0),
+                                                           cur.stride(1), n, 3, 0, out.data_ptr(), quality.data_ptr(), _stream_ptr(s)))
+            return out, quality
         check(self._lib.mof_fft_process_batch_device_bgr(self._h, cur.data_ptr(), cur.stride(0), prev.data_ptr(),
                                                          prev.stride(0), cur.stride(1), n, out.data_ptr(),
                                                          _stream_ptr(s)))

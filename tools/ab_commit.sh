@@ -1,25 +1,25 @@
 #!/bin/bash
-# Same-box A/B of the current library against the kernels of an older commit.
-#   local:  tools/ab_commit.sh prepare <commit>        (exports that commit's csrc/ + include/ to tmp_ab/)
-#   on box: tools/ab_commit.sh run [bench args...]     (builds tmp_ab into /tmp/lib_old.so, alternates 3x)
-set -e
-R=${GRAFT_REPO_ROOT:-/root/repo}
+# Same-box A/B of the current tree against an older commit -- the older commit's WHOLE tree (its library, its Python binding, its
+# bench.py), so that a change of the C ABI between the two does not matter.
+#   where hipcc is (no GPU needed): tools/ab_commit.sh prepare <commit>   exports that commit to tmp_ab/parent/ and builds its library there
+#   on the GPU box:                 tools/ab_commit.sh run [bench args...]  alternates old / new, three times (AB_REPS), one line per run:
+#                                                                           "<old|new> <pairs/s> <kernel_ms>"
+# Nothing is built by `run`, and the product library is never overwritten.
+set -e -o pipefail
+R=$(cd "$(dirname "$0")/.." && pwd)
 if [ "$1" == "prepare" ]; then
-  rm -rf $R/tmp_ab && mkdir -p $R/tmp_ab/csrc $R/tmp_ab/include/mof
-  for f in $(git -C $R ls-tree --name-only $2 mrs_optic_flow_amd/csrc/); do git -C $R show $2:$f > $R/tmp_ab/csrc/$(basename $f); done
-  git -C $R show $2:include/mof.h > $R/tmp_ab/include/mof.h
-  echo "prepared tmp_ab from $2"; exit 0
+  rm -rf $R/tmp_ab && mkdir -p $R/tmp_ab/parent
+  git -C $R archive $2 | tar -x -C $R/tmp_ab/parent
+  make -C $R/tmp_ab/parent/mrs_optic_flow_amd/csrc -s -j${AB_JOBS:-8}
+  make -C $R/tmp_ab/parent/oracle -s all
+  echo "prepared tmp_ab/parent from $2"; exit 0
 fi
 shift
-cd $R/tmp_ab/csrc
-BASE="-O3 -std=c++17 -fPIC -fno-slp-vectorize -Wno-unused-parameter -Wno-unused-function"
-OBJS=""
-for f in *.hip; do hipcc --offload-arch=gfx950 $BASE -I../include -I. -c -o /tmp/old_${f%.hip}.o $f; OBJS="$OBJS /tmp/old_${f%.hip}.o"; done
-hipcc --offload-arch=gfx950 -shared -o /tmp/lib_old.so $OBJS
-# the old library is selected through MOF_LIB_PATH: the product library is never overwritten
-for rep in 1 2 3; do
+[ -f $R/tmp_ab/parent/mrs_optic_flow_amd/libmof_hip.so ] || { echo "run 'tools/ab_commit.sh prepare <commit>' first"; exit 2; }
+for rep in $(seq 1 ${AB_REPS:-3}); do
   for v in old new; do
-    LIB=$R/mrs_optic_flow_amd/libmof_hip.so; [ $v == old ] && LIB=/tmp/lib_old.so
-    echo "$v $(MOF_LIB_PATH=$LIB python3 $R/bench.py --no-cpu-baseline --no-others --sustain-s 0 --steps 30 "$@" | python3 -c 'import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(round(d["value"]), d["roofline"]["kernel_ms"])')"
+    D=$R; [ $v == old ] && D=$R/tmp_ab/parent
+    out=$(cd $D && timeout -k 10 ${AB_STEP_LIMIT:-240} python3 bench.py --no-cpu-baseline --no-others --sustain-s 0 --steps 30 "$@" | python3 -c 'import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(round(d["value"]), d["roofline"]["kernel_ms"])') || { echo "$v run failed: stopping"; exit 1; }
+    echo "$v $out"
   done
 done
