@@ -28,7 +28,7 @@
 #include <type_traits>
 
 #include "mof_kernels.h"
-#include "pc_common.hpp"  // rgb2gray_fixed, gray16_from_bgr48
+#include "pc_common.hpp"  // fetch_px4, gray16_from_bgr48
 
 namespace mof {
 
@@ -70,27 +70,6 @@ __device__ __forceinline__ void static_for(F&& f) {
 // 40 K dwords).
 __device__ __forceinline__ uint32_t fast_div(uint32_t i, uint32_t m) { return m ? __umulhi(i, m) : i; }
 __device__ __forceinline__ uint32_t div_magic(uint32_t d) { return d == 1 ? 0u : (uint32_t)((0x100000000ull + d - 1) / d); }
-
-// four gray pixels (packed u8x4) from 4 gray bytes or 12 interleaved BGR bytes, any alignment
-__device__ __forceinline__ uint32_t load_gray4(const uint8_t* p, int channels) {
-  if (channels == 1) {
-    uint32_t v;
-    __builtin_memcpy(&v, p, 4);
-    return v;
-  }
-  uint32_t w[3];
-  __builtin_memcpy(w, p, 12);
-  uint32_t packed = 0;
-#pragma unroll
-  for (int b = 0; b < 4; ++b) {
-    const int i = 3 * b;
-    const uint32_t c0 = (w[i >> 2] >> (8 * (i & 3))) & 0xffu;
-    const uint32_t c1 = (w[(i + 1) >> 2] >> (8 * ((i + 1) & 3))) & 0xffu;
-    const uint32_t c2 = (w[(i + 2) >> 2] >> (8 * ((i + 2) & 3))) & 0xffu;
-    packed |= rgb2gray_fixed(c0, c1, c2) << (8 * b);
-  }
-  return packed;
-}
 
 template <int XB, int G>
 __global__ void __launch_bounds__(BM_THREADS_MAX) bm_scan_kernel(BmArgs a, int bpw, int groups_per_row, int WPD, int slot_dwords) {
@@ -135,7 +114,7 @@ __global__ void __launch_bounds__(BM_THREADS_MAX) bm_scan_kernel(BmArgs a, int b
       while (y >= rows) y -= rows, ++sl;
 #pragma unroll 2
       for (; sl < nb;) {
-        uint32_t v = load_gray4(base + (size_t)y * a.pitch + (size_t)(sl * S + off) * CH, CH);  // any alignment
+        uint32_t v = CH == 1 ? fetch_px4<1, 1>(base, a.pitch, y, sl * S + off) : fetch_px4<1, 3>(base, a.pitch, y, sl * S + off);  // any alignment
         v >>= sh;
         lds[sl * slot_dwords + lds_off + y * row_pitch_dw + xd] = v;
         y += rstep;

@@ -328,7 +328,6 @@ __device__ __forceinline__ Best wave_best(Best b) {
   return wave_best_level<1>(b);
 }
 
-
 // cv::cvtColor(.., CV_RGB2GRAY) on 8-bit data (fixed point, yuv_shift 14): gray = (c0*R2Y + c1*G2Y + c2*B2Y + 2^13) >> 14
 // with R2Y 4899, G2Y 9617, B2Y 1868. The node feeds it BGR8 data (optic_flow.cpp:1465 toCvCopy(BGR8), :1622
 // CV_RGB2GRAY), so the blue byte gets the red weight -- reproduced as is.
@@ -336,41 +335,72 @@ __device__ __forceinline__ uint32_t rgb2gray_fixed(uint32_t c0, uint32_t c1, uin
   return (c0 * 4899u + c1 * 9617u + c2 * 1868u + 8192u) >> 14;
 }
 
-// 16 gray pixels from 48 interleaved bytes (12 dwords, any alignment)
-__device__ __forceinline__ void gray16_from_bgr48(const uint8_t* p, uint32_t* g /*[4] packed u8x4*/) {
+// byte i of a little-endian dword array; the gray value of the interleaved pixel that starts there; four of them (u8x4) from byte 12 q on
+__device__ __forceinline__ uint32_t byte_at(const uint32_t* w, int i) { return (w[i >> 2] >> (8 * (i & 3))) & 0xffu; }
+__device__ __forceinline__ uint32_t gray_at(const uint32_t* w, int i) { return rgb2gray_fixed(byte_at(w, i), byte_at(w, i + 1), byte_at(w, i + 2)); }
+__device__ __forceinline__ uint32_t gray4_at(const uint32_t* w, int q) {
+  uint32_t packed = 0;
+#pragma unroll
+  for (int b = 0; b < 4; ++b) packed |= gray_at(w, 3 * (4 * q + b)) << (8 * b);
+  return packed;
+}
+
+// 4 / 16 / 8 gray pixels (packed u8x4) from 12 / 48 / 24 interleaved bytes, any alignment, ONE load of that width each
+__device__ __forceinline__ uint32_t gray4_from_bgr12(const uint8_t* p) {
+  uint32_t w[3];
+  __builtin_memcpy(w, p, 12);
+  return gray4_at(w, 0);
+}
+__device__ __forceinline__ void gray16_from_bgr48(const uint8_t* p, uint32_t* g /*[4]*/) {
   uint32_t w[12];
   __builtin_memcpy(w, p, 48);
 #pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    uint32_t packed = 0;
-#pragma unroll
-    for (int b = 0; b < 4; ++b) {
-      const int i = 3 * (4 * q + b);  // byte index of pixel 4q+b
-      const uint32_t c0 = (w[i >> 2] >> (8 * (i & 3))) & 0xffu;
-      const uint32_t c1 = (w[(i + 1) >> 2] >> (8 * ((i + 1) & 3))) & 0xffu;
-      const uint32_t c2 = (w[(i + 2) >> 2] >> (8 * ((i + 2) & 3))) & 0xffu;
-      packed |= rgb2gray_fixed(c0, c1, c2) << (8 * b);
-    }
-    g[q] = packed;
-  }
+  for (int q = 0; q < 4; ++q) g[q] = gray4_at(w, q);
 }
-
-// 8 gray pixels from 24 interleaved bytes (6 dwords, any alignment)
-__device__ __forceinline__ void gray8_from_bgr24(const uint8_t* p, uint32_t* g /*[2] packed u8x4*/) {
+__device__ __forceinline__ void gray8_from_bgr24(const uint8_t* p, uint32_t* g /*[2]*/) {
   uint32_t w[6];
   __builtin_memcpy(w, p, 24);
 #pragma unroll
-  for (int q = 0; q < 2; ++q) {
-    uint32_t packed = 0;
+  for (int q = 0; q < 2; ++q) g[q] = gray4_at(w, q);
+}
+
+// one pixel (row y, column x of the patch whose top-left pixel is `base`): as it is, through the node's CV_RGB2GRAY on BGR8 data (CH = 3),
+// or the quarter-resolution pixel of the long-range mode (DS = 4: cv::resize(.., 1/4, 1/4), FftMethod.cpp:1931-1932) -- pc_field_kernel's front ends
+template <int DS, int CH>
+__device__ __forceinline__ uint32_t fetch_px(const uint8_t* __restrict__ base, size_t pitch, int y, int x) {
+  if constexpr (DS == 4) {
+    const uint8_t* r1 = base + (size_t)(4 * y + 1) * pitch + 4 * x;
+    const uint8_t* r2 = r1 + pitch;
+    return ((uint32_t)r1[1] + r1[2] + r2[1] + r2[2] + 2u) >> 2;
+  } else if constexpr (CH == 3) {
+    const uint8_t* p = base + (size_t)y * pitch + 3 * x;
+    return rgb2gray_fixed(p[0], p[1], p[2]);
+  } else {
+    return base[(size_t)y * pitch + x];
+  }
+}
+
+// four consecutive pixels x0 .. x0 + 3 of row y, one byte each (x0 + 3 inside the patch): ONE unaligned dword of a gray frame, three dwords
+// of a BGR8 frame, or -- the long-range mode -- the 2 x 2 taps of four quarter-resolution pixels from two 16-byte runs of the frame rows
+// 4 y + 1 and 4 y + 2 (cv::resize(1/4, INTER_LINEAR): columns 4 x + 1 and 4 x + 2)
+template <int DS, int CH>
+__device__ __forceinline__ uint32_t fetch_px4(const uint8_t* __restrict__ base, size_t pitch, int y, int x0) {
+  if constexpr (DS == 4) {
+    const uint8_t* r1 = base + (size_t)(4 * y + 1) * pitch + 4 * (size_t)x0;
+    uint32_t w1[4], w2[4];
+    __builtin_memcpy(w1, r1, 16);
+    __builtin_memcpy(w2, r1 + pitch, 16);
+    uint32_t g = 0;
 #pragma unroll
-    for (int b = 0; b < 4; ++b) {
-      const int i = 3 * (4 * q + b);
-      const uint32_t c0 = (w[i >> 2] >> (8 * (i & 3))) & 0xffu;
-      const uint32_t c1 = (w[(i + 1) >> 2] >> (8 * ((i + 1) & 3))) & 0xffu;
-      const uint32_t c2 = (w[(i + 2) >> 2] >> (8 * ((i + 2) & 3))) & 0xffu;
-      packed |= rgb2gray_fixed(c0, c1, c2) << (8 * b);
-    }
-    g[q] = packed;
+    for (int b = 0; b < 4; ++b)
+      g |= ((((w1[b] >> 8) & 0xffu) + ((w1[b] >> 16) & 0xffu) + ((w2[b] >> 8) & 0xffu) + ((w2[b] >> 16) & 0xffu) + 2u) >> 2) << (8 * b);
+    return g;
+  } else if constexpr (CH == 3) {
+    return gray4_from_bgr12(base + (size_t)y * pitch + 3 * (size_t)x0);
+  } else {
+    uint32_t w;
+    __builtin_memcpy(&w, base + (size_t)y * pitch + x0, 4);
+    return w;
   }
 }
 
@@ -495,12 +525,27 @@ struct PeakModel {
   static constexpr int W = 2 * RAD + 1;
 };
 
+// Lane -> its element of the W x W window around the first maximum of an m x m surface: (*ys, *xs) in fft-SHIFTED coordinates; returns `in` = the
+// surface held a maximum (best.idx != 0x7fffffff: some value compared equal to it, i.e. not every value is NaN), lane < W^2 and the
+// element lies on the surface (the window is clamped to the -- padded -- patch). peak_unshift: shifted -> un-shifted coordinate, the
+// inverse of fftShift's i -> (i + (m >> 1)) mod m for even and odd m alike (:1257-1323).
+template <int PK>
+__device__ __forceinline__ bool peak_window(Best best, int lane, int m, int* ys, int* xs) {
+  constexpr int RAD = PeakModel<PK>::RAD, W = PeakModel<PK>::W;
+  const int py = best.idx / m, px = best.idx % m;  // (no maximum: a row far below the surface)
+  *ys = py - RAD + lane / W;
+  *xs = px - RAD + lane % W;
+  return best.idx != 0x7fffffff && lane < W * W && *ys >= 0 && *ys <= m - 1 && *xs >= 0 && *xs <= m - 1;
+}
+__device__ __forceinline__ int peak_unshift(int s, int m) {
+  const int H = m >> 1;
+  return s - H < 0 ? s - H + m : s - H;
+}
+
 template <int N, int PK = 0, class Surface>
 __device__ __forceinline__ float centroid_window_value(Best best, int lane, Surface surface) {
-  constexpr int RAD = PeakModel<PK>::RAD, W = PeakModel<PK>::W;
-  const int px = best.idx % N, py = best.idx / N;
-  const int ys = py - RAD + lane / W, xs = px - RAD + lane % W;
-  if (lane < W * W && ys >= 0 && ys <= N - 1 && xs >= 0 && xs <= N - 1) {  // window clamped to the patch
+  int ys, xs;
+  if (peak_window<PK>(best, lane, N, &ys, &xs)) {
     const float v = surface(ys, xs);
     if constexpr (PK == 1) return v > 0.f ? v : 0.f;
     return v;
@@ -512,7 +557,7 @@ __device__ __forceinline__ float centroid_window_value(Best best, int lane, Surf
 // wave-uniform test of a kernarg pointer, no second instantiation). It does not depend on the gate.
 //   PK = 0: q[0] = cv::phaseCorrelate's `response` = window sum (before DBL_EPSILON) / M^2, q[1] = the first maximum / M^2   (:1337-1383)
 //   PK = 1: q[0] = refine()'s sum (seeded with FLT_EPSILON), q[1] = the first maximum, of the surface the kernel has scaled  (cl:1315-1379)
-// `have` = the surface held a maximum (best.idx != 0x7fffffff; else NaN, NaN). A constant patch (`degenerate`): the flat surface c_dc of
+// `have` = the surface held a maximum (else NaN, NaN). A constant patch (`degenerate`): the flat surface c_dc of
 // PK = 0 -- peak c_dc / M^2, nine of them in the clamped 3 x 3 window -- and NaN, NaN under PK = 1, as for the shift.
 template <int PK>
 __device__ __forceinline__ void quality_store(double* q, double window_sum, float peak, double mm, bool have, bool degenerate, float c_dc) {
@@ -534,52 +579,133 @@ __device__ __forceinline__ void quality_store(double* q, double window_sum, floa
   q[1] = pk;
 }
 
-// degenerate: one of the two patches is constant; c_dc = the DC bin of the cross-power spectrum (see above); quality: nullable (quality_store)
+// The finish of every peak tail, by lane 0 after wave_sum3: (cx, cy, window_sum) = sums of xs v, ys v, v over the window of an m x m
+// surface whose patch is n x n (m > n: zero-padded). degenerate: one of the two patches is constant (each caller decides that from its own
+// flags); c_dc = the DC bin of the cross-power spectrum (see above), read only then; quality: nullable (quality_store).
+template <int PK>
+__device__ __forceinline__ void peak_finish(double cx, double cy, double window_sum, Best best, int m, int n, bool degenerate, float c_dc,
+                                            double max_px_speed_sq, double* out, double* quality) {
+  const bool have = best.idx != 0x7fffffff;
+  const double sum = window_sum + (PK == 1 ? 1.1920928955078125e-07 : 2.220446049250313e-16);  // FLT_EPSILON cl:1342 / DBL_EPSILON :1378
+  if (quality) quality_store<PK>(quality, PK == 1 ? sum : window_sum, best.v, (double)m * (double)m, have, degenerate, c_dc);
+  // shift = -(center - t) = t - M / 2.0 (:1836): cv::phaseCorrelate's centre is that of the PADDED image; the OpenCL branch returns
+  // centroid - N/2 un-negated (cl:1370, :1833) -- the same number
+  const double half_m = (double)m / 2.0, half_n = (double)n / 2.0;
+  double sx = cx / sum - half_m, sy = cy / sum - half_m;
+  if (degenerate) {
+    if constexpr (PK == 1) {
+      sx = sy = __builtin_nan("");  // 1 / (a b) with b = 0 in the three other real-only slots (cl:1029): no finite surface
+    } else {
+      const double c9 = 9.0 * (double)c_dc;
+      sx = sy = (c9 > 0.0 ? c9 / (c9 + 2.220446049250313e-16) : 0.0) - half_m;
+    }
+  }
+  // the gate compares with samplePointSize / 2 -- the UNPADDED size (:1841-1842). !have: the whole surface is NaN (a spectrum with
+  // infinities, e.g. 1/0 in a real-only slot under the OpenCL model) -> invalid, as a NaN centroid is
+  const bool bad = (sx * sx + sy * sy > max_px_speed_sq) || (fabs(sx) > half_n) || (fabs(sy) > half_n) || (sx != sx) || (sy != sy) ||
+                   (!have && !degenerate);
+  if (bad) sx = sy = __builtin_nan("");
+  out[0] = sx;
+  out[1] = sy;
+}
+
+// the compile-time N = M = n form: `wval` = the lane's centroid_window_value
 template <int N, int PK = 0>
 __device__ __forceinline__ void centroid_gate_store(Best best, float wval, int lane, double max_px_speed_sq, double* out, double* quality,
                                                     bool degenerate = false, float c_dc = 0.f) {
-  constexpr int RAD = PeakModel<PK>::RAD, W = PeakModel<PK>::W;
-  const int px = best.idx % N, py = best.idx / N;
-  const int ys = py - RAD + lane / W, xs = px - RAD + lane % W;
+  int ys, xs;
+  peak_window<PK>(best, lane, N, &ys, &xs);
   const double val = (double)wval;  // 0 for lanes outside the window
   double cx = (double)xs * val, cy = (double)ys * val, sum = val;
   wave_sum3(cx, cy, sum);
-  if (lane == 0) {
-    const double window_sum = sum;
-    sum += PK == 1 ? 1.1920928955078125e-07 : 2.220446049250313e-16;  // FLT_EPSILON cl:1342 / DBL_EPSILON :1378
-    if (quality) quality_store<PK>(quality, PK == 1 ? sum : window_sum, best.v, (double)N * (double)N, best.idx != 0x7fffffff, degenerate, c_dc);
-    // shift = -(center - t) = t - N/2   (:1836); the OpenCL branch returns centroid - N/2 un-negated (cl:1370, :1833)
-    double sx = cx / sum - (double)N / 2.0;
-    double sy = cy / sum - (double)N / 2.0;
-    if (degenerate) {
-      if constexpr (PK == 1) {
-        sx = sy = __builtin_nan("");  // 1 / (a b) with b = 0 in the three other real-only slots (cl:1029): no finite surface
-      } else {
-        const double c9 = 9.0 * (double)c_dc;
-        sx = sy = (c9 > 0.0 ? c9 / (c9 + 2.220446049250313e-16) : 0.0) - (double)N / 2.0;
-      }
-    }
-    // best.idx == 0x7fffffff: no value compared equal to the maximum, i.e. the whole surface is NaN (a patch whose
-    // spectrum holds infinities, e.g. 1/0 in a real-only slot under the OpenCL model) -> invalid, as a NaN centroid is
-    const bool bad = (sx * sx + sy * sy > max_px_speed_sq) || (fabs(sx) > (double)N / 2.0) ||
-                     (fabs(sy) > (double)N / 2.0) || (sx != sx) || (sy != sy) || (best.idx == 0x7fffffff && !degenerate);
-    if (bad) sx = sy = __builtin_nan("");
-    out[0] = sx;
-    out[1] = sy;
-  }
+  if (lane == 0) peak_finish<PK>(cx, cy, sum, best, N, N, degenerate, c_dc, max_px_speed_sq, out, quality);
 }
 
-// PK = 1 only: value (y, x) of the UN-shifted surface after the kernel's scaling and +-search_radius mask
-// (cl:733, :737-746, :823-826): rows / columns with search_radius < index < N - search_radius read as 0.
-template <int N>
-__device__ __forceinline__ float ocl_scale_mask(float v, int y, int x, int sr) {
-  const bool masked = (y > sr && y < N - sr) || (x > sr && x < N - sr);
-  return masked ? 0.f : v * (1.0f / (float)(N * N));
+// The estimator's finish, by lane 0: pt = cv::phaseCorrelate(cur_lp, prev_lp) = center - t, NOT negated (scaleRotationEstimator.cpp:117);
+// |pt.x| > resolution / 2 (int division) -> (1, 0) (:119-121); scale = exp(pt.x / M), rot = (pt.y / Ky) pi/180, Ky = resolution / 360
+// (:123-124). flat_zero: an all-zero log-polar image -- flat zero surface: first index, centroid 0 / (0 + eps). out4 = scale, rot, pt.x, pt.y
+__device__ __forceinline__ void sr_finish(double cx, double cy, double sum, int m, int n, double M_log, bool flat_zero, double* out4) {
+  sum += 2.220446049250313e-16;
+  const double half_m = (double)m / 2.0;
+  double ptx = half_m - cx / sum, pty = half_m - cy / sum;
+  if (flat_zero) ptx = pty = half_m;
+  double scale = 1.0, rot = 0.0;
+  if (!(fabs(ptx) > (double)(n / 2))) {
+    scale = exp(ptx / M_log);
+    rot = (pty / ((double)n / 360.0)) * (3.14159265358979323846 / 180.0);
+  }
+  out4[0] = scale;
+  out4[1] = rot;
+  out4[2] = ptx;
+  out4[3] = pty;
 }
-// ... at a run-time size m (the large-patch pipeline, pc_large_kernel.hip); scale = 1.0f / (float)(m * m), hoisted by the caller
+
+// The W x W window of a surface that exists only as the half spectrum of its rows (Dt[u][y], u <= m / 2: K8 and L8 keep no surface),
+// re-evaluated in double: S[y][x] = Re G[y][0] + [m even: (-1)^x Re G[y][m/2]] + 2 sum_{u=1}^{(m-1)/2} Re(G[y][u] W^{ux}), what the
+// inverse row transform computes for that point. One wave: the first maximum of `cand` (*best_out, in every lane), the sums split over
+// the lanes by u (lane, lane + 64, ..), W^2 partial sums each, handed over through the kernel's part[W^2][65], lane k < W^2 adds the 64
+// of its window point in a fixed order. Returns the lane's window value (the surface is CV_32F), 0 outside the clamped window.
+// NS > 0: the compile-time transform size; NS = 0: m_rt.
+template <int W, int NS>
+__device__ __forceinline__ float spectrum_window(const float2* __restrict__ cand, int n_cand, const cf* __restrict__ Dt,
+                                                 const float* __restrict__ twiddles, int m_rt, int lane, double (*part)[65], Best* best_out) {
+  constexpr int PK = W == PeakModel<1>::W ? 1 : 0, WW = W * W;
+  static_assert(W == PeakModel<PK>::W, "a peak model's window");
+  const int m = NS > 0 ? NS : m_rt, H = m >> 1;
+  const bool even = (m & 1) == 0;
+  const int umax = even ? H - 1 : H;
+  Best best = {-__builtin_huge_valf(), 0x7fffffff};
+  for (int i = lane; i < n_cand; i += 64) {
+    const float2 c = cand[i];
+    best = better(best, Best{c.x, __float_as_int(c.y)});
+  }
+  best = wave_best(best);
+  *best_out = best;
+  int ys, xs;
+  peak_window<PK>(best, 0, m, &ys, &xs);  // the window's first row and column; un-shifted and wrapped (entries outside the clamped window are skipped below;
+                                          // no maximum: ys is far below the surface, the double modulo still leaves every wy / wx in [0, m))
+  int wy[W], wx[W];
+#pragma unroll
+  for (int k = 0; k < W; ++k) {
+    wy[k] = ((((ys + k) % m) + m) % m - H + m) % m;
+    wx[k] = ((((xs + k) % m) + m) % m - H + m) % m;
+  }
+  double acc[WW];
+#pragma unroll
+  for (int k = 0; k < WW; ++k) acc[k] = 0.0;
+  for (int u = 1 + lane; u <= umax; u += 64) {
+    cf f[W];
+#pragma unroll
+    for (int r = 0; r < W; ++r) f[r] = Dt[(size_t)u * m + wy[r]];
+#pragma unroll
+    for (int c = 0; c < W; ++c) {
+      const float2 t = *reinterpret_cast<const float2*>(twiddles + 2 * (int)(((long)u * wx[c]) % m));  // (cos, -sin)
+#pragma unroll
+      for (int r = 0; r < W; ++r) acc[r * W + c] += (double)f[r].x * (double)t.x - (double)f[r].y * (double)t.y;
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < WW; ++k) part[k][lane] = acc[k];
+  __syncthreads();
+  if (!peak_window<PK>(best, lane, m, &ys, &xs)) return 0.f;
+  const int y = wy[lane / W], x = wx[lane % W];
+  double s2 = 0.0;
+  for (int l = 0; l < 64; ++l) s2 += part[lane][l];
+  double s0 = (double)Dt[y].x;
+  if (even) s0 += ((x & 1) ? -1.0 : 1.0) * (double)Dt[(size_t)H * m + y].x;
+  return (float)(s0 + 2.0 * s2);
+}
+
+// PK = 1 only: value (y, x) of the UN-shifted m x m surface after the kernel's scaling and +-search_radius mask
+// (cl:733, :737-746, :823-826): rows / columns with search_radius < index < m - search_radius read as 0.
+// scale = 1.0f / (float)(m * m), hoisted by the caller
 __device__ __forceinline__ float ocl_scale_mask(float v, int y, int x, int sr, int m, float scale) {
   const bool masked = (y > sr && y < m - sr) || (x > sr && x < m - sr);
   return masked ? 0.f : v * scale;
+}
+template <int N>
+__device__ __forceinline__ float ocl_scale_mask(float v, int y, int x, int sr) {
+  return ocl_scale_mask(v, y, x, sr, N, 1.0f / (float)(N * N));
 }
 
 }  // namespace

@@ -434,30 +434,6 @@ __global__ void __launch_bounds__(HalfPlanOf<MS>::T, HalfPlanOf<MS>::WPE) pc_hal
   const int nl = H - l0 < 0 ? 0 : (H - l0 > LPW ? LPW : H - l0);
   const Walk rows = {P, 1, 0, SKM, 0, HALF_LINE_PERM, SH, RSK, 0}, cols = {1, P2, SKM, 0, 1, 0, SH, 0, RSK};
 
-  auto px_gray = [&](const uint8_t* q) -> uint32_t {  // four pixels -> four gray bytes
-    if constexpr (CH == 1) {
-      uint32_t w;
-      __builtin_memcpy(&w, q, 4);
-      return w;
-    } else {
-      uint32_t w[3];
-      __builtin_memcpy(w, q, 12);
-      uint32_t g = 0;
-#pragma unroll
-      for (int b = 0; b < 4; ++b) {
-        const int i = 3 * b;
-        const uint32_t c0 = (w[i >> 2] >> (8 * (i & 3))) & 0xffu, c1 = (w[(i + 1) >> 2] >> (8 * ((i + 1) & 3))) & 0xffu,
-                       c2 = (w[(i + 2) >> 2] >> (8 * ((i + 2) & 3))) & 0xffu;
-        g |= rgb2gray_fixed(c0, c1, c2) << (8 * b);
-      }
-      return g;
-    }
-  };
-  auto px_one = [&](const uint8_t* q) -> uint32_t {
-    if constexpr (CH == 1) return q[0];
-    else return rgb2gray_fixed(q[0], q[1], q[2]);
-  };
-
   // ---- one image: pixels of the wave's lines -> LDS (u8 -> f32: convertTo, :1805-1806; zeros beyond n x n: copyMakeBorder of
   //      cv::phaseCorrelate), row transforms, untangle into the spec layout. Wave-local throughout. Chunk q = lane + 64 k of the wave's
   //      lines = four pixels of rows 2j and 2j + 1: chunk_load brings them into two registers, chunk_commit stages them in the tile.
@@ -485,21 +461,19 @@ __global__ void __launch_bounds__(HalfPlanOf<MS>::T, HalfPlanOf<MS>::WPE) pc_hal
         const uint32_t pitch = (uint32_t)a.pitch;
         const uint32_t off = (uint32_t)(2 * (l0 + li0)) * pitch + (uint32_t)(4 * CH * xc0) + (uint32_t)(2 * DL) * pitch + (uint32_t)(4 * CH * DX) +
                              (wrap ? 2u * pitch - (uint32_t)(4 * CH * CPR) : 0u);
-        const uint8_t* qa = img + off;
-        *pa = px_gray(qa);
-        *pb = px_gray(qa + pitch);
+        *pa = fetch_px4<1, CH>(img + off, pitch, 0, 0);
+        *pb = fetch_px4<1, CH>(img + off, pitch, 1, 0);
       }
     } else {
       const int q = lane + 64 * k, li = q / CPR, x0 = 4 * (q % CPR), y = 2 * (l0 + li);
       if (li < nl && x0 < n) {
-        const uint8_t* qa = img + (size_t)y * a.pitch + (size_t)CH * x0;
         if (x0 + 3 < n) {
-          if (y < n) *pa = px_gray(qa);
-          if (y + 1 < n) *pb = px_gray(qa + a.pitch);
+          if (y < n) *pa = fetch_px4<1, CH>(img, a.pitch, y, x0);
+          if (y + 1 < n) *pb = fetch_px4<1, CH>(img, a.pitch, y + 1, x0);
         } else {  // the last chunk of a row whose length is not a multiple of four: the pixels inside the patch
           for (int b = 0; x0 + b < n; ++b) {
-            if (y < n) *pa |= px_one(qa + CH * b) << (8 * b);
-            if (y + 1 < n) *pb |= px_one(qa + a.pitch + CH * b) << (8 * b);
+            if (y < n) *pa |= fetch_px<1, CH>(img, a.pitch, y, x0 + b) << (8 * b);
+            if (y + 1 < n) *pb |= fetch_px<1, CH>(img, a.pitch, y + 1, x0 + b) << (8 * b);
           }
         }
       }
@@ -589,7 +563,7 @@ __global__ void __launch_bounds__(HalfPlanOf<MS>::T, HalfPlanOf<MS>::WPE) pc_hal
   };
   // one image, loads and staging back to back (sub-batches of SB chunks: the loads of a sub-batch in flight together)
   auto load_and_rows = [&](const uint8_t* img, int which) {
-    const uint32_t first = px_one(img), pat = first * 0x01010101u;
+    const uint32_t first = fetch_px<1, CH>(img, a.pitch, 0, 0), pat = first * 0x01010101u;
     uint32_t diff = 0u;
     auto both = [&](auto tag) {
 #pragma unroll
@@ -651,7 +625,7 @@ __global__ void __launch_bounds__(HalfPlanOf<MS>::T, HalfPlanOf<MS>::WPE) pc_hal
   constexpr bool PREFETCH = MOF_HALF_PREFETCH != 0 && CH == 1 && !SEQ;  // (SEQ: once per run only, and its registers would be live across the run's loop: 39 spills at M = 120)
   uint32_t ca[PREFETCH ? NCH : 1], cb[PREFETCH ? NCH : 1], cfirst = 0u;
   if constexpr (PREFETCH) {
-    cfirst = px_one(cur);
+    cfirst = fetch_px<1, CH>(cur, a.pitch, 0, 0);
     if (fills) {
 #pragma unroll
       for (int k = 0; k < NCH; ++k) chunk_load(std::true_type{}, k, cur, &ca[k], &cb[k]);
@@ -875,39 +849,21 @@ have_current:
   // ---- weighted centroid in double + validity gate (:1337-1383, :1838-1856), wave 0
   if (wave == 0) {
     for (int w = 1; w < WAVES; ++w) best = better(best, red[w]);
-    const bool have = best.idx != 0x7fffffff;
-    const int py = have ? best.idx / M : 0, pxk = have ? best.idx - py * M : 0;
-    const int ys = py - 2 + lane / 5, xs = pxk - 2 + lane % 5;
+    int ys, xs;
     double val = 0.0;
-    if (have && lane < 25 && ys >= 0 && ys <= M - 1 && xs >= 0 && xs <= M - 1) {  // window clamped to the (padded) patch
-      const int y = ys - H < 0 ? ys - H + M : ys - H, x = xs - H < 0 ? xs - H + M : xs - H;  // un-shifted position
-      const cf s = z[rows_at(y >> 1, x)];
+    if (peak_window<0>(best, lane, M, &ys, &xs)) {  // window clamped to the (padded) patch
+      const int y = peak_unshift(ys, M);
+      const cf s = z[rows_at(y >> 1, peak_unshift(xs, M))];
       val = (double)((y & 1) ? s.y : s.x);
     }
     double cx = (double)xs * val, cy = (double)ys * val, sum = val;
     wave_sum3(cx, cy, sum);
     if (lane == 0) {
-      const double window_sum = sum;
-      sum += 2.220446049250313e-16;  // DBL_EPSILON :1378
-      // shift = -(center - t) = t - M / 2.0 (:1836): cv::phaseCorrelate's centre is that of the PADDED image
-      const double half_m = (double)M / 2.0, half_n = (double)n / 2.0;
-      double sx = cx / sum - half_m, sy = cy / sum - half_m;
-      // a constant patch: its transform is exactly zero off DC, the surface is flat = C_dc (pc_common.hpp). With padding
-      // (m > n) only the all-zero patch stays constant on the padded image.
+      // a constant patch (pc_common.hpp, degenerate pairs); padded (m > n), only the all-zero patch stays constant
       const bool cconst = flags[0] == 0, pconst = flags[1] == 0;
       const bool degenerate = M == n ? (cconst || pconst) : ((cconst && flags[3] == 0) || (pconst && flags[4] == 0));
-      if (degenerate) {
-        const double c9 = 9.0 * (double)__int_as_float(flags[2]);
-        sx = sy = (c9 > 0.0 ? c9 / (c9 + 2.220446049250313e-16) : 0.0) - half_m;
-      }
-      if (a.quality)
-        quality_store<0>(a.quality + 2 * p, window_sum, best.v, (double)M * (double)M, have, degenerate, degenerate ? __int_as_float(flags[2]) : 0.f);
-      // the gate compares with samplePointSize / 2 -- the UNPADDED size (:1841-1842)
-      const bool bad = (sx * sx + sy * sy > a.max_px_speed_sq) || (fabs(sx) > half_n) || (fabs(sy) > half_n) || (sx != sx) ||
-                       (sy != sy) || (!have && !degenerate);
-      if (bad) sx = sy = __builtin_nan("");
-      a.out[2 * p] = sx;
-      a.out[2 * p + 1] = sy;
+      peak_finish<0>(cx, cy, sum, best, M, n, degenerate, degenerate ? __int_as_float(flags[2]) : 0.f, a.max_px_speed_sq, a.out + 2 * p,
+                     a.quality ? a.quality + 2 * p : nullptr);
       if constexpr (SEQ) {  // the current frame becomes the previous one (this lane was the flags' last reader)
         flags[1] = flags[0];
         flags[4] = flags[3];

@@ -28,61 +28,6 @@
 
 namespace mof {
 
-namespace {
-
-// one pixel of the correlated image (row y, column x of the patch whose top-left pixel is `base`): as it is, through the
-// node's CV_RGB2GRAY on BGR8 data (CH = 3), or as the quarter-resolution pixel of the long-range mode (DS = 4) -- the same
-// three front ends as pc_field_kernel (pc_kernel.hip)
-template <int DS, int CH>
-__device__ __forceinline__ uint32_t fetch_px(const uint8_t* __restrict__ base, size_t pitch, int y, int x) {
-  if constexpr (DS == 4) {
-    const uint8_t* r1 = base + (size_t)(4 * y + 1) * pitch + 4 * x;
-    const uint8_t* r2 = r1 + pitch;
-    return ((uint32_t)r1[1] + r1[2] + r2[1] + r2[2] + 2u) >> 2;
-  } else if constexpr (CH == 3) {
-    const uint8_t* p = base + (size_t)y * pitch + 3 * x;
-    return rgb2gray_fixed(p[0], p[1], p[2]);
-  } else {
-    return base[(size_t)y * pitch + x];
-  }
-}
-
-// four consecutive pixels x0 .. x0 + 3 of row y, one byte each (x0 + 3 inside the patch): ONE unaligned dword of a gray frame, three dwords
-// of a BGR8 frame (12 bytes -> four CV_RGB2GRAY values, as K1h's px_gray), or -- the long-range mode -- the 2 x 2 taps of four quarter-resolution
-// pixels from two 16-byte runs of the frame rows 4 y + 1 and 4 y + 2 (cv::resize(1/4, INTER_LINEAR): columns 4 x + 1 and 4 x + 2)
-template <int DS, int CH>
-__device__ __forceinline__ uint32_t fetch_px4(const uint8_t* __restrict__ base, size_t pitch, int y, int x0) {
-  if constexpr (DS == 4) {
-    const uint8_t* r1 = base + (size_t)(4 * y + 1) * pitch + 4 * (size_t)x0;
-    uint32_t w1[4], w2[4];
-    __builtin_memcpy(w1, r1, 16);
-    __builtin_memcpy(w2, r1 + pitch, 16);
-    uint32_t g = 0;
-#pragma unroll
-    for (int b = 0; b < 4; ++b)
-      g |= ((((w1[b] >> 8) & 0xffu) + ((w1[b] >> 16) & 0xffu) + ((w2[b] >> 8) & 0xffu) + ((w2[b] >> 16) & 0xffu) + 2u) >> 2) << (8 * b);
-    return g;
-  } else if constexpr (CH == 3) {
-    uint32_t w[3];
-    __builtin_memcpy(w, base + (size_t)y * pitch + 3 * (size_t)x0, 12);
-    uint32_t g = 0;
-#pragma unroll
-    for (int b = 0; b < 4; ++b) {
-      const int i = 3 * b;
-      const uint32_t c0 = (w[i >> 2] >> (8 * (i & 3))) & 0xffu, c1 = (w[(i + 1) >> 2] >> (8 * ((i + 1) & 3))) & 0xffu,
-                     c2 = (w[(i + 2) >> 2] >> (8 * ((i + 2) & 3))) & 0xffu;
-      g |= rgb2gray_fixed(c0, c1, c2) << (8 * b);
-    }
-    return g;
-  } else {
-    uint32_t w;
-    __builtin_memcpy(&w, base + (size_t)y * pitch + x0, 4);
-    return w;
-  }
-}
-
-}  // namespace
-
 // the planned kernel's arg-max as a sink of the inverse transform's last stage (pc_plan.hpp: stage_rt): line c, element y of the
 // Hermitian column-pair pass carries the surface values at (y, c) and (y, c + H)
 struct ScanSink {
@@ -452,11 +397,7 @@ __global__ void __launch_bounds__(StaticPlanOf<MS>::T, StaticPlanOf<MS>::WPE) pc
     } else {
       s = zat(y, x).x;
     }
-    if constexpr (PK == 1) {
-      const int sr = a.search_radius;
-      const bool masked = (y > sr && y < m - sr) || (x > sr && x < m - sr);
-      s = masked ? 0.f : s * ocl_scale;
-    }
+    if constexpr (PK == 1) s = ocl_scale_mask(s, y, x, a.search_radius, m, ocl_scale);
     return s;
   };
 
@@ -479,46 +420,21 @@ __global__ void __launch_bounds__(StaticPlanOf<MS>::T, StaticPlanOf<MS>::WPE) pc
   if ((MOF_GABL == 5 || MOF_GABL == 7) && tid == 0) a.out[2 * p] = a.out[2 * p + 1] = (double)best.v;
   if (wave == 0 && MOF_GABL != 5 && MOF_GABL != 7) {
     for (int w = 1; w < WAVES; ++w) best = better(best, red[w]);
-    constexpr int RAD = PeakModel<PK>::RAD, W = PeakModel<PK>::W;
-    const bool have = best.idx != 0x7fffffff;
-    const int py = have ? best.idx / m : 0, pxk = have ? best.idx - py * m : 0;
-    const int ys = py - RAD + lane / W, xs = pxk - RAD + lane % W;
+    int ys, xs;
     double val = 0.0;
-    if (have && lane < W * W && ys >= 0 && ys <= m - 1 && xs >= 0 && xs <= m - 1) {  // window clamped to the (padded) patch
-      const int y = ys - H < 0 ? ys - H + m : ys - H, x = xs - H < 0 ? xs - H + m : xs - H;  // un-shifted position
-      const float v = surf(y, x);
+    if (peak_window<PK>(best, lane, m, &ys, &xs)) {  // window clamped to the (padded) patch
+      const float v = surf(peak_unshift(ys, m), peak_unshift(xs, m));
       val = (double)((PK == 1 && !(v > 0.f)) ? 0.f : v);
     }
     double cx = (double)xs * val, cy = (double)ys * val, sum = val;
     wave_sum3(cx, cy, sum);
     if (lane == 0) {
-      const double window_sum = sum;
-      sum += PK == 1 ? 1.1920928955078125e-07 : 2.220446049250313e-16;  // FLT_EPSILON cl:1342 / DBL_EPSILON :1378
-      // shift = -(center - t) = t - M / 2.0 (:1836): cv::phaseCorrelate's centre is that of the PADDED image
-      const double half_m = (double)m / 2.0, half_n = (double)n / 2.0;
-      double sx = cx / sum - half_m, sy = cy / sum - half_m;
-      // a constant patch: its separate transform is exactly zero off DC, the surface is flat = C_dc (pc_common.hpp). With
-      // padding (m > n) only the all-zero patch stays constant on the padded image.
+      // a constant patch (pc_common.hpp, degenerate pairs); padded (m > n), only the all-zero patch stays constant
       const bool cconst = flags[0] == 0, pconst = flags[1] == 0;
       const bool degenerate = m == n ? (cconst || pconst)
                                      : ((cconst && fetch_px<DS, CH>(cur, a.pitch, 0, 0) == 0u) || (pconst && fetch_px<DS, CH>(prev, a.pitch, 0, 0) == 0u));
-      if (degenerate) {
-        if constexpr (PK == 1) {
-          sx = sy = __builtin_nan("");
-        } else {
-          const double c9 = 9.0 * (double)__int_as_float(flags[2]);
-          sx = sy = (c9 > 0.0 ? c9 / (c9 + 2.220446049250313e-16) : 0.0) - half_m;
-        }
-      }
-      if (a.quality)
-        quality_store<PK>(a.quality + 2 * p, PK == 1 ? sum : window_sum, best.v, (double)m * (double)m, have, degenerate,
-                          degenerate ? __int_as_float(flags[2]) : 0.f);
-      // the gate compares with samplePointSize / 2 -- the UNPADDED size (:1841-1842)
-      const bool bad = (sx * sx + sy * sy > a.max_px_speed_sq) || (fabs(sx) > half_n) || (fabs(sy) > half_n) || (sx != sx) ||
-                       (sy != sy) || (!have && !degenerate);
-      if (bad) sx = sy = __builtin_nan("");
-      a.out[2 * p] = sx;
-      a.out[2 * p + 1] = sy;
+      peak_finish<PK>(cx, cy, sum, best, m, n, degenerate, degenerate ? __int_as_float(flags[2]) : 0.f, a.max_px_speed_sq, a.out + 2 * p,
+                      a.quality ? a.quality + 2 * p : nullptr);
     }
   }
 }

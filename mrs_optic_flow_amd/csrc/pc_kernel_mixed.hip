@@ -320,12 +320,10 @@ __global__ void __launch_bounds__(T) pc_field_kernel_120(PcArgs a) {
           c[0] = pfc[b][0]; c[1] = pfc[b][1];
           pv[0] = pfp[b][0]; pv[1] = pfp[b][1];
         } else {  // BGR8 front end (optic_flow.cpp:1622): 8 pixels = 24 bytes = 6 dwords
-          auto byte_of = [](const uint32_t* w, int i) -> uint32_t { return (w[i >> 2] >> (8 * (i & 3))) & 0xffu; };
-          c[0] = c[1] = pv[0] = pv[1] = 0;
 #pragma unroll
-          for (int i = 0; i < 8; ++i) {
-            c[i >> 2] |= rgb2gray_fixed(byte_of(pfc[b], 3 * i), byte_of(pfc[b], 3 * i + 1), byte_of(pfc[b], 3 * i + 2)) << (8 * (i & 3));
-            pv[i >> 2] |= rgb2gray_fixed(byte_of(pfp[b], 3 * i), byte_of(pfp[b], 3 * i + 1), byte_of(pfp[b], 3 * i + 2)) << (8 * (i & 3));
+          for (int h2 = 0; h2 < 2; ++h2) {
+            c[h2] = gray4_at(pfc[b], h2);
+            pv[h2] = gray4_at(pfp[b], h2);
           }
         }
       } else {

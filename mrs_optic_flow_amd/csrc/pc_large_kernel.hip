@@ -15,7 +15,7 @@
 //                     real-only-slot rule (pc_common.hpp; the slots are (0 | M/2, 0 | M/2) for even M, DC alone for odd M),
 //                     conjugate, column transform back -> Dt[u][y]
 //   L7 pcl_rows_inv : Hermitian rows, two per complex transform (16 rows per workgroup), fft-shifted first maximum -> candidates
-//   L8 pcl_final    : first-maximum reduction, the 5 x 5 window re-evaluated from Dt in fp64 (as K8, sr_kernel.hip), centroid;
+//   L8 pcl_final    : first-maximum reduction, the 5 x 5 window re-evaluated from Dt in fp64 (spectrum_window, shared with K8), centroid;
 //                     then EITHER pt -> (scale, rot) with the estimator's gate (scaleRotationEstimator.cpp:119-124) OR
 //                     shift = -pt with FftMethod's gate (FftMethod.cpp:1838-1856, against samplePointSize / 2 -- unpadded).
 // FftMethod under useOCL=true (MOF_PEAK_OCL: even 5-smooth patches, never padded) runs the PK = 1 forms of L6 - L8: the OpenCL kernel's
@@ -39,52 +39,6 @@ constexpr int PCL_LINES = 8;    // lines per workgroup in L5 / L7 (16 image rows
 
 __device__ __forceinline__ int sk(int x) { return x + (x >> 3); }  // line skew: stride-8 stage writes spread over the banks
 
-template <int DS, int CH>
-__device__ __forceinline__ uint32_t fetch_px_l(const uint8_t* __restrict__ base, size_t pitch, int y, int x) {
-  if constexpr (DS == 4) {  // long-range mode: the quarter-resolution pixel of cv::resize(.., 1/4, 1/4) (FftMethod.cpp:1931-1932)
-    const uint8_t* r1 = base + (size_t)(4 * y + 1) * pitch + 4 * x;
-    const uint8_t* r2 = r1 + pitch;
-    return ((uint32_t)r1[1] + r1[2] + r2[1] + r2[2] + 2u) >> 2;
-  } else if constexpr (CH == 3) {  // CV_RGB2GRAY on BGR8 data, as the node applies it (optic_flow.cpp:1622)
-    const uint8_t* p = base + (size_t)y * pitch + 3 * x;
-    return rgb2gray_fixed(p[0], p[1], p[2]);
-  } else {
-    return base[(size_t)y * pitch + x];
-  }
-}
-
-// four consecutive pixels x0 .. x0 + 3 of row y, one byte each (x0 + 3 inside the patch): as pc_kernel_generic.hip's fetch_px4 (r06)
-template <int DS, int CH>
-__device__ __forceinline__ uint32_t fetch_px4_l(const uint8_t* __restrict__ base, size_t pitch, int y, int x0) {
-  if constexpr (DS == 4) {
-    const uint8_t* r1 = base + (size_t)(4 * y + 1) * pitch + 4 * (size_t)x0;
-    uint32_t w1[4], w2[4];
-    __builtin_memcpy(w1, r1, 16);
-    __builtin_memcpy(w2, r1 + pitch, 16);
-    uint32_t g = 0;
-#pragma unroll
-    for (int b = 0; b < 4; ++b)
-      g |= ((((w1[b] >> 8) & 0xffu) + ((w1[b] >> 16) & 0xffu) + ((w2[b] >> 8) & 0xffu) + ((w2[b] >> 16) & 0xffu) + 2u) >> 2) << (8 * b);
-    return g;
-  } else if constexpr (CH == 3) {
-    uint32_t w[3];
-    __builtin_memcpy(w, base + (size_t)y * pitch + 3 * (size_t)x0, 12);
-    uint32_t g = 0;
-#pragma unroll
-    for (int b = 0; b < 4; ++b) {
-      const int i = 3 * b;
-      const uint32_t c0 = (w[i >> 2] >> (8 * (i & 3))) & 0xffu, c1 = (w[(i + 1) >> 2] >> (8 * ((i + 1) & 3))) & 0xffu,
-                     c2 = (w[(i + 2) >> 2] >> (8 * ((i + 2) & 3))) & 0xffu;
-      g |= rgb2gray_fixed(c0, c1, c2) << (8 * b);
-    }
-    return g;
-  } else {
-    uint32_t w;
-    __builtin_memcpy(&w, base + (size_t)y * pitch + x0, 4);
-    return w;
-  }
-}
-
 // ---- L5 ------------------------------------------------------------------------------------------------------------------
 template <int DS, int CH, bool EXACT>
 __global__ void __launch_bounds__(PCL_T) pcl_rows_kernel(PclSrc src, PcPlan pl, const float* __restrict__ twiddles,
@@ -106,7 +60,7 @@ __global__ void __launch_bounds__(PCL_T) pcl_rows_kernel(PclSrc src, PcPlan pl, 
   for (int k = tid; k < m; k += PCL_T) tw[k] = {twiddles[2 * k], twiddles[2 * k + 1]};
   // the wave's two lines: line l = image rows (row0 + 2l, row0 + 2l + 1) as real and imaginary part; zeros beyond n x n
   // (copyMakeBorder of cv::phaseCorrelate), u8 -> f32 (convertTo, FftMethod.cpp:1805-1806 / scaleRotationEstimator.cpp:115)
-  const uint32_t p00 = fetch_px_l<DS, CH>(base, src.pitch, 0, 0);
+  const uint32_t p00 = fetch_px<DS, CH>(base, src.pitch, 0, 0);
   uint32_t diff = 0u;
   {
     // all of the lane's pixel loads go out before the first is used (a load-use loop pays the memory latency once per trip); r06: FOUR pixels
@@ -119,13 +73,13 @@ __global__ void __launch_bounds__(PCL_T) pcl_rows_kernel(PclSrc src, PcPlan pl, 
       if (tiny) {
         if (y >= n || x0 >= n) return 0u;
         uint32_t v = 0u;
-        for (int b = 0; x0 + b < n; ++b) v |= fetch_px_l<DS, CH>(base, src.pitch, y, x0 + b) << (8 * b);
+        for (int b = 0; x0 + b < n; ++b) v |= fetch_px<DS, CH>(base, src.pitch, y, x0 + b) << (8 * b);
         return v;
       }
       // branch-free (r06, as the tuned row kernel's px4): an unconditional load of row min(y, n - 1), of the four pixels that end no later
       // than the row does; what lies outside the patch is shifted / masked away -- so that all of a lane's loads are in flight together
       const int yc = y < n ? y : n - 1, xc = x0 < n - 4 ? x0 : n - 4, sh = x0 - xc;
-      uint32_t v = fetch_px4_l<DS, CH>(base, src.pitch, yc, xc);
+      uint32_t v = fetch_px4<DS, CH>(base, src.pitch, yc, xc);
       v = sh >= 4 ? 0u : v >> (8 * (sh & 3));
       return y < n ? v : 0u;
     };
@@ -339,112 +293,39 @@ __global__ void __launch_bounds__(PCL_T) pcl_rows_inv_kernel(const float* __rest
 }
 
 // ---- L8 ------------------------------------------------------------------------------------------------------------------
-// The W x W window values (W = 5, PK = 1: 7) are re-evaluated from the half spectrum of their rows (Dt), in double, as K8 (sr_kernel.hip) does:
-//   S[y][x] = Re G[y][0] + [M even: (-1)^x Re G[y][M/2]] + 2 sum_{u=1}^{(M-1)/2} Re(G[y][u] W^{ux})
-// PK = 1 (mode 1 only): each value cast to float, scaled and masked as L7 scanned it, values <= 0 dropped, the sum seeded with FLT_EPSILON
-// (pc_common.hpp, PeakModel / centroid_gate_store); a constant patch has no finite surface (1 / 0 in a real-only slot) and gives NaN.
+// The W x W window values (W = 5, PK = 1: 7) are re-evaluated from the half spectrum of their rows (Dt), in double (pc_common.hpp, spectrum_window).
+// PK = 1 (mode 1 only): each value scaled and masked as L7 scanned it, values <= 0 dropped, the sum seeded with FLT_EPSILON
+// (pc_common.hpp, PeakModel / peak_finish); a constant patch has no finite surface (1 / 0 in a real-only slot) and gives NaN.
 template <int PK>
 __global__ void __launch_bounds__(64) pcl_final_kernel(PclFinal a) {
-  constexpr int RAD = PeakModel<PK>::RAD, W = PeakModel<PK>::W, WW = W * W;
+  constexpr int W = PeakModel<PK>::W, WW = W * W;
   __shared__ double part[WW][65];
-  const int m = a.m, H = m >> 1;
-  const bool even = (m & 1) == 0;
-  const int umax = even ? H - 1 : H;
-  const int lane = threadIdx.x, pair = blockIdx.x;
-  Best best = {-__builtin_huge_valf(), 0x7fffffff};
-  for (int i = lane; i < a.n_cand; i += 64) {
-    const float2 c = a.cand[(size_t)pair * a.n_cand + i];
-    best = better(best, Best{c.x, __float_as_int(c.y)});
+  const int m = a.m, lane = threadIdx.x;
+  const size_t pair = blockIdx.x;
+  Best best;
+  float v = spectrum_window<W, 0>(a.cand + pair * a.n_cand, a.n_cand, reinterpret_cast<const cf*>(a.Dt) + pair * ((m >> 1) + 1) * m, a.twiddles, m,
+                                  lane, part, &best);
+  int ys, xs;
+  peak_window<PK>(best, lane, m, &ys, &xs);
+  if constexpr (PK == 1) {
+    v = ocl_scale_mask(v, peak_unshift(ys, m), peak_unshift(xs, m), a.search_radius, m, 1.0f / (float)(m * m));
+    v = v > 0.f ? v : 0.f;
   }
-  best = wave_best(best);
-  const cf* Dt = reinterpret_cast<const cf*>(a.Dt) + (size_t)pair * (H + 1) * m;
-  const bool have = best.idx != 0x7fffffff;
-  const int px = have ? best.idx % m : 0, py = have ? best.idx / m : 0;
-  int wy[W], wx[W];  // window rows / columns in un-shifted coordinates
-#pragma unroll
-  for (int k = 0; k < W; ++k) {
-    wy[k] = ((((py - RAD + k) % m) + m) % m - H + m) % m;
-    wx[k] = ((((px - RAD + k) % m) + m) % m - H + m) % m;
-  }
-  double acc[WW];
-#pragma unroll
-  for (int k = 0; k < WW; ++k) acc[k] = 0.0;
-  for (int u = 1 + lane; u <= umax; u += 64) {
-    cf f[W];
-#pragma unroll
-    for (int r = 0; r < W; ++r) f[r] = Dt[(size_t)u * m + wy[r]];
-#pragma unroll
-    for (int c = 0; c < W; ++c) {
-      const float2 w = *reinterpret_cast<const float2*>(a.twiddles + 2 * (int)(((long)u * wx[c]) % m));  // (cos, -sin)
-#pragma unroll
-      for (int r = 0; r < W; ++r) acc[r * W + c] += (double)f[r].x * (double)w.x - (double)f[r].y * (double)w.y;
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < WW; ++k) part[k][lane] = acc[k];
-  __syncthreads();
-  const int ys = py - RAD + lane / W, xs = px - RAD + lane % W;
-  double cx = 0.0, cy = 0.0, sum = 0.0;
-  if (have && lane < WW && ys >= 0 && ys <= m - 1 && xs >= 0 && xs <= m - 1) {  // window clamped to the (padded) image
-    const int y = wy[lane / W], x = wx[lane % W];
-    double s2 = 0.0;
-    for (int l = 0; l < 64; ++l) s2 += part[lane][l];
-    double s0 = (double)Dt[y].x;
-    if (even) s0 += ((x & 1) ? -1.0 : 1.0) * (double)Dt[(size_t)H * m + y].x;
-    double val = (double)(float)(s0 + 2.0 * s2);  // the surface is CV_32F
-    if constexpr (PK == 1) {
-      const float v = ocl_scale_mask((float)val, y, x, a.search_radius, m, 1.0f / (float)(m * m));
-      val = v > 0.f ? (double)v : 0.0;
-    }
-    cx = (double)xs * val;
-    cy = (double)ys * val;
-    sum = val;
-  }
+  const double val = (double)v;  // 0 for lanes outside the window
+  double cx = (double)xs * val, cy = (double)ys * val, sum = val;
   wave_sum3<(WW > 32 ? 32 : 16)>(cx, cy, sum);
   if (lane != 0) return;
-  const double window_sum = sum;
-  sum += PK == 1 ? 1.1920928955078125e-07 : 2.220446049250313e-16;  // FLT_EPSILON cl:1342 / DBL_EPSILON, FftMethod.cpp:1378
-  const double half_m = (double)m / 2.0;  // cv::phaseCorrelate's centre: that of the PADDED image
-  if (PK == 0 && a.mode == 0) {
-    // scaleRotationEstimator: pt = center - t, NOT negated (:117); |pt.x| > resolution / 2 (int division) -> (1, 0) (:119-121)
-    const double ptx = half_m - cx / sum, pty = half_m - cy / sum;
-    double scale = 1.0, rot = 0.0;
-    if (!(fabs(ptx) > (double)(a.n / 2))) {
-      scale = exp(ptx / a.M_log);
-      rot = (pty / ((double)a.n / 360.0)) * (3.14159265358979323846 / 180.0);
-    }
-    double* o = a.out + 4 * (size_t)pair;
-    o[0] = scale;
-    o[1] = rot;
-    o[2] = ptx;
-    o[3] = pty;
-  } else {
-    // FftMethod: shift = -cv::phaseCorrelate(cur, prev) = t - M/2 (:1836); the OpenCL branch returns t - M/2 un-negated (:1833) -- the
-    // same number; gate against samplePointSize / 2 (:1838-1856)
-    double sx = cx / sum - half_m, sy = cy / sum - half_m;
+  if (PK == 0 && a.mode == 0) {  // scaleRotationEstimator
+    sr_finish(cx, cy, sum, m, a.n, a.M_log, false, a.out + 4 * pair);
+  } else {  // FftMethod
     bool degenerate = false;
     if (a.flags) {  // a constant patch (pc_common.hpp, degenerate pairs); padded, only the all-zero patch stays constant
       const int fc = a.flags[2 * pair], fp = a.flags[2 * pair + 1];
       const bool cc = (fc & 1) == 0, pc = (fp & 1) == 0;
       degenerate = m == a.n ? (cc || pc) : ((cc && (fc & 2) == 0) || (pc && (fp & 2) == 0));
     }
-    if (degenerate) {
-      if constexpr (PK == 1) {
-        sx = sy = __builtin_nan("");  // 1 / (a b) with b = 0 in the other real-only slots (cl:1029): no finite surface
-      } else {
-        const double c9 = 9.0 * (double)a.cdc[pair];
-        sx = sy = (c9 > 0.0 ? c9 / (c9 + 2.220446049250313e-16) : 0.0) - half_m;
-      }
-    }
-    if (a.quality)
-      quality_store<PK>(a.quality + 2 * (size_t)pair, PK == 1 ? sum : window_sum, best.v, (double)m * (double)m, have, degenerate,
-                        (PK == 0 && degenerate) ? a.cdc[pair] : 0.f);
-    const double half_n = (double)a.n / 2.0;
-    const bool bad = (sx * sx + sy * sy > a.max_px_speed_sq) || (fabs(sx) > half_n) || (fabs(sy) > half_n) || (sx != sx) ||
-                     (sy != sy) || (!have && !degenerate);
-    if (bad) sx = sy = __builtin_nan("");
-    a.out[2 * (size_t)pair] = sx;
-    a.out[2 * (size_t)pair + 1] = sy;
+    peak_finish<PK>(cx, cy, sum, best, m, a.n, degenerate, (PK == 0 && degenerate) ? a.cdc[pair] : 0.f, a.max_px_speed_sq, a.out + 2 * pair,
+                    a.quality ? a.quality + 2 * pair : nullptr);
   }
 }
 

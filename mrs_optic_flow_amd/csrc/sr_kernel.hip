@@ -688,79 +688,21 @@ __global__ void __launch_bounds__(K7Cfg<N>::T) sr_rows_inv_kernel(SrPcArgs a) {
 }
 
 // ---- K8: peak, centroid, (scale, rot) ----------------------------------------------------------------------
-// out[pair] = {scale, rot, pt.x, pt.y}; pt = cv::phaseCorrelate(cur_lp, prev_lp) = center - t (NOT negated, :117);
-// |pt.x| > res/2 -> (1, 0) (:119-121); scale = exp(pt.x / M), rot = (pt.y / Ky) pi/180, Ky = res/360 (:123-124).
-// The 25 surface values of the window are re-evaluated from the half spectrum of their rows (Dt), in double:
-//   S[y][x] = Re F[y][0] + (-1)^x Re F[y][N/2] + 2 sum_{u=1}^{N/2-1} (Re F[y][u] cos(2 pi u x / N) + Im F[y][u] sin(..))
-// which is what K7's transform computes for that point (K7 keeps no surface).
+// out[pair] = {scale, rot, pt.x, pt.y} (pc_common.hpp, sr_finish). K7 keeps no surface: the 25 values of the window are re-evaluated from the
+// half spectrum of their rows (Dt), in double (spectrum_window).
 template <int N>
 __global__ void __launch_bounds__(64) sr_final_kernel(SrPcArgs a) {
-  constexpr int H = N / 2;
   __shared__ double part[25][65];
-  const int lane = threadIdx.x, pair = blockIdx.x;
-  Best best = {-__builtin_huge_valf(), 0x7fffffff};
-  for (int i = lane; i < a.n_cand; i += 64) {
-    const float2 c = a.cand[(size_t)pair * a.n_cand + i];
-    best = better(best, Best{c.x, __float_as_int(c.y)});
-  }
-  best = wave_best(best);
-  const cf* Dt = reinterpret_cast<const cf*>(a.Dt) + (size_t)pair * (H + 1) * N;
-  const bool have = best.idx != 0x7fffffff;
-  const int px = have ? best.idx % N : 0, py = have ? best.idx / N : 0;
-  // window rows / columns in un-shifted coordinates (entries outside the clamped window are skipped at the end)
-  int wy[5], wx[5];
-#pragma unroll
-  for (int k = 0; k < 5; ++k) {
-    wy[k] = (((py - 2 + k) % N + N) + H) % N;
-    wx[k] = (((px - 2 + k) % N + N) + H) % N;
-  }
-  // the 240-term sums are split over the lanes by u (lane, lane + 64, ..), 25 partial sums each, ...
-  double acc[25];
-#pragma unroll
-  for (int k = 0; k < 25; ++k) acc[k] = 0.0;
-  for (int u = 1 + lane; u < H; u += 64) {
-    cf f[5];
-#pragma unroll
-    for (int r = 0; r < 5; ++r) f[r] = Dt[(size_t)u * N + wy[r]];
-#pragma unroll
-    for (int c = 0; c < 5; ++c) {
-      const float2 w = *reinterpret_cast<const float2*>(a.twiddles + 2 * (int)(((long)u * wx[c]) % N));  // (cos, -sin)
-#pragma unroll
-      for (int r = 0; r < 5; ++r) acc[r * 5 + c] += (double)f[r].x * (double)w.x - (double)f[r].y * (double)w.y;
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < 25; ++k) part[k][lane] = acc[k];
-  __syncthreads();
-  // ... and lane k < 25 adds the 64 partial sums of its window point in a fixed order
-  const int ys = py - 2 + lane / 5, xs = px - 2 + lane % 5;
-  double cx = 0.0, cy = 0.0, sum = 0.0;
-  if (have && lane < 25 && ys >= 0 && ys <= N - 1 && xs >= 0 && xs <= N - 1) {
-    const int y = wy[lane / 5], x = wx[lane % 5];
-    double s2 = 0.0;
-    for (int l = 0; l < 64; ++l) s2 += part[lane][l];
-    const double s0 = (double)Dt[y].x + ((x & 1) ? -1.0 : 1.0) * (double)Dt[(size_t)H * N + y].x;
-    const double val = (double)(float)(s0 + 2.0 * s2);  // the surface is CV_32F
-    cx = (double)xs * val;
-    cy = (double)ys * val;
-    sum = val;
-  }
+  const int lane = threadIdx.x;
+  const size_t pair = blockIdx.x;
+  Best best;
+  const double val = (double)spectrum_window<5, N>(a.cand + pair * a.n_cand, a.n_cand, reinterpret_cast<const cf*>(a.Dt) + pair * (N / 2 + 1) * N,
+                                                   a.twiddles, N, lane, part, &best);
+  int ys, xs;
+  peak_window<0>(best, lane, N, &ys, &xs);
+  double cx = (double)xs * val, cy = (double)ys * val, sum = val;
   wave_sum3<16>(cx, cy, sum);
-  if (lane == 0) {
-    sum += 2.220446049250313e-16;
-    double ptx = (double)N / 2.0 - cx / sum, pty = (double)N / 2.0 - cy / sum;
-    if (a.degen && a.degen[pair]) ptx = pty = (double)N / 2.0;  // flat zero surface: first index, centroid 0 / (0 + eps)
-    double scale = 1.0, rot = 0.0;
-    if (!(fabs(ptx) > (double)(N / 2))) {
-      scale = exp(ptx / a.M);
-      rot = (pty / ((double)N / 360.0)) * (3.14159265358979323846 / 180.0);
-    }
-    double* o = a.out + 4 * (size_t)pair;
-    o[0] = scale;
-    o[1] = rot;
-    o[2] = ptx;
-    o[3] = pty;
-  }
+  if (lane == 0) sr_finish(cx, cy, sum, N, N, a.M, a.degen && a.degen[pair], a.out + 4 * pair);
 }
 
 // (the list: MOF_SR_TUNED_SIZES, sr_common.hpp)

@@ -13,6 +13,7 @@ import torch
 
 import oracle_lib as O
 from mrs_optic_flow_amd import FftMethod
+from mrs_optic_flow_amd.engine import PEAK_OCL
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-4
@@ -59,6 +60,32 @@ def test_peak_on_every_corner_and_edge(gpu, n, variant):
         for k in (0, 7, 35):
             seq = fm.process_sequence_device(torch.stack([p[k], c[k]])).cpu().numpy()[0, 0]
             assert np.array_equal(seq, got[k], equal_nan=True), (k, seq, got[k])
+
+
+@functools.lru_cache(maxsize=None)
+def _case_ocl(n):
+    """the same 36 pairs under the OpenCL kernel's peak model with search_radius = n (no row or column masked): the f64 oracle's [36, 2]"""
+    prev, cur, _ = _case(n)
+    lay = O.fft_layout(n, n, n, 1, 1, max_px_speed=SPEED)
+    want = np.stack([O.fft_process_ocl(c, prev, lay, search_radius=n, precision=64)[0][0] for c in cur])
+    want.setflags(write=False)
+    return want
+
+
+@pytest.mark.parametrize("n,variant", [(64, "stockham"), (60, "planned"), (144, "planned-large")])
+def test_ocl_window_clamped_at_every_corner_and_edge(gpu, n, variant):
+    """The OpenCL model's 7 x 7 window (49 lanes, values > 0 only) clamped at the surface's edges: K1 (64), the planned kernel (60), the
+    large-patch pipeline (144). With only positive values in a window clamped at 0 the centroid cannot leave +-n/2: no pair is gated
+    (on these pairs the f32 and f64 oracles agree within 3.7e-6 / 4.4e-6 / 1.35e-5 px and on the NaN pattern -- checked once on the CPU)."""
+    prev, cur, _ = _case(n)
+    want = _case_ocl(n)
+    fm = FftMethod(sample_point_size=n, max_px_speed=SPEED, frame_shape=(n, n), grid=(1, 1), peak_model=PEAK_OCL, search_radius=n)
+    assert fm.kernel_variant == variant, fm.kernel_variant
+    assert not np.isnan(want).any()
+    c = torch.from_numpy(np.ascontiguousarray(cur)).to(gpu)
+    p = torch.from_numpy(np.ascontiguousarray(prev)).to(gpu).expand(len(cur), n, n).contiguous()
+    got = fm.process_batch_device(c, p).cpu().numpy()[:, 0]
+    _check(got, want, f"n={n} {fm.kernel_variant} OpenCL model")
 
 
 def _tiled(n, g, order):
