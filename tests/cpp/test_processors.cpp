@@ -7,6 +7,9 @@
 //          test_processors fsbm <w> <h> <sps> <step> <radius> <nframes> <file>
 //          test_processors fftseq <frameSize> <sps> <max_px_speed> <nframes> <file>   (video on the device, sequence entry)
 //          test_processors srseq <res> <M> <nframes> <file>                          (estimator: sequence entry + stateful loop)
+//          test_processors fftq <frameSize> <sps> <max_px_speed> <nframes> <file>     (stateful loop with lastQuality(); the LAST frame goes
+//                                                                                      through processImageLongRange)
+//          test_processors fftseqq <frameSize> <sps> <max_px_speed> <nframes> <file>  (processBatchDeviceQ and processSequenceDeviceQ on a video)
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -116,6 +119,57 @@ int main(int argc, char** argv) {
       }
       (void)hipFree(d_frames);
       (void)hipFree(d_out);
+      return 0;
+    }
+    if (argc >= 7 && !std::strcmp(argv[1], "fftq")) {
+      const int fs = std::atoi(argv[2]), sps = std::atoi(argv[3]), n = std::atoi(argv[5]);
+      const double mps = std::atof(argv[4]);
+      auto frames = read_all(argv[6], (size_t)fs * fs * n);
+      mof::FftMethod proc(fs, sps, mps);
+      std::vector<uint8_t> zeros((size_t)fs * fs, 0);
+      proc.setImPrev(mof::ImageView{zeros.data(), fs, fs, (size_t)fs});
+      std::vector<mof::Point2d> raw;
+      for (int t = 0; t < n; ++t) {
+        const mof::ImageView im{frames.data() + (size_t)t * fs * fs, fs, fs, (size_t)fs};
+        const bool lr = t == n - 1;
+        auto v = lr ? proc.processImageLongRange(im, false, false, mof::Point2i{fs / 2, fs / 2}, 0.0, mof::Point2d{0, 0}, raw, 300, 300)
+                    : proc.processImage(im, false, false, mof::Point2i{fs / 2, fs / 2}, 0.0, mof::Point2d{0, 0}, raw, 300, 300);
+        const auto& q = proc.lastQuality();
+        if (q.size() != v.size()) throw std::runtime_error("lastQuality() is not indexed as the vectors");
+        std::printf("%s %d n %zu", lr ? "lr" : "frame", t, v.size());
+        for (size_t i = 0; i < v.size(); ++i) std::printf(" %.17g %.17g %.17g %.17g", v[i].x, v[i].y, q[i].response, q[i].peak);
+        std::printf("\n");
+      }
+      return 0;
+    }
+    if (argc >= 7 && !std::strcmp(argv[1], "fftseqq")) {
+      const int fs = std::atoi(argv[2]), sps = std::atoi(argv[3]), n = std::atoi(argv[5]);
+      const double mps = std::atof(argv[4]);
+      auto frames = read_all(argv[6], (size_t)fs * fs * n);
+      mof::FftMethod proc(fs, sps, mps);
+      const size_t per = (size_t)proc.sqNum() * proc.sqNum() * 2, total = per * (n - 1), fb = (size_t)fs * fs;
+      uint8_t* d_frames = nullptr;
+      double* d_res = nullptr;  // shifts | quality of the pair entry, shifts | quality of the video entry
+      if (n < 2 || hipMalloc((void**)&d_frames, frames.size()) != hipSuccess || hipMalloc((void**)&d_res, 4 * total * sizeof(double)) != hipSuccess ||
+          hipMemcpy(d_frames, frames.data(), frames.size(), hipMemcpyHostToDevice) != hipSuccess)
+        throw std::runtime_error("device buffers");
+      proc.processBatchDeviceQ(d_frames + fb, fb, d_frames, fb, (size_t)fs, n - 1, d_res, d_res + total);
+      proc.processSequenceDeviceQ(d_frames, fb, (size_t)fs, n, d_res + 2 * total, d_res + 3 * total);
+      std::vector<double> res(4 * total);
+      if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(res.data(), d_res, res.size() * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+        throw std::runtime_error("read-back");
+      for (int e = 0; e < 2; ++e)
+        for (int t = 0; t + 1 < n; ++t) {
+          std::printf("%s %d n %zu", e ? "seq" : "pair", t, per / 2);
+          for (size_t i = 0; i < per / 2; ++i) {
+            const size_t at = (size_t)t * per + 2 * i;
+            std::printf(" %.17g %.17g %.17g %.17g", res[2 * e * total + at], res[2 * e * total + at + 1], res[(2 * e + 1) * total + at],
+                        res[(2 * e + 1) * total + at + 1]);
+          }
+          std::printf("\n");
+        }
+      (void)hipFree(d_frames);
+      (void)hipFree(d_res);
       return 0;
     }
     if (argc >= 6 && !std::strcmp(argv[1], "srseq")) {

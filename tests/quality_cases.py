@@ -21,6 +21,12 @@ CIRCULAR_SIZES = ((32, "stockham"), (64, "stockham"), (120, "planned-half"), (54
 PADDED_SIZES = ((62, "planned"), (142, "planned-half"), (196, "planned-large"))
 VIDEO_SIZES = (64, 120, 128, 200)
 OCL_SIZES = ((64, "stockham"), (60, "planned"), (144, "planned-large"))
+# the long videos: (frame width, frames, seed, grid) -- more pairs than one run of the sequence kernels walks (runs of 2 at 64, of 4 on the
+# half tile at 120 / 128 with nothing forced: mof_capi.hip fft_sequence and the launchers), a ragged last run, passes of the large video form
+LONG_VIDEOS = {64: (192, 38, 6400, (3, 1)), 120: (240, 22, 12000, (2, 1)), 128: (256, 11, 12800, (2, 1)), 200: (400, 11, 20000, (2, 1))}
+# long-range launches stay on the family's kernel (the planned kernel at 60, the tuned 120 kernel, L5 - L8 at 200); kernel_variant names
+# the full-resolution route
+LONG_RANGE_SIZES = ((60, "planned-half"), (120, "planned-half"), (200, "planned-large"))
 
 
 def circular_shifts(n):
@@ -148,12 +154,94 @@ def ocl(n):
     return Batch(f"OpenCL model n={n}", n, cur, prev, ocl=True)
 
 
+@functools.lru_cache(maxsize=None)
+def grid64():
+    """n = 64, 7 pairs of a NON-square grid (3 x 2): a transposed patch index, invisible on 2 x 2 only by luck, shows here; seven pairs
+    make four host chunks of two with a ragged last one"""
+    cur, prev = crop_pairs(128, 192, 7, seed=9600)
+    return Batch("grid 3 x 2 n=64", 64, cur, prev, grid=(3, 2))
+
+
+@functools.lru_cache(maxsize=None)
+def passes200():
+    """10 pairs of two 200-pixel patches: four passes of three pairs through the large pipeline's scratch"""
+    cur, prev = crop_pairs(200, 400, 10, seed=7200)
+    return Batch("passes n=200", 200, cur, prev, grid=(2, 1))
+
+
+@functools.lru_cache(maxsize=None)
+def ocl_passes144():
+    """7 pairs of two 144-pixel patches under the OpenCL model (L5 - L8): three passes of three pairs"""
+    cur, prev = crop_pairs(144, 288, 7, seed=14400)
+    return Batch("OpenCL passes n=144", 144, cur, prev, grid=(2, 1), ocl=True)
+
+
+@functools.lru_cache(maxsize=None)
+def long_video(n):
+    w, frames, seed, grid = LONG_VIDEOS[n]
+    f = crop_video(n, w, frames, seed=seed)
+    b = Batch(f"long video n={n}", n, f[1:], f[:-1], grid=grid)
+    b.frames = f
+    return b
+
+
+@functools.lru_cache(maxsize=None)
+def padded246():
+    cur, prev = crop_pairs(246, 246, 6, seed=246)
+    return Batch("padded crops n=246 (M = 250)", 246, cur, prev)
+
+
+@functools.lru_cache(maxsize=None)
+def crops400():
+    cur, prev = crop_pairs(400, 400, 4, seed=400)
+    return Batch("crops n=400", 400, cur, prev)
+
+
+@functools.lru_cache(maxsize=None)
+def long_range_n(n):
+    """4n x 4n frames, patch size n (sqNum = 4: one quarter-resolution patch of n pixels), shifts of whole quarter-resolution pixels"""
+    cur, prev = crop_pairs(4 * n, 4 * n, 4, seed=40 * n, step=4)
+    qc, qp = np.stack([O.resize_quarter(c) for c in cur]), np.stack([O.resize_quarter(p) for p in prev])
+    return Batch(f"long range {4 * n} / {n}", n, cur, prev, oracle_cur=qc, oracle_prev=qp)
+
+
+@functools.lru_cache(maxsize=None)
+def cpp_video():
+    """the C++ mirror's frames (test_gpu_cpp_host.py): a 6-frame video of 128 x 128 frames, patch size 32 (a 4 x 4 grid, so the geometry
+    has a long-range form)"""
+    f = crop_video(128, 128, 6, seed=3200)
+    b = Batch("C++ mirror video 128 / 32", 32, f[1:], f[:-1], grid=(4, 4))
+    b.frames = f
+    return b
+
+
+SPLIT_SIZES = ((32, "stockham"), (16, "planned"), (60, "planned-half"))
+
+
+@functools.lru_cache(maxsize=None)
+def split_period(n):
+    """Eight circular shifts of one random n x n patch along a closed walk: pair k = (shift k + 1, shift k), k mod 8 -- the period of the
+    65 540-pair batches that cross a launch split of the pair kernels (the pair index rides gridDim.z, 65535 at most)"""
+    base = np.random.default_rng(900 + n).integers(0, 256, (n, n), dtype=np.uint8)
+    pos = np.concatenate([[(0, 0)], np.cumsum([(1, -2), (-3, 2), (0, 1), (2, 0), (1, -2), (-3, 2), (0, 1)], axis=0)])
+    protos = np.stack([np.roll(base, (int(y), int(x)), axis=(0, 1)) for x, y in pos])
+    b = Batch(f"split period n={n}", n, protos[(np.arange(8) + 1) % 8], protos)
+    b.protos = protos
+    return b
+
+
 def _registry():
     r = {f"circular-{n}": functools.partial(circular, n) for n, _ in CIRCULAR_SIZES}
     r.update({f"padded-{n}": functools.partial(padded, n) for n, _ in PADDED_SIZES})
     r.update({f"video-{n}": functools.partial(video, n) for n in VIDEO_SIZES})
     r.update({"crops-64": crops64, "long-range": long_range})
     r.update({f"ocl-{n}": functools.partial(ocl, n) for n, _ in OCL_SIZES})
+    r.update({"grid-64": grid64, "passes-200": passes200, "ocl-passes-144": ocl_passes144, "padded-246": padded246, "crops-400": crops400,
+              "cpp-video": cpp_video})
+    r.update({f"long-video-{n}": functools.partial(long_video, n) for n in LONG_VIDEOS})
+    r.update({f"circular-{n}": functools.partial(circular, n) for n in (128, 250)})
+    r.update({f"long-range-{n}": functools.partial(long_range_n, n) for n, _ in LONG_RANGE_SIZES})
+    r.update({f"split-{n}": functools.partial(split_period, n) for n, _ in SPLIT_SIZES})
     return r
 
 

@@ -146,3 +146,78 @@ def test_cpp_mirror_sequence_entries(gpu, tmp_path):
         assert abs(seq[0] - ws) < 1e-5 and abs(seq[1] - wr) < 1e-5
         if t > 0:
             assert np.allclose(seq[2:], ref.pt, rtol=0, atol=1e-4)
+
+
+def _quads(tok):
+    """the (x, y, response, peak) quadruples of one printed line -> shifts [patches, 2], quality [patches, 2]"""
+    a = np.array([float(v) for v in tok[4:]]).reshape(int(tok[3]), 4)
+    return a[:, :2], a[:, 2:]
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
+
+
+def test_cpp_mirror_stateful_quality(gpu, tmp_path):
+    """mof::FftMethod::lastQuality() beside the vectors of the stateful loop (mode fftq): the 6-frame video of quality_cases.cpp_video
+    (128 x 128 frames, patch size 32, a 4 x 4 grid) and then the first long-range pair of quality_cases.long_range -- its previous
+    frame through processImage, its current one through processImageLongRange. The quality of pairs 1 .. 5 and of the long-range
+    call against the f64 oracle at 360 d (each batch's own d); the first frame correlates with itself (`first`): its response lies in
+    (0.9, 1 + bar] and every frame's vectors are what the `fft` mode prints. (Frame 6 against frame 5 is an unrelated pair with no
+    clear peak: its vectors are held to the `fft` mode's bits, its quality to no value.)"""
+    import quality_cases as Q
+
+    b, lr = Q.cpp_video(), Q.long_range()
+    frames = np.concatenate([b.frames, lr.prev[:1], lr.cur[:1]])
+    n = len(frames)
+    lines = _run(["fftq", 128, 32, Q.SPEED, n], frames, tmp_path)
+    plain = _run(["fft", 128, 32, Q.SPEED, n - 1], frames[:-1], tmp_path)
+    assert len(lines) == n and [tok[0] for tok in lines] == ["frame"] * (n - 1) + ["lr"]
+    got = []
+    for t, tok in enumerate(lines[:-1]):
+        assert int(tok[1]) == t and int(tok[3]) == 16
+        s, q = _quads(tok)
+        assert np.array_equal(_bits(s), _bits(np.array([float(v) for v in plain[t][4:]]).reshape(16, 2))), t
+        got.append(q)
+    first = got[0]
+    print(f"first frame against itself: response {first[:, 0].min():.9f} .. {first[:, 0].max():.9f}, bar 1 + {b.bar:.3e}")
+    assert (first[:, 0] > 0.9).all() and (first[:, 0] <= 1.0 + b.bar).all() and np.isfinite(first).all(), first
+    err = np.abs(np.stack(got[1:len(b.frames)]) - b.want).reshape(-1, 2).max(axis=0)
+    print(f"lastQuality() of pairs 1 .. {len(b.frames) - 1}: max |response - f64 oracle| = {err[0]:.3e}, max |peak - f64 oracle| = {err[1]:.3e}, "
+          f"bar 360 x {b.d:.2e} = {b.bar:.3e}")
+    assert err.max() <= b.bar, (err.tolist(), b.bar)
+    tok = lines[-1]
+    assert int(tok[1]) == n - 1 and int(tok[3]) == 1
+    s, q = _quads(tok)
+    err = np.abs(q - lr.want[0]).max(axis=0)
+    print(f"lastQuality() of processImageLongRange: |response - f64 oracle| = {err[0]:.3e}, |peak - f64 oracle| = {err[1]:.3e}, "
+          f"bar 360 x {lr.d:.2e} = {lr.bar:.3e}")
+    assert err.max() <= lr.bar, (err.tolist(), lr.bar)
+    assert np.allclose(s, lr.shifts[0], rtol=0, atol=1e-4, equal_nan=True), (s, lr.shifts[0])
+
+
+def test_cpp_mirror_device_entries_with_quality(gpu, tmp_path):
+    """mof::FftMethod::processBatchDeviceQ on (frames[1:], frames[:-1]) and processSequenceDeviceQ on the video (mode fftseqq), the
+    frames of quality_cases.cpp_video: shifts and quality have the bits the Python binding's entries return on the same frames, and
+    the quality is the f64 oracle's at 360 d."""
+    import torch
+
+    import quality_cases as Q
+    from mrs_optic_flow_amd import FftMethod
+
+    b = Q.cpp_video()
+    n = len(b.frames)
+    lines = _run(["fftseqq", 128, 32, Q.SPEED, n], b.frames, tmp_path)
+    assert len(lines) == 2 * (n - 1) and [tok[0] for tok in lines] == ["pair"] * (n - 1) + ["seq"] * (n - 1)
+    fm = FftMethod(128, 32, Q.SPEED)
+    f = torch.from_numpy(b.frames).to(gpu)
+    want = {"pair": fm.process_batch_device(f[1:], f[:-1], return_quality=True), "seq": fm.process_sequence_device(f, return_quality=True)}
+    for e, name in enumerate(("pair", "seq")):
+        got = [_quads(tok) for tok in lines[e * (n - 1):(e + 1) * (n - 1)]]
+        s, q = np.stack([g[0] for g in got]), np.stack([g[1] for g in got])
+        err = np.abs(q - b.want).reshape(-1, 2).max(axis=0)
+        print(f"{name} entry through the C++ mirror: max |response - f64 oracle| = {err[0]:.3e}, max |peak - f64 oracle| = {err[1]:.3e}, "
+              f"bar 360 x {b.d:.2e} = {b.bar:.3e}")
+        assert err.max() <= b.bar, (name, err.tolist(), b.bar)
+        assert np.array_equal(_bits(s), _bits(want[name][0].cpu().numpy())), name
+        assert np.array_equal(_bits(q), _bits(want[name][1].cpu().numpy())), name

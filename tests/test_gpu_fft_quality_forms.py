@@ -1,0 +1,164 @@
+"""GPU tests of the per-patch correlation quality on the kernel forms a knob selects and on forced pass / run / chunk boundaries.
+
+The MOF_FFT_* knobs are read once per process (mof_capi.hip fft_route, launch_large, fft_sequence; host_pipe.hpp), so every form runs
+in ONE child process with the environment set -- the convention of test_gpu_kernel_forms.py and test_gpu_generic.py. The child runs
+the route tests of test_gpu_fft_quality.py (the f64 oracle at 360 d, quality_cases.py; the shifts' bits with and without the quality
+output), which take their batches and the kernel_variant or bit relation they expect from MOF_QUALITY_PAIRS / _LONG_RANGE / _VIDEOS:
+the existing tests' asserts of the DEFAULT variants stay as they are and are not selected here. Children run one after another, each
+under its own time limit, pytest -x; a child that ends on a signal or a non-zero status fails its parent test, which shows the tail
+of the child's output. The parent prints every line the child measured (run with -s).
+
+Evidence that a knob took effect is asserted wherever the library exposes the route: kernel_variant (checked in the child against the
+parametrisation and again here in the child's output), and the video entry taking the pair entry's bits where it has bits of its own by
+default (test_sequence_runs asserts either). Where nothing exposes the route the docstring says so."""
+import os
+import re
+import subprocess
+import sys
+
+import pytest
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+TARGET = os.path.join(ROOT, "tests", "test_gpu_fft_quality.py")
+
+
+def _cases(pairs):
+    return ",".join(f"{name}={what}" for name, what in pairs)
+
+
+_DIED = []  # a child that ended on a signal or at its time limit: no later test of this module starts another on the same card
+
+
+def _child(env, select, pairs=(), long_range=(), videos=(), timeout=600):
+    """One child: the selected route tests under `env`. Returns its stdout after the status checks; every expected route line
+    ('route <name>: kernel_variant <variant>', printed by the child before it asserts) must be there."""
+    if _DIED:
+        pytest.fail(f"not started: an earlier child of this module died ({_DIED[0]}); find its cause first")
+    e = dict(os.environ, **env)
+    e.update(MOF_QUALITY_PAIRS=_cases(pairs), MOF_QUALITY_LONG_RANGE=_cases(long_range), MOF_QUALITY_VIDEOS=_cases(videos))
+    try:
+        r = subprocess.run([sys.executable, "-m", "pytest", TARGET, "-m", "gpu", "-x", "-q", "-s", "-k", select, "-p", "no:cacheprovider"],
+                           capture_output=True, text=True, timeout=timeout, cwd=ROOT, env=e)
+    except subprocess.TimeoutExpired:
+        _DIED.append(f"{env}: no end within {timeout} s")
+        raise
+    if r.returncode < 0 or r.returncode in (124, 134, 137, 139):
+        _DIED.append(f"{env}: status {r.returncode}")
+    for line in r.stdout.splitlines():
+        if "bar " in line or "route " in line or " passed" in line:
+            print(f"[{' '.join(f'{k}={v}' for k, v in env.items())}] {line}")
+    assert r.returncode == 0 and " passed" in r.stdout and " skipped" not in r.stdout and " deselected" in r.stdout, \
+        (env, r.returncode, r.stdout[-3000:], r.stderr[-1500:])
+    for name, variant in list(pairs) + list(long_range):
+        assert f"route {name}: kernel_variant {variant}" in r.stdout, (env, name, variant, r.stdout[-3000:])
+    for name, bits in videos:
+        m = re.search(rf"route {re.escape(name)}: kernel_variant \S+, video entry == pair entry bits: (True|False)", r.stdout)
+        assert m and m.group(1) == str(bits == "pair"), (env, name, bits, r.stdout[-3000:])
+    return r.stdout
+
+
+ROUTES = "test_pair_entry_on_its_route or test_sequence_runs"
+CONSTANTS = "test_constant_and_zero"  # (patches, frames in a video: they assert no variant, they print it)
+
+
+def test_the_older_forms(gpu):
+    """MOF_FFT_HALF=0, MOF_FFT_LARGE_TUNED=0, MOF_PLANNED_STATIC=0, MOF_FFT_SEQ_PAIRS=1 (they act on different sizes): 142 -> 144 and
+    120 without the half tile (the large pipeline; the tuned 120 kernel of pc_kernel_mixed.hip), 200 and 196 -> 200 on L5 - L8, 54 and
+    62 on the run-time plan, every video on the pair form; the constant and zero patches of every family on these forms.
+    Evidence: kernel_variant at 120 and 142 (planned-half by default); the video entry has the pair entry's bits at 64 and 128, where
+    the sequence kernels are kernels of their own (test_sequence_runs asserts by default that it has not). Nothing exposes
+    MOF_FFT_LARGE_TUNED or MOF_PLANNED_STATIC: kernel_variant is 'planned-large' / 'planned' either way."""
+    _child({"MOF_FFT_HALF": "0", "MOF_FFT_LARGE_TUNED": "0", "MOF_PLANNED_STATIC": "0", "MOF_FFT_SEQ_PAIRS": "1"},
+           f"{ROUTES} or {CONSTANTS}",
+           pairs=[("circular-120", "stockham"), ("padded-142", "planned-large"), ("circular-200", "planned-large"),
+                  ("padded-196", "planned-large"), ("passes-200", "planned-large"), ("circular-54", "planned"), ("padded-62", "planned")],
+           videos=[("long-video-64", "pair"), ("long-video-120", "pair"), ("long-video-128", "pair"), ("long-video-200", "pair")])
+
+
+def test_the_half_tile_everywhere(gpu):
+    """MOF_FFT_HALF=1: 64 and 128 through the half-tile kernel, pairs (the tiled 128 frames: 512 patches) and its sequence form on the
+    long videos (fft_route takes the half tile's video form before it looks at MOF_FFT_SEQ_HALF64 / 128, so those have a child of
+    their own); the constant and zero patches. Evidence: kernel_variant 'planned-half' at 64 and 128 ('stockham' by default); the
+    video entry has the pair entry's bits at 64 and 128 (the half tile's two forms share their arithmetic, as at 120 by default)."""
+    _child({"MOF_FFT_HALF": "1"}, f"{ROUTES} or {CONSTANTS}",
+           pairs=[("circular-64", "planned-half"), ("crops-64", "planned-half"), ("grid-64", "planned-half"),
+                  ("circular-128", "planned-half"), ("tiled-128", "planned-half")],
+           videos=[("long-video-64", "pair"), ("long-video-128", "pair"), ("video-64", "pair"), ("video-128", "pair")])
+
+
+def test_the_older_half_tile_sequence_kernels(gpu):
+    """MOF_FFT_SEQ_HALF64=1, MOF_FFT_SEQ_HALF128=1, MOF_FFT_SEQ_RUN=3: pc_seq_half.hip's sequence kernel at 64 and 128 in runs of three
+    (it takes 16 by default, which the 10 pairs at 128 would not fill: both instantiations must see a second run), and a constant and
+    a zero frame in its stream at 64. Nothing exposes the route: kernel_variant names the pair kernels, 'stockham' either way, and
+    the video entry has not the pair entry's bits with or without the knobs."""
+    _child({"MOF_FFT_SEQ_HALF64": "1", "MOF_FFT_SEQ_HALF128": "1", "MOF_FFT_SEQ_RUN": "3"},
+           "test_sequence_runs or test_constant_and_zero_frames_in_a_video",
+           videos=[("long-video-64", "own"), ("long-video-128", "own"), ("video-64", "own"), ("video-128", "own")])
+
+
+def test_forced_planned_kernel(gpu):
+    """MOF_FFT_FORCE_PLANNED=1: 32, 64, 120 and 128 through the planned kernel (pc_kernel_generic.hip), also under the OpenCL model at
+    64, the long-range mode at 120 and the videos (the pair form); the constant and zero patches. Evidence: kernel_variant 'planned'
+    ('stockham' / 'planned-half' by default); the video entry has the pair entry's bits at 64 and 128."""
+    _child({"MOF_FFT_FORCE_PLANNED": "1"}, f"{ROUTES} or test_long_range_beyond_32 or {CONSTANTS}",
+           pairs=[("circular-32", "planned"), ("circular-64", "planned"), ("grid-64", "planned"), ("circular-120", "planned"),
+                  ("circular-128", "planned"), ("ocl-64", "planned")],
+           long_range=[("long-range-120", "planned")],
+           videos=[("long-video-64", "pair"), ("long-video-120", "pair"), ("long-video-128", "pair")])
+
+
+def test_forced_large_pipeline(gpu):
+    """MOF_FFT_FORCE_LARGE=1: 64, 120 and 142 -> 144 through the pipeline in device memory (L5 - L8: below 200 there are no tuned
+    transforms), the OpenCL model at 144 in one and in several pairs per frame; fft_route sends the OpenCL model at the planned sizes
+    to the planned kernel, so 64 and 60 run that. The constant and zero patches at 64, 120 and 144 (the counted bar of the large
+    pipeline). Evidence: kernel_variant."""
+    _child({"MOF_FFT_FORCE_LARGE": "1"}, f"{ROUTES} or (test_constant_and_zero_patches and (64 or 120 or 144))",
+           pairs=[("circular-64", "planned-large"), ("grid-64", "planned-large"), ("circular-120", "planned-large"),
+                  ("padded-142", "planned-large"), ("ocl-144", "planned-large"), ("ocl-passes-144", "planned-large"),
+                  ("ocl-64", "planned"), ("ocl-60", "planned")],
+           videos=[("long-video-64", "pair"), ("long-video-120", "pair")])
+
+
+def test_videos_on_the_pair_form_of_their_family(gpu):
+    """MOF_FFT_LARGE_VIDEO=0, MOF_FFT_HALF_SEQ=0: the videos at 200 and 120 as pairs of consecutive frames (every frame transformed
+    twice). The video entry must keep the pair entry's bits; it has them by default too at these sizes, so nothing exposes the route."""
+    _child({"MOF_FFT_LARGE_VIDEO": "0", "MOF_FFT_HALF_SEQ": "0"}, "test_sequence_runs",
+           videos=[("long-video-200", "pair"), ("long-video-120", "pair"), ("video-200", "pair"), ("video-120", "pair")])
+
+
+def test_pair_kernel_on_the_half_tile_at_128(gpu):
+    """MOF_FFT_PAIR_HALF=1: pc_pair_half_kernel on THREE tiled 128 frames -- 768 patch pairs against one slab per workgroup, two
+    workgroups per CU (512 on 256 CUs), so half of the workgroups walk a second patch pair: the prefetch of the next previous image,
+    the slab's reuse, the store at a.quality + 2 p for p >= gridDim.x -- and on the 36 pairs alone. Nothing exposes the route:
+    kernel_variant stays 'stockham'."""
+    _child({"MOF_FFT_PAIR_HALF": "1"}, "test_pair_entry_on_its_route", pairs=[("tiled-128x3", "stockham"), ("circular-128", "stockham")])
+
+
+def test_forced_pass_run_and_chunk_boundaries(gpu):
+    """MOF_FFT_LARGE_PASS=3, MOF_FFT_SEQ_RUN=3, MOF_HOST_CHUNK=2: the 10 pairs at 200 and the 7 under the OpenCL model at 144 take four
+    and three passes of the scratch (launch_large's k0 offset), the video at 200 passes of its video form, the long videos at 64, 120
+    and 128 runs of three with a ragged last one (the run walkers' p0 offset), the 7 pairs of 3 x 2 patches four host chunks as pairs
+    and as a video (the HostPipe's second output). The boundaries are not exposed; what is asserted is that the quality stays the
+    oracle's and, for the host entry, the device entry's bits."""
+    _child({"MOF_FFT_LARGE_PASS": "3", "MOF_FFT_SEQ_RUN": "3", "MOF_HOST_CHUNK": "2"}, f"{ROUTES} or test_host_entry_chunks or test_grid_order_3x2",
+           pairs=[("passes-200", "planned-large"), ("ocl-passes-144", "planned-large"), ("padded-246", "planned-large")],
+           videos=[("long-video-64", "own"), ("long-video-120", "pair"), ("long-video-128", "own"), ("long-video-200", "pair")])
+
+
+@pytest.mark.parametrize("target", ["mfma", "quad"])
+def test_ab_library_of_k1(gpu, target):
+    """The A/B libraries of K1 at 64 (`make mfma`; `make quad`, whose kernel MOF_PC_QUAD=1 selects there), loaded through MOF_LIB_PATH:
+    the 64-pixel batches and the long video; on the MFMA library, which is K1 with another first stage, the constant patches too.
+    The quad formulation (pc_kernel_quad.hip) never carried the constant-patch rule of pc_common.hpp -- it detects no constant patch,
+    so shift AND quality of one are the noise that rule exists to replace (its shift tests select no such pair either): the constant
+    answer is not part of what that library is held to, here or there. Skipped with a message where the library is not built, as
+    the shift tests of these libraries are. Evidence: kernel_variant 'quad' for the quad library; nothing exposes the MFMA stage."""
+    lib = os.path.join(ROOT, "mrs_optic_flow_amd", "csrc", "ab", f"libmof_hip_{target}.so")
+    if not os.path.exists(lib):
+        pytest.skip(f"csrc/ab/libmof_hip_{target}.so not built (`make -C mrs_optic_flow_amd/csrc {target}`)")
+    pairs = [("circular-64", "stockham"), ("crops-64", "stockham"), ("grid-64", "stockham")]
+    if target == "quad":
+        _child({"MOF_LIB_PATH": lib, "MOF_PC_QUAD": "1"}, ROUTES, pairs=[(name, "quad") for name, _ in pairs], videos=[("long-video-64", "own")])
+    else:
+        _child({"MOF_LIB_PATH": lib}, f"{ROUTES} or (test_constant_and_zero_patches and 64)", pairs=pairs, videos=[("long-video-64", "own")])

@@ -189,7 +189,8 @@ def test_bgr_video_front_end(gpu, n, fs):
 
 def test_more_pairs_than_one_grid_dimension_holds(gpu):
     """The run index rides gridDim.z (65535 at most): with MOF_FFT_SEQ_RUN=1 a video of 65541 frames needs two launches.
-    Run in a child process (the run length is read once per process). Circular shifts: every pair has a known answer."""
+    Run in a child process (the run length is read once per process). Circular shifts: every pair has a known answer. The same
+    video with the quality output: the second launch stores it at an offset of 65535 pairs, formed apart from the shifts'."""
     import os
     import subprocess
     import sys
@@ -212,6 +213,23 @@ step = np.array([(P[(k + 1) %% 8][0] - P[k][0], P[(k + 1) %% 8][1] - P[k][1]) fo
 want = step[np.arange(F - 1) %% 8]
 err = np.abs(got - want).max(axis=1)
 print("ok" if err.max() < 5e-5 else ("bad", err.max(), int(err.argmax())))
+# the quality output across the launch boundary (fft_sequence offsets it by k0 pairs on its own): the video has period 8, so pair k
+# must carry the bits of pair k %% 8, and the first eight the f64 oracle's values at 360 d (tests/quality_cases.py)
+import quality_cases as Q
+fm = FftMethod(n, n, 80.0)
+s2, q2 = fm.process_sequence_device(video, return_quality=True)
+bits = lambda a: np.ascontiguousarray(a).view(np.uint64)
+assert np.array_equal(bits(s2.cpu().numpy()), bits(fm.process_sequence_device(video).cpu().numpy())), "shifts depend on the quality output"
+q = q2.cpu().numpy()[:, 0]
+pn = protos.cpu().numpy()
+b = Q.Batch("sequence split", n, pn[(np.arange(8) + 1) %% 8], pn[np.arange(8)])
+assert (b.ratio < 0.5).all() and b.d <= 2e-7, (float(b.ratio.max()), b.d)
+e8 = float(np.abs(q[:8] - b.want[:, 0]).max())
+off = np.argwhere((bits(q) != bits(q[:8])[np.arange(F - 1) %% 8]).any(axis=1)).ravel()
+print("quality ok: first period %%.3e against the bar 360 x %%.2e = %%.3e, every later pair its bits" %% (e8, b.d, b.bar) if e8 <= b.bar and off.size == 0
+      else ("quality bad", e8, b.bar, off[:4].tolist(), int(off.size)))
 """ % (os.path.dirname(os.path.dirname(os.path.abspath(__file__))), os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=600, env=dict(os.environ, MOF_FFT_SEQ_RUN="1"))
-    assert r.returncode == 0 and r.stdout.strip().endswith("ok"), (r.stdout[-500:], r.stderr[-1500:])
+    lines = r.stdout.strip().splitlines()
+    print(lines[-1] if lines else "")
+    assert r.returncode == 0 and len(lines) >= 2 and lines[-2] == "ok" and lines[-1].startswith("quality ok"), (r.stdout[-500:], r.stderr[-1500:])

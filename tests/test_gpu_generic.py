@@ -224,9 +224,10 @@ def test_large_patches_reference_constructor_and_stateful_entry(gpu, fs, n):
 
 
 def test_large_patches_front_ends_and_passes(gpu):
-    """BGR8 frames, the long-range mode and a video on a large patch size; a batch that spans several passes of the scratch
-    (MOF_FFT_LARGE_PASS is not set: the pass size follows from the 1.5 GB budget, so force small passes through a second engine
-    that has only seen small batches)."""
+    """BGR8 frames, the long-range mode and a video on a large patch size. (MOF_FFT_LARGE_PASS is not set: the pass size follows from
+    the 1.5 GB budget and launch_large regrows the scratch to it, so these four pairs take ONE pass; several passes are forced in child
+    processes with MOF_FFT_LARGE_PASS=3 -- test_video_form_of_the_tuned_large_patch_path below for the shifts,
+    test_gpu_fft_quality_forms.py::test_forced_pass_run_and_chunk_boundaries for shifts and quality.)"""
     n, gx, gy = 160, 2, 1
     w, h = 2 * n + 7, n + 5
     rng = np.random.default_rng(5)
