@@ -21,6 +21,7 @@
 #include "capi_graph.hpp"
 #include "host_pipe.hpp"
 #include "mof_kernels.h"
+#include "pc_launch.hpp"
 
 namespace {
 thread_local char g_err[512] = "";
@@ -354,7 +355,7 @@ static int launch_large(mof_fft_engine* e, const mof::PcArgs& a, int n_pairs, hi
     HIP_TRY(hipMemsetAsync(flags, 0, (size_t)units * per_unit * sizeof(int), s));
     if (tuned && r.odd_tail) HIP_TRY(hipMemsetAsync(sums, 0, (size_t)4 * units * per_unit * sizeof(int), s));
     // (the row launchers split at 65534 images, a pair form on pair boundaries: keep a launch's image count a multiple of a unit below that)
-    const int units_per_launch = 65534 / per_unit > 0 ? 65534 / per_unit : 1;
+    const int units_per_launch = mof::PC_MAX_GRID_IMAGES / per_unit > 0 ? mof::PC_MAX_GRID_IMAGES / per_unit : 1;
     for (int j0 = 0; j0 < units; j0 += units_per_launch) {
       const int nj = units - j0 < units_per_launch ? units - j0 : units_per_launch;
       const mof::PclSrc sj = units_on(k0 + j0);
@@ -557,10 +558,7 @@ int mof_fft_create(const mof_fft_config* cfg, mof_fft_engine** out) try {
   if (r.video == FftRoute::SEQ) CREATE_TRY(mof::pc_configure_sequence());
   if (r.video == FftRoute::SEQ_HALF) CREATE_TRY(mof::pc_configure_sequence_half(r.m));
   if (r.pair_half_wgs != 0) {
-    int dev = 0, cus = 256;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-    e->n_pair_slabs = r.pair_half_wgs * cus;
+    e->n_pair_slabs = r.pair_half_wgs * mof::pc_cu_count();
     CREATE_TRY(mof::pc_configure_pair_half(r.m));
     CREATE_TRY(hipMalloc(&e->d_pair_slabs, (size_t)e->n_pair_slabs * mof::pc_pair_half_slab_floats(r.m) * sizeof(float)));
   }

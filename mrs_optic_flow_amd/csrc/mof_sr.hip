@@ -24,6 +24,7 @@
 #include "host_pipe.hpp"
 #include "mof.h"
 #include "mof_kernels.h"
+#include "pc_launch.hpp"
 
 namespace mof {
 int capi_fail(int code, const char* fmt, ...);  // mof_capi.hip: records the thread's last error
@@ -367,8 +368,7 @@ hipError_t cols_fused(const mof_sr_engine* e, const uint8_t* lp_prev, const uint
 // are transformed too), the launch lasts ceil(workgroups / slots) rounds: the shortest run within 3 % of the least product.
 int seq_run_for(const mof_sr_engine* e, int m) {
   if (e->route.seq_run > 0) return e->route.seq_run;
-  int cus = 0;
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, e->cfg.device) != hipSuccess || cus <= 0) cus = 256;
+  const int cus = mof::pc_cu_count(e->cfg.device);
   const int tn = e->route.m;
   const int cw = mof::sr_seq_columns_per_wave(tn);  // columns per wave
   if (cw == 0) return 16;  // (no K6s at this size: the planned L6 walks no runs)

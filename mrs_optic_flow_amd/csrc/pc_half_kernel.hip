@@ -41,6 +41,7 @@
 
 #include "mof_kernels.h"
 #include "pc_common.hpp"
+#include "pc_launch.hpp"
 #include <type_traits>
 #include "pc_plan.hpp"
 #include "pc_plan_build.hpp"
@@ -901,16 +902,17 @@ have_current:
 
 constexpr bool half_seq_size(int m) { return m != 162; }  // (162's last column stage runs long lines: no register-resident spectrum)
 
-template <int CH, int MS>
-hipError_t configure_half_one() {
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&pc_half_kernel<CH, MS>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     HalfPlanOf<MS>::HP.lds_bytes);
-  if constexpr (half_seq_size(MS)) {
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute(reinterpret_cast<const void*>(&pc_half_kernel<CH, MS, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              HalfPlanOf<MS>::HP.lds_bytes);
-  }
-  return e;
+// gray and BGR8 of the forms that exist at padded size MS: the pair form (PAIR: the sizes of MOF_HALF_SIZES) and the video form
+template <int MS, bool PAIR>
+hipError_t configure_half_size() {
+  return pc_each_form<PC_FORMS_CH>([](auto, auto ch, auto) {
+    hipError_t e = hipSuccess;
+    if constexpr (PAIR) e = pc_raise_lds(&pc_half_kernel<ch, MS>, HalfPlanOf<MS>::HP.lds_bytes);
+    if constexpr (half_seq_size(MS)) {
+      if (e == hipSuccess) e = pc_raise_lds(&pc_half_kernel<ch, MS, true>, HalfPlanOf<MS>::HP.lds_bytes);
+    }
+    return e;
+  });
 }
 
 }  // namespace
@@ -935,28 +937,17 @@ int pc_half_workgroups_per_cu(int m) {
   }
 }
 
-template <int CH, int MS>
-hipError_t configure_half_seq_only() {
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(&pc_half_kernel<CH, MS, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                             HalfPlanOf<MS>::HP.lds_bytes);
-}
-
 // raises the dynamic-LDS limit of the ONE padded size `m` an engine will launch (pair form and, where it exists, video form; both
 // channel counts) on the calling thread's current device -- not of all ~60 instantiations: that loaded every code object at every
 // engine create, on every device of a shard group
 hipError_t pc_configure_half(int m) {
-  hipError_t e;
   switch (m) {
-#define X(M)                                                               \
-  case M:                                                                  \
-    if ((e = configure_half_one<1, M>()) != hipSuccess) return e;          \
-    return configure_half_one<3, M>();
+#define X(M) \
+  case M: return configure_half_size<M, true>();
     MOF_HALF_SIZES(X)
 #undef X
-#define X(M)                                                               \
-  case M:                                                                  \
-    if ((e = configure_half_seq_only<1, M>()) != hipSuccess) return e;     \
-    return configure_half_seq_only<3, M>();
+#define X(M) \
+  case M: return configure_half_size<M, false>();
     MOF_HALF_SEQ_SIZES(X)
 #undef X
     default: return hipErrorInvalidValue;
@@ -966,28 +957,20 @@ hipError_t pc_configure_half(int m) {
 // a.downscale must be 1 and a.peak_model 0 (the caller keeps the other front ends on their pipelines); m = the padded size, n the patch
 hipError_t launch_pc_half(const PcArgs& a_in, int m, int n, int n_pairs, hipStream_t stream) {
   if (a_in.downscale != 1 || a_in.peak_model != 0 || (a_in.channels != 1 && a_in.channels != 3) || n > m || n < 2) return hipErrorInvalidValue;
-  const int patches = a_in.grid_x * a_in.grid_y;
-  for (int k0 = 0; k0 < n_pairs; k0 += 65535) {  // the pair index rides gridDim.z
-    const int nk = n_pairs - k0 < 65535 ? n_pairs - k0 : 65535;
-    PcArgs c = a_in;
-    c.cur = a_in.cur + (size_t)k0 * a_in.cur_stride;
-    c.prev = a_in.prev + (size_t)k0 * a_in.prev_stride;
-    c.out = a_in.out + (size_t)k0 * patches * 2;
-    if (a_in.quality) c.quality = a_in.quality + (size_t)k0 * patches * 2;
-    c.total = nk * patches;
+  return pc_split_pairs(a_in, n_pairs, [&](const PcArgs& c, int nk) {  // the pair index rides gridDim.z
     const dim3 g((unsigned)c.grid_x, (unsigned)c.grid_y, (unsigned)nk);
     switch (m) {
 #define X(M)                                                                                                                             \
   case M:                                                                                                                                \
-    if (c.channels == 3) hipLaunchKernelGGL((pc_half_kernel<3, M>), g, dim3((unsigned)HalfPlanOf<M>::T), (size_t)HalfPlanOf<M>::HP.lds_bytes, stream, c, n, nk, 1); \
-    else hipLaunchKernelGGL((pc_half_kernel<1, M>), g, dim3((unsigned)HalfPlanOf<M>::T), (size_t)HalfPlanOf<M>::HP.lds_bytes, stream, c, n, nk, 1);          \
-    break;
+    return pc_dispatch_form<PC_FORMS_CH>(c, [&](auto, auto ch, auto) {                                                                   \
+      hipLaunchKernelGGL((pc_half_kernel<ch, M>), g, dim3((unsigned)HalfPlanOf<M>::T), (size_t)HalfPlanOf<M>::HP.lds_bytes, stream, c, n, nk, 1); \
+      return hipGetLastError();                                                                                                          \
+    });
       MOF_HALF_SIZES(X)
 #undef X
       default: return hipErrorInvalidValue;
     }
-  }
-  return hipGetLastError();
+  });
 }
 
 bool pc_half_sequence_supported(int m) {
@@ -1008,9 +991,7 @@ bool pc_half_sequence_supported(int m) {
 hipError_t launch_pc_half_sequence(const PcArgs& a, int m, int n, int n_pairs, int run, hipStream_t stream) {
   if (a.downscale != 1 || a.peak_model != 0 || (a.channels != 1 && a.channels != 3) || n > m || n < 2 || run < 0 || n_pairs < 1) return hipErrorInvalidValue;
   if (run == 0) {
-    int dev = 0, cus = 0;  // per call: the devices of a shard group need not be alike (an attribute query, no synchronisation)
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-    const long slots = (long)cus * (pc_half_workgroups_per_cu(m) > 0 ? pc_half_workgroups_per_cu(m) : 1), patches = (long)a.grid_x * a.grid_y;
+    const long slots = (long)pc_cu_count() * (pc_half_workgroups_per_cu(m) > 0 ? pc_half_workgroups_per_cu(m) : 1), patches = (long)a.grid_x * a.grid_y;
     double best = 0.0;
     for (int r = 4; r <= 64; ++r) {
       const long wgs = patches * ((n_pairs + r - 1) / r), rounds = (wgs + slots - 1) / slots;
@@ -1024,21 +1005,20 @@ hipError_t launch_pc_half_sequence(const PcArgs& a, int m, int n, int n_pairs, i
   c.total = n_pairs * a.grid_x * a.grid_y;
   const dim3 g((unsigned)c.grid_x, (unsigned)c.grid_y, (unsigned)n_runs);
   switch (m) {
-#define X(M)                                                                                                                                  \
-  case M:                                                                                                                                     \
-    if constexpr (half_seq_size(M)) {                                                                                                         \
-      if (c.channels == 3) hipLaunchKernelGGL((pc_half_kernel<3, M, true>), g, dim3((unsigned)HalfPlanOf<M>::T), (size_t)HalfPlanOf<M>::HP.lds_bytes, stream, c, n, n_pairs, run); \
-      else hipLaunchKernelGGL((pc_half_kernel<1, M, true>), g, dim3((unsigned)HalfPlanOf<M>::T), (size_t)HalfPlanOf<M>::HP.lds_bytes, stream, c, n, n_pairs, run);                 \
-    } else {                                                                                                                                  \
-      return hipErrorInvalidValue;                                                                                                            \
-    }                                                                                                                                         \
-    break;
+#define X(M)                                                                                                                               \
+  case M:                                                                                                                                  \
+    if constexpr (half_seq_size(M))                                                                                                        \
+      return pc_dispatch_form<PC_FORMS_CH>(c, [&](auto, auto ch, auto) {                                                                   \
+        hipLaunchKernelGGL((pc_half_kernel<ch, M, true>), g, dim3((unsigned)HalfPlanOf<M>::T), (size_t)HalfPlanOf<M>::HP.lds_bytes, stream, c, n, n_pairs, run); \
+        return hipGetLastError();                                                                                                          \
+      });                                                                                                                                  \
+    else                                                                                                                                   \
+      return hipErrorInvalidValue;
     MOF_HALF_SIZES(X)
     MOF_HALF_SEQ_SIZES(X)
 #undef X
     default: return hipErrorInvalidValue;
   }
-  return hipGetLastError();
 }
 
 }  // namespace mof

@@ -37,6 +37,7 @@
 #include "mfma_frag.hpp"
 #include "mof_kernels.h"
 #include "pc_common.hpp"
+#include "pc_launch.hpp"
 
 #include "pc_passes.hpp"
 #include "pc_passes3.hpp"
@@ -358,79 +359,40 @@ __global__ void __launch_bounds__(PcTraits<N>::T) pc_field_kernel(PcArgs a) {
   }  // persistent loop
 }
 
-// Diagnostic knob (occupancy experiments only): MOF_PC_EXTRA_LDS=<bytes> pads the dynamic LDS request.
-static size_t extra_lds() {
-  static const size_t v = [] {
-    const char* e = getenv("MOF_PC_EXTRA_LDS");
-    return e ? (size_t)atol(e) : (size_t)0;
-  }();
-  return v;
-}
-
-template <int N, int DS, int CH, int PK>
-static hipError_t configure_one(int lds) {
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(&pc_field_kernel<N, DS, CH, PK>),
-                             hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-}
-
 template <int N>
 static hipError_t configure_n() {
-  const int lds = (int)(PcTraits<N>::LDS_BYTES + extra_lds());
-  hipError_t e;
-  if ((e = configure_one<N, 1, 1, 0>(lds)) != hipSuccess) return e;
-  if ((e = configure_one<N, 1, 3, 0>(lds)) != hipSuccess) return e;
-  if ((e = configure_one<N, 4, 1, 0>(lds)) != hipSuccess) return e;
-  if ((e = configure_one<N, 1, 1, 1>(lds)) != hipSuccess) return e;
-  if ((e = configure_one<N, 1, 3, 1>(lds)) != hipSuccess) return e;
-  return configure_one<N, 4, 1, 1>(lds);
+  const size_t lds = PcTraits<N>::LDS_BYTES + pc_extra_lds();
+  return pc_each_form([&](auto ds, auto ch, auto pk) { return pc_raise_lds(&pc_field_kernel<N, ds, ch, pk>, lds); });
 }
-
-static int g_cu_count = 0;  // set by pc_configure()
 
 template <int N>
 static hipError_t launch_n(const PcArgs& a_in, int n_pairs, hipStream_t stream) {
   using Tr = PcTraits<N>;
   PcArgs a = a_in;
   a.total = n_pairs * a.grid_x * a.grid_y;
-  a.stagger_div = g_cu_count > 0 ? g_cu_count : 256;
+  const int cus = pc_cu_count();
+  a.stagger_div = cus;
   {
     static const int units = [] { const char* e = getenv("MOF_PC_STAGGER"); return e ? atoi(e) : 0; }();
     a.stagger_units = units;
   }
-  if (a.downscale == 4 && a.channels == 3) return hipErrorInvalidValue;
   const dim3 b(Tr::T);
-  const size_t lds = Tr::LDS_BYTES + extra_lds();
+  const size_t lds = Tr::LDS_BYTES + pc_extra_lds();
   auto launch = [&](const PcArgs& aa, dim3 g) {
-    if (aa.peak_model == 1) {
-      if (aa.downscale == 4) hipLaunchKernelGGL((pc_field_kernel<N, 4, 1, 1>), g, b, lds, stream, aa);
-      else if (aa.channels == 3) hipLaunchKernelGGL((pc_field_kernel<N, 1, 3, 1>), g, b, lds, stream, aa);
-      else hipLaunchKernelGGL((pc_field_kernel<N, 1, 1, 1>), g, b, lds, stream, aa);
-    } else {
-      if (aa.downscale == 4) hipLaunchKernelGGL((pc_field_kernel<N, 4, 1, 0>), g, b, lds, stream, aa);
-      else if (aa.channels == 3) hipLaunchKernelGGL((pc_field_kernel<N, 1, 3, 0>), g, b, lds, stream, aa);
-      else hipLaunchKernelGGL((pc_field_kernel<N, 1, 1, 0>), g, b, lds, stream, aa);
-    }
+    return pc_dispatch_form(aa, [&](auto ds, auto ch, auto pk) {
+      hipLaunchKernelGGL((pc_field_kernel<N, ds, ch, pk>), g, b, lds, stream, aa);
+      return hipGetLastError();
+    });
   };
   if constexpr (Tr::PERSIST) {
     // as many workgroups as are resident at once (LDS-limited), each loops over patches (c4: +9 % over one per patch)
-    const int per_cu = (int)((160u * 1024u) / (Tr::LDS_BYTES + extra_lds()));
-    const int resident = (g_cu_count > 0 ? g_cu_count : 256) * (per_cu < 1 ? 1 : (per_cu > 16 ? 16 : per_cu));
-    launch(a, dim3((unsigned)(a.total < resident ? a.total : resident)));
+    const int per_cu = (int)((160u * 1024u) / lds);
+    const int resident = cus * (per_cu < 1 ? 1 : (per_cu > 16 ? 16 : per_cu));
+    return launch(a, dim3((unsigned)(a.total < resident ? a.total : resident)));
   } else {
-    // one workgroup per patch; the pair index rides gridDim.z (at most 65535 per launch)
-    const int patches = a.grid_x * a.grid_y;
-    for (int k0 = 0; k0 < n_pairs; k0 += 65535) {
-      const int nk = n_pairs - k0 < 65535 ? n_pairs - k0 : 65535;
-      PcArgs c = a;
-      c.cur = a.cur + (size_t)k0 * a.cur_stride;
-      c.prev = a.prev + (size_t)k0 * a.prev_stride;
-      c.out = a.out + (size_t)k0 * patches * 2;
-      if (a.quality) c.quality = a.quality + (size_t)k0 * patches * 2;
-      c.total = nk * patches;
-      launch(c, dim3((unsigned)a.grid_x, (unsigned)a.grid_y, (unsigned)nk));
-    }
+    // one workgroup per patch; the pair index rides gridDim.z
+    return pc_split_pairs(a, n_pairs, [&](const PcArgs& c, int nk) { return launch(c, dim3((unsigned)a.grid_x, (unsigned)a.grid_y, (unsigned)nk)); });
   }
-  return hipGetLastError();
 }
 
 // The quad-per-line formulation of pc_kernel_quad.hip (an evaluated alternative: a third of the LDS traffic, 35 % more
@@ -463,9 +425,6 @@ void pc_mfma_s1_fragments(uint32_t* out) {
 }
 
 hipError_t pc_configure(int patch_size) {
-  int dev = 0;
-  hipDeviceProp_t prop;
-  if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) g_cu_count = prop.multiProcessorCount;
   switch (patch_size) {
     case 32: return configure_n<32>();
     case 64: {

@@ -23,6 +23,7 @@
 
 #include "mof_kernels.h"
 #include "pc_common.hpp"
+#include "pc_launch.hpp"
 #include "pc_plan.hpp"
 #include "pc_plan_build.hpp"
 
@@ -455,27 +456,33 @@ bool pc_build_plan(int n, PcPlan* out) {
   X(16) X(18) X(20) X(24) X(25) X(27) X(30) X(32) X(36) X(40) X(45) X(48) X(50) X(54) X(60) X(64) X(72) X(75) X(80) X(81) \
   X(90) X(96) X(100) X(108) X(120) X(125) X(128) X(135)
 
-template <int DS, int CH, int PK, int MS>
-static hipError_t configure_generic_one() {
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(&pc_generic_kernel<DS, CH, PK, MS>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                             160 * 1024);
+// a run-time transform size to its compile-time plan -- f(pc_const<M>{}) --, or f(pc_const<0>{}): the run-time plan
+template <class F>
+static hipError_t dispatch_static_size(int m, F&& f) {
+  switch (m) {
+#define X(M) \
+  case M: return f(pc_const<M>{});
+    MOF_STATIC_SIZES(X)
+#undef X
+    default: return f(pc_const<0>{});
+  }
+}
+// the forms built on plan MS: all six on the run-time plan (0), cv::phaseCorrelate's model alone on the compile-time plans
+template <int MS>
+constexpr int generic_forms = MS == 0 ? PC_FORMS_ALL : PC_FORMS_DS_CH;
+
+template <int MS>
+static hipError_t configure_generic_plan() {
+  return pc_each_form<generic_forms<MS>>([](auto ds, auto ch, auto pk) { return pc_raise_lds(&pc_generic_kernel<ds, ch, pk, MS>, 160 * 1024); });
 }
 
 hipError_t pc_configure_generic() {
-  hipError_t e;
-  if ((e = configure_generic_one<1, 1, 0, 0>()) != hipSuccess) return e;
-  if ((e = configure_generic_one<1, 3, 0, 0>()) != hipSuccess) return e;
-  if ((e = configure_generic_one<4, 1, 0, 0>()) != hipSuccess) return e;
-  if ((e = configure_generic_one<1, 1, 1, 0>()) != hipSuccess) return e;
-  if ((e = configure_generic_one<1, 3, 1, 0>()) != hipSuccess) return e;
-  if ((e = configure_generic_one<4, 1, 1, 0>()) != hipSuccess) return e;
-#define X(M)                                                                    \
-  if ((e = configure_generic_one<1, 1, 0, M>()) != hipSuccess) return e;          \
-  if ((e = configure_generic_one<1, 3, 0, M>()) != hipSuccess) return e;          \
-  if ((e = configure_generic_one<4, 1, 0, M>()) != hipSuccess) return e;
+  hipError_t e = configure_generic_plan<0>();
+#define X(M) \
+  if (e == hipSuccess) e = configure_generic_plan<M>();
   MOF_STATIC_SIZES(X)
 #undef X
-  return hipSuccess;
+  return e;
 }
 
 hipError_t launch_pc_generic(const PcArgs& a_in, const PcPlan& pl, int n_pairs, hipStream_t stream) {
@@ -483,63 +490,23 @@ hipError_t launch_pc_generic(const PcArgs& a_in, const PcPlan& pl, int n_pairs, 
   if (pl.threads < 64 || pl.threads > 1024 || pl.lds_bytes > 160 * 1024) return hipErrorInvalidValue;
   // MOF_PLANNED_STATIC=0: the run-time plan also where a compile-time instantiation exists (A/B and the tests of that form)
   static const bool use_static = [] { const char* v = getenv("MOF_PLANNED_STATIC"); return !v || atoi(v) != 0; }();
-  const int patches = a_in.grid_x * a_in.grid_y;
-  const dim3 b((unsigned)pl.threads);
-  for (int k0 = 0; k0 < n_pairs; k0 += 65535) {  // the pair index rides gridDim.z
-    const int nk = n_pairs - k0 < 65535 ? n_pairs - k0 : 65535;
-    PcArgs c = a_in;
-    c.cur = a_in.cur + (size_t)k0 * a_in.cur_stride;
-    c.prev = a_in.prev + (size_t)k0 * a_in.prev_stride;
-    c.out = a_in.out + (size_t)k0 * patches * 2;
-    if (a_in.quality) c.quality = a_in.quality + (size_t)k0 * patches * 2;
-    c.total = nk * patches;
+  // gray and BGR8 frames (the latter promise the gray path's bits, include/mof.h) and the long-range mode (FftMethod.cpp:1905-2007; r06:
+  // lr60 / lr96 ran the run-time-plan kernel at a third of the gray compile-time-plan rate) take the compile-time plan of the transform
+  // size where there is one; the OpenCL model runs on run-time plans
+  const int static_m = (use_static && a_in.peak_model != 1) ? pl.m : 0;
+  return pc_split_pairs(a_in, n_pairs, [&](const PcArgs& c, int nk) {  // the pair index rides gridDim.z
     const dim3 g((unsigned)c.grid_x, (unsigned)c.grid_y, (unsigned)nk);
-    if (c.peak_model == 1) {
-      if (c.downscale == 4) hipLaunchKernelGGL((pc_generic_kernel<4, 1, 1, 0>), g, b, (size_t)pl.lds_bytes, stream, c, pl);
-      else if (c.channels == 3) hipLaunchKernelGGL((pc_generic_kernel<1, 3, 1, 0>), g, b, (size_t)pl.lds_bytes, stream, c, pl);
-      else hipLaunchKernelGGL((pc_generic_kernel<1, 1, 1, 0>), g, b, (size_t)pl.lds_bytes, stream, c, pl);
-    } else if (c.downscale == 4) {
-      // the long-range mode (FftMethod.cpp:1905-2007) under the transform size's compile-time plan too (r06: lr60 / lr96 ran the run-time-plan
-      // kernel at a third of the gray compile-time-plan rate)
-      bool done = false;
-      if (use_static) {
-        switch (pl.m) {
-#define X(M)                                                                                                                                                    \
-  case M:                                                                                                                                                       \
-    hipLaunchKernelGGL((pc_generic_kernel<4, 1, 0, M>), g, dim3((unsigned)StaticPlanOf<M>::T), (size_t)StaticPlanOf<M>::P.lds_bytes, stream, c, pl);           \
-    done = true;                                                                                                                                                \
-    break;
-          MOF_STATIC_SIZES(X)
-#undef X
-          default: break;
-        }
-      }
-      if (!done) hipLaunchKernelGGL((pc_generic_kernel<4, 1, 0, 0>), g, b, (size_t)pl.lds_bytes, stream, c, pl);
-    } else {
-      // gray and BGR8 frames (the latter promise the gray path's bits, include/mof.h): the compile-time instantiation of the
-      // transform size where there is one
-      const bool bgr = c.channels == 3;
-      bool done = false;
-      if (use_static) {
-        switch (pl.m) {
-#define X(M)                                                                                                                            \
-  case M:                                                                                                                               \
-    if (bgr) hipLaunchKernelGGL((pc_generic_kernel<1, 3, 0, M>), g, dim3((unsigned)StaticPlanOf<M>::T), (size_t)StaticPlanOf<M>::P.lds_bytes, stream, c, pl); \
-    else hipLaunchKernelGGL((pc_generic_kernel<1, 1, 0, M>), g, dim3((unsigned)StaticPlanOf<M>::T), (size_t)StaticPlanOf<M>::P.lds_bytes, stream, c, pl);     \
-    done = true;                                                                                                                        \
-    break;
-          MOF_STATIC_SIZES(X)
-#undef X
-          default: break;
-        }
-      }
-      if (!done) {
-        if (bgr) hipLaunchKernelGGL((pc_generic_kernel<1, 3, 0, 0>), g, b, (size_t)pl.lds_bytes, stream, c, pl);
-        else hipLaunchKernelGGL((pc_generic_kernel<1, 1, 0, 0>), g, b, (size_t)pl.lds_bytes, stream, c, pl);
-      }
-    }
-  }
-  return hipGetLastError();
+    return dispatch_static_size(static_m, [&](auto ms) {
+      constexpr int MS = decltype(ms)::value;
+      return pc_dispatch_form<generic_forms<MS>>(c, [&](auto ds, auto ch, auto pk) {
+        if constexpr (MS != 0)
+          hipLaunchKernelGGL((pc_generic_kernel<ds, ch, pk, MS>), g, dim3((unsigned)StaticPlanOf<MS>::T), (size_t)StaticPlanOf<MS>::P.lds_bytes, stream, c, pl);
+        else
+          hipLaunchKernelGGL((pc_generic_kernel<ds, ch, pk, 0>), g, dim3((unsigned)pl.threads), (size_t)pl.lds_bytes, stream, c, pl);
+        return hipGetLastError();
+      });
+    });
+  });
 }
 
 }  // namespace mof

@@ -19,6 +19,7 @@
 
 #include "mof_kernels.h"
 #include "pc_common.hpp"
+#include "pc_launch.hpp"
 
 namespace mof {
 
@@ -441,46 +442,19 @@ __global__ void __launch_bounds__(T) pc_field_kernel_120(PcArgs a) {
   }  // persistent loop
 }
 
-template <int DS, int CH, int PK>
-static hipError_t configure_one_120() {
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(&pc_field_kernel_120<DS, CH, PK>),
-                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES_120);
-}
-
 hipError_t pc_configure_120() {
-  hipError_t e;
-  if ((e = configure_one_120<1, 1, 0>()) != hipSuccess) return e;
-  if ((e = configure_one_120<1, 3, 0>()) != hipSuccess) return e;
-  if ((e = configure_one_120<4, 1, 0>()) != hipSuccess) return e;
-  if ((e = configure_one_120<1, 1, 1>()) != hipSuccess) return e;
-  if ((e = configure_one_120<1, 3, 1>()) != hipSuccess) return e;
-  return configure_one_120<4, 1, 1>();
+  return pc_each_form([](auto ds, auto ch, auto pk) { return pc_raise_lds(&pc_field_kernel_120<ds, ch, pk>, LDS_BYTES_120); });
 }
-
-static int g_cu_count_120 = 0;
 
 hipError_t launch_pc_field_120(const PcArgs& a_in, int n_pairs, hipStream_t stream) {
   PcArgs a = a_in;
   a.total = n_pairs * a.grid_x * a.grid_y;
-  if (g_cu_count_120 == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    g_cu_count_120 = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
-                         ? prop.multiProcessorCount : 256;
-  }
-  const unsigned blocks = (unsigned)(a.total < g_cu_count_120 ? a.total : g_cu_count_120);  // one resident workgroup per CU
-  if (a.downscale == 4 && a.channels == 3) return hipErrorInvalidValue;
-  const dim3 g(blocks), b(T);
-  if (a.peak_model == 1) {
-    if (a.downscale == 4) hipLaunchKernelGGL((pc_field_kernel_120<4, 1, 1>), g, b, LDS_BYTES_120, stream, a);
-    else if (a.channels == 3) hipLaunchKernelGGL((pc_field_kernel_120<1, 3, 1>), g, b, LDS_BYTES_120, stream, a);
-    else hipLaunchKernelGGL((pc_field_kernel_120<1, 1, 1>), g, b, LDS_BYTES_120, stream, a);
-  } else {
-    if (a.downscale == 4) hipLaunchKernelGGL((pc_field_kernel_120<4, 1, 0>), g, b, LDS_BYTES_120, stream, a);
-    else if (a.channels == 3) hipLaunchKernelGGL((pc_field_kernel_120<1, 3, 0>), g, b, LDS_BYTES_120, stream, a);
-    else hipLaunchKernelGGL((pc_field_kernel_120<1, 1, 0>), g, b, LDS_BYTES_120, stream, a);
-  }
-  return hipGetLastError();
+  const int cus = pc_cu_count();
+  const dim3 g((unsigned)(a.total < cus ? a.total : cus)), b(T);  // one resident workgroup per CU
+  return pc_dispatch_form(a, [&](auto ds, auto ch, auto pk) {
+    hipLaunchKernelGGL((pc_field_kernel_120<ds, ch, pk>), g, b, LDS_BYTES_120, stream, a);
+    return hipGetLastError();
+  });
 }
 
 }  // namespace mof

@@ -35,6 +35,7 @@
 
 #include "mof_kernels.h"
 #include "pc_common.hpp"
+#include "pc_launch.hpp"
 
 namespace mof {
 
@@ -397,37 +398,18 @@ __global__ void __launch_bounds__(T, 4) pc_quad64_kernel(PcArgs a) {
 
 #undef MOF_QUAD_LANE
 
-template <int DS, int CH, int PK>
-static hipError_t configure_quad_one() {
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(&pc_quad64_kernel<DS, CH, PK>),
-                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES_Q64);
-}
-
 hipError_t pc_configure_quad64() {
-  hipError_t e;
-  if ((e = configure_quad_one<1, 1, 0>()) != hipSuccess) return e;
-  if ((e = configure_quad_one<1, 3, 0>()) != hipSuccess) return e;
-  if ((e = configure_quad_one<4, 1, 0>()) != hipSuccess) return e;
-  if ((e = configure_quad_one<1, 1, 1>()) != hipSuccess) return e;
-  if ((e = configure_quad_one<1, 3, 1>()) != hipSuccess) return e;
-  return configure_quad_one<4, 1, 1>();
+  return pc_each_form([](auto ds, auto ch, auto pk) { return pc_raise_lds(&pc_quad64_kernel<ds, ch, pk>, LDS_BYTES_Q64); });
 }
 
 hipError_t launch_pc_field_quad64(const PcArgs& a_in, int n_pairs, hipStream_t stream) {
   PcArgs a = a_in;
   a.total = n_pairs * a.grid_x * a.grid_y;
-  if (a.downscale == 4 && a.channels == 3) return hipErrorInvalidValue;
   const dim3 g((unsigned)a.total), b(T);
-  if (a.peak_model == 1) {
-    if (a.downscale == 4) hipLaunchKernelGGL((pc_quad64_kernel<4, 1, 1>), g, b, LDS_BYTES_Q64, stream, a);
-    else if (a.channels == 3) hipLaunchKernelGGL((pc_quad64_kernel<1, 3, 1>), g, b, LDS_BYTES_Q64, stream, a);
-    else hipLaunchKernelGGL((pc_quad64_kernel<1, 1, 1>), g, b, LDS_BYTES_Q64, stream, a);
-  } else {
-    if (a.downscale == 4) hipLaunchKernelGGL((pc_quad64_kernel<4, 1, 0>), g, b, LDS_BYTES_Q64, stream, a);
-    else if (a.channels == 3) hipLaunchKernelGGL((pc_quad64_kernel<1, 3, 0>), g, b, LDS_BYTES_Q64, stream, a);
-    else hipLaunchKernelGGL((pc_quad64_kernel<1, 1, 0>), g, b, LDS_BYTES_Q64, stream, a);
-  }
-  return hipGetLastError();
+  return pc_dispatch_form(a, [&](auto ds, auto ch, auto pk) {
+    hipLaunchKernelGGL((pc_quad64_kernel<ds, ch, pk>), g, b, LDS_BYTES_Q64, stream, a);
+    return hipGetLastError();
+  });
 }
 
 }  // namespace mof

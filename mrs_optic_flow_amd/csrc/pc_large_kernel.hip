@@ -27,6 +27,7 @@
 
 #include "mof_kernels.h"
 #include "pc_common.hpp"
+#include "pc_launch.hpp"
 #include "pc_plan.hpp"
 #include "pc_plan_build.hpp"
 
@@ -344,12 +345,6 @@ bool needs_exact(const PcPlan& pl) {
   return false;
 }
 
-template <class K>
-hipError_t allow_lds(K kernel, size_t bytes) {
-  return bytes > 48 * 1024 ? hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes)
-                           : hipSuccess;
-}
-
 }  // namespace
 
 bool pc_build_line_plan(int n, PcPlan* out) {
@@ -384,14 +379,14 @@ hipError_t launch_pcl_rows(const PclSrc& src, const PcPlan& pl, const float* twi
   const int line = pcl_line(pl.m);
   const size_t lds = pcl_lds_bytes(pl.m);
   const bool ex = needs_exact(pl);
-  hipError_t e;
-  if ((e = allow_lds(&pcl_rows_kernel<1, 1, false>, lds)) != hipSuccess || (e = allow_lds(&pcl_rows_kernel<1, 3, false>, lds)) != hipSuccess ||
-      (e = allow_lds(&pcl_rows_kernel<4, 1, false>, lds)) != hipSuccess || (e = allow_lds(&pcl_rows_kernel<1, 1, true>, lds)) != hipSuccess ||
-      (e = allow_lds(&pcl_rows_kernel<1, 3, true>, lds)) != hipSuccess || (e = allow_lds(&pcl_rows_kernel<4, 1, true>, lds)) != hipSuccess)
-    return e;
+  hipError_t e = pc_each_form<PC_FORMS_DS_CH>([&](auto ds, auto ch, auto) {
+    const hipError_t e0 = pc_raise_lds_beyond_default(&pcl_rows_kernel<ds, ch, false>, lds);
+    return e0 != hipSuccess ? e0 : pc_raise_lds_beyond_default(&pcl_rows_kernel<ds, ch, true>, lds);
+  });
+  if (e != hipSuccess) return e;
   const unsigned gx = (unsigned)((pl.m + 2 * PCL_LINES - 1) / (2 * PCL_LINES));
-  for (int f0 = 0; f0 < n_images; f0 += 65534) {  // the image index rides gridDim.y (an even count keeps cur / prev pairs together)
-    const int nf = n_images - f0 < 65534 ? n_images - f0 : 65534;
+  for (int f0 = 0; f0 < n_images; f0 += PC_MAX_GRID_IMAGES) {  // the image index rides gridDim.y (an even count keeps cur / prev pairs together)
+    const int nf = n_images - f0 < PC_MAX_GRID_IMAGES ? n_images - f0 : PC_MAX_GRID_IMAGES;
     PclSrc s = src;
     float* z0 = zh + (size_t)f0 * zh_stride;
     int* fl = flags ? flags + f0 : nullptr;
@@ -405,17 +400,14 @@ hipError_t launch_pcl_rows(const PclSrc& src, const PcPlan& pl, const float* twi
       s.base[0] += (size_t)f0 * s.stride[0];
     }
     const dim3 g(gx, (unsigned)nf);
-#define PCL_ROWS(DS_, CH_)                                                                                                              \
-  do {                                                                                                                                  \
-    if (ex) hipLaunchKernelGGL((pcl_rows_kernel<DS_, CH_, true>), g, dim3(PCL_T), lds, stream, s, pl, twiddles, z0, zh_stride, fl, line); \
-    else hipLaunchKernelGGL((pcl_rows_kernel<DS_, CH_, false>), g, dim3(PCL_T), lds, stream, s, pl, twiddles, z0, zh_stride, fl, line);   \
-  } while (0)
-    if (downscale == 4) PCL_ROWS(4, 1);
-    else if (channels == 3) PCL_ROWS(1, 3);
-    else PCL_ROWS(1, 1);
-#undef PCL_ROWS
+    e = pc_dispatch_form<PC_FORMS_DS_CH>(downscale, channels, 0, [&](auto ds, auto ch, auto) {
+      if (ex) hipLaunchKernelGGL((pcl_rows_kernel<ds, ch, true>), g, dim3(PCL_T), lds, stream, s, pl, twiddles, z0, zh_stride, fl, line);
+      else hipLaunchKernelGGL((pcl_rows_kernel<ds, ch, false>), g, dim3(PCL_T), lds, stream, s, pl, twiddles, z0, zh_stride, fl, line);
+      return hipGetLastError();
+    });
+    if (e != hipSuccess) return e;
   }
-  return hipGetLastError();
+  return hipSuccess;
 }
 
 hipError_t launch_pcl_cols(const float* zh_prev, const float* zh_cur, size_t zh_stride, const PcPlan& pl, const float* twiddles,
@@ -427,10 +419,10 @@ hipError_t launch_pcl_cols(const float* zh_prev, const float* zh_cur, size_t zh_
   const bool ex = needs_exact(pl);
   auto kernel = peak_model == 1 ? (ex ? &pcl_cols_kernel<true, 1> : &pcl_cols_kernel<false, 1>)
                                 : (ex ? &pcl_cols_kernel<true, 0> : &pcl_cols_kernel<false, 0>);
-  hipError_t e = allow_lds(kernel, lds);
+  hipError_t e = pc_raise_lds_beyond_default(kernel, lds);
   if (e != hipSuccess) return e;
-  for (int p0 = 0; p0 < n_pairs; p0 += 65535) {
-    const int np = n_pairs - p0 < 65535 ? n_pairs - p0 : 65535;
+  for (int p0 = 0; p0 < n_pairs; p0 += PC_MAX_GRID_PAIRS) {
+    const int np = n_pairs - p0 < PC_MAX_GRID_PAIRS ? n_pairs - p0 : PC_MAX_GRID_PAIRS;
     hipLaunchKernelGGL(kernel, dim3((unsigned)((NU + 3) / 4), (unsigned)np), dim3(PCL_T), lds, stream, zh_prev + (size_t)p0 * zh_stride,
                        zh_cur + (size_t)p0 * zh_stride, zh_stride, pl, twiddles, Dt + (size_t)p0 * NU * pl.m * 2, cdc ? cdc + p0 : nullptr,
                        flags ? flags + 2 * (size_t)p0 : nullptr, line);
@@ -439,8 +431,8 @@ hipError_t launch_pcl_cols(const float* zh_prev, const float* zh_cur, size_t zh_
 }
 
 hipError_t launch_pcl_cdc(const float* zh_prev, const float* zh_cur, size_t zh_stride, int m, float* cdc, int n_pairs, hipStream_t stream) {
-  for (int p0 = 0; p0 < n_pairs; p0 += 65535) {
-    const int np = n_pairs - p0 < 65535 ? n_pairs - p0 : 65535;
+  for (int p0 = 0; p0 < n_pairs; p0 += PC_MAX_GRID_PAIRS) {
+    const int np = n_pairs - p0 < PC_MAX_GRID_PAIRS ? n_pairs - p0 : PC_MAX_GRID_PAIRS;
     hipLaunchKernelGGL(pcl_cdc_kernel, dim3((unsigned)np), dim3(64), 0, stream, zh_prev + (size_t)p0 * zh_stride, zh_cur + (size_t)p0 * zh_stride,
                        zh_stride, m, cdc + p0);
   }
@@ -458,10 +450,10 @@ hipError_t launch_pcl_peak(const PclFinal& a_in, const PcPlan& pl, int n_pairs, 
   auto inv = pk == 1 ? (ex ? &pcl_rows_inv_kernel<true, 1> : &pcl_rows_inv_kernel<false, 1>)
                      : (ex ? &pcl_rows_inv_kernel<true, 0> : &pcl_rows_inv_kernel<false, 0>);
   auto fin = pk == 1 ? &pcl_final_kernel<1> : &pcl_final_kernel<0>;
-  hipError_t e = allow_lds(inv, lds);
+  hipError_t e = pc_raise_lds_beyond_default(inv, lds);
   if (e != hipSuccess) return e;
-  for (int p0 = 0; p0 < n_pairs; p0 += 65535) {
-    const int np = n_pairs - p0 < 65535 ? n_pairs - p0 : 65535;
+  for (int p0 = 0; p0 < n_pairs; p0 += PC_MAX_GRID_PAIRS) {
+    const int np = n_pairs - p0 < PC_MAX_GRID_PAIRS ? n_pairs - p0 : PC_MAX_GRID_PAIRS;
     PclFinal a = a_in;
     a.m = pl.m;
     a.n = pl.n;

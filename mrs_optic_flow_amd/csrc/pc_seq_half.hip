@@ -21,6 +21,7 @@
 
 #include "mof_kernels.h"
 #include "pc_common.hpp"
+#include "pc_launch.hpp"
 
 namespace mof {
 
@@ -611,22 +612,10 @@ __global__ void __launch_bounds__(HalfTile<N>::T, MOF_PAIR_HALF_WPE) pc_pair_hal
   }
 }
 
-size_t half_extra_lds() {
-  static const size_t v = [] {
-    const char* e = getenv("MOF_PC_EXTRA_LDS");
-    return e ? (size_t)atol(e) : (size_t)0;
-  }();
-  return v;
-}
-
 template <int N>
 hipError_t configure_half() {
-  const int lds = (int)(HalfTile<N>::LDS_BYTES + half_extra_lds());
-  hipError_t e;
-  if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(&pc_seq_half_kernel<N, 0, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, lds)) != hipSuccess) return e;
-  if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(&pc_seq_half_kernel<N, 1, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, lds)) != hipSuccess) return e;
-  if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(&pc_seq_half_kernel<N, 0, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, lds)) != hipSuccess) return e;
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(&pc_seq_half_kernel<N, 1, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+  const size_t lds = HalfTile<N>::LDS_BYTES + pc_extra_lds();
+  return pc_each_form<PC_FORMS_CH_PK>([&](auto, auto ch, auto pk) { return pc_raise_lds(&pc_seq_half_kernel<N, pk, ch>, lds); });
 }
 
 template <int N>
@@ -634,16 +623,11 @@ hipError_t launch_half(const PcArgs& a, int n_pairs, int run, hipStream_t stream
   const int runs = (n_pairs + run - 1) / run;
   if (runs > 65535 || (a.channels != 1 && a.channels != 3) || a.downscale != 1) return hipErrorInvalidValue;
   const dim3 g((unsigned)a.grid_x, (unsigned)a.grid_y, (unsigned)runs);
-  const size_t lds = HalfTile<N>::LDS_BYTES + half_extra_lds();
-  if (a.channels == 3) {
-    if (a.peak_model == 1) hipLaunchKernelGGL((pc_seq_half_kernel<N, 1, 3>), g, dim3(HalfTile<N>::T), lds, stream, a, n_pairs, run);
-    else hipLaunchKernelGGL((pc_seq_half_kernel<N, 0, 3>), g, dim3(HalfTile<N>::T), lds, stream, a, n_pairs, run);
-  } else if (a.peak_model == 1) {
-    hipLaunchKernelGGL((pc_seq_half_kernel<N, 1, 1>), g, dim3(HalfTile<N>::T), lds, stream, a, n_pairs, run);
-  } else {
-    hipLaunchKernelGGL((pc_seq_half_kernel<N, 0, 1>), g, dim3(HalfTile<N>::T), lds, stream, a, n_pairs, run);
-  }
-  return hipGetLastError();
+  const size_t lds = HalfTile<N>::LDS_BYTES + pc_extra_lds();
+  return pc_dispatch_form<PC_FORMS_CH_PK>(a, [&](auto, auto ch, auto pk) {
+    hipLaunchKernelGGL((pc_seq_half_kernel<N, pk, ch>), g, dim3(HalfTile<N>::T), lds, stream, a, n_pairs, run);
+    return hipGetLastError();
+  });
 }
 
 template <int N>
@@ -652,27 +636,18 @@ hipError_t launch_pair_half(const PcArgs& a_in, int n_pairs, float* slabs, int n
   PcArgs a = a_in;
   a.total = n_pairs * a.grid_x * a.grid_y;
   const unsigned blocks = (unsigned)(a.total < n_slabs ? a.total : n_slabs);
-  const size_t lds = HalfTile<N>::LDS_BYTES + half_extra_lds();
+  const size_t lds = HalfTile<N>::LDS_BYTES + pc_extra_lds();
   float2* sl = reinterpret_cast<float2*>(slabs);
-  if (a.channels == 3) {
-    if (a.peak_model == 1) hipLaunchKernelGGL((pc_pair_half_kernel<N, 1, 3>), dim3(blocks), dim3(HalfTile<N>::T), lds, stream, a, sl);
-    else hipLaunchKernelGGL((pc_pair_half_kernel<N, 0, 3>), dim3(blocks), dim3(HalfTile<N>::T), lds, stream, a, sl);
-  } else if (a.peak_model == 1) {
-    hipLaunchKernelGGL((pc_pair_half_kernel<N, 1, 1>), dim3(blocks), dim3(HalfTile<N>::T), lds, stream, a, sl);
-  } else {
-    hipLaunchKernelGGL((pc_pair_half_kernel<N, 0, 1>), dim3(blocks), dim3(HalfTile<N>::T), lds, stream, a, sl);
-  }
-  return hipGetLastError();
+  return pc_dispatch_form<PC_FORMS_CH_PK>(a, [&](auto, auto ch, auto pk) {
+    hipLaunchKernelGGL((pc_pair_half_kernel<N, pk, ch>), dim3(blocks), dim3(HalfTile<N>::T), lds, stream, a, sl);
+    return hipGetLastError();
+  });
 }
 
 template <int N>
 hipError_t configure_pair_half() {
-  const int lds = (int)(HalfTile<N>::LDS_BYTES + half_extra_lds());
-  hipError_t e;
-  if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(&pc_pair_half_kernel<N, 0, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, lds)) != hipSuccess) return e;
-  if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(&pc_pair_half_kernel<N, 1, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, lds)) != hipSuccess) return e;
-  if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(&pc_pair_half_kernel<N, 0, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, lds)) != hipSuccess) return e;
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(&pc_pair_half_kernel<N, 1, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+  const size_t lds = HalfTile<N>::LDS_BYTES + pc_extra_lds();
+  return pc_each_form<PC_FORMS_CH_PK>([&](auto, auto ch, auto pk) { return pc_raise_lds(&pc_pair_half_kernel<N, pk, ch>, lds); });
 }
 
 }  // namespace

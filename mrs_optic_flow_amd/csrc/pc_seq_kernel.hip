@@ -28,6 +28,7 @@
 
 #include "mof_kernels.h"
 #include "pc_common.hpp"
+#include "pc_launch.hpp"
 #include "pc_passes.hpp"
 
 namespace mof {
@@ -287,24 +288,9 @@ __global__ void __launch_bounds__(256) pc_seq_kernel(PcArgs a, int n_pairs, int 
 
 bool pc_sequence_supported(int patch_size) { return patch_size == 64; }
 
-// Diagnostic knob (co-scheduling experiments): MOF_PC_EXTRA_LDS=<bytes> pads the dynamic LDS request, i.e. caps the
-// workgroups per CU (as for K1, pc_kernel.hip)
-static size_t seq_extra_lds() {
-  static const size_t v = [] {
-    const char* e = getenv("MOF_PC_EXTRA_LDS");
-    return e ? (size_t)atol(e) : (size_t)0;
-  }();
-  return v;
-}
-
-
 hipError_t pc_configure_sequence() {
-  const int lds = (int)(PcTraits<64>::LDS_BYTES + seq_extra_lds());
-  hipError_t e;
-  if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(&pc_seq_kernel<0, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, lds)) != hipSuccess) return e;
-  if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(&pc_seq_kernel<1, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, lds)) != hipSuccess) return e;
-  if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(&pc_seq_kernel<0, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, lds)) != hipSuccess) return e;
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(&pc_seq_kernel<1, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+  const size_t lds = PcTraits<64>::LDS_BYTES + pc_extra_lds();
+  return pc_each_form<PC_FORMS_CH_PK>([&](auto, auto ch, auto pk) { return pc_raise_lds(&pc_seq_kernel<pk, ch>, lds); });
 }
 
 // a.cur = frame 0, a.cur_stride = bytes between frames; pair k = (frame k + 1, frame k), k < n_pairs; a.prev unused.
@@ -314,9 +300,7 @@ hipError_t launch_pc_sequence(const PcArgs& a, int n_pairs, int run, hipStream_t
     // r06 (tools/video_probe.py: 128 pairs of 8 x 8 patches ran slower as a video than as pairs): fixed runs of 16 pairs left half of the
     // resident slots empty on a short video. As the half-tile kernel does (pc_half_kernel.hip): workgroups of a launch all last run + ~0.5
     // transforms (a run's first frame has no inverse), the launch lasts ceil(workgroups / slots) rounds of that -- the least product wins.
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-    const long slots = (long)cus * 4, patches = (long)a.grid_x * a.grid_y;  // four workgroups per CU (one 36 KB tile each)
+    const long slots = (long)pc_cu_count() * 4, patches = (long)a.grid_x * a.grid_y;  // four workgroups per CU (one 36 KB tile each)
     auto cost = [&](int r) {
       const long wgs = patches * ((n_pairs + r - 1) / r), rounds = (wgs + slots - 1) / slots;
       return (double)rounds * ((double)r + 0.5);
@@ -332,16 +316,11 @@ hipError_t launch_pc_sequence(const PcArgs& a, int n_pairs, int run, hipStream_t
   const int runs = (n_pairs + run - 1) / run;
   if (runs > 65535 || (a.channels != 1 && a.channels != 3) || a.downscale != 1) return hipErrorInvalidValue;
   const dim3 g((unsigned)a.grid_x, (unsigned)a.grid_y, (unsigned)runs);
-  const size_t lds = PcTraits<64>::LDS_BYTES + seq_extra_lds();
-  if (a.channels == 3) {
-    if (a.peak_model == 1) hipLaunchKernelGGL((pc_seq_kernel<1, 3>), g, dim3(256), lds, stream, a, n_pairs, run);
-    else hipLaunchKernelGGL((pc_seq_kernel<0, 3>), g, dim3(256), lds, stream, a, n_pairs, run);
-  } else if (a.peak_model == 1) {
-    hipLaunchKernelGGL((pc_seq_kernel<1, 1>), g, dim3(256), lds, stream, a, n_pairs, run);
-  } else {
-    hipLaunchKernelGGL((pc_seq_kernel<0, 1>), g, dim3(256), lds, stream, a, n_pairs, run);
-  }
-  return hipGetLastError();
+  const size_t lds = PcTraits<64>::LDS_BYTES + pc_extra_lds();
+  return pc_dispatch_form<PC_FORMS_CH_PK>(a, [&](auto, auto ch, auto pk) {
+    hipLaunchKernelGGL((pc_seq_kernel<pk, ch>), g, dim3(256), lds, stream, a, n_pairs, run);
+    return hipGetLastError();
+  });
 }
 
 }  // namespace mof

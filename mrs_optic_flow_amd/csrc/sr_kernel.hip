@@ -25,6 +25,7 @@
 
 #include "mof_kernels.h"
 #include "pc_common.hpp"
+#include "pc_launch.hpp"
 #include "sr_common.hpp"
 
 namespace mof {
@@ -716,14 +717,8 @@ bool sr_pair_kernels_supported(int res) { return res == 240 || res == 256 || res
 
 template <int K>
 static hipError_t launch_lp_lds(const SrLpArgs& a, int n_images, hipStream_t stream) {
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    cus = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ? prop.multiProcessorCount : 256;
-  }
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&sr_logpolar_lds_kernel<K>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)LpLds<K>::BYTES);
+  const int cus = pc_cu_count();
+  hipError_t e = pc_raise_lds(&sr_logpolar_lds_kernel<K>, LpLds<K>::BYTES);
   if (e != hipSuccess) return e;
   const int tiles = (a.res + 7) / 8;
   const long total = (long)n_images * tiles * tiles;
@@ -808,10 +803,8 @@ static hipError_t launch_sr_pc_n(const SrPcArgs& a, int n_pairs, hipStream_t str
   constexpr int H = N / 2;
   static_assert(N % FWD_ROWS == 0 && H % SR_LINES == 0, "rows and row pairs divide evenly over the workgroups");
   constexpr size_t fwd_lds = sizeof(cf) * FWD_ROWS * SrPlan<N>::LINE;
-  if (fwd_lds > 48 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&sr_rows_fwd_kernel<N>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fwd_lds);
-    if (e != hipSuccess) return e;
-  }
+  const hipError_t e = pc_raise_lds_beyond_default(&sr_rows_fwd_kernel<N>, fwd_lds);
+  if (e != hipSuccess) return e;
   hipLaunchKernelGGL(sr_rows_fwd_kernel<N>, dim3(N / FWD_ROWS, (unsigned)n_pairs), dim3(FWD_T), fwd_lds, stream, a);
   hipLaunchKernelGGL(sr_cols_kernel<N>, dim3((H + 1 + COLS_CW - 1) / COLS_CW, (unsigned)n_pairs), dim3(SR_T), 0, stream, a);
   hipLaunchKernelGGL(sr_rows_inv_kernel<N>, dim3(H / SR_LINES, (unsigned)n_pairs), dim3(K7Cfg<N>::T), 0, stream, a);
@@ -842,8 +835,8 @@ hipError_t launch_sr_peak(const SrPcArgs& a, int res, int n_pairs, hipStream_t s
 // K7 alone (r04): Dt -> peak candidates, for the FFT engine's large patches of 240 / 256 / 480 pixels (pc_large_kernel.hip's L8 follows)
 template <int N>
 static hipError_t launch_sr_rows_inv_n(const SrPcArgs& a, int n_pairs, hipStream_t stream) {
-  for (int p0 = 0; p0 < n_pairs; p0 += 65535) {
-    const int np = n_pairs - p0 < 65535 ? n_pairs - p0 : 65535;
+  for (int p0 = 0; p0 < n_pairs; p0 += PC_MAX_GRID_PAIRS) {
+    const int np = n_pairs - p0 < PC_MAX_GRID_PAIRS ? n_pairs - p0 : PC_MAX_GRID_PAIRS;
     SrPcArgs b = a;
     b.Dt = a.Dt + (size_t)p0 * (N / 2 + 1) * N * 2;
     b.cand = a.cand + (size_t)p0 * a.n_cand;

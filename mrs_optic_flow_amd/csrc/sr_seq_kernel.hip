@@ -22,6 +22,7 @@
 
 #include "mof_kernels.h"
 #include "pc_common.hpp"
+#include "pc_launch.hpp"
 #include "sr_common.hpp"
 
 namespace mof {
@@ -526,11 +527,8 @@ hipError_t launch_rows_real_n(const uint8_t* lp, size_t lp_stride, const float* 
   using R = RowsReal<N>;
   static_assert(N % R::ROWS == 0, "rows divide evenly over the workgroups");
   constexpr size_t lds = sizeof(cf) * R::LINES * SrPlan<N>::LINE;
-  if (lds > 48 * 1024) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&sr_rows_real_kernel<N>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
+  const hipError_t e = pc_raise_lds_beyond_default(&sr_rows_real_kernel<N>, lds);
+  if (e != hipSuccess) return e;
   hipLaunchKernelGGL(sr_rows_real_kernel<N>, dim3(N / R::ROWS, (unsigned)n_frames), dim3(R::T), lds, stream, lp, lp_stride, tw, zh,
                      zh_stride);
   return hipGetLastError();
@@ -542,14 +540,12 @@ hipError_t launch_rows_real_src_n(const PclSrc& src, const float* tw, float* zh,
   using R = RowsReal<N>;
   constexpr size_t lds = sizeof(cf) * R::LINES * SrPlan<N>::LINE;
   const bool pad = n < N;
-  if (lds > 48 * 1024) {
-    const void* f = channels == 3 ? (pad ? reinterpret_cast<const void*>(&sr_rows_real_src_kernel<N, 3, true>) : reinterpret_cast<const void*>(&sr_rows_real_src_kernel<N, 3, false>))
-                                  : (pad ? reinterpret_cast<const void*>(&sr_rows_real_src_kernel<N, 1, true>) : reinterpret_cast<const void*>(&sr_rows_real_src_kernel<N, 1, false>));
-    const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
-  for (int f0 = 0; f0 < n_images; f0 += 65534) {  // (the image index rides gridDim.y; even chunks keep cur | prev pairs together)
-    const int nf = n_images - f0 < 65534 ? n_images - f0 : 65534;
+  auto kernel = channels == 3 ? (pad ? &sr_rows_real_src_kernel<N, 3, true> : &sr_rows_real_src_kernel<N, 3, false>)
+                              : (pad ? &sr_rows_real_src_kernel<N, 1, true> : &sr_rows_real_src_kernel<N, 1, false>);
+  const hipError_t e = pc_raise_lds_beyond_default(kernel, lds);
+  if (e != hipSuccess) return e;
+  for (int f0 = 0; f0 < n_images; f0 += PC_MAX_GRID_IMAGES) {  // (the image index rides gridDim.y; even chunks keep cur | prev pairs together)
+    const int nf = n_images - f0 < PC_MAX_GRID_IMAGES ? n_images - f0 : PC_MAX_GRID_IMAGES;
     PclSrc s = src;
     const int patches = src.grid_x * src.grid_y;
     const int per_unit = src.paired == 2 ? patches : 2 * patches;  // images per frame (a video) / per frame pair
@@ -560,13 +556,7 @@ hipError_t launch_rows_real_src_n(const PclSrc& src, const float* tw, float* zh,
     float* zo = zh + (size_t)f0 * zh_stride;
     int* fl = flags ? flags + f0 : nullptr;
     int* su = sums ? sums + (size_t)(src.sums_stride ? src.sums_stride : 4) * f0 : nullptr;
-    if (channels == 3) {
-      if (pad) hipLaunchKernelGGL((sr_rows_real_src_kernel<N, 3, true>), g, b, lds, stream, s, tw, zo, zh_stride, fl, n, su);
-      else hipLaunchKernelGGL((sr_rows_real_src_kernel<N, 3, false>), g, b, lds, stream, s, tw, zo, zh_stride, fl, n, su);
-    } else {
-      if (pad) hipLaunchKernelGGL((sr_rows_real_src_kernel<N, 1, true>), g, b, lds, stream, s, tw, zo, zh_stride, fl, n, su);
-      else hipLaunchKernelGGL((sr_rows_real_src_kernel<N, 1, false>), g, b, lds, stream, s, tw, zo, zh_stride, fl, n, su);
-    }
+    hipLaunchKernelGGL(kernel, g, b, lds, stream, s, tw, zo, zh_stride, fl, n, su);
   }
   return hipGetLastError();
 }

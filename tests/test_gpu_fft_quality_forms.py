@@ -21,6 +21,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TARGET = os.path.join(ROOT, "tests", "test_gpu_fft_quality.py")
+FORMS_TARGET = os.path.join(ROOT, "tests", "test_gpu_fft_launch_forms.py")
 
 
 def _cases(pairs):
@@ -30,15 +31,23 @@ def _cases(pairs):
 _DIED = []  # a child that ended on a signal or at its time limit: no later test of this module starts another on the same card
 
 
-def _child(env, select, pairs=(), long_range=(), videos=(), timeout=600):
+def _child(env, select, pairs=(), long_range=(), videos=(), forms=(), timeout=600):
     """One child: the selected route tests under `env`. Returns its stdout after the status checks; every expected route line
-    ('route <name>: kernel_variant <variant>', printed by the child before it asserts) must be there."""
+    ('route <name>: kernel_variant <variant>', printed by the child before it asserts) must be there.
+    `forms`: (case, kernel_variant) of tests/launch_form_cases.py -- the front-end forms (BGR8, the OpenCL model, the long-range mode)
+    of the kernels the knob selects, held to the oracle by test_gpu_fft_launch_forms.py::test_launch_form_on_its_route in the same
+    child ('form <name>: kernel_variant <variant>')."""
     if _DIED:
         pytest.fail(f"not started: an earlier child of this module died ({_DIED[0]}); find its cause first")
     e = dict(os.environ, **env)
     e.update(MOF_QUALITY_PAIRS=_cases(pairs), MOF_QUALITY_LONG_RANGE=_cases(long_range), MOF_QUALITY_VIDEOS=_cases(videos))
+    targets = [TARGET]
+    if forms:
+        e.update(MOF_LAUNCH_FORM_CASES=_cases(forms))
+        targets.append(FORMS_TARGET)
+        select = f"({select}) or test_launch_form_on_its_route"
     try:
-        r = subprocess.run([sys.executable, "-m", "pytest", TARGET, "-m", "gpu", "-x", "-q", "-s", "-k", select, "-p", "no:cacheprovider"],
+        r = subprocess.run([sys.executable, "-m", "pytest", *targets, "-m", "gpu", "-x", "-q", "-s", "-k", select, "-p", "no:cacheprovider"],
                            capture_output=True, text=True, timeout=timeout, cwd=ROOT, env=e)
     except subprocess.TimeoutExpired:
         _DIED.append(f"{env}: no end within {timeout} s")
@@ -46,16 +55,22 @@ def _child(env, select, pairs=(), long_range=(), videos=(), timeout=600):
     if r.returncode < 0 or r.returncode in (124, 134, 137, 139):
         _DIED.append(f"{env}: status {r.returncode}")
     for line in r.stdout.splitlines():
-        if "bar " in line or "route " in line or " passed" in line:
+        if "bar " in line or "route " in line or "form " in line or " passed" in line:
             print(f"[{' '.join(f'{k}={v}' for k, v in env.items())}] {line}")
     assert r.returncode == 0 and " passed" in r.stdout and " skipped" not in r.stdout and " deselected" in r.stdout, \
         (env, r.returncode, r.stdout[-3000:], r.stderr[-1500:])
     for name, variant in list(pairs) + list(long_range):
         assert f"route {name}: kernel_variant {variant}" in r.stdout, (env, name, variant, r.stdout[-3000:])
+    for name, variant in forms:
+        assert f"form {name}: kernel_variant {variant}" in r.stdout, (env, name, variant, r.stdout[-3000:])
     for name, bits in videos:
         m = re.search(rf"route {re.escape(name)}: kernel_variant \S+, video entry == pair entry bits: (True|False)", r.stdout)
         assert m and m.group(1) == str(bits == "pair"), (env, name, bits, r.stdout[-3000:])
     return r.stdout
+
+
+def _forms(variant, *names):
+    return [(name, variant) for name in names]
 
 
 ROUTES = "test_pair_entry_on_its_route or test_sequence_runs"
@@ -73,28 +88,41 @@ def test_the_older_forms(gpu):
            f"{ROUTES} or {CONSTANTS}",
            pairs=[("circular-120", "stockham"), ("padded-142", "planned-large"), ("circular-200", "planned-large"),
                   ("padded-196", "planned-large"), ("passes-200", "planned-large"), ("circular-54", "planned"), ("padded-62", "planned")],
-           videos=[("long-video-64", "pair"), ("long-video-120", "pair"), ("long-video-128", "pair"), ("long-video-200", "pair")])
+           videos=[("long-video-64", "pair"), ("long-video-120", "pair"), ("long-video-128", "pair"), ("long-video-200", "pair")],
+           forms=_forms("planned", "planned-11-gray-cv", "planned-11-bgr-cv", "planned-11-lr-cv", "planned-20-gray-cv", "planned-20-bgr-cv",
+                        "planned-20-lr-cv", "planned-20-gray-ocl", "planned-20-bgr-ocl", "planned-20-lr-ocl", "planned-74-gray-cv",
+                        "planned-74-bgr-cv", "planned-74-lr-cv", "video-50-bgr-cv")
+           + _forms("stockham", "k1-120-gray-cv", "k1-120-bgr-cv", "k1-120-lr-cv", "video-64-bgr-cv", "video-64-gray-ocl", "video-64-bgr-ocl",
+                    "video-128-bgr-cv", "video-128-bgr-ocl", "video-120-bgr-cv")
+           + _forms("planned-large", "half-144-gray", "half-144-bgr"))
 
 
 def test_the_half_tile_everywhere(gpu):
     """MOF_FFT_HALF=1: 64 and 128 through the half-tile kernel, pairs (the tiled 128 frames: 512 patches) and its sequence form on the
     long videos (fft_route takes the half tile's video form before it looks at MOF_FFT_SEQ_HALF64 / 128, so those have a child of
     their own); the constant and zero patches. Evidence: kernel_variant 'planned-half' at 64 and 128 ('stockham' by default); the
-    video entry has the pair entry's bits at 64 and 128 (the half tile's two forms share their arithmetic, as at 120 by default)."""
+    video entry has the pair entry's bits at 64 and 128 (the half tile's two forms share their arithmetic, as at 120 by default).
+    The front-end forms: gray and BGR8 pairs and videos at 64 and 128 on the half tile; the OpenCL model, which the half tile does
+    not have, stays on K1 ('stockham'), and so does the long-range mode (kernel_variant names the full-resolution route)."""
     _child({"MOF_FFT_HALF": "1"}, f"{ROUTES} or {CONSTANTS}",
            pairs=[("circular-64", "planned-half"), ("crops-64", "planned-half"), ("grid-64", "planned-half"),
                   ("circular-128", "planned-half"), ("tiled-128", "planned-half")],
-           videos=[("long-video-64", "pair"), ("long-video-128", "pair"), ("video-64", "pair"), ("video-128", "pair")])
+           videos=[("long-video-64", "pair"), ("long-video-128", "pair"), ("video-64", "pair"), ("video-128", "pair")],
+           forms=_forms("planned-half", "k1-64-gray-cv", "k1-64-bgr-cv", "k1-128-gray-cv", "k1-128-bgr-cv", "video-64-gray-cv", "video-64-bgr-cv",
+                        "video-128-bgr-cv", "k1-64-lr-cv")
+           + _forms("stockham", "k1-64-bgr-ocl", "k1-128-bgr-ocl"))
 
 
 def test_the_older_half_tile_sequence_kernels(gpu):
     """MOF_FFT_SEQ_HALF64=1, MOF_FFT_SEQ_HALF128=1, MOF_FFT_SEQ_RUN=3: pc_seq_half.hip's sequence kernel at 64 and 128 in runs of three
     (it takes 16 by default, which the 10 pairs at 128 would not fill: both instantiations must see a second run), and a constant and
     a zero frame in its stream at 64. Nothing exposes the route: kernel_variant names the pair kernels, 'stockham' either way, and
-    the video entry has not the pair entry's bits with or without the knobs."""
+    the video entry has not the pair entry's bits with or without the knobs. The front-end forms: gray and BGR8 videos under both peak
+    models at 64 and 128 -- the four instantiations of pc_seq_half_kernel at either size."""
     _child({"MOF_FFT_SEQ_HALF64": "1", "MOF_FFT_SEQ_HALF128": "1", "MOF_FFT_SEQ_RUN": "3"},
            "test_sequence_runs or test_constant_and_zero_frames_in_a_video",
-           videos=[("long-video-64", "own"), ("long-video-128", "own"), ("video-64", "own"), ("video-128", "own")])
+           videos=[("long-video-64", "own"), ("long-video-128", "own"), ("video-64", "own"), ("video-128", "own")],
+           forms=_forms("stockham", *(f"video-{n}-{f}-{m}" for n in (64, 128) for f in ("gray", "bgr") for m in ("cv", "ocl"))))
 
 
 def test_forced_planned_kernel(gpu):
@@ -131,8 +159,10 @@ def test_pair_kernel_on_the_half_tile_at_128(gpu):
     """MOF_FFT_PAIR_HALF=1: pc_pair_half_kernel on THREE tiled 128 frames -- 768 patch pairs against one slab per workgroup, two
     workgroups per CU (512 on 256 CUs), so half of the workgroups walk a second patch pair: the prefetch of the next previous image,
     the slab's reuse, the store at a.quality + 2 p for p >= gridDim.x -- and on the 36 pairs alone. Nothing exposes the route:
-    kernel_variant stays 'stockham'."""
-    _child({"MOF_FFT_PAIR_HALF": "1"}, "test_pair_entry_on_its_route", pairs=[("tiled-128x3", "stockham"), ("circular-128", "stockham")])
+    kernel_variant stays 'stockham'. The front-end forms: gray and BGR8 under both peak models, the four instantiations of
+    pc_pair_half_kernel; the long-range mode stays on K1."""
+    _child({"MOF_FFT_PAIR_HALF": "1"}, "test_pair_entry_on_its_route", pairs=[("tiled-128x3", "stockham"), ("circular-128", "stockham")],
+           forms=_forms("stockham", "k1-128-gray-cv", "k1-128-bgr-cv", "k1-128-gray-ocl", "k1-128-bgr-ocl", "k1-128-lr-cv"))
 
 
 def test_forced_pass_run_and_chunk_boundaries(gpu):
@@ -153,12 +183,14 @@ def test_ab_library_of_k1(gpu, target):
     The quad formulation (pc_kernel_quad.hip) never carried the constant-patch rule of pc_common.hpp -- it detects no constant patch,
     so shift AND quality of one are the noise that rule exists to replace (its shift tests select no such pair either): the constant
     answer is not part of what that library is held to, here or there. Skipped with a message where the library is not built, as
-    the shift tests of these libraries are. Evidence: kernel_variant 'quad' for the quad library; nothing exposes the MFMA stage."""
+    the shift tests of these libraries are. Evidence: kernel_variant 'quad' for the quad library; nothing exposes the MFMA stage.
+    The quad library also runs the six front-end forms of pc_quad64_kernel (gray, BGR8, long-range under both peak models)."""
     lib = os.path.join(ROOT, "mrs_optic_flow_amd", "csrc", "ab", f"libmof_hip_{target}.so")
     if not os.path.exists(lib):
         pytest.skip(f"csrc/ab/libmof_hip_{target}.so not built (`make -C mrs_optic_flow_amd/csrc {target}`)")
     pairs = [("circular-64", "stockham"), ("crops-64", "stockham"), ("grid-64", "stockham")]
     if target == "quad":
-        _child({"MOF_LIB_PATH": lib, "MOF_PC_QUAD": "1"}, ROUTES, pairs=[(name, "quad") for name, _ in pairs], videos=[("long-video-64", "own")])
+        _child({"MOF_LIB_PATH": lib, "MOF_PC_QUAD": "1"}, ROUTES, pairs=[(name, "quad") for name, _ in pairs], videos=[("long-video-64", "own")],
+               forms=_forms("quad", *(f"k1-64-{f}-{m}" for f in ("gray", "bgr", "lr") for m in ("cv", "ocl"))))
     else:
         _child({"MOF_LIB_PATH": lib}, f"{ROUTES} or (test_constant_and_zero_patches and 64)", pairs=pairs, videos=[("long-video-64", "own")])

@@ -7,7 +7,8 @@ The corpus goes through every tail of csrc/pc_common.hpp (peak_window / peak_fin
 front end that shares its byte extraction: the batches of tests/quality_cases.py through the quality entries (the sequence entry
 for the video batches, the OpenCL model for the ocl-* ones), the 36 circular-shift pairs under the OpenCL model with no mask, BGR8
 batches, the long-range mode, constant and all-zero patches against texture on padded sizes, the scale / rotation estimator on
-tests/sr_scenes.py views with black frames, one BGR8 block-matching batch."""
+tests/sr_scenes.py views with black frames, one BGR8 block-matching batch; and through every front-end form of every FFT launcher on
+the default route (tests/launch_form_cases.py: gray, BGR8 and long-range under both peak models, pairs and videos)."""
 import os
 import sys
 
@@ -55,6 +56,9 @@ def run(path):
             put(name, *fm.process_sequence_device(gpu(b.frames), return_quality=True))
         else:
             put(name, *fm.process_batch_device(gpu(b.cur), gpu(b.prev), return_quality=True))
+    import launch_form_cases as L
+    for name, case in L.CASES.items():  # every front-end form of every FFT launcher on the default route (3 frames or 2 pairs each)
+        put(f"form-{name}", *L.run(case, L.engine(case), dev, return_quality=True))
     for n in (64, 60, 144):  # the 7 x 7 window clamped at the surface's edges (tests/test_gpu_peak_tail.py)
         cur, prev = Q.circular_pairs(n)
         put(f"ocl-circular-{n}", *one_patch(n, peak_model=PEAK_OCL, search_radius=n).process_batch_device(gpu(cur), gpu(prev), return_quality=True))
