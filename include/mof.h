@@ -70,6 +70,10 @@ int mof_device_count(void);
  * and do not pin. There is no reference counterpart: the reference is one synchronous call per frame. */
 int mof_purge_deferred(void);  /* frees every parked engine; returns how many */
 int mof_deferred_count(void);  /* engines parked now */
+/* Test and diagnostic aid: device and pinned-host allocations the library's engines hold now, in this process (every engine kind,
+ * their host-batch pipelines and scratch, parked engines included; streams and events are not counted). Back at its earlier value
+ * once an engine is destroyed -- an exact "nothing leaked" on a GPU whose free memory other processes move. */
+int mof_live_buffers(void);
 
 /* ------------------------------------------------------------------------------------------ */
 /* FFT phase correlation (FftMethod)                                                          */

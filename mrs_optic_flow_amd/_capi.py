@@ -65,6 +65,7 @@ SYMBOLS = {
     "mof_device_count": (_I, []),
     "mof_purge_deferred": (_I, []),
     "mof_deferred_count": (_I, []),
+    "mof_live_buffers": (_I, []),
     "mof_fft_release_graphs": (_I, [_VP]),
     "mof_fft_graph_pinned": (_I, [_VP]),
     "mof_bm_release_graphs": (_I, [_VP]),

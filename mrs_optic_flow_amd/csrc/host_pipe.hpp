@@ -18,6 +18,8 @@
 #include <thread>
 #include <vector>
 
+#include "dev_mem.hpp"
+
 namespace mof {
 
 // routing only: hipMemcpyAsync is correct on any host pointer (the runtime stages what it does not know to be pinned) -- it is just slow there
@@ -54,7 +56,6 @@ class HostPipe {
     const char* v = getenv("MOF_HOST_VIDEO");
     video_on_ = !v || atoi(v) != 0;
   }
-  ~HostPipe() { release(); }
   HostPipe(const HostPipe&) = delete;
   HostPipe& operator=(const HostPipe&) = delete;
 
@@ -97,7 +98,7 @@ class HostPipe {
       if (*err != hipSuccess) { rc = -1; break; }
       ch.stride = fb_;
       ch.count = c;
-      for (int i = 0; i < n_outs_; ++i) ch.d_out[i] = s.d_out[i];
+      for (int i = 0; i < n_outs_; ++i) ch.d_out[i] = s.d_out[i].get();
       rc = run(ch, compute);
       if (rc != 0) break;
       for (int i = 0; i < n_outs_ && *err == hipSuccess; ++i)
@@ -160,7 +161,7 @@ class HostPipe {
       ch.d_prev = nullptr;
       ch.stride = fb_;
       ch.count = c;
-      for (int k = 0; k < n_outs_; ++k) ch.d_out[k] = s.d_out[k];
+      for (int k = 0; k < n_outs_; ++k) ch.d_out[k] = s.d_out[k].get();
       rc = run(ch, compute);
       if (rc != 0) break;
       for (int k = 0; k < n_outs_ && *err == hipSuccess; ++k)
@@ -179,30 +180,13 @@ class HostPipe {
     return rc;
   }
 
-  void release() {
-    for (Slot& s : slot_) {
-      if (s.d_frames) (void)hipFree(s.d_frames);
-      if (s.h_frames) (void)hipHostFree(s.h_frames);
-      for (int i = 0; i < MAX_OUTS; ++i) {
-        if (s.d_out[i]) (void)hipFree(s.d_out[i]);
-        if (s.h_out[i]) (void)hipHostFree(s.h_out[i]);
-      }
-      if (s.up) (void)hipEventDestroy(s.up);
-      if (s.done) (void)hipEventDestroy(s.done);
-      s = Slot{};
-    }
-    if (copy_) (void)hipStreamDestroy(copy_);
-    copy_ = nullptr;
-    ready_ = staged_ = false;
-  }
-
  private:
   struct Slot {
-    uint8_t* d_frames = nullptr;  // 2 * chunk frames: cur block | prev block, or the chunk + 1 frames of a video run
-    uint8_t* h_frames = nullptr;  // pinned staging of the same shape (pageable callers only)
-    void* d_out[MAX_OUTS] = {nullptr, nullptr, nullptr};
-    void* h_out[MAX_OUTS] = {nullptr, nullptr, nullptr};  // pinned
-    hipEvent_t up = nullptr, done = nullptr;
+    Event up, done;
+    DevMem<uint8_t> d_frames;     // 2 * chunk frames: cur block | prev block, or the chunk + 1 frames of a video run
+    PinnedMem<uint8_t> h_frames;  // pinned staging of the same shape (pageable callers only)
+    DevMem<uint8_t> d_out[MAX_OUTS];
+    PinnedMem<uint8_t> h_out[MAX_OUTS];
     int first = 0, count = 0;
     bool busy = false;
   };
@@ -210,15 +194,12 @@ class HostPipe {
   hipError_t ensure_device() {
     if (ready_) return hipSuccess;
     hipError_t e;
-    if ((e = hipStreamCreateWithFlags(&copy_, hipStreamNonBlocking)) != hipSuccess) return e;
+    if ((e = copy_.create()) != hipSuccess) return e;
     for (Slot& s : slot_) {
-      if ((e = hipMalloc(&s.d_frames, (size_t)2 * chunk_ * fb_)) != hipSuccess) return e;
-      for (int i = 0; i < n_outs_; ++i) {
-        if ((e = hipMalloc(&s.d_out[i], out_bpp_[i] * (size_t)2 * chunk_)) != hipSuccess) return e;  // (2 x: a slot of the FRAMES form holds two chunks)
-        if ((e = hipHostMalloc(&s.h_out[i], out_bpp_[i] * (size_t)2 * chunk_, hipHostMallocDefault)) != hipSuccess) return e;
-      }
-      if ((e = hipEventCreateWithFlags(&s.up, hipEventDisableTiming)) != hipSuccess) return e;
-      if ((e = hipEventCreateWithFlags(&s.done, hipEventDisableTiming)) != hipSuccess) return e;
+      if ((e = s.d_frames.alloc((size_t)2 * chunk_ * fb_)) != hipSuccess) return e;
+      for (int i = 0; i < n_outs_; ++i)  // (2 x: a slot of the FRAMES form holds two chunks)
+        if ((e = alloc_all(s.d_out[i], out_bpp_[i] * (size_t)2 * chunk_, s.h_out[i], out_bpp_[i] * (size_t)2 * chunk_)) != hipSuccess) return e;
+      if ((e = s.up.create()) != hipSuccess || (e = s.done.create()) != hipSuccess) return e;
     }
     ready_ = true;
     return hipSuccess;
@@ -226,7 +207,7 @@ class HostPipe {
   hipError_t ensure_staging() {
     if (staged_) return hipSuccess;
     for (Slot& s : slot_) {
-      const hipError_t e = hipHostMalloc(&s.h_frames, (size_t)2 * chunk_ * fb_, hipHostMallocDefault);
+      const hipError_t e = s.h_frames.alloc((size_t)2 * chunk_ * fb_);
       if (e != hipSuccess) return e;
     }
     staged_ = true;
@@ -284,7 +265,7 @@ class HostPipe {
   size_t out_bpp_[MAX_OUTS] = {0, 0, 0};
   int n_outs_, chunk_ = 1, threads_ = 4;
   bool video_on_ = true, ready_ = false, staged_ = false;
-  hipStream_t copy_ = nullptr;
+  Stream copy_;  // (declared before the slots: they are released first)
   Slot slot_[SLOTS];
 };
 

@@ -14,6 +14,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <vector>
@@ -28,7 +29,7 @@ thread_local char g_err[512] = "";
 }  // namespace
 
 namespace mof {
-// shared with mof_sr.hip: records the calling thread's last error text, returns `code`
+// shared with the other host files (capi_graph.hpp): records the calling thread's last error text, returns `code`
 int capi_fail(int code, const char* fmt, ...) {
   va_list ap;
   va_start(ap, fmt);
@@ -88,24 +89,7 @@ namespace {
 
 constexpr auto& fail = mof::capi_fail;
 
-#define HIP_TRY(expr)                                                                          \
-  do {                                                                                         \
-    hipError_t _e = (expr);                                                                    \
-    if (_e != hipSuccess) return fail(MOF_ERR_HIP, "%s: %s", #expr, hipGetErrorString(_e));    \
-  } while (0)
-
 using mof::BusyGuard;
-
-int select_device(int device) {
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) {
-    (void)hipGetLastError();
-    return fail(MOF_ERR_NO_DEVICE, "no HIP device available (this library has no CPU fallback)");
-  }
-  if (device < 0 || device >= n) return fail(MOF_ERR_BAD_ARG, "device %d out of range (0..%d)", device, n - 1);
-  HIP_TRY(hipSetDevice(device));
-  return MOF_OK;
-}
 
 // Which kernels an engine launches, decided once at create (fft_route)
 struct FftRoute {
@@ -209,61 +193,49 @@ bool fft_route(const mof_fft_config& c, mof::PcPlan* plan, FftRoute* r) {
 
 }  // namespace
 
+// Member order is the teardown order in reverse (dev_mem.hpp): the stream and the fence's event are declared before the buffers, the
+// host pipes last, so `delete e` -- after the waits of fft_destroy_now -- releases pipes, buffers, event, stream in that order.
 struct mof_fft_engine {
   mof_fft_config cfg{};
-  hipStream_t stream = nullptr;
-  float* d_twiddles = nullptr;
-  uint8_t* d_frames[2] = {nullptr, nullptr};  // [cur_slot], [1-cur_slot] = previous
+  mof::Stream stream;
+  mof::ScratchFence fence;                // cross-stream ordering of the large-patch scratch
+  mof::DevMem<float> d_twiddles;
+  mof::DevMem<uint8_t> d_frames[2];       // [cur_slot], [1-cur_slot] = previous
   int prev_slot = 0;
   size_t frame_bytes = 0;
-  double* d_out = nullptr;       // one frame's results
-  double* h_out = nullptr;       // pinned
-  double* d_quality = nullptr;   // one frame's (response, peak) per patch, beside d_out / h_out (the stateful *_q entries)
-  double* h_quality = nullptr;   // pinned
-  uint8_t* h_stage = nullptr;    // pinned upload staging (tightly packed frame)
-  bool first = true;             // FftMethod.cpp:1761
+  mof::DevMem<double> d_out;              // one frame's results
+  mof::PinnedMem<double> h_out;
+  mof::DevMem<double> d_quality;          // one frame's (response, peak) per patch, beside d_out / h_out (the stateful *_q entries)
+  mof::PinnedMem<double> h_quality;
+  mof::PinnedMem<uint8_t> h_stage;        // upload staging (tightly packed frame)
+  bool first = true;                      // FftMethod.cpp:1761
   FftRoute route;
-  mof::PcPlan plan{};            // route.family PLANNED / LARGE
-  float* d_pair_slabs = nullptr; // route.pair_half_wgs: slabs of the pair kernel on the half tile, one per workgroup
+  mof::PcPlan plan{};                     // route.family PLANNED / LARGE
+  mof::DevMem<float> d_pair_slabs;        // route.pair_half_wgs: slabs of the pair kernel on the half tile, one per workgroup
   int n_pair_slabs = 0;
   // scratch of the large-patch pipeline, for `cap` patch pairs per pass: row half-spectra of 2 cap patches, Dt, peak
   // candidates, constant-patch flags, C_dc. Grown by a batch that needs more (never under a graph capture, never while pinned).
-  float *d_zh = nullptr, *d_dt = nullptr, *d_cdc = nullptr;
-  float2* d_cand = nullptr;
-  int* d_flags = nullptr;
+  mof::DevMem<float> d_zh, d_dt, d_cdc;
+  mof::DevMem<float2> d_cand;
+  mof::DevMem<int> d_flags;
   int cap = 0;
-  mof::ScratchFence fence;                // cross-stream ordering of that scratch
   std::atomic<bool> busy{false};
   std::atomic<bool> graph_pinned{false};  // a batch call was captured into a HIP graph (capi_graph.hpp)
   std::mutex host_mu;                     // mof_fft_process_batch_host: upload / run / download pipeline (host_pipe.hpp), made by its first call
-  mof::HostPipe* host_pipe = nullptr;
-  mof::HostPipe* host_pipe_q = nullptr;   // mof_fft_process_batch_host_q with a quality output: the same pipeline with a second output
+  std::unique_ptr<mof::HostPipe> host_pipe;
+  std::unique_ptr<mof::HostPipe> host_pipe_q;  // mof_fft_process_batch_host_q with a quality output: the same pipeline with a second output
 };
-
-static void large_free(mof_fft_engine* e) {
-  void* bufs[] = {e->d_zh, e->d_dt, e->d_cdc, e->d_cand, e->d_flags};
-  for (void* b : bufs)
-    if (b) (void)hipFree(b);
-  e->d_zh = e->d_dt = e->d_cdc = nullptr;
-  e->d_cand = nullptr;
-  e->d_flags = nullptr;
-  e->cap = 0;
-}
 
 static hipError_t large_alloc(mof_fft_engine* e, int cap) {
   mof::RelaxedCapture relaxed;
-  large_free(e);
-  const size_t zhf = mof::pcl_zh_floats(e->plan);
-  hipError_t err;
-  if ((err = hipMalloc(&e->d_zh, (size_t)2 * cap * zhf * sizeof(float))) != hipSuccess) return err;
-  if ((err = hipMalloc(&e->d_dt, (size_t)cap * zhf * sizeof(float))) != hipSuccess) return err;
-  if ((err = hipMalloc(&e->d_cand, (size_t)cap * mof::pcl_candidates(e->plan) * sizeof(float2))) != hipSuccess) return err;
-  // [0, 2 cap): flags per pair (cur | prev); [2 cap, 4 cap): flags per image of a video pass; [4 cap, 12 cap): four exact pixel sums per image
-  // (the tuned transform sizes whose Nyquist bin is not exact: 250, 400, 432)
-  if ((err = hipMalloc(&e->d_flags, (size_t)12 * cap * sizeof(int))) != hipSuccess) return err;
-  if ((err = hipMalloc(&e->d_cdc, (size_t)cap * sizeof(float))) != hipSuccess) return err;
-  e->cap = cap;
-  return hipSuccess;
+  const size_t zhf = mof::pcl_zh_floats(e->plan), n = (size_t)cap;
+  e->cap = 0;
+  // d_flags: [0, 2 cap): flags per pair (cur | prev); [2 cap, 4 cap): flags per image of a video pass; [4 cap, 12 cap): four exact pixel sums
+  // per image (the tuned transform sizes whose Nyquist bin is not exact: 250, 400, 432)
+  const hipError_t err = mof::alloc_all(e->d_zh, 2 * n * zhf, e->d_dt, n * zhf, e->d_cand, n * mof::pcl_candidates(e->plan), e->d_flags, 12 * n,
+                                        e->d_cdc, n);
+  if (err == hipSuccess) e->cap = cap;
+  return err;
 }
 
 // Frame pairs per pass of the large-patch pipeline: as many as keep the scratch (three Zh-sized planes per patch pair) under
@@ -282,22 +254,11 @@ static int launch_large(mof_fft_engine* e, const mof::PcArgs& a, int n_pairs, hi
   const int patches = a.grid_x * a.grid_y;
   const int pass_max = large_pass_pairs(e, patches);
   const int want_pairs = n_pairs < pass_max ? n_pairs : pass_max;
-  const bool capturing = mof::stream_capturing(s);
-  if ((long)want_pairs * patches > e->cap) {
-    if (e->graph_pinned.load())
-      return fail(MOF_ERR_BUSY, "the large-patch scratch would have to grow, but a captured HIP graph still points into it: run the "
-                                "largest batch once before capturing, or call mof_fft_release_graphs once the graphs are gone");
-    if (capturing)
-      return fail(MOF_ERR_BAD_ARG, "the large-patch scratch must grow to %d patch pairs, which cannot happen inside a graph capture: "
-                                   "run one batch of this size before capturing", want_pairs * patches);
-    e->fence.wait_idle();
-    (void)hipStreamSynchronize(e->stream);
-    const hipError_t err = large_alloc(e, want_pairs * patches);
-    if (err != hipSuccess) {
-      (void)large_alloc(e, e->cfg.grid_x * e->cfg.grid_y);  // keep the stateful entry usable
-      return fail(err == hipErrorOutOfMemory ? MOF_ERR_NO_MEMORY : MOF_ERR_HIP, "large-patch scratch for %d patch pairs: %s",
-                  want_pairs * patches, hipGetErrorString(err));
-    }
+  {
+    const int rc = mof::grow_scratch(e->graph_pinned.load(), e->fence, {e->stream}, mof::stream_capturing(s), "the large-patch scratch (patch pairs)",
+                                     e->cap, (long)want_pairs * patches, (long)e->cfg.grid_x * e->cfg.grid_y,
+                                     [e](long cap) { return large_alloc(e, (int)cap); });
+    if (rc != MOF_OK) return rc;
   }
   HIP_TRY(e->fence.acquire(s));
   const size_t zhf = mof::pcl_zh_floats(e->plan);
@@ -407,27 +368,50 @@ static int launch_field(mof_fft_engine* e, const mof::PcArgs& a, int n_pairs, hi
     if (_rc != MOF_OK) return _rc; \
   } while (0)
 
+// (member order = teardown order in reverse, as mof_fft_engine: stream, buffers, host pipe)
 struct mof_bm_engine {
   mof_bm_config cfg{};
-  hipStream_t stream = nullptr;
-  uint8_t* d_frames[2] = {nullptr, nullptr};
+  mof::Stream stream;
+  mof::DevMem<uint8_t> d_frames[2];
   int prev_slot = 0;
   size_t frame_bytes = 0;
-  int8_t* d_dx = nullptr;
-  int8_t* d_dy = nullptr;
-  int8_t* d_mode = nullptr;
-  int8_t* h_res = nullptr;     // pinned: dx | dy | mode
-  uint8_t* h_stage = nullptr;
+  mof::DevMem<int8_t> d_dx, d_dy, d_mode;
+  mof::PinnedMem<int8_t> h_res;  // dx | dy | mode
+  mof::PinnedMem<uint8_t> h_stage;
   // BlockMethod::Refine scratch (allocated on first use): the two 2x images, nine SADs
-  uint8_t* d_up[2] = {nullptr, nullptr};
-  unsigned long long* d_sad9 = nullptr;
-  unsigned long long* h_sad9 = nullptr;
+  mof::DevMem<uint8_t> d_up[2];
+  mof::DevMem<unsigned long long> d_sad9;
+  mof::PinnedMem<unsigned long long> h_sad9;
   bool have_pair = false;      // a processImage call has been made (both frame slots are meaningful)
   std::atomic<bool> busy{false};
   std::atomic<bool> graph_pinned{false};
   std::mutex host_mu;          // mof_bm_process_batch_host's pipeline (host_pipe.hpp)
-  mof::HostPipe* host_pipe = nullptr;
+  std::unique_ptr<mof::HostPipe> host_pipe;
 };
+
+static void pack_frame(uint8_t* dst, const uint8_t* src, size_t pitch, int w, int h) {
+  for (int y = 0; y < h; ++y) std::memcpy(dst + (size_t)y * w, src + (size_t)y * pitch, (size_t)w);
+}
+
+// the stateful entries' upload: `frame` packed into the pinned staging, then into frame slot `slot` on the engine's stream
+template <class Engine>
+static hipError_t upload_frame(Engine* e, int slot, const uint8_t* frame, size_t pitch) {
+  pack_frame(e->h_stage, frame, pitch, e->cfg.frame_width, e->cfg.frame_height);
+  return hipMemcpyAsync(e->d_frames[slot], e->h_stage, e->frame_bytes, hipMemcpyHostToDevice, e->stream);
+}
+
+// setImPrev of both engine kinds
+template <class Engine>
+static int set_prev(Engine* e, const uint8_t* frame, size_t pitch) {
+  if (!e) return fail(MOF_ERR_NOT_INIT, "null engine");
+  if (!frame || pitch < (size_t)e->cfg.frame_width) return fail(MOF_ERR_BAD_ARG, "bad frame/pitch");
+  BusyGuard g(e->busy);
+  if (!g.owned) return fail(MOF_ERR_BUSY, "engine busy");
+  HIP_TRY(hipSetDevice(e->cfg.device));
+  HIP_TRY(upload_frame(e, e->prev_slot, frame, pitch));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  return MOF_OK;
+}
 
 extern "C" {
 
@@ -499,23 +483,34 @@ static int validate_fft(const mof_fft_config* c) {
   return MOF_OK;
 }
 
+// the waits that must precede any release of an engine's memory, then the release itself (member order, see the struct)
+static void fft_destroy_now(void* p) {
+  mof_fft_engine* e = static_cast<mof_fft_engine*>(p);
+  mof::RelaxedCapture relaxed;  // frees must not invalidate a capture running on another thread
+  (void)hipSetDevice(e->cfg.device);
+  if (e->stream) (void)hipStreamSynchronize(e->stream);
+  e->fence.wait_idle();
+  delete e;
+}
+struct FftDestroyNow {
+  void operator()(mof_fft_engine* e) const { fft_destroy_now(e); }
+};
+
 int mof_fft_create(const mof_fft_config* cfg, mof_fft_engine** out) try {
   if (!out) return fail(MOF_ERR_BAD_ARG, "null out");
   *out = nullptr;
   int rc = validate_fft(cfg);
   if (rc) return rc;
-  rc = select_device(cfg->device);
+  rc = mof::select_device(cfg->device);
   if (rc) return rc;
   mof::RelaxedCapture relaxed;  // allocating an engine must not invalidate a capture on another thread
   const size_t res = (size_t)cfg->grid_x * cfg->grid_y * 2;
-  mof_fft_engine* e = new (std::nothrow) mof_fft_engine();
+  std::unique_ptr<mof_fft_engine, FftDestroyNow> e(new (std::nothrow) mof_fft_engine());  // every early return tears down what exists
   if (!e) return fail(MOF_ERR_NO_MEMORY, "out of host memory");
   e->cfg = *cfg;
   e->frame_bytes = (size_t)cfg->frame_width * cfg->frame_height;
-  if (!fft_route(*cfg, &e->plan, &e->route)) {  // (validate_fft has checked that a plan exists)
-    delete e;
+  if (!fft_route(*cfg, &e->plan, &e->route))  // (validate_fft has checked that a plan exists)
     return fail(MOF_ERR_UNSUPPORTED, "no plan for patch_size %d", cfg->patch_size);
-  }
   const FftRoute& r = e->route;
   std::vector<float> tw = mof::twiddle_table(r.m);
   if (r.family == FftRoute::TUNED && r.m == 64) {  // the tuned N = 64 kernel's matrix-core stage reads its DFT-16 fragments from behind the twiddles
@@ -524,46 +519,31 @@ int mof_fft_create(const mof_fft_config* cfg, mof_fft_engine** out) try {
     tw.resize(128 + 1024);
     std::memcpy(tw.data() + 128, frag.data(), 4096);
   }
-#define CREATE_TRY(expr)                                                                        \
-  do {                                                                                          \
-    hipError_t _e = (expr);                                                                     \
-    if (_e != hipSuccess) {                                                                     \
-      fail(MOF_ERR_HIP, "%s: %s", #expr, hipGetErrorString(_e));                                \
-      mof_fft_destroy(e);                                                                       \
-      return MOF_ERR_HIP;                                                                       \
-    }                                                                                           \
-  } while (0)
-  CREATE_TRY(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
-  CREATE_TRY(hipMalloc(&e->d_twiddles, tw.size() * sizeof(float)));
-  CREATE_TRY(mof::copy_on(e->stream, e->d_twiddles, tw.data(), tw.size() * sizeof(float), hipMemcpyHostToDevice));
-  CREATE_TRY(hipMalloc(&e->d_frames[0], e->frame_bytes));
-  CREATE_TRY(hipMalloc(&e->d_frames[1], e->frame_bytes));
-  CREATE_TRY(mof::fill_on(e->stream, e->d_frames[0], 0, e->frame_bytes));
-  CREATE_TRY(mof::fill_on(e->stream, e->d_frames[1], 0, e->frame_bytes));
-  CREATE_TRY(hipMalloc(&e->d_out, res * sizeof(double)));
-  CREATE_TRY(hipHostMalloc(&e->h_out, res * sizeof(double), hipHostMallocDefault));
-  CREATE_TRY(hipMalloc(&e->d_quality, res * sizeof(double)));
-  CREATE_TRY(hipHostMalloc(&e->h_quality, res * sizeof(double), hipHostMallocDefault));
-  CREATE_TRY(hipHostMalloc(&e->h_stage, e->frame_bytes, hipHostMallocDefault));
-  // the kernels the route can launch (a video's half-tile form runs at half_m whenever that is set)
-  if (r.half_m > 0 || r.video == FftRoute::HALF_SEQ) CREATE_TRY(mof::pc_configure_half(r.half_m > 0 ? r.half_m : r.video_m));
-  if (r.family == FftRoute::LARGE) {
-    CREATE_TRY(e->fence.create());
-    CREATE_TRY(large_alloc(e, cfg->grid_x * cfg->grid_y));  // one frame pair; a batch grows it to a whole pass
-  } else if (r.family == FftRoute::PLANNED) {
-    CREATE_TRY(mof::pc_configure_generic());
-  } else {
-    CREATE_TRY(mof::pc_configure(r.m));
+  HIP_TRY(e->stream.create());
+  HIP_TRY(mof::upload(e->d_twiddles, tw, e->stream));
+  for (auto& frame : e->d_frames) {
+    HIP_TRY(frame.alloc(e->frame_bytes));
+    HIP_TRY(mof::fill_on(e->stream, frame, 0, e->frame_bytes));
   }
-  if (r.video == FftRoute::SEQ) CREATE_TRY(mof::pc_configure_sequence());
-  if (r.video == FftRoute::SEQ_HALF) CREATE_TRY(mof::pc_configure_sequence_half(r.m));
+  HIP_TRY(mof::alloc_all(e->d_out, res, e->h_out, res, e->d_quality, res, e->h_quality, res, e->h_stage, e->frame_bytes));
+  // the kernels the route can launch (a video's half-tile form runs at half_m whenever that is set)
+  if (r.half_m > 0 || r.video == FftRoute::HALF_SEQ) HIP_TRY(mof::pc_configure_half(r.half_m > 0 ? r.half_m : r.video_m));
+  if (r.family == FftRoute::LARGE) {
+    HIP_TRY(e->fence.create());
+    HIP_TRY(large_alloc(e.get(), cfg->grid_x * cfg->grid_y));  // one frame pair; a batch grows it to a whole pass
+  } else if (r.family == FftRoute::PLANNED) {
+    HIP_TRY(mof::pc_configure_generic());
+  } else {
+    HIP_TRY(mof::pc_configure(r.m));
+  }
+  if (r.video == FftRoute::SEQ) HIP_TRY(mof::pc_configure_sequence());
+  if (r.video == FftRoute::SEQ_HALF) HIP_TRY(mof::pc_configure_sequence_half(r.m));
   if (r.pair_half_wgs != 0) {
     e->n_pair_slabs = r.pair_half_wgs * mof::pc_cu_count();
-    CREATE_TRY(mof::pc_configure_pair_half(r.m));
-    CREATE_TRY(hipMalloc(&e->d_pair_slabs, (size_t)e->n_pair_slabs * mof::pc_pair_half_slab_floats(r.m) * sizeof(float)));
+    HIP_TRY(mof::pc_configure_pair_half(r.m));
+    HIP_TRY(e->d_pair_slabs.alloc((size_t)e->n_pair_slabs * mof::pc_pair_half_slab_floats(r.m)));
   }
-#undef CREATE_TRY
-  *out = e;
+  *out = e.release();
   return MOF_OK;
 } catch (const std::bad_alloc&) {
   return fail(MOF_ERR_NO_MEMORY, "mof_fft_create: out of host memory");
@@ -575,29 +555,6 @@ const char* mof_fft_kernel_variant(const mof_fft_engine* e) {
   return r.half_m > 0 ? "planned-half"
                       : (r.family == FftRoute::LARGE ? "planned-large"
                                                      : (r.family == FftRoute::PLANNED ? "planned" : mof::pc_kernel_variant(e->cfg.patch_size)));
-}
-
-static void fft_destroy_now(void* p) {
-  mof_fft_engine* e = static_cast<mof_fft_engine*>(p);
-  mof::RelaxedCapture relaxed;  // frees must not invalidate a capture running on another thread
-  (void)hipSetDevice(e->cfg.device);
-  if (e->stream) (void)hipStreamSynchronize(e->stream);
-  e->fence.wait_idle();
-  delete e->host_pipe;
-  delete e->host_pipe_q;
-  large_free(e);
-  e->fence.destroy();
-  if (e->d_twiddles) (void)hipFree(e->d_twiddles);
-  if (e->d_pair_slabs) (void)hipFree(e->d_pair_slabs);
-  if (e->d_frames[0]) (void)hipFree(e->d_frames[0]);
-  if (e->d_frames[1]) (void)hipFree(e->d_frames[1]);
-  if (e->d_out) (void)hipFree(e->d_out);
-  if (e->h_out) (void)hipHostFree(e->h_out);
-  if (e->d_quality) (void)hipFree(e->d_quality);
-  if (e->h_quality) (void)hipHostFree(e->h_quality);
-  if (e->h_stage) (void)hipHostFree(e->h_stage);
-  if (e->stream) (void)hipStreamDestroy(e->stream);
-  delete e;
 }
 
 void mof_fft_destroy(mof_fft_engine* e) {
@@ -619,10 +576,7 @@ int mof_fft_graph_pinned(const mof_fft_engine* e) { return e && e->graph_pinned.
 
 int mof_purge_deferred(void) { return mof::purge_parked(); }
 int mof_deferred_count(void) { return mof::parked_count(); }
-
-static void pack_frame(uint8_t* dst, const uint8_t* src, size_t pitch, int w, int h) {
-  for (int y = 0; y < h; ++y) std::memcpy(dst + (size_t)y * w, src + (size_t)y * pitch, (size_t)w);
-}
+int mof_live_buffers(void) { return mof::g_live_buffers.load(); }
 
 static mof::PcArgs fft_args(const mof_fft_engine* e, const uint8_t* cur, size_t cs, const uint8_t* prev, size_t ps,
                             size_t pitch, double* out, double* quality) {
@@ -649,17 +603,7 @@ static mof::PcArgs fft_args(const mof_fft_engine* e, const uint8_t* cur, size_t 
   return a;
 }
 
-int mof_fft_set_prev(mof_fft_engine* e, const uint8_t* frame, size_t pitch) {
-  if (!e) return fail(MOF_ERR_NOT_INIT, "null engine");
-  if (!frame || pitch < (size_t)e->cfg.frame_width) return fail(MOF_ERR_BAD_ARG, "bad frame/pitch");
-  BusyGuard g(e->busy);
-  if (!g.owned) return fail(MOF_ERR_BUSY, "engine busy");
-  HIP_TRY(hipSetDevice(e->cfg.device));
-  pack_frame(e->h_stage, frame, pitch, e->cfg.frame_width, e->cfg.frame_height);
-  HIP_TRY(hipMemcpyAsync(e->d_frames[e->prev_slot], e->h_stage, e->frame_bytes, hipMemcpyHostToDevice, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  return MOF_OK;
-}
+int mof_fft_set_prev(mof_fft_engine* e, const uint8_t* frame, size_t pitch) { return set_prev(e, frame, pitch); }
 
 int mof_fft_reset(mof_fft_engine* e) {
   if (!e) return fail(MOF_ERR_NOT_INIT, "null engine");
@@ -703,11 +647,10 @@ static int fft_process_frame(mof_fft_engine* e, const uint8_t* frame, size_t pit
   if (!g.owned) return fail(MOF_ERR_BUSY, "engine busy");  // reference: returns an empty vector
   HIP_TRY(hipSetDevice(e->cfg.device));
   const int cur_slot = 1 - e->prev_slot;
-  pack_frame(e->h_stage, frame, pitch, e->cfg.frame_width, e->cfg.frame_height);
-  HIP_TRY(hipMemcpyAsync(e->d_frames[cur_slot], e->h_stage, e->frame_bytes, hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(upload_frame(e, cur_slot, frame, pitch));
   // `first`: the frame is correlated with itself (FftMethod.cpp:1791-1793, :1920-1922)
   const uint8_t* prev = e->first ? e->d_frames[cur_slot] : e->d_frames[e->prev_slot];
-  mof::PcArgs a = fft_args(e, e->d_frames[cur_slot], 0, prev, 0, (size_t)e->cfg.frame_width, e->d_out, quality ? e->d_quality : nullptr);
+  mof::PcArgs a = fft_args(e, e->d_frames[cur_slot], 0, prev, 0, (size_t)e->cfg.frame_width, e->d_out, quality ? e->d_quality.get() : nullptr);
   if (long_range) {
     int rc = long_range_args(e, &a);
     if (rc) return rc;
@@ -868,12 +811,12 @@ int mof_fft_process_batch_host_q(mof_fft_engine* e, const uint8_t* cur, size_t c
   const size_t res = (size_t)e->cfg.grid_x * e->cfg.grid_y * 2 * sizeof(double);
   {
     std::lock_guard<std::mutex> lock(e->host_mu);
-    if (!e->host_pipe) e->host_pipe = new mof::HostPipe(e->frame_bytes, &res, 1);
+    if (!e->host_pipe) e->host_pipe.reset(new mof::HostPipe(e->frame_bytes, &res, 1));
     const size_t res2[2] = {res, res};
-    if (quality && !e->host_pipe_q) e->host_pipe_q = new mof::HostPipe(e->frame_bytes, res2, 2);
+    if (quality && !e->host_pipe_q) e->host_pipe_q.reset(new mof::HostPipe(e->frame_bytes, res2, 2));
   }
   const mof::HostPipe::Out out[2] = {{out_xy, res}, {quality, res}};
-  mof::HostPipe* pipe = quality ? e->host_pipe_q : e->host_pipe;
+  mof::HostPipe* pipe = (quality ? e->host_pipe_q : e->host_pipe).get();
   hipError_t he = hipSuccess;
   // chunks of frames go up on the pipe's copy stream while the engine's stream runs the previous chunk through the DEVICE batch entry
   // (its kernels, its bits); a video -- cur = prev + one frame -- arrives as the two views of ONE uploaded run
@@ -990,62 +933,38 @@ static mof::BmArgs bm_args(const mof_bm_engine* e, const uint8_t* cur, size_t cs
   return a;
 }
 
-int mof_bm_create(const mof_bm_config* cfg, mof_bm_engine** out) {
-  if (!out) return fail(MOF_ERR_BAD_ARG, "null out");
-  *out = nullptr;
-  int rc = validate_bm(cfg);
-  if (rc) return rc;
-  rc = select_device(cfg->device);
-  if (rc) return rc;
-  mof::RelaxedCapture relaxed;
-  mof_bm_engine* e = new (std::nothrow) mof_bm_engine();
-  if (!e) return fail(MOF_ERR_NO_MEMORY, "out of host memory");
-  e->cfg = *cfg;
-  e->frame_bytes = (size_t)cfg->frame_width * cfg->frame_height;
-  const size_t nb = (size_t)cfg->grid_x * cfg->grid_y;
-#define CREATE_TRY(expr)                                                                        \
-  do {                                                                                          \
-    hipError_t _e = (expr);                                                                     \
-    if (_e != hipSuccess) {                                                                     \
-      fail(MOF_ERR_HIP, "%s: %s", #expr, hipGetErrorString(_e));                                \
-      mof_bm_destroy(e);                                                                        \
-      return MOF_ERR_HIP;                                                                       \
-    }                                                                                           \
-  } while (0)
-  CREATE_TRY(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
-  CREATE_TRY(hipMalloc(&e->d_frames[0], e->frame_bytes));
-  CREATE_TRY(hipMalloc(&e->d_frames[1], e->frame_bytes));
-  CREATE_TRY(mof::fill_on(e->stream, e->d_frames[0], 0, e->frame_bytes));  // imPrev = Scalar(0), BlockMethod.cpp:17-18
-  CREATE_TRY(mof::fill_on(e->stream, e->d_frames[1], 0, e->frame_bytes));
-  CREATE_TRY(hipMalloc(&e->d_dx, nb));
-  CREATE_TRY(hipMalloc(&e->d_dy, nb));
-  CREATE_TRY(hipMalloc(&e->d_mode, 8));
-  CREATE_TRY(hipHostMalloc(&e->h_res, 2 * nb + 8, hipHostMallocDefault));
-  CREATE_TRY(hipHostMalloc(&e->h_stage, e->frame_bytes, hipHostMallocDefault));
-#undef CREATE_TRY
-  *out = e;
-  return MOF_OK;
-}
-
 static void bm_destroy_now(void* p) {
   mof_bm_engine* e = static_cast<mof_bm_engine*>(p);
   mof::RelaxedCapture relaxed;
   (void)hipSetDevice(e->cfg.device);
   if (e->stream) (void)hipStreamSynchronize(e->stream);
-  delete e->host_pipe;
-  if (e->d_frames[0]) (void)hipFree(e->d_frames[0]);
-  if (e->d_frames[1]) (void)hipFree(e->d_frames[1]);
-  if (e->d_dx) (void)hipFree(e->d_dx);
-  if (e->d_dy) (void)hipFree(e->d_dy);
-  if (e->d_mode) (void)hipFree(e->d_mode);
-  if (e->h_res) (void)hipHostFree(e->h_res);
-  if (e->h_stage) (void)hipHostFree(e->h_stage);
-  if (e->d_up[0]) (void)hipFree(e->d_up[0]);
-  if (e->d_up[1]) (void)hipFree(e->d_up[1]);
-  if (e->d_sad9) (void)hipFree(e->d_sad9);
-  if (e->h_sad9) (void)hipHostFree(e->h_sad9);
-  if (e->stream) (void)hipStreamDestroy(e->stream);
   delete e;
+}
+struct BmDestroyNow {
+  void operator()(mof_bm_engine* e) const { bm_destroy_now(e); }
+};
+
+int mof_bm_create(const mof_bm_config* cfg, mof_bm_engine** out) {
+  if (!out) return fail(MOF_ERR_BAD_ARG, "null out");
+  *out = nullptr;
+  int rc = validate_bm(cfg);
+  if (rc) return rc;
+  rc = mof::select_device(cfg->device);
+  if (rc) return rc;
+  mof::RelaxedCapture relaxed;
+  std::unique_ptr<mof_bm_engine, BmDestroyNow> e(new (std::nothrow) mof_bm_engine());
+  if (!e) return fail(MOF_ERR_NO_MEMORY, "out of host memory");
+  e->cfg = *cfg;
+  e->frame_bytes = (size_t)cfg->frame_width * cfg->frame_height;
+  const size_t nb = (size_t)cfg->grid_x * cfg->grid_y;
+  HIP_TRY(e->stream.create());
+  for (auto& frame : e->d_frames) {
+    HIP_TRY(frame.alloc(e->frame_bytes));
+    HIP_TRY(mof::fill_on(e->stream, frame, 0, e->frame_bytes));  // imPrev = Scalar(0), BlockMethod.cpp:17-18
+  }
+  HIP_TRY(mof::alloc_all(e->d_dx, nb, e->d_dy, nb, e->d_mode, 8, e->h_res, 2 * nb + 8, e->h_stage, e->frame_bytes));
+  *out = e.release();
+  return MOF_OK;
 }
 
 void mof_bm_destroy(mof_bm_engine* e) {
@@ -1065,17 +984,7 @@ int mof_bm_release_graphs(mof_bm_engine* e) {
 
 int mof_bm_graph_pinned(const mof_bm_engine* e) { return e && e->graph_pinned.load() ? 1 : 0; }
 
-int mof_bm_set_prev(mof_bm_engine* e, const uint8_t* frame, size_t pitch) {
-  if (!e) return fail(MOF_ERR_NOT_INIT, "null engine");
-  if (!frame || pitch < (size_t)e->cfg.frame_width) return fail(MOF_ERR_BAD_ARG, "bad frame/pitch");
-  BusyGuard g(e->busy);
-  if (!g.owned) return fail(MOF_ERR_BUSY, "engine busy");
-  HIP_TRY(hipSetDevice(e->cfg.device));
-  pack_frame(e->h_stage, frame, pitch, e->cfg.frame_width, e->cfg.frame_height);
-  HIP_TRY(hipMemcpyAsync(e->d_frames[e->prev_slot], e->h_stage, e->frame_bytes, hipMemcpyHostToDevice, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  return MOF_OK;
-}
+int mof_bm_set_prev(mof_bm_engine* e, const uint8_t* frame, size_t pitch) { return set_prev(e, frame, pitch); }
 
 int mof_bm_reset(mof_bm_engine* e) {
   if (!e) return fail(MOF_ERR_NOT_INIT, "null engine");
@@ -1095,8 +1004,7 @@ int mof_bm_process(mof_bm_engine* e, const uint8_t* frame, size_t pitch, int8_t*
   HIP_TRY(hipSetDevice(e->cfg.device));
   const int cur_slot = 1 - e->prev_slot;
   const size_t nb = (size_t)e->cfg.grid_x * e->cfg.grid_y;
-  pack_frame(e->h_stage, frame, pitch, e->cfg.frame_width, e->cfg.frame_height);
-  HIP_TRY(hipMemcpyAsync(e->d_frames[cur_slot], e->h_stage, e->frame_bytes, hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(upload_frame(e, cur_slot, frame, pitch));
   mof::BmArgs a = bm_args(e, e->d_frames[cur_slot], 0, e->d_frames[e->prev_slot], 0, (size_t)e->cfg.frame_width,
                           e->d_dx, e->d_dy, e->d_mode);
   HIP_TRY(mof::launch_bm_scan(a, 1, e->stream));
@@ -1126,10 +1034,7 @@ int mof_bm_refine(mof_bm_engine* e, int fullpix_x, int fullpix_y, int passes, in
   const int w = e->cfg.frame_width, h = e->cfg.frame_height, W2 = 2 * w, H2 = 2 * h;
   if (!e->d_up[0]) {
     mof::RelaxedCapture relaxed;
-    HIP_TRY(hipMalloc(&e->d_up[0], (size_t)W2 * H2));
-    HIP_TRY(hipMalloc(&e->d_up[1], (size_t)W2 * H2));
-    HIP_TRY(hipMalloc(&e->d_sad9, 9 * sizeof(unsigned long long)));
-    HIP_TRY(hipHostMalloc(&e->h_sad9, 9 * sizeof(unsigned long long), hipHostMallocDefault));
+    HIP_TRY(mof::alloc_all(e->d_up[1], (size_t)W2 * H2, e->d_sad9, 9, e->h_sad9, 9, e->d_up[0], (size_t)W2 * H2));  // (d_up[0], the test above, last)
   }
   // after mof_bm_process the frame just processed sits in the "previous" slot, its predecessor in the other one
   const uint8_t* cur = e->d_frames[e->prev_slot];
@@ -1167,12 +1072,12 @@ int mof_bm_refine(mof_bm_engine* e, int fullpix_x, int fullpix_y, int passes, in
   return MOF_OK;
 }
 
-int mof_bm_process_batch_device(mof_bm_engine* e, const uint8_t* d_cur, size_t cur_stride, const uint8_t* d_prev,
-                                size_t prev_stride, size_t pitch, int n_pairs, int8_t* d_dx, int8_t* d_dy,
-                                int8_t* d_mode, void* stream) {
+// The device batch entries: n_pairs frame pairs of `channels` interleaved channels (1 gray, 3 BGR8)
+static int bm_batch(mof_bm_engine* e, const uint8_t* d_cur, size_t cur_stride, const uint8_t* d_prev, size_t prev_stride, size_t pitch,
+                    int n_pairs, int8_t* d_dx, int8_t* d_dy, int8_t* d_mode, void* stream, int channels) {
   if (!e) return fail(MOF_ERR_NOT_INIT, "null engine");
   if (n_pairs == 0) return MOF_OK;  // an empty batch carries no pointers to check
-  if (!d_cur || !d_prev || !d_dx || !d_dy || !d_mode || n_pairs < 0 || pitch < (size_t)e->cfg.frame_width)
+  if (!d_cur || !d_prev || !d_dx || !d_dy || !d_mode || n_pairs < 0 || pitch < (size_t)channels * (size_t)e->cfg.frame_width)
     return fail(MOF_ERR_BAD_ARG, "bad batch arguments");
   if ((unsigned long long)n_pairs * (unsigned long long)(e->cfg.grid_x * e->cfg.grid_y) > 0x7fffffffull)
     return fail(MOF_ERR_BAD_ARG, "batch too large for one launch");
@@ -1180,29 +1085,22 @@ int mof_bm_process_batch_device(mof_bm_engine* e, const uint8_t* d_cur, size_t c
   if (!g.owned) return fail(MOF_ERR_BUSY, "engine busy");
   HIP_TRY(hipSetDevice(e->cfg.device));
   hipStream_t s = (hipStream_t)stream;  // (a captured block-matching batch reads no engine-owned memory: no pin)
-  mof::BmArgs a = bm_args(e, d_cur, cur_stride, d_prev, prev_stride, pitch, d_dx, d_dy, d_mode);
+  mof::BmArgs a = bm_args(e, d_cur, cur_stride, d_prev, prev_stride, pitch, d_dx, d_dy, d_mode, channels);
   HIP_TRY(mof::launch_bm_scan(a, n_pairs, s));
   HIP_TRY(mof::launch_bm_mode(a, n_pairs, s));
   return MOF_OK;
 }
 
+int mof_bm_process_batch_device(mof_bm_engine* e, const uint8_t* d_cur, size_t cur_stride, const uint8_t* d_prev,
+                                size_t prev_stride, size_t pitch, int n_pairs, int8_t* d_dx, int8_t* d_dy,
+                                int8_t* d_mode, void* stream) {
+  return bm_batch(e, d_cur, cur_stride, d_prev, prev_stride, pitch, n_pairs, d_dx, d_dy, d_mode, stream, 1);
+}
+
 int mof_bm_process_batch_device_bgr(mof_bm_engine* e, const uint8_t* d_cur, size_t cur_stride, const uint8_t* d_prev,
                                     size_t prev_stride, size_t pitch, int n_pairs, int8_t* d_dx, int8_t* d_dy,
                                     int8_t* d_mode, void* stream) {
-  if (!e) return fail(MOF_ERR_NOT_INIT, "null engine");
-  if (n_pairs == 0) return MOF_OK;
-  if (!d_cur || !d_prev || !d_dx || !d_dy || !d_mode || n_pairs < 0 || pitch < 3 * (size_t)e->cfg.frame_width)
-    return fail(MOF_ERR_BAD_ARG, "bad batch arguments");
-  if ((unsigned long long)n_pairs * (unsigned long long)(e->cfg.grid_x * e->cfg.grid_y) > 0x7fffffffull)
-    return fail(MOF_ERR_BAD_ARG, "batch too large for one launch");
-  BusyGuard g(e->busy);
-  if (!g.owned) return fail(MOF_ERR_BUSY, "engine busy");
-  HIP_TRY(hipSetDevice(e->cfg.device));
-  hipStream_t s = (hipStream_t)stream;  // (a captured block-matching batch reads no engine-owned memory: no pin)
-  mof::BmArgs a = bm_args(e, d_cur, cur_stride, d_prev, prev_stride, pitch, d_dx, d_dy, d_mode, 3);
-  HIP_TRY(mof::launch_bm_scan(a, n_pairs, s));
-  HIP_TRY(mof::launch_bm_mode(a, n_pairs, s));
-  return MOF_OK;
+  return bm_batch(e, d_cur, cur_stride, d_prev, prev_stride, pitch, n_pairs, d_dx, d_dy, d_mode, stream, 3);
 }
 
 int mof_bm_process_batch_host(mof_bm_engine* e, const uint8_t* cur, size_t cur_stride, const uint8_t* prev,
@@ -1217,7 +1115,7 @@ int mof_bm_process_batch_host(mof_bm_engine* e, const uint8_t* cur, size_t cur_s
   const size_t bpp[3] = {nb, nb, 8};
   {
     std::lock_guard<std::mutex> lock(e->host_mu);
-    if (!e->host_pipe) e->host_pipe = new mof::HostPipe(e->frame_bytes, bpp, 3);
+    if (!e->host_pipe) e->host_pipe.reset(new mof::HostPipe(e->frame_bytes, bpp, 3));
   }
   const mof::HostPipe::Out outs[3] = {{dx, nb}, {dy, nb}, {mode, 8}};
   hipError_t he = hipSuccess;

@@ -7,11 +7,8 @@
 
 #include <cmath>
 
+#include "capi_graph.hpp"
 #include "mof_kernels.h"
-
-namespace mof {
-int capi_fail(int code, const char* fmt, ...);  // mof_capi.hip: records the thread's last error
-}
 
 namespace {
 
@@ -98,10 +95,8 @@ int mof_frontend_batch_device(const mof_frontend_config* cfg, const uint8_t* d_s
   if ((unsigned long long)cfg->crop_height * (unsigned long long)((cfg->crop_width + P - 1) / P) > (1ull << 31))
     return fail(MOF_ERR_BAD_ARG, "crop %d x %d is too large for one launch", cfg->crop_width, cfg->crop_height);
   int devices = 0;
-  if (hipGetDeviceCount(&devices) != hipSuccess || devices <= 0) {
-    (void)hipGetLastError();
-    return fail(MOF_ERR_NO_DEVICE, "no HIP device available (this library has no CPU fallback)");
-  }
+  rc = mof::require_device(&devices);  // (the stream's device is the caller's: nothing is selected here)
+  if (rc) return rc;
   mof::FeArgs a{};
   a.src = d_src;
   a.src_stride = src_stride;

@@ -24,6 +24,7 @@
 #include <new>
 #include <vector>
 
+#include "dev_mem.hpp"
 #include "mof.h"
 
 namespace mof {
@@ -98,7 +99,7 @@ struct ShardCore {
   int n_dev = 0;
   bool shared = false;            // some device carries more than one shard (rehearsal knob)
   std::vector<int> devices;
-  std::vector<hipStream_t> streams;
+  std::vector<mof::Stream> streams;
   std::vector<rcclComm_t> comms;  // empty until init_gather (communicators cost ~0.1 s and some device memory)
 
   int create(const int* devs, int n_devices) {
@@ -115,11 +116,11 @@ struct ShardCore {
           shared = true;
         }
       devices.push_back(d);
-      streams.push_back(nullptr);
+      streams.emplace_back();
     }
     for (int i = 0; i < n_devices; ++i) {
       hipError_t he = hipSetDevice(devices[i]);
-      if (he == hipSuccess) he = hipStreamCreateWithFlags(&streams[i], hipStreamNonBlocking);
+      if (he == hipSuccess) he = streams[i].create();
       if (he != hipSuccess) return mof::capi_fail(MOF_ERR_HIP, "stream on device %d: %s", devices[i], hipGetErrorString(he));
     }
     return MOF_OK;
@@ -200,7 +201,7 @@ struct ShardCore {
     for (int i = 0; i < (int)streams.size(); ++i)
       if (streams[i]) {
         (void)hipSetDevice(devices[i]);
-        (void)hipStreamDestroy(streams[i]);
+        streams[i].reset();
       }
   }
 };

@@ -16,6 +16,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <vector>
@@ -25,10 +26,6 @@
 #include "mof.h"
 #include "mof_kernels.h"
 #include "pc_launch.hpp"
-
-namespace mof {
-int capi_fail(int code, const char* fmt, ...);  // mof_capi.hip: records the thread's last error
-}
 
 namespace {
 
@@ -69,12 +66,6 @@ int chunk_pairs(int cfg_chunk) {
   return cfg_chunk >= 1 && cfg_chunk <= 4096 ? cfg_chunk : kChunkDefault;
 }
 bool two_lane_default(int cfg_lanes) { return sr_knobs().overlap >= 0 ? sr_knobs().overlap != 0 : cfg_lanes == 2; }
-
-#define SR_TRY(expr)                                                                                  \
-  do {                                                                                                \
-    hipError_t _e = (expr);                                                                           \
-    if (_e != hipSuccess) return mof::capi_fail(MOF_ERR_HIP, "%s: %s", #expr, hipGetErrorString(_e)); \
-  } while (0)
 
 void kernel_1d(int ksize, float x, float* c) {
   if (ksize == 4) {  // bicubic, A = -0.75
@@ -286,31 +277,42 @@ bool sr_route(int res, const SrKnobs& k, PcPlan* plan, SrRoute* r) {
 using mof::BusyGuard;
 using mof::SrRoute;
 
+// Member order is the teardown order in reverse (dev_mem.hpp): the streams and the events are declared before the buffers, the host
+// pipe last, so `delete e` -- after the waits of sr_destroy_now -- releases pipe, buffers, events, streams in that order.
 struct mof_sr_engine {
   mof_sr_config cfg{};
-  hipStream_t stream = nullptr;
-  mof::SrMapEntry* d_map = nullptr;
-  mof::SrTileBox* d_boxes[2] = {nullptr, nullptr};  // cubic, Lanczos4
+  mof::Stream stream;
+  // Two-lane batch pipeline: the log-polar remaps of chunk k+1 (bound by LDS / L1 latency, little HBM traffic) run on
+  // `remap_stream` while the transforms of chunk k (bound by HBM) run on the caller's stream; the log-polar images are
+  // double-buffered and handed over with events.
+  mof::Stream remap_stream;
+  mof::Event ev_fork;
+  mof::Event ev_lp[2];   // remaps of the chunk using buffer b are done
+  mof::Event ev_fft[2];  // transforms reading buffer b are done (it may be overwritten)
+  mof::ScratchFence fence;  // ordering of the engine-owned scratch (d_lp, d_Zt, d_Dt, d_cand, d_out) across streams
+  mof::DevMem<mof::SrMapEntry> d_map;
+  mof::DevMem<mof::SrTileBox> d_boxes[2];  // cubic, Lanczos4
   int lds_per_wave[2] = {0, 0};
-  int16_t* d_w_cubic = nullptr;
-  int16_t* d_w_lanczos = nullptr;
-  uint32_t* d_wp[2] = {nullptr, nullptr};  // byte planes of the two tables (cubic, Lanczos4)
-  mof::SrTileBox* d_sboxes[2] = {nullptr, nullptr};  // super-tile boxes (cubic, Lanczos4); null when res % 16 != 0
+  mof::DevMem<int16_t> d_w_cubic, d_w_lanczos;
+  mof::DevMem<uint32_t> d_wp[2];           // byte planes of the two tables (cubic, Lanczos4)
+  mof::DevMem<mof::SrTileBox> d_sboxes[2]; // super-tile boxes (cubic, Lanczos4); null when res % 16 != 0
   int sbox_dwords[2] = {0, 0};
-  float* d_twiddles = nullptr;
-  uint8_t* d_frame = nullptr;    // staging for the stateful path (res*res)
-  uint8_t* d_temp_im = nullptr;  // tempIm, :27
-  uint32_t* d_wfrag = nullptr;   // K56 (sr_fused_kernel.hip): f16 hi / lo fragments of the row-DFT matrix, tuned resolutions only
-  float* d_zh_prev = nullptr;    // prevIm_F32 (:48, :128), kept as what the correlation needs of it: its row half-spectra
-                                 // (sr_seq_kernel.hip, K5s) -- each frame is remapped and row-transformed ONCE
-  uint8_t* d_lp = nullptr;       // batch: [kChunk][2][res*res] log-polar images (cur, prev)
-  float *d_Zt = nullptr, *d_Dt = nullptr;
-  float2* d_cand = nullptr;
-  double* d_out = nullptr;       // [kChunk][4]
-  int* d_degen = nullptr;        // [kChunk]: K6 -> K8 flag of the pair pipeline (an all-zero log-polar image)
-  uint8_t* h_stage = nullptr;
-  double* h_out = nullptr;
-  double* h_seq = nullptr;       // pinned [chunk][4]: a pass's results, read back when a sequence call resolves the gate
+  mof::DevMem<float> d_twiddles;
+  mof::DevMem<uint8_t> d_frame;    // staging for the stateful path (res*res)
+  mof::DevMem<uint8_t> d_temp_im;  // tempIm, :27
+  mof::DevMem<uint32_t> d_wfrag;   // K56 (sr_fused_kernel.hip): f16 hi / lo fragments of the row-DFT matrix, tuned resolutions only
+  mof::DevMem<float> d_zh_prev;    // prevIm_F32 (:48, :128), kept as what the correlation needs of it: its row half-spectra
+                                   // (sr_seq_kernel.hip, K5s) -- each frame is remapped and row-transformed ONCE
+  // the pipeline scratch (scratch_alloc). A batch call captured into a HIP graph bakes raw pointers into it into the graph's kernel
+  // nodes, so from then on it neither grows nor is freed until mof_sr_release_graphs (capi_graph.hpp)
+  mof::DevMem<uint8_t> d_lp;       // batch: [kChunk][2][res*res] log-polar images (cur, prev)
+  mof::DevMem<float> d_Zt, d_Dt;
+  mof::DevMem<float2> d_cand;
+  mof::DevMem<double> d_out;       // [kChunk][4]
+  mof::DevMem<int> d_degen;        // [kChunk]: K6 -> K8 flag of the pair pipeline (an all-zero log-polar image)
+  mof::PinnedMem<uint8_t> h_stage;
+  mof::PinnedMem<double> h_out;
+  mof::PinnedMem<double> h_seq;    // [chunk][4]: a pass's results, read back when a sequence call resolves the gate
   int chunk = 0;                 // frame pairs per pipeline pass
   int scratch_pairs = 0;         // pairs per pass the scratch holds now (1 after create, `chunk` after the first batch)
   bool two_lanes = false;        // remap of pass k+1 beside the transforms of pass k (mof_sr_config.pipeline_lanes == 2)
@@ -318,19 +320,9 @@ struct mof_sr_engine {
   SrRoute route;                 // which transforms every launch runs (sr_route)
   mof::PcPlan plan{};            // route.family TUNED_PAD / PLANNED: the line plan of the padded size route.m
   std::atomic<bool> busy{false};
+  std::atomic<bool> graph_pinned{false};  // a batch call was captured into a HIP graph
   std::mutex host_mu;  // mof_sr_process_sequence_host: the upload pipeline (host_pipe.hpp), made by its first call
-  mof::HostPipe* host_pipe = nullptr;
-  // a batch call was captured into a HIP graph: the graph's kernel nodes hold raw pointers into the scratch below, so
-  // from then on the scratch neither grows nor is freed until mof_sr_release_graphs (capi_graph.hpp)
-  std::atomic<bool> graph_pinned{false};
-  mof::ScratchFence fence;  // ordering of the engine-owned scratch (d_lp, d_Zt, d_Dt, d_cand, d_out) across streams
-  // Two-lane batch pipeline: the log-polar remaps of chunk k+1 (bound by LDS / L1 latency, little HBM traffic) run on
-  // `remap_stream` while the transforms of chunk k (bound by HBM) run on the caller's stream; the log-polar images are
-  // double-buffered and handed over with events.
-  hipStream_t remap_stream = nullptr;
-  hipEvent_t ev_fork = nullptr;
-  hipEvent_t ev_lp[2] = {nullptr, nullptr};   // remaps of the chunk using buffer b are done
-  hipEvent_t ev_fft[2] = {nullptr, nullptr};  // transforms reading buffer b are done (it may be overwritten)
+  std::unique_ptr<mof::HostPipe> host_pipe;
 };
 
 namespace {
@@ -413,29 +405,16 @@ hipError_t peak(const mof_sr_engine* e, const mof::SrPcArgs& a, int n_pairs, hip
 // The pipeline scratch (log-polar images of two passes, Zt, Dt, peak candidates, results) for `pairs` pairs per pass.
 hipError_t scratch_alloc(mof_sr_engine* e, int pairs) {
   mof::RelaxedCapture relaxed;  // allocation / release must not invalidate a capture on another thread
-  const int res = e->cfg.resolution;
-  const size_t nn = (size_t)res * res;
-  void** bufs[] = {(void**)&e->d_lp, (void**)&e->d_Zt, (void**)&e->d_Dt, (void**)&e->d_cand, (void**)&e->d_out, (void**)&e->d_degen};
-  for (void** b : bufs) {
-    if (*b) (void)hipFree(*b);
-    *b = nullptr;
-  }
+  const size_t nn = (size_t)e->cfg.resolution * e->cfg.resolution, zhf = e->route.zh_floats, n = (size_t)pairs;
+  // d_Zt: the pair pipeline's packed row spectra, nn complex per pair; the sequence pipeline's (pairs + 1) frames of half spectra;
+  // pairs through the frame kernels: 2 * pairs frames of half spectra
+  const size_t zt = e->route.family == SrRoute::TUNED ? n * nn * 2 : 0, zh = (n + 1 > 2 * n ? n + 1 : 2 * n) * zhf;
   e->scratch_pairs = 0;
-  hipError_t err;
-  if ((err = hipMalloc(&e->d_lp, (size_t)2 * pairs * 2 * nn)) != hipSuccess) return err;  // two passes: remap of pass k+1 beside the transforms of pass k
-  {
-    // pair pipeline: packed row spectra Zt, nn complex per pair; sequence pipeline: (pairs + 1) frames of half spectra
-    // (or, pairs through the frame kernels: 2 * pairs frames of half spectra)
-    const size_t zhf = e->route.zh_floats, zt = e->route.family == SrRoute::TUNED ? (size_t)pairs * nn * 2 * sizeof(float) : 0,
-                 zh1 = (size_t)(pairs + 1) * zhf * sizeof(float), zh2 = (size_t)2 * pairs * zhf * sizeof(float), zh = zh1 > zh2 ? zh1 : zh2;
-    if ((err = hipMalloc(&e->d_Zt, zt > zh ? zt : zh)) != hipSuccess) return err;
-  }
-  if ((err = hipMalloc(&e->d_Dt, (size_t)pairs * e->route.zh_floats * sizeof(float))) != hipSuccess) return err;  // Dt has Zh's shape
-  if ((err = hipMalloc(&e->d_cand, (size_t)pairs * e->route.candidates * sizeof(float2))) != hipSuccess) return err;
-  if ((err = hipMalloc(&e->d_out, (size_t)pairs * 4 * sizeof(double))) != hipSuccess) return err;
-  if ((err = hipMalloc(&e->d_degen, (size_t)pairs * sizeof(int))) != hipSuccess) return err;
-  e->scratch_pairs = pairs;
-  return hipSuccess;
+  // d_lp holds two passes: remap of pass k+1 beside the transforms of pass k; Dt has Zh's shape
+  const hipError_t err = mof::alloc_all(e->d_lp, 2 * n * 2 * nn, e->d_Zt, zt > zh ? zt : zh, e->d_Dt, n * zhf, e->d_cand, n * e->route.candidates,
+                                        e->d_out, n * 4, e->d_degen, n);
+  if (err == hipSuccess) e->scratch_pairs = pairs;
+  return err;
 }
 
 // Pairs per pass a batch of n pairs needs: n rounded up to a power of two (growing batches re-allocate O(log) times),
@@ -450,25 +429,8 @@ int scratch_want(const mof_sr_engine* e, int n_pairs) {
 // being captured into a graph (run one batch, or mof_sr_reserve, before the capture), and only after every earlier
 // user of the scratch has finished. Returns a MOF status.
 int scratch_reserve(mof_sr_engine* e, int pairs, hipStream_t s) {
-  if (pairs <= e->scratch_pairs) return MOF_OK;
-  if (e->graph_pinned.load())
-    return mof::capi_fail(MOF_ERR_BUSY, "the estimator's scratch would have to grow from %d to %d pairs per pass, but a captured HIP graph "
-                                         "still points into it: reserve the largest batch before capturing, or call "
-                                         "mof_sr_release_graphs once the graphs are gone", e->scratch_pairs, pairs);
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(s, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone)
-    return mof::capi_fail(MOF_ERR_BAD_ARG, "the estimator's scratch must grow to %d pairs per pass, which cannot happen inside a graph capture: "
-                                            "call mof_sr_reserve (or run one batch) before capturing", pairs);
-  e->fence.wait_idle();
-  (void)hipStreamSynchronize(e->stream);
-  (void)hipStreamSynchronize(e->remap_stream);
-  const hipError_t err = scratch_alloc(e, pairs);
-  if (err != hipSuccess) {
-    (void)scratch_alloc(e, 1);  // keep the stateful entry usable
-    return mof::capi_fail(err == hipErrorOutOfMemory ? MOF_ERR_NO_MEMORY : MOF_ERR_HIP, "scale/rotation scratch for %d pairs: %s", pairs,
-                          hipGetErrorString(err));
-  }
-  return MOF_OK;
+  return mof::grow_scratch(e->graph_pinned.load(), e->fence, {e->stream, e->remap_stream}, mof::stream_capturing(s),
+                           "the estimator's scratch (pairs per pass)", e->scratch_pairs, pairs, 1, [e](long n) { return scratch_alloc(e, (int)n); });
 }
 
 }  // namespace
@@ -480,7 +442,7 @@ int mof_sr_reserve(mof_sr_engine* e, int n_pairs) {
   if (n_pairs < 0) return mof::capi_fail(MOF_ERR_BAD_ARG, "n_pairs must be >= 0");
   BusyGuard g(e->busy);
   if (!g.owned) return mof::capi_fail(MOF_ERR_BUSY, "engine busy");
-  if (hipSetDevice(e->cfg.device) != hipSuccess) return mof::capi_fail(MOF_ERR_HIP, "hipSetDevice failed");
+  HIP_TRY(hipSetDevice(e->cfg.device));
   return scratch_reserve(e, scratch_want(e, n_pairs), e->stream);
 }
 
@@ -489,23 +451,13 @@ static void sr_destroy_now(void* p) {
   mof::RelaxedCapture relaxed;
   (void)hipSetDevice(e->cfg.device);
   if (e->stream) (void)hipStreamSynchronize(e->stream);
-  e->fence.wait_idle();
-  delete e->host_pipe;
-  void* dev[] = {e->d_boxes[0], e->d_boxes[1], e->d_sboxes[0], e->d_sboxes[1], e->d_map, e->d_w_cubic, e->d_w_lanczos, e->d_wp[0], e->d_wp[1], e->d_twiddles, e->d_frame, e->d_temp_im, e->d_zh_prev, e->d_wfrag,
-                 e->d_lp,  e->d_Zt,      e->d_Dt,        e->d_cand,     e->d_out, e->d_degen};
-  for (void* p : dev)
-    if (p) (void)hipFree(p);
-  if (e->h_stage) (void)hipHostFree(e->h_stage);
-  if (e->h_out) (void)hipHostFree(e->h_out);
-  if (e->h_seq) (void)hipHostFree(e->h_seq);
-  e->fence.destroy();
   if (e->remap_stream) (void)hipStreamSynchronize(e->remap_stream);
-  for (hipEvent_t ev : {e->ev_fork, e->ev_lp[0], e->ev_lp[1], e->ev_fft[0], e->ev_fft[1]})
-    if (ev) (void)hipEventDestroy(ev);
-  if (e->remap_stream) (void)hipStreamDestroy(e->remap_stream);
-  if (e->stream) (void)hipStreamDestroy(e->stream);
+  e->fence.wait_idle();
   delete e;
 }
+struct SrDestroyNow {
+  void operator()(mof_sr_engine* e) const { sr_destroy_now(e); }
+};
 
 void mof_sr_destroy(mof_sr_engine* e) {
   if (!e) return;
@@ -540,13 +492,10 @@ int mof_sr_create(const mof_sr_config* cfg, mof_sr_engine** out) try {
   if (!mof::sr_route(cfg->resolution, sr_knobs(), &plan, &route))
     return mof::capi_fail(MOF_ERR_UNSUPPORTED, "resolution %d pads to %d: beyond the planned transforms (<= 960)", cfg->resolution,
                           mof::pc_optimal_dft_size(cfg->resolution));
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-    (void)hipGetLastError();
-    return mof::capi_fail(MOF_ERR_NO_DEVICE, "no HIP device available (this library has no CPU fallback)");
+  {
+    const int rc = mof::select_device(cfg->device);
+    if (rc) return rc;
   }
-  if (cfg->device < 0 || cfg->device >= ndev) return mof::capi_fail(MOF_ERR_BAD_ARG, "device %d out of range", cfg->device);
-  SR_TRY(hipSetDevice(cfg->device));
   mof::RelaxedCapture relaxed;  // allocating an engine must not invalidate a capture on another thread
   const int res = cfg->resolution;
   const size_t nn = (size_t)res * res;
@@ -562,78 +511,48 @@ int mof_sr_create(const mof_sr_config* cfg, mof_sr_engine** out) try {
     sbl = mof::sr_tile_boxes(map, res, 8, &slds_l, 16);
   }
   const std::vector<float> tw = mof::twiddle_table(route.m);
-  mof_sr_engine* e = new (std::nothrow) mof_sr_engine();
+  std::unique_ptr<mof_sr_engine, SrDestroyNow> e(new (std::nothrow) mof_sr_engine());  // every early return tears down what exists
   if (!e) return mof::capi_fail(MOF_ERR_NO_MEMORY, "out of host memory");
   e->cfg = *cfg;
   e->route = route;
   e->plan = plan;
   e->chunk = chunk_pairs(cfg->batch_chunk);
   e->two_lanes = two_lane_default(cfg->pipeline_lanes);
-#define CREATE_TRY(expr)                                                                  \
-  do {                                                                                    \
-    hipError_t _e = (expr);                                                               \
-    if (_e != hipSuccess) {                                                               \
-      mof::capi_fail(MOF_ERR_HIP, "%s: %s", #expr, hipGetErrorString(_e));                \
-      mof_sr_destroy(e);                                                                  \
-      return MOF_ERR_HIP;                                                                 \
-    }                                                                                     \
-  } while (0)
-  CREATE_TRY(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
-  CREATE_TRY(e->fence.create());
-  CREATE_TRY(hipStreamCreateWithFlags(&e->remap_stream, hipStreamNonBlocking));
-  CREATE_TRY(hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming));
+  HIP_TRY(e->stream.create());
+  HIP_TRY(e->fence.create());
+  HIP_TRY(e->remap_stream.create());
+  HIP_TRY(e->ev_fork.create());
   for (int b = 0; b < 2; ++b) {
-    CREATE_TRY(hipEventCreateWithFlags(&e->ev_lp[b], hipEventDisableTiming));
-    CREATE_TRY(hipEventCreateWithFlags(&e->ev_fft[b], hipEventDisableTiming));
+    HIP_TRY(e->ev_lp[b].create());
+    HIP_TRY(e->ev_fft[b].create());
   }
-  CREATE_TRY(hipMalloc(&e->d_map, map.size() * sizeof(mof::SrMapEntry)));
-  CREATE_TRY(mof::copy_on(e->stream, e->d_map, map.data(), map.size() * sizeof(mof::SrMapEntry), hipMemcpyHostToDevice));
+  HIP_TRY(mof::upload(e->d_map, map, e->stream));
   e->lds_per_wave[0] = lds_c;
   e->lds_per_wave[1] = lds_l;
-  CREATE_TRY(hipMalloc(&e->d_boxes[0], bc.size() * sizeof(mof::SrTileBox)));
-  CREATE_TRY(mof::copy_on(e->stream, e->d_boxes[0], bc.data(), bc.size() * sizeof(mof::SrTileBox), hipMemcpyHostToDevice));
-  CREATE_TRY(hipMalloc(&e->d_boxes[1], bl.size() * sizeof(mof::SrTileBox)));
-  CREATE_TRY(mof::copy_on(e->stream, e->d_boxes[1], bl.data(), bl.size() * sizeof(mof::SrTileBox), hipMemcpyHostToDevice));
+  HIP_TRY(mof::upload(e->d_boxes[0], bc, e->stream));
+  HIP_TRY(mof::upload(e->d_boxes[1], bl, e->stream));
   if (!sbc.empty()) {
     e->sbox_dwords[0] = slds_c / 4;
     e->sbox_dwords[1] = slds_l / 4;
     if (sr_knobs().verbose)  // diagnostics: the staged remap's largest boxes (dwords)
       fprintf(stderr, "mof_sr: res %d: largest super-tile box cubic %d, lanczos4 %d dwords; per-wave boxes %d / %d bytes\n", res, e->sbox_dwords[0],
               e->sbox_dwords[1], lds_c, lds_l);
-    CREATE_TRY(hipMalloc(&e->d_sboxes[0], sbc.size() * sizeof(mof::SrTileBox)));
-    CREATE_TRY(mof::copy_on(e->stream, e->d_sboxes[0], sbc.data(), sbc.size() * sizeof(mof::SrTileBox), hipMemcpyHostToDevice));
-    CREATE_TRY(hipMalloc(&e->d_sboxes[1], sbl.size() * sizeof(mof::SrTileBox)));
-    CREATE_TRY(mof::copy_on(e->stream, e->d_sboxes[1], sbl.data(), sbl.size() * sizeof(mof::SrTileBox), hipMemcpyHostToDevice));
+    HIP_TRY(mof::upload(e->d_sboxes[0], sbc, e->stream));
+    HIP_TRY(mof::upload(e->d_sboxes[1], sbl, e->stream));
   }
-  CREATE_TRY(hipMalloc(&e->d_w_cubic, wc.size() * sizeof(int16_t)));
-  CREATE_TRY(mof::copy_on(e->stream, e->d_w_cubic, wc.data(), wc.size() * sizeof(int16_t), hipMemcpyHostToDevice));
-  CREATE_TRY(hipMalloc(&e->d_w_lanczos, wl.size() * sizeof(int16_t)));
-  CREATE_TRY(mof::copy_on(e->stream, e->d_w_lanczos, wl.data(), wl.size() * sizeof(int16_t), hipMemcpyHostToDevice));
-  {
-    const std::vector<uint32_t> pc = mof::sr_weight_planes(wc, 4), pl = mof::sr_weight_planes(wl, 8);
-    CREATE_TRY(hipMalloc(&e->d_wp[0], pc.size() * sizeof(uint32_t)));
-    CREATE_TRY(mof::copy_on(e->stream, e->d_wp[0], pc.data(), pc.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    CREATE_TRY(hipMalloc(&e->d_wp[1], pl.size() * sizeof(uint32_t)));
-    CREATE_TRY(mof::copy_on(e->stream, e->d_wp[1], pl.data(), pl.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-  }
-  CREATE_TRY(hipMalloc(&e->d_twiddles, tw.size() * sizeof(float)));
-  CREATE_TRY(mof::copy_on(e->stream, e->d_twiddles, tw.data(), tw.size() * sizeof(float), hipMemcpyHostToDevice));
-  if (route.pairs == SrRoute::FUSED) {  // (1 MB of f16 matrix fragments at 480: only for the opt-in path)
-    const std::vector<uint32_t> fr = mof::sr_fused_fragments(res);
-    CREATE_TRY(hipMalloc(&e->d_wfrag, fr.size() * sizeof(uint32_t)));
-    CREATE_TRY(mof::copy_on(e->stream, e->d_wfrag, fr.data(), fr.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-  }
-  CREATE_TRY(hipMalloc(&e->d_frame, nn));
-  CREATE_TRY(hipMalloc(&e->d_temp_im, nn));
-  CREATE_TRY(hipMalloc(&e->d_zh_prev, route.zh_floats * sizeof(float)));
-  CREATE_TRY(mof::fill_on(e->stream, e->d_temp_im, 0, nn));  // tempIm = cv::Mat::zeros, :27
-  CREATE_TRY(mof::fill_on(e->stream, e->d_zh_prev, 0, route.zh_floats * sizeof(float)));
-  CREATE_TRY(scratch_alloc(e, 1));  // the stateful call needs one pair; a batch grows it to a whole pass (scratch_reserve)
-  CREATE_TRY(hipHostMalloc(&e->h_stage, nn, hipHostMallocDefault));
-  CREATE_TRY(hipHostMalloc(&e->h_out, 4 * sizeof(double), hipHostMallocDefault));
-  CREATE_TRY(hipHostMalloc(&e->h_seq, (size_t)e->chunk * 4 * sizeof(double), hipHostMallocDefault));
-#undef CREATE_TRY
-  *out = e;
+  HIP_TRY(mof::upload(e->d_w_cubic, wc, e->stream));
+  HIP_TRY(mof::upload(e->d_w_lanczos, wl, e->stream));
+  HIP_TRY(mof::upload(e->d_wp[0], mof::sr_weight_planes(wc, 4), e->stream));
+  HIP_TRY(mof::upload(e->d_wp[1], mof::sr_weight_planes(wl, 8), e->stream));
+  HIP_TRY(mof::upload(e->d_twiddles, tw, e->stream));
+  if (route.pairs == SrRoute::FUSED)  // (1 MB of f16 matrix fragments at 480: only for the opt-in path)
+    HIP_TRY(mof::upload(e->d_wfrag, mof::sr_fused_fragments(res), e->stream));
+  HIP_TRY(mof::alloc_all(e->d_frame, nn, e->d_temp_im, nn, e->d_zh_prev, route.zh_floats));
+  HIP_TRY(mof::fill_on(e->stream, e->d_temp_im, 0, nn));  // tempIm = cv::Mat::zeros, :27
+  HIP_TRY(mof::fill_on(e->stream, e->d_zh_prev, 0, route.zh_floats * sizeof(float)));
+  HIP_TRY(scratch_alloc(e.get(), 1));  // the stateful call needs one pair; a batch grows it to a whole pass (scratch_reserve)
+  HIP_TRY(mof::alloc_all(e->h_stage, nn, e->h_out, 4, e->h_seq, (size_t)e->chunk * 4));
+  *out = e.release();
   return MOF_OK;
 } catch (const std::bad_alloc&) {
   return mof::capi_fail(MOF_ERR_NO_MEMORY, "mof_sr_create: out of host memory");
@@ -643,9 +562,9 @@ int mof_sr_reset(mof_sr_engine* e) {
   if (!e) return mof::capi_fail(MOF_ERR_NOT_INIT, "null engine");
   BusyGuard g(e->busy);
   if (!g.owned) return mof::capi_fail(MOF_ERR_BUSY, "engine busy");
-  SR_TRY(hipSetDevice(e->cfg.device));
-  SR_TRY(hipMemsetAsync(e->d_temp_im, 0, (size_t)e->cfg.resolution * e->cfg.resolution, e->stream));
-  SR_TRY(hipStreamSynchronize(e->stream));
+  HIP_TRY(hipSetDevice(e->cfg.device));
+  HIP_TRY(hipMemsetAsync(e->d_temp_im, 0, (size_t)e->cfg.resolution * e->cfg.resolution, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
   e->first = true;
   return MOF_OK;
 }
@@ -691,10 +610,10 @@ int mof_sr_process(mof_sr_engine* e, const uint8_t* frame, size_t pitch, double*
   if (!frame || !out_scale_rot || pitch < (size_t)res) return mof::capi_fail(MOF_ERR_BAD_ARG, "bad frame/pitch/out");
   BusyGuard g(e->busy);
   if (!g.owned) return mof::capi_fail(MOF_ERR_BUSY, "engine busy");
-  SR_TRY(hipSetDevice(e->cfg.device));
+  HIP_TRY(hipSetDevice(e->cfg.device));
   const size_t nn = (size_t)res * res, zh_bytes = e->route.zh_floats * sizeof(float);
   for (int y = 0; y < res; ++y) std::memcpy(e->h_stage + (size_t)y * res, frame + (size_t)y * pitch, (size_t)res);
-  SR_TRY(hipMemcpyAsync(e->d_frame, e->h_stage, nn, hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemcpyAsync(e->d_frame, e->h_stage, nn, hipMemcpyHostToDevice, e->stream));
   mof::SrLpArgs lp{};
   lp.src = e->d_frame;
   lp.src_stride = 0;
@@ -705,29 +624,29 @@ int mof_sr_process(mof_sr_engine* e, const uint8_t* frame, size_t pitch, double*
   lp.res = res;
   const int interp = e->first ? 2 : 4;  // INTER_CUBIC for the very first frame (:45), INTER_LANCZOS4 from then on (:112)
   lp_tables(e, interp, &lp);
-  SR_TRY(mof::launch_sr_logpolar(lp, interp, 1, e->stream));
-  SR_TRY(e->fence.acquire(e->stream));
+  HIP_TRY(mof::launch_sr_logpolar(lp, interp, 1, e->stream));
+  HIP_TRY(e->fence.acquire(e->stream));
   // tempIm.convertTo(CV_32FC1) (:47, :115) + the row half of the forward DFT of cv::phaseCorrelate (:117): K5s
-  SR_TRY(rows_real(e, e->d_temp_im, 0, e->d_Zt, 0, 1, e->stream));
+  HIP_TRY(rows_real(e, e->d_temp_im, 0, e->d_Zt, 0, 1, e->stream));
   if (e->first) {
-    SR_TRY(hipMemcpyAsync(e->d_zh_prev, e->d_Zt, zh_bytes, hipMemcpyDeviceToDevice, e->stream));  // prevIm_F32 = .., :48
-    SR_TRY(e->fence.release(e->stream));
-    SR_TRY(hipStreamSynchronize(e->stream));
+    HIP_TRY(hipMemcpyAsync(e->d_zh_prev, e->d_Zt, zh_bytes, hipMemcpyDeviceToDevice, e->stream));  // prevIm_F32 = .., :48
+    HIP_TRY(e->fence.release(e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
     e->first = false;  // :73
     out_scale_rot[0] = 1.0;
     out_scale_rot[1] = 0.0;  // :74
     return MOF_OK;
   }
-  SR_TRY(seq_one_pair(e, e->d_zh_prev, e->d_Zt, e->d_out, e->stream));  // :117
-  SR_TRY(hipMemcpyAsync(e->h_out, e->d_out, 4 * sizeof(double), hipMemcpyDeviceToHost, e->stream));
-  SR_TRY(hipStreamSynchronize(e->stream));
+  HIP_TRY(seq_one_pair(e, e->d_zh_prev, e->d_Zt, e->d_out, e->stream));  // :117
+  HIP_TRY(hipMemcpyAsync(e->h_out, e->d_out, 4 * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
   out_scale_rot[0] = e->h_out[0];
   out_scale_rot[1] = e->h_out[1];
   // the reference returns early on the gate, BEFORE prevIm_F32 = tempIm_F32.clone() (:119-121 vs :128)
   if (!(std::fabs(e->h_out[2]) > (double)(res / 2)))
-    SR_TRY(hipMemcpyAsync(e->d_zh_prev, e->d_Zt, zh_bytes, hipMemcpyDeviceToDevice, e->stream));
-  SR_TRY(e->fence.release(e->stream));
-  SR_TRY(hipStreamSynchronize(e->stream));
+    HIP_TRY(hipMemcpyAsync(e->d_zh_prev, e->d_Zt, zh_bytes, hipMemcpyDeviceToDevice, e->stream));
+  HIP_TRY(e->fence.release(e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
   return MOF_OK;
 }
 
@@ -742,7 +661,7 @@ int mof_sr_process_sequence_device(mof_sr_engine* e, const uint8_t* d_frames, si
   if (!d_frames || !d_out || n_frames < 0 || pitch < (size_t)res) return mof::capi_fail(MOF_ERR_BAD_ARG, "bad sequence arguments");
   BusyGuard g(e->busy);
   if (!g.owned) return mof::capi_fail(MOF_ERR_BUSY, "engine busy");
-  SR_TRY(hipSetDevice(e->cfg.device));
+  HIP_TRY(hipSetDevice(e->cfg.device));
   hipStream_t s = (hipStream_t)stream;
   const bool capturing = mof::stream_capturing(s);
   if (capturing && n_gated)
@@ -757,7 +676,7 @@ int mof_sr_process_sequence_device(mof_sr_engine* e, const uint8_t* d_frames, si
   if (capturing && e->first)
     return mof::capi_fail(MOF_ERR_BAD_ARG, "capturing a sequence on a fresh estimator would bake its one-off first-frame branch "
                                             "(INTER_CUBIC, scaleRotationEstimator.cpp:45) into the graph: process one frame first");
-  SR_TRY(e->fence.acquire(s));
+  HIP_TRY(e->fence.acquire(s));
   if (capturing) e->graph_pinned.store(true);
   const int C = e->scratch_pairs < e->chunk ? e->scratch_pairs : e->chunk;  // new frames per pass
   float* zh = e->d_Zt;
@@ -781,15 +700,15 @@ int mof_sr_process_sequence_device(mof_sr_engine* e, const uint8_t* d_frames, si
         lp.src = d_frames + (size_t)done * frame_stride;
         lp.dst = e->d_lp;
         lp_tables(e, 2, &lp);
-        SR_TRY(mof::launch_sr_logpolar(lp, 2, 1, s));
-        SR_TRY(rows_real(e, e->d_lp, nn, zh, zhf, 1, s));
-        SR_TRY(mof::launch_sr_identity(d_out + 4 * (size_t)done, s));
+        HIP_TRY(mof::launch_sr_logpolar(lp, 2, 1, s));
+        HIP_TRY(rows_real(e, e->d_lp, nn, zh, zhf, 1, s));
+        HIP_TRY(mof::launch_sr_identity(d_out + 4 * (size_t)done, s));
         first = false;  // :73
         ++done;
       } else if (carry < 0) {
-        SR_TRY(hipMemcpyAsync(zh, e->d_zh_prev, zh_bytes, hipMemcpyDeviceToDevice, s));
+        HIP_TRY(hipMemcpyAsync(zh, e->d_zh_prev, zh_bytes, hipMemcpyDeviceToDevice, s));
       } else if (carry > 0) {
-        SR_TRY(hipMemcpyAsync(zh, zh + (size_t)carry * zhf, zh_bytes, hipMemcpyDeviceToDevice, s));
+        HIP_TRY(hipMemcpyAsync(zh, zh + (size_t)carry * zhf, zh_bytes, hipMemcpyDeviceToDevice, s));
       }
       const int m = n_frames - done < C ? n_frames - done : C;
       carry = 0;
@@ -797,26 +716,26 @@ int mof_sr_process_sequence_device(mof_sr_engine* e, const uint8_t* d_frames, si
         lp.src = d_frames + (size_t)done * frame_stride;
         lp.dst = e->d_lp + nn;
         lp_tables(e, 4, &lp);
-        SR_TRY(mof::launch_sr_logpolar(lp, 4, m, s));  // INTER_LANCZOS4, :112 -- every frame once
-        SR_TRY(rows_real(e, e->d_lp + nn, nn, zh + zhf, zhf, m, s));
-        SR_TRY(cols_seq(e, zh, zh + zhf, zhf, m, seq_run_for(e, m), s));
+        HIP_TRY(mof::launch_sr_logpolar(lp, 4, m, s));  // INTER_LANCZOS4, :112 -- every frame once
+        HIP_TRY(rows_real(e, e->d_lp + nn, nn, zh + zhf, zhf, m, s));
+        HIP_TRY(cols_seq(e, zh, zh + zhf, zhf, m, seq_run_for(e, m), s));
         mof::SrPcArgs a = pc_args(e, nullptr, nullptr, 0, d_out + 4 * (size_t)done);
-        SR_TRY(peak(e, a, m, s));
+        HIP_TRY(peak(e, a, m, s));
         carry = m;
         if (n_gated) {
           // The gate (:119-121): a frame whose |pt.x| > res/2 returns (1, 0) and does NOT become prev. The pass above
           // correlated every frame with its immediate predecessor; behind a gated frame that is the wrong partner, so
           // walk the results in order and redo the (rare) pairs whose reference partner is an older frame.
-          SR_TRY(hipMemcpyAsync(e->h_seq, d_out + 4 * (size_t)done, (size_t)m * 4 * sizeof(double), hipMemcpyDeviceToHost, s));
-          SR_TRY(hipStreamSynchronize(s));
+          HIP_TRY(hipMemcpyAsync(e->h_seq, d_out + 4 * (size_t)done, (size_t)m * 4 * sizeof(double), hipMemcpyDeviceToHost, s));
+          HIP_TRY(hipStreamSynchronize(s));
           int prev_slot = 0;
           for (int i = 1; i <= m; ++i) {
             double ptx = e->h_seq[4 * (size_t)(i - 1) + 2];
             if (prev_slot != i - 1) {
               double* o = d_out + 4 * (size_t)(done + i - 1);
-              SR_TRY(seq_one_pair(e, zh + (size_t)prev_slot * zhf, zh + (size_t)i * zhf, o, s));
-              SR_TRY(hipMemcpyAsync(e->h_out, o, 4 * sizeof(double), hipMemcpyDeviceToHost, s));
-              SR_TRY(hipStreamSynchronize(s));
+              HIP_TRY(seq_one_pair(e, zh + (size_t)prev_slot * zhf, zh + (size_t)i * zhf, o, s));
+              HIP_TRY(hipMemcpyAsync(e->h_out, o, 4 * sizeof(double), hipMemcpyDeviceToHost, s));
+              HIP_TRY(hipStreamSynchronize(s));
               ptx = e->h_out[2];
             }
             if (std::fabs(ptx) > (double)(res / 2)) ++gated_total;
@@ -828,7 +747,7 @@ int mof_sr_process_sequence_device(mof_sr_engine* e, const uint8_t* d_frames, si
       }
     }
     // prevIm_F32 <- the last frame that passed the gate (:128)
-    if (carry >= 0) SR_TRY(hipMemcpyAsync(e->d_zh_prev, zh + (size_t)carry * zhf, zh_bytes, hipMemcpyDeviceToDevice, s));
+    if (carry >= 0) HIP_TRY(hipMemcpyAsync(e->d_zh_prev, zh + (size_t)carry * zhf, zh_bytes, hipMemcpyDeviceToDevice, s));
     return MOF_OK;
   }();
   if (rc != MOF_OK) {
@@ -836,9 +755,9 @@ int mof_sr_process_sequence_device(mof_sr_engine* e, const uint8_t* d_frames, si
     return rc;
   }
   e->first = first;
-  SR_TRY(e->fence.release(s));
+  HIP_TRY(e->fence.release(s));
   if (n_gated) {
-    SR_TRY(hipStreamSynchronize(s));
+    HIP_TRY(hipStreamSynchronize(s));
     *n_gated = gated_total;
   }
   return MOF_OK;
@@ -851,12 +770,12 @@ int mof_sr_process_sequence_host(mof_sr_engine* e, const uint8_t* frames, size_t
   if (n_frames == 0) return MOF_OK;
   const int res = e->cfg.resolution;
   if (!frames || !out || n_frames < 0 || pitch < (size_t)res) return mof::capi_fail(MOF_ERR_BAD_ARG, "bad video arguments");
-  SR_TRY(hipSetDevice(e->cfg.device));
+  HIP_TRY(hipSetDevice(e->cfg.device));
   mof::RelaxedCapture relaxed;
   const size_t bpp = 4 * sizeof(double);
   {
     std::lock_guard<std::mutex> lock(e->host_mu);
-    if (!e->host_pipe) e->host_pipe = new mof::HostPipe((size_t)res * res, &bpp, 1);
+    if (!e->host_pipe) e->host_pipe.reset(new mof::HostPipe((size_t)res * res, &bpp, 1));
   }
   const mof::HostPipe::Out o{out, bpp};
   hipError_t he = hipSuccess;
@@ -887,14 +806,14 @@ int mof_sr_process_batch_device(mof_sr_engine* e, const uint8_t* d_cur, size_t c
   if (!d_cur || !d_prev || !d_out || n_pairs < 0 || pitch < (size_t)res) return mof::capi_fail(MOF_ERR_BAD_ARG, "bad batch arguments");
   BusyGuard g(e->busy);
   if (!g.owned) return mof::capi_fail(MOF_ERR_BUSY, "engine busy");
-  SR_TRY(hipSetDevice(e->cfg.device));
+  HIP_TRY(hipSetDevice(e->cfg.device));
   hipStream_t s = (hipStream_t)stream;
   const size_t nn = (size_t)res * res;
   {
     const int rc = scratch_reserve(e, scratch_want(e, n_pairs), s);
     if (rc != MOF_OK) return rc;
   }
-  SR_TRY(e->fence.acquire(s));
+  HIP_TRY(e->fence.acquire(s));
   if (mof::stream_capturing(s)) e->graph_pinned.store(true);
   const int kChunk = e->chunk;
   // Under graph capture the fork / join below pulls the engine's stream into the caller's capture (event record on the
@@ -902,8 +821,8 @@ int mof_sr_process_batch_device(mof_sr_engine* e, const uint8_t* d_cur, size_t c
   const bool two_lanes = e->two_lanes && n_pairs > kChunk;
   hipStream_t sr = two_lanes ? e->remap_stream : s;
   if (two_lanes) {  // fork: the remap lane starts behind whatever the caller's stream holds (also under graph capture)
-    SR_TRY(hipEventRecord(e->ev_fork, s));
-    SR_TRY(hipStreamWaitEvent(sr, e->ev_fork, 0));
+    HIP_TRY(hipEventRecord(e->ev_fork, s));
+    HIP_TRY(hipStreamWaitEvent(sr, e->ev_fork, 0));
   }
   int chunk_no = 0;
   for (int k0 = 0; k0 < n_pairs; k0 += kChunk, ++chunk_no) {
@@ -913,7 +832,7 @@ int mof_sr_process_batch_device(mof_sr_engine* e, const uint8_t* d_cur, size_t c
     // every pair is the two-call sequence of a fresh estimator: prev -> INTER_CUBIC (:45), cur -> INTER_LANCZOS4
     // (:112) onto the same zero-initialised tempIm; the transparent pixels are the same for both maps, so both
     // remaps simply write zeros there (zero_invalid) and the scratch needs no clearing pass
-    if (two_lanes && chunk_no >= 2) SR_TRY(hipStreamWaitEvent(sr, e->ev_fft[b], 0));  // buffer b is free again
+    if (two_lanes && chunk_no >= 2) HIP_TRY(hipStreamWaitEvent(sr, e->ev_fft[b], 0));  // buffer b is free again
     mof::SrLpArgs lp{};
     lp.zero_invalid = 1;
     lp.pitch = pitch;
@@ -924,33 +843,33 @@ int mof_sr_process_batch_device(mof_sr_engine* e, const uint8_t* d_cur, size_t c
     lp.src_stride = prev_stride;
     lp.dst = lp_buf + nn;
     lp_tables(e, 2, &lp);
-    SR_TRY(mof::launch_sr_logpolar(lp, 2, n, sr));
+    HIP_TRY(mof::launch_sr_logpolar(lp, 2, n, sr));
     lp.src = d_cur + (size_t)k0 * cur_stride;
     lp.src_stride = cur_stride;
     lp.dst = lp_buf;
     lp_tables(e, 4, &lp);
-    SR_TRY(mof::launch_sr_logpolar(lp, 4, n, sr));
+    HIP_TRY(mof::launch_sr_logpolar(lp, 4, n, sr));
     if (two_lanes) {
-      SR_TRY(hipEventRecord(e->ev_lp[b], sr));
-      SR_TRY(hipStreamWaitEvent(s, e->ev_lp[b], 0));  // also the join: every remap precedes a wait on the caller's stream
+      HIP_TRY(hipEventRecord(e->ev_lp[b], sr));
+      HIP_TRY(hipStreamWaitEvent(s, e->ev_lp[b], 0));  // also the join: every remap precedes a wait on the caller's stream
     }
     mof::SrPcArgs a = pc_args(e, lp_buf, lp_buf + nn, 2 * nn, d_out + 4 * (size_t)k0);
     if (e->route.pairs == SrRoute::PACKED) {
       a.degen = e->d_degen;
-      SR_TRY(mof::launch_sr_phase_correlate(a, res, n, s));
+      HIP_TRY(mof::launch_sr_phase_correlate(a, res, n, s));
     } else {
       const size_t zhf = e->route.zh_floats;
       if (e->route.pairs == SrRoute::FUSED) {
-        SR_TRY(cols_fused(e, lp_buf + nn, lp_buf, 2 * nn, n, 1, s));
+        HIP_TRY(cols_fused(e, lp_buf + nn, lp_buf, 2 * nn, n, 1, s));
       } else {  // the frame kernels: image 2p = cur of pair p, 2p + 1 = prev
-        SR_TRY(rows_real(e, lp_buf, nn, e->d_Zt, zhf, 2 * n, s));
-        SR_TRY(cols_seq(e, e->d_Zt + zhf, e->d_Zt, 2 * zhf, n, 1, s));
+        HIP_TRY(rows_real(e, lp_buf, nn, e->d_Zt, zhf, 2 * n, s));
+        HIP_TRY(cols_seq(e, e->d_Zt + zhf, e->d_Zt, 2 * zhf, n, 1, s));
       }
-      SR_TRY(peak(e, a, n, s));
+      HIP_TRY(peak(e, a, n, s));
     }
-    if (two_lanes) SR_TRY(hipEventRecord(e->ev_fft[b], s));
+    if (two_lanes) HIP_TRY(hipEventRecord(e->ev_fft[b], s));
   }
-  SR_TRY(e->fence.release(s));
+  HIP_TRY(e->fence.release(s));
   return MOF_OK;
 }
 
@@ -965,7 +884,7 @@ int mof_sr_logpolar_batch_device(mof_sr_engine* e, const uint8_t* d_src, size_t 
     return mof::capi_fail(MOF_ERR_BAD_ARG, "interpolation must be MOF_INTER_CUBIC (2) or MOF_INTER_LANCZOS4 (4)");
   BusyGuard g(e->busy);
   if (!g.owned) return mof::capi_fail(MOF_ERR_BUSY, "engine busy");
-  SR_TRY(hipSetDevice(e->cfg.device));
+  HIP_TRY(hipSetDevice(e->cfg.device));
   mof::SrLpArgs lp{};
   lp.src = d_src;
   lp.src_stride = src_stride;
@@ -976,7 +895,7 @@ int mof_sr_logpolar_batch_device(mof_sr_engine* e, const uint8_t* d_src, size_t 
   lp.res = res;
   lp_tables(e, interpolation, &lp);
   if (mof::stream_capturing((hipStream_t)stream)) e->graph_pinned.store(true);  // the map and the tables are the engine's
-  SR_TRY(mof::launch_sr_logpolar(lp, interpolation, n_images, (hipStream_t)stream));  // touches no engine scratch
+  HIP_TRY(mof::launch_sr_logpolar(lp, interpolation, n_images, (hipStream_t)stream));  // touches no engine scratch
   return MOF_OK;
 }
 

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "dev_mem.hpp"
 #include "pc_common.hpp"
 
 namespace mof {
@@ -93,14 +94,13 @@ __global__ __launch_bounds__(64) void wave_ops_selftest_kernel(int* mismatches) 
 
 // number of mismatches (0 = pass), or -1 when the device could not be used
 extern "C" int mof_selftest_wave_ops(void) {
-  int* d = nullptr;
+  mof::DevMem<int> d;
   int h = -1;
-  if (hipMalloc(&d, sizeof(int)) != hipSuccess) return -1;
+  if (d.alloc(1) != hipSuccess) return -1;
   bool ok = hipMemset(d, 0, sizeof(int)) == hipSuccess;
   if (ok) {
-    hipLaunchKernelGGL(mof::wave_ops_selftest_kernel, dim3(1), dim3(64), 0, 0, d);
+    hipLaunchKernelGGL(mof::wave_ops_selftest_kernel, dim3(1), dim3(64), 0, 0, d.get());
     ok = hipGetLastError() == hipSuccess && hipMemcpy(&h, d, sizeof(int), hipMemcpyDeviceToHost) == hipSuccess;
   }
-  (void)hipFree(d);
   return ok ? h : -1;
 }

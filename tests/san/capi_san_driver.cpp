@@ -6,13 +6,17 @@
 //     weight tables), compared entry by entry with the oracle's tables,
 //   * the geometry tail's host forms (getRT / get2DT and their stages),
 //   * the estimator's create-time route (sr_route) for every even resolution against tests/golden/sr_route_table.txt, recorded from the
-//     code before SrRoute existed, and the one list of tuned transform sizes seen through each of its three users.
+//     code before SrRoute existed, and the one list of tuned transform sizes seen through each of its three users,
+//   * the engines' resource owners (csrc/dev_mem.hpp) and the scratch-growth guard (csrc/capi_graph.hpp) with stub callables.
 // Where a device IS present the create() calls succeed and the engines are destroyed again.
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
+#include "capi_graph.hpp"
 #include "mof.h"
 #include "mof_kernels.h"
 #include "sr_common.hpp"
@@ -246,6 +250,42 @@ int main() {
     CHECK(mof_geom_get_rt_batch_device(nullptr, &L, &cam, nullptr, 3, 8, nullptr, nullptr) == MOF_ERR_BAD_ARG);
     CHECK(mof_geom_get_2dt_batch_device(nullptr, &L, &cam, nullptr, 3, nullptr, nullptr) == MOF_ERR_BAD_ARG);
     CHECK(mof_geom_get_rt_batch_device(nullptr, &L, &cam, nullptr, 0, 8, nullptr, nullptr) == MOF_OK);
+  }
+  // ---- the engines' owners and the one growth guard (dev_mem.hpp, capi_graph.hpp) ----
+  {
+    static_assert(!std::is_copy_constructible<mof::DevMem<float>>::value && !std::is_copy_assignable<mof::PinnedMem<double>>::value &&
+                  !std::is_copy_constructible<mof::Stream>::value && !std::is_copy_constructible<mof::Event>::value, "owners are move-only");
+    const int live0 = mof_live_buffers();
+    {
+      mof::DevMem<float> d, d2;
+      mof::PinnedMem<double> h;
+      mof::Stream s;
+      mof::Event ev;
+      d.reset();  // empty owners: reset and the destructors do nothing
+      const bool device = mof_device_count() > 0;
+      CHECK((d.alloc(64) == hipSuccess) == device && (d.get() != nullptr) == device);
+      CHECK((h.alloc(64) == hipSuccess) == device && (h.get() != nullptr) == device);
+      CHECK((s.create() == hipSuccess) == device && (ev.create() == hipSuccess) == device && (s.get() != nullptr) == device);
+      CHECK(mof_live_buffers() == live0 + (device ? 2 : 0));
+      float* raw = d.get();
+      d2 = std::move(d);  // the source is left empty, nothing is released
+      CHECK(d.get() == nullptr && d2.get() == raw && mof_live_buffers() == live0 + (device ? 2 : 0));
+      mof::DevMem<float> d3(std::move(d2));
+      CHECK(d2.get() == nullptr && d3.get() == raw);
+      CHECK((mof::upload(d, std::vector<float>(16, 2.f), s) == hipSuccess) == device);
+      d3.reset();
+      d3.reset();
+      CHECK(d3.get() == nullptr);
+    }
+    CHECK(mof_live_buffers() == live0);
+    mof::ScratchFence fence;
+    std::vector<long> asked;
+    auto realloc = [&asked](long n) { asked.push_back(n); return n == 1 ? hipSuccess : hipErrorOutOfMemory; };
+    CHECK(mof::grow_scratch(true, fence, {}, true, "scratch", 4, 4, 1, realloc) == MOF_OK && asked.empty());
+    CHECK(mof::grow_scratch(true, fence, {}, false, "scratch", 4, 8, 1, realloc) == MOF_ERR_BUSY && std::strstr(mof_last_error(), "graph") && asked.empty());
+    CHECK(mof::grow_scratch(false, fence, {}, true, "scratch", 4, 8, 1, realloc) == MOF_ERR_BAD_ARG && std::strstr(mof_last_error(), "graph") && asked.empty());
+    CHECK(mof::grow_scratch(false, fence, {}, false, "scratch", 4, 8, 1, realloc) == MOF_ERR_NO_MEMORY && asked == std::vector<long>({8, 1}));
+    CHECK(mof::grow_scratch(false, fence, {}, false, "scratch", 0, 1, 1, realloc) == MOF_OK && asked == std::vector<long>({8, 1, 1}));
   }
   std::printf("C-ABI sanitizer driver: ok\n");
   return 0;

@@ -4,8 +4,8 @@
 #   where hipcc is (no GPU needed): tools/ab_commit.sh prepare <commit>   exports that commit to tmp_ab/parent/ and builds its library there
 #   on the GPU box:                 tools/ab_commit.sh run [bench args...]  alternates old / new, three times (AB_REPS), one line per run:
 #                                                                           "<old|new> <pairs/s> <kernel_ms>"
-#                                   tools/ab_commit.sh bits                 tools/tail_bits.py's corpus through the old and the new LIBRARY (the
-#                                                                           current tree's binding: same C ABI), one process each, compared on the CPU
+#                                   tools/ab_commit.sh bits                 tools/tail_bits.py's corpus through the old and the new tree (each
+#                                                                           library under its own binding), one process each, compared on the CPU
 # Nothing is built by `run` or `bits`, and the product library is never overwritten.
 set -e -o pipefail
 R=$(cd "$(dirname "$0")/.." && pwd)
@@ -18,8 +18,8 @@ if [ "$1" == "prepare" ]; then
 fi
 if [ "$1" == "bits" ]; then
   [ -f $R/tmp_ab/parent/mrs_optic_flow_amd/libmof_hip.so ] || { echo "run 'tools/ab_commit.sh prepare <commit>' first"; exit 2; }
-  O=${AB_BITS_DIR:-$R/tmp_ab}
-  MOF_LIB_PATH=$R/tmp_ab/parent/mrs_optic_flow_amd/libmof_hip.so timeout -k 10 ${AB_STEP_LIMIT:-240} python3 $R/tools/tail_bits.py run $O/bits_old.npz &&
+  O=$(cd ${AB_BITS_DIR:-$R/tmp_ab} && pwd)
+  timeout -k 10 ${AB_STEP_LIMIT:-240} python3 $R/tmp_ab/parent/tools/tail_bits.py run $O/bits_old.npz &&
     timeout -k 10 ${AB_STEP_LIMIT:-240} python3 $R/tools/tail_bits.py run $O/bits_new.npz && python3 $R/tools/tail_bits.py compare $O/bits_old.npz $O/bits_new.npz
   exit $?
 fi

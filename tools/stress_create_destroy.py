@@ -1,7 +1,9 @@
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch, time
-from mrs_optic_flow_amd import FftMethod, FastSpacedBMMethod, ScaleRotationEstimator
+from mrs_optic_flow_amd import FftMethod, FastSpacedBMMethod, ScaleRotationEstimator, _capi
+live = _capi.load().mof_live_buffers  # the engines' device + pinned allocations: exact, whatever other processes do to the free memory
+live0 = live()
 t0=time.time()
 free0 = torch.cuda.mem_get_info()[0]
 rng=np.random.default_rng(0)
@@ -19,4 +21,4 @@ for i in range(N_CYC):
         sr = ScaleRotationEstimator(240, 40.0); sr.processImage(rng.integers(0,256,(240,240),dtype=np.uint8)); del sr
 torch.cuda.synchronize()
 free1 = torch.cuda.mem_get_info()[0]
-print("cycles ok in %.1fs; device free before %.1f MB after %.1f MB"%(time.time()-t0, free0/1e6, free1/1e6))
+print("cycles ok in %.2fs; device free before %.1f MB after %.1f MB; live buffers before %d after %d"%(time.time()-t0, free0/1e6, free1/1e6, live0, live()))
