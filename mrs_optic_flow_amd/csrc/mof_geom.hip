@@ -410,9 +410,6 @@ __global__ void __launch_bounds__(64) geom_get_rt_kernel(const double* __restric
     leave(kTooFewPoints);
     return;
   }
-#ifdef MOF_GEOM_PROF  // diagnostic build (tools/geom_stage_cycles.py): stage cycle counts instead of results
-  const unsigned long long t_a = __builtin_readcyclecounter();
-#endif
   const double thr2 = kRansacThreshold * kRansacThreshold;
   double best[9];
   bool found = false;
@@ -452,9 +449,6 @@ __global__ void __launch_bounds__(64) geom_get_rt_kernel(const double* __restric
     leave(remaining < thr ? kTooFewInliers : kNoHomography);
     return;
   }
-#ifdef MOF_GEOM_PROF
-  const unsigned long long t_b = __builtin_readcyclecounter();
-#endif
   // refit on the inliers: by the whole wave when its LDS work space was granted (up to kWaveFitPoints patches), else by
   // lane 0 through the host form
   double H[9];
@@ -464,22 +458,12 @@ __global__ void __launch_bounds__(64) geom_get_rt_kernel(const double* __restric
   } else {
     fitted = lane == 0 && homography_fit(a, b, mask, n, H);
   }
-#ifdef MOF_GEOM_PROF
-  const unsigned long long t_c = __builtin_readcyclecounter();
-#endif
   if (lane == 0) {  // decomposition + IMU-consistent pick: sequential
     double res[7] = {0, 0, 0, 1, 0, 0, 0};
     if (!fitted)
       for (int k = 0; k < 9; ++k) H[k] = best[k];
     const int status = pick_motion(H, p, res);
-#ifdef MOF_GEOM_PROF
-    res[0] = (double)(t_b - t_a), res[1] = (double)(t_c - t_b), res[2] = (double)(__builtin_readcyclecounter() - t_c);
-#endif
-#ifdef MOF_GEOM_PROF
-    const bool keep = true;
-#else
     const bool keep = status == kOk;
-#endif
     for (int k = 0; k < 7; ++k) o[k] = keep ? res[k] : (k == 3 ? 1.0 : 0.0);
     o[7] = (double)status;
   }

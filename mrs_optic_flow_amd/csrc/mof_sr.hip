@@ -31,9 +31,6 @@ namespace {
 
 constexpr int kTab = 32;            // INTER_TAB_SIZE
 constexpr int kCoefScale = 1 << 15; // INTER_REMAP_COEF_SCALE
-#ifndef MOF_SR_CHUNK
-#define MOF_SR_CHUNK 512
-#endif
 // frame pairs per pipeline pass: 512 pairs of 480^2 = 1.9 GB of scratch (log-polar images, Zt, Dt). Same-box sweeps at c5
 // (tools/sweep_c5.sh, profiles/r02_c5_sweep.txt): 64 / 128 / 256 pairs -> 240 / 277 / 308 k pairs/s on one lane, 512 ->
 // 326 k, 1024 -> 324 k; with the second lane 254 / 283 / 312 / 318 / 313 k -- once a pass is long enough to fill the
@@ -43,7 +40,7 @@ constexpr int kCoefScale = 1 << 15; // INTER_REMAP_COEF_SCALE
 // passes are worth +1.7 % at c5 and cost 3.8 GB of scratch that stays allocated (and pinned once a graph captured the engine),
 // so the DEFAULT stays 512 pairs = 1.9 GB (r04, advisor); a caller that has the memory opts in through
 // mof_sr_config.batch_chunk (bench.py does for c5 / c5seq).
-constexpr int kChunkDefault = MOF_SR_CHUNK;
+constexpr int kChunkDefault = 512;
 // The MOF_SR_* knobs of the engine (README), read once per process. MOF_SR_CHUNK / MOF_SR_OVERLAP override mof_sr_config.batch_chunk /
 // .pipeline_lanes at create() (sweeps)
 const mof::SrKnobs& sr_knobs() {

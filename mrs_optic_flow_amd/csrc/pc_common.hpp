@@ -43,9 +43,6 @@ __device__ __forceinline__ void butterfly<4>(cf* v) {
 
 template <>
 __device__ __forceinline__ void butterfly<8>(cf* v) {
-#ifdef MOF_ABLATE_NOBFLY
-  return;  // diagnostic build: keeps the LDS traffic, drops the butterfly arithmetic
-#endif
   const float h = 0.70710678118654752440f;
   cf e[4] = {v[0], v[2], v[4], v[6]};
   cf o[4] = {v[1], v[3], v[5], v[7]};
@@ -99,18 +96,10 @@ __device__ __forceinline__ void butterfly8_tw(cf* v, const cf* tw) {
   v[7] = csub(e3, w3);
 }
 
-// A/B (-DMOF_BFLY_PRIO_IN=a -DMOF_BFLY_PRIO_OUT=b): issue priority of a wave inside its radix-16 butterflies against the LDS phases around
-// them (r06, profiles/r06_bfly_prio_ab.txt: butterflies first -4 .. -5 % at c2 and -7 % at c4, LDS phases first +-0 -- off)
-#if defined(MOF_BFLY_PRIO_IN)
-#define MOF_BFLY_ENTER() __builtin_amdgcn_s_setprio(MOF_BFLY_PRIO_IN)
-#define MOF_BFLY_LEAVE() __builtin_amdgcn_s_setprio(MOF_BFLY_PRIO_OUT)
-#else
-#define MOF_BFLY_ENTER() ((void)0)
-#define MOF_BFLY_LEAVE() ((void)0)
-#endif
+// (a raised or lowered issue priority, s_setprio, inside the radix-16 butterflies against the LDS phases around them: butterflies first
+// -4 .. -5 % at c2 and -7 % at c4, LDS phases first +-0, profiles/r06_bfly_prio_ab.txt -- none is set)
 template <>
 __device__ __forceinline__ void butterfly<16>(cf* v) {
-  MOF_BFLY_ENTER();
   // 16 = 4 x 4: four radix-4 over n1 (stride 4), twiddle W16^{n2 k1}, four radix-4 over n2
   const float c1 = 0.92387953251128675613f, s1 = 0.38268343236508977173f, h = 0.70710678118654752440f;
   cf t[4][4];
@@ -133,7 +122,6 @@ __device__ __forceinline__ void butterfly<16>(cf* v) {
 #pragma unroll
     for (int k2 = 0; k2 < 4; ++k2) v[k1 + 4 * k2] = a[k2];
   }
-  MOF_BFLY_LEAVE();
 }
 
 __device__ __forceinline__ void butterfly3(cf* a) {

@@ -57,7 +57,6 @@ struct HalfPlan {
   int waves = 0;
   int pitch = 0;
   int skew = 0;  // 1: element x of a line sits at x + (x >> shift) (both layouts); 0 where only the unskewed tile fits (M = 192)
-  int rskew = 0; // r06 (A/B): row skew -- tile row r starts rskew * (r >> 4) complex elements later (pc_plan.hpp: Walk::lrs / ers)
   int shift = 3; // the skew's shift: 4 for the radix-16-first sizes 96 / 128 / 160 (tools/design/half_lanes.py: stage-0 outputs 16 x + p of the
                  // eight butterflies of a line land in eight different banks mod 16 only with x + (x >> 4))
   int lds_bytes = 0;
@@ -65,73 +64,39 @@ struct HalfPlan {
   bool ok = false;
 };
 
-#ifndef MOF_HALF_RSKEW  // (A/B) the row skew of every instantiation, complex elements per 16 rows; 0 = none (the product)
-#define MOF_HALF_RSKEW 0
-#endif
-constexpr int half_rskew(int m) { return MOF_HALF_RSKEW; }
-// complex elements the row skew adds behind the tile: rskew * ((M - 1) >> 4) for the last row, rounded up
-constexpr int half_rskew_room(int m) { return half_rskew(m) * ((m >> 4) + 1); }
-// LDS behind the tile: the row skew's room, twiddles (m complex), 16 (value, index) slots, 16 flag words
-constexpr size_t half_extra(int m) { return sizeof(float) * 2 * ((size_t)m + half_rskew_room(m)) + 16 * 8 + 64; }
+// LDS behind the tile: twiddles (m complex), 16 (value, index) slots, 16 flag words
+constexpr size_t half_extra(int m) { return sizeof(float) * 2 * (size_t)m + 16 * 8 + 64; }
 
 constexpr int half_stage_lines(int m, int R) {  // lines one group of a stage covers (pc_plan.hpp: stage_rt)
   const int bpl = m / R, nb = 16 / pc_slots(R);
   return bpl <= 64 ? nb * (64 / bpl) : 1;
 }
 
-#ifndef MOF_HALF_PITCH  // (A/B) force the pitch of every instantiation; 0 = the rule below
-#define MOF_HALF_PITCH 0
-#endif
-#ifndef MOF_HALF_SKEW  // (A/B, with MOF_HALF_PITCH) 0 / 1: force the unskewed / skewed layout; -1 = the rule
-#define MOF_HALF_SKEW (-1)
-#endif
-#ifndef MOF_HALF_PITCH_TABLE  // 0: the generic pitch rule for every size (A/B)
-#define MOF_HALF_PITCH_TABLE 1
-#endif
 // (pitch, skew) with the fewest LDS cycles in the bank model of tools/design/half_banks.py (every ds_read_b64 / ds_write_b64 of a
 // patch pair with the lane groups and bank widths of MI355X_MICROARCH.md) among the pitches that keep the workgroups per CU; 0 = the
 // rule below. Where the unskewed tile is within a few per cent of the best it is preferred: its element offsets are immediates.
-#ifndef MOF_HALF_SHIFT  // (A/B) force the skew shift of every skewed instantiation; 0 = the table / 3
-#define MOF_HALF_SHIFT 0
-#endif
 constexpr int half_table_shift(int m) {
-  if (MOF_HALF_SHIFT > 0) return MOF_HALF_SHIFT;
-  if (!MOF_HALF_PITCH_TABLE) return 3;
   switch (m) {
     case 96: case 128: case 160: case 192: return 4;  // (192: the skewed tile only fits with this shift: 204 x 96 lines)
     default: return 3;
   }
 }
 constexpr int half_table_pitch(int m, int* skew) {
-  if (!MOF_HALF_PITCH_TABLE) return 0;
   switch (m) {
-    case 96:  // (with shift 4: x1.09 of the conflict-free LDS cycles in the model against x1.40 at the rule's 120 with shift 3)
-      if (half_table_shift(96) != 4) return 0;
-      *skew = 1;
-      return 104;
+    case 96: *skew = 1; return 104;   // (with shift 4: x1.09 of the conflict-free LDS cycles in the model against x1.40 at the rule's 120 with shift 3)
     case 60: *skew = 0; return 68;    // (box: 68 / 76 unskewed 1.36 M at p60, the rule's 72 skewed 1.29 M; profiles/r05_half_pitch60_sweep.txt)
-    case 120: *skew = 0; return 136;  // (measured too, tools/sweep_half_pitch.sh, profiles/r05_half_pitch120_sweep.txt: 136 unskewed 1.14 M, 120 1.13 M, 152 1.13 M, 128 0.93 M; skewed 136 / 152: 1.05 M)
+    case 120: *skew = 0; return 136;  // (measured too, profiles/r05_half_pitch120_sweep.txt: 136 unskewed 1.14 M, 120 1.13 M, 152 1.13 M, 128 0.93 M; skewed 136 / 152: 1.05 M)
     case 144: *skew = 1; return 202;
-    case 160:  // (box, shift 4: 172 / 170 / 200 729 k at l160, the rule's 184 725 k; shift 3 at 184: 712 k -- profiles/r05_half_pitch160_shift_sweep.txt)
-      if (half_table_shift(160) != 4) return 0;
-      *skew = 1;
-      return 172;
+    case 160: *skew = 1; return 172;  // (box, shift 4: 172 / 170 / 200 729 k at l160, the rule's 184 725 k; shift 3 at 184: 712 k -- profiles/r05_half_pitch160_shift_sweep.txt)
     case 150: *skew = 0; return 180;
     case 162: *skew = 0; return 186;
     case 180: *skew = 0; return 184;
     default: return 0;
   }
 }
-#ifndef MOF_HALF_SWAP160  // the product's choice for M = 160 (0 until the A/B says otherwise)
-#define MOF_HALF_SWAP160 0
-#endif
-#ifndef MOF_HALF_SWAP  // (A/B) 1: a two-stage chain's radices in the other order (the last one must stay even: pc_plan_build.hpp's exactness rule)
-#define MOF_HALF_SWAP 0
-#endif
-// sizes whose two-stage chain runs the SMALLER radix first (r06, tools/design/half_lanes.py in counter terms + same-box A/B): 160 = 10 x 16 --
-// with 16 first the stage-0 outputs 16 x + p of neighbouring butterflies of a column sit 16 rows = 16 P/2 complex = 0 (mod 32 dwords) apart
-// for ANY pitch, a 3-way conflict on every first-stage column write
-constexpr bool half_swapped(int m) { return MOF_HALF_SWAP != 0 ? true : (m == 160 && MOF_HALF_SWAP160); }
+// (r06: the two-stage chain of 160 = 10 x 16 with the SMALLER radix first -- with 16 first the stage-0 outputs 16 x + p of neighbouring
+// butterflies of a column sit 16 rows = 0 (mod 32 dwords) apart for ANY pitch, a 3-way conflict on every first-stage column write -- puts
+// radix 16 last and spills 112 - 165 VGPRs there, docs/history/r06.md: every chain keeps the order of pc_two_stage_chain)
 constexpr HalfPlan half_plan(int m) {
   HalfPlan hp{};
   if (m < 16 || m > 192 || (m & 1)) return hp;
@@ -139,11 +104,6 @@ constexpr HalfPlan half_plan(int m) {
   if (!pc_line_plan_c(m, pl) || pl.m != m) return hp;  // 5-smooth sizes only (n = m); the generic radix chain as a start
   int Ra = 0, Rb = 0;
   if (pc_two_stage_chain(m, Ra, Rb)) {
-    if (half_swapped(m) && (Ra & 1) == 0) {
-      const int t = Ra;
-      Ra = Rb;
-      Rb = t;
-    }
     pl.n_stages = 2;
     pl.radix[0] = Ra;
     pl.radix[1] = Rb;
@@ -182,9 +142,6 @@ constexpr HalfPlan half_plan(int m) {
   // would put a fifth wave on two SIMDs). Six lines per wave = eight emptier waves, two workgroups = 16 waves: p96 892 -> 907 k pairs/s
   // same-box (profiles/r05_half_lpw96_ab.txt; four lines = 12 waves: 600 k)
   if (m == 96) hp.lpw = 6;
-#ifdef MOF_HALF_LPW  // (A/B, with MOF_HALF_ONLY) lines per wave: fewer than a whole stage group = more, emptier waves
-  hp.lpw = MOF_HALF_LPW;
-#endif
   hp.waves = (H + hp.lpw - 1) / hp.lpw;
   // pitch: even, room for both skews; P/2 = 4 (mod 8) spreads the rows of a column walk over the banks (8 rows x 4 columns per
   // 32-lane read group) -- the first such pitch that still fits, else the smallest; without the skew where nothing else fits
@@ -200,21 +157,18 @@ constexpr HalfPlan half_plan(int m) {
     p = pmin;
     while ((p / 2) % 8 != 4) p += 2;
     if ((size_t)H * p * 8 + half_extra(m) > cap) p = pmin;
-    if (MOF_HALF_PITCH > 0 && MOF_HALF_PITCH >= pmin && (MOF_HALF_PITCH & 1) == 0) p = MOF_HALF_PITCH;
-    if (MOF_HALF_SKEW >= 0 && skew != MOF_HALF_SKEW) continue;
     if ((size_t)H * p * 8 + half_extra(m) <= cap) break;
   }
   if (skew < 0) return hp;
   {
     int tsk = 0;
     const int tp = half_table_pitch(m, &tsk);
-    if (tp > 0 && MOF_HALF_PITCH == 0 && (size_t)H * tp * 8 + half_extra(m) <= cap) {
+    if (tp > 0 && (size_t)H * tp * 8 + half_extra(m) <= cap) {
       p = tp;
       skew = tsk;
     }
   }
   hp.skew = skew;
-  hp.rskew = half_rskew(m);
   hp.pitch = p;
   hp.lds_bytes = (int)((size_t)H * p * 8 + half_extra(m));
   int wgs = (int)(cap / (size_t)hp.lds_bytes);
@@ -233,14 +187,8 @@ constexpr HalfPlan half_plan(int m) {
 // most waves per SIMD the launch bounds ask the register allocator for: 4 (128 VGPRs). Measured at 5 (96 VGPRs; profiles/r05_half_wpe5_ab.txt):
 // M = 96 -- six-wave workgroups, two per CU at 4, three at 5 -- gains 3.5 % (p96 893 -> 925 k pairs/s) but spills 26 VGPRs, and the scratch
 // traffic shows as 2.2 x the algorithmic bytes on the fabric counters (1.0 x without); p60 loses 6 %, 100 loses 3 %, 6 waves at 96 lose 21 %.
-// Not adopted: the clean 1.0 x is worth more than 3.5 %. MOF_HALF_WPE_CAP forces a value (A/B).
-constexpr int half_wpe_cap(int m) {
-#ifdef MOF_HALF_WPE_CAP
-  return MOF_HALF_WPE_CAP;
-#else
-  return 4;
-#endif
-}
+// Not adopted: the clean 1.0 x is worth more than 3.5 %.
+constexpr int HALF_WPE_CAP = 4;
 template <int MS>
 struct HalfPlanOf {
   static constexpr HalfPlan HP = half_plan(MS);
@@ -249,7 +197,7 @@ struct HalfPlanOf {
   static constexpr int T = 64 * HP.waves;
   // waves per SIMD the registers must allow: what the LDS lets sit on a CU, at most 4 (128 VGPRs)
   static constexpr int WPE_ = (HP.wgs_per_cu * HP.waves + 3) / 4;
-  static constexpr int WPE = WPE_ < 1 ? 1 : (WPE_ > half_wpe_cap(MS) ? half_wpe_cap(MS) : WPE_);
+  static constexpr int WPE = WPE_ < 1 ? 1 : (WPE_ > HALF_WPE_CAP ? HALF_WPE_CAP : WPE_);
 };
 
 // arg-max as the sink of the inverse row pass's last stage: line j, element x carries the surface at (2j, x) and (2j + 1, x)
@@ -268,32 +216,25 @@ struct HalfScanSink {
 // raw pixel staging (as the tuned kernels, pc_passes.hpp raw_store): a chunk's 4 + 4 pixels (rows 2j, 2j + 1) leave as ONE
 // ds_write_b64 of interleaved bytes (a0 b0 a1 b1 ..) into the first 2 M bytes of the line's own tile span, and the first row stage
 // converts them on its way into the butterfly (u8 -> f32: convertTo, :1805-1806) -- four ds_write_b64 of floats per chunk less
-#ifndef MOF_HALF_RAW
-#define MOF_HALF_RAW 1
-#endif
 struct HalfRawSrc {
   static constexpr bool active = true;
   int pitch;  // complex elements per line
-  int rs;     // row skew (complex elements per 8 lines)
   __device__ __forceinline__ cf operator()(const cf* z, int l, int e) const {
     typedef const volatile uint16_t __attribute__((address_space(3))) * lds_u16_ptr;
-    const uint32_t ab = *(lds_u16_ptr)(reinterpret_cast<const unsigned char*>(z + l * pitch + rs * (l >> 3)) + 2 * e);
+    const uint32_t ab = *(lds_u16_ptr)(reinterpret_cast<const unsigned char*>(z + l * pitch) + 2 * e);
     return {(float)(ab & 0xffu), (float)(ab >> 8)};
   }
 };
 
 // the pairing of the inverse row pass (spec -> rows layout) as the SOURCE of its first stage: element e of line j is built from the two
 // spec rows 2j | 2j + 1 on the way into the butterfly -- the sweep of its own (a read and a write of the half tile) disappears
-#ifndef MOF_HALF_PAIR_SRC
-#define MOF_HALF_PAIR_SRC 1
-#endif
 struct HalfPairSrc {
   static constexpr bool active = true;
-  int p2, m, skm, sh, rs;
+  int p2, m, skm, sh;
   __device__ __forceinline__ cf operator()(const cf* z, int l, int e) const {
     const int H = m >> 1;
     const int u = e < H ? e : (e == H ? 0 : m - e);
-    const int o = u + ((u >> sh) & skm) + rs * (l >> 3);  // (rows 2l and 2l + 1 share (2l) >> 4 = l >> 3)
+    const int o = u + ((u >> sh) & skm);
     const cf d1 = lds_read(&z[(2 * l) * p2 + o]), d2 = lds_read(&z[(2 * l + 1) * p2 + o]);
     if (e == 0) return {d1.x, d2.x};
     if (e == H) return {d1.y, d2.y};
@@ -307,14 +248,11 @@ struct HalfPairSrc {
 // the butterfly; the stage's outputs land in the spec layout, over rows-layout bins that OTHER waves' columns read -- so a workgroup
 // barrier stands between the stage's reads and its writes (WorkgroupSync). The sweep of its own (17 reads + 16 writes per lane and
 // image) disappears for 15 more reads and one more barrier.
-#ifndef MOF_HALF_UNTANGLE_SRC
-#define MOF_HALF_UNTANGLE_SRC 1
-#endif
 struct HalfUntangleSrc {
   static constexpr bool active = true;
-  int p, m, skm, sh, rs;
+  int p, m, skm, sh;
   __device__ __forceinline__ cf operator()(const cf* z, int l, int e) const {  // column l, row e
-    const cf* line = z + (e >> 1) * p + rs * (e >> 4);
+    const cf* line = z + (e >> 1) * p;
     const int H = m >> 1, um = l == 0 ? H : m - l;
     const cf zk = lds_read(&line[l + ((l >> sh) & skm)]), zm = lds_read(&line[um + ((um >> sh) & skm)]);
     cf A, B;
@@ -333,12 +271,7 @@ struct HalfUntangleSrc {
 // it still has to be taken apart with its partner bins), and the last stage of the current image's pass meets them there -- same
 // lane, same register slot -- and writes the CONJUGATED CROSS-POWER SPECTRUM instead of the spectrum (HalfXpowSink). Gone: the copy of
 // the previous spectrum into registers, its tile write, and the cross-power sweep's read and write of the wave's columns.
-#ifndef MOF_HALF_XPOW_SINK
-#define MOF_HALF_XPOW_SINK 1
-#endif
-#ifndef MOF_HALF_MAX_GROUPS  // groups of a fused stage a wave may hold in registers at once (1: the r05 first form, sizes up to 144 only)
-#define MOF_HALF_MAX_GROUPS 2
-#endif
+constexpr int HALF_MAX_GROUPS = 2;  // groups of a fused stage a wave may hold in registers at once (1: the r05 first form, sizes up to 144 only)
 struct HalfSaveSink {
   static constexpr bool active = true;
   static constexpr bool transforms = true;
@@ -367,17 +300,6 @@ struct HalfXpowSink {
   }
 };
 
-#ifndef MOF_HALF_FAST_LOAD  // 0: the general pixel loader for every patch (A/B)
-#define MOF_HALF_FAST_LOAD 1
-#endif
-#ifndef MOF_HALF_PREFETCH  // 0: the current image is loaded after the previous image's column pass (A/B)
-#define MOF_HALF_PREFETCH 1
-#endif
-#ifndef MOF_HABL  // diagnostic builds (results wrong by design): 1 no transform passes, 2 no cross-power, 3 no pixel loads, 4 no previous image
-                  // (what a sequence form that keeps a frame's spectrum for the next pair could save at most)
-#define MOF_HABL 0
-#endif
-
 // SEQ (the video form, mof_fft_process_sequence_device): blockIdx.z is a RUN of `run` consecutive pairs of one patch position, frame f at
 // a.cur + f * a.cur_stride. The run's first frame is transformed as the previous image of the pair form; after that every frame is the
 // CURRENT image once, and its spectrum -- the forward column pass's last-stage outputs, already in the lanes' registers where the
@@ -390,8 +312,7 @@ __global__ void __launch_bounds__(HalfPlanOf<MS>::T, HalfPlanOf<MS>::WPE) pc_hal
   constexpr int M = MS, H = M / 2, P = HP.pitch, P2 = P / 2, T = SP::T, WAVES = HP.waves, LPW = HP.lpw;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_h[];
   cf* z = reinterpret_cast<cf*>(smem_h);
-  constexpr int RSK = HP.rskew;
-  cf* tw = z + (size_t)H * P + half_rskew_room(M);
+  cf* tw = z + (size_t)H * P;
   Best* red = reinterpret_cast<Best*>(tw + M);
   int* flags = reinterpret_cast<int*>(red + 16);  // [0] cur differs from its first pixel, [1] prev does, [2] C_dc bits, [3] / [4] first pixel of cur / prev
   int tid = threadIdx.x, lane = tid & 63;  // (not const: the sequence form hides them from the optimiser once per pair, below)
@@ -402,8 +323,8 @@ __global__ void __launch_bounds__(HalfPlanOf<MS>::T, HalfPlanOf<MS>::WPE) pc_hal
   // lines 0 2 1 3 in the later row stages where two lines of a 32-lane read half overlap in the banks: neighbouring lines P complex = 2 P
   // dwords apart, a line's 16 complex = 32 dwords -- conflict-free iff 2 P = 32 (mod 64); lines two apart: 4 P = 32 (mod 64) iff P = 8 (mod 16)
   constexpr int HALF_LINE_PERM = ((2 * P) % 64 != 32 && (4 * P) % 64 == 32) ? 1 : 0;
-  auto rows_at = [&](int j, int x) -> int { return j * P + RSK * (j >> 3) + x + ((x >> SH) & SKM); };
-  auto spec_at = [&](int r, int u) -> int { return r * P2 + RSK * (r >> 4) + u + ((u >> SH) & SKM); };
+  auto rows_at = [&](int j, int x) -> int { return j * P + x + ((x >> SH) & SKM); };
+  auto spec_at = [&](int r, int u) -> int { return r * P2 + u + ((u >> SH) & SKM); };
 
   // ---- patch origin (one workgroup per patch on a 3-D grid: column, row, pair)
   const int px0 = a.origin_x + (int)blockIdx.x * a.stride_x, py0 = a.origin_y + (int)blockIdx.y * a.stride_y;
@@ -424,16 +345,16 @@ __global__ void __launch_bounds__(HalfPlanOf<MS>::T, HalfPlanOf<MS>::WPE) pc_hal
   // the wave's columns as NG0 compile-time groups of the first column stage (stage_rt_ng; r05: one group -- 64 .. 144 -- or two -- the
   // sizes of 150 .. 192, 32 complex values per lane in flight)
   constexpr int NG0 = (LPW + GROUP0 - 1) / GROUP0;
-  constexpr bool UFUSE = MOF_HALF_UNTANGLE_SRC != 0 && NG0 <= MOF_HALF_MAX_GROUPS;
+  constexpr bool UFUSE = NG0 <= HALF_MAX_GROUPS;
   constexpr int RL = SP::P.radix[SP::P.n_stages - 1], BPLL = M / RL, NBL = 16 / pc_slots(RL), GROUPL = BPLL <= 64 ? NBL * (64 / BPLL) : 0;
   constexpr int NGL = GROUPL > 0 ? (LPW + GROUPL - 1) / GROUPL : 99;  // ... and of the last one (162's radix-2 stage has long lines: none)
-  constexpr bool XSINK = MOF_HALF_XPOW_SINK != 0 && UFUSE && NGL <= MOF_HALF_MAX_GROUPS && SP::P.n_stages >= 2;
+  constexpr bool XSINK = UFUSE && NGL <= HALF_MAX_GROUPS && SP::P.n_stages >= 2;
   static_assert(!UFUSE || (WAVES - 1) * LPW < H, "every wave owns a line: the barrier inside the fused stage is met by all");
   static_assert(!SEQ || XSINK, "the sequence form keeps the spectrum in the cross-power sink's registers");
   // wave w owns lines [l0, l0 + nl): row pairs in the row passes, columns in the column passes
   const int l0 = wave * LPW;
   const int nl = H - l0 < 0 ? 0 : (H - l0 > LPW ? LPW : H - l0);
-  const Walk rows = {P, 1, 0, SKM, 0, HALF_LINE_PERM, SH, RSK, 0}, cols = {1, P2, SKM, 0, 1, 0, SH, 0, RSK};
+  const Walk rows = {P, 1, 0, SKM, 0, HALF_LINE_PERM, SH, 0}, cols = {1, P2, SKM, 0, 1, 0, SH, 0};
 
   // ---- one image: pixels of the wave's lines -> LDS (u8 -> f32: convertTo, :1805-1806; zeros beyond n x n: copyMakeBorder of
   //      cv::phaseCorrelate), row transforms, untangle into the spec layout. Wave-local throughout. Chunk q = lane + 64 k of the wave's
@@ -446,14 +367,14 @@ __global__ void __launch_bounds__(HalfPlanOf<MS>::T, HalfPlanOf<MS>::WPE) pc_hal
   // form spends ~70 instructions per chunk on q / CPR, q % CPR, a 64-bit row offset and four bounds; this one a dozen. A scalar
   // branch: n is a kernel argument. Same-box (profiles/r05_half_fastload_ab.txt): l160 +2 %, p60 +1.7 %, p96 +-0, ref -0.7 % -- the
   // loader's arithmetic mostly hides behind its own loads; M = 120 keeps the general form.
-  const bool fills = MOF_HALF_FAST_LOAD != 0 && MOF_HALF_RAW != 0 && (M % 4 == 0) && M != 120 && n == M;
+  const bool fills = (M % 4 == 0) && M != 120 && n == M;
   int li0 = lane / CPR, xc0 = lane - li0 * CPR;  // (not const: SEQ, below)
   // (FILLS rides in as a type: the scalar branch on `fills` stands ONCE around a whole loop of chunks -- a branch per chunk puts every
   // load into a basic block of its own and cost 6 - 8 % at p60 / p96 / l160)
   auto chunk_load = [&](auto fills_tag, int k, const uint8_t* img, uint32_t* pa, uint32_t* pb) {
     constexpr bool FILLS = decltype(fills_tag)::value;
     *pa = *pb = 0u;
-    if (k >= NCH || MOF_HABL == 3) return;
+    if (k >= NCH) return;
     if constexpr (FILLS) {
       const int DL = (64 * k) / CPR, DX = (64 * k) % CPR;
       const bool wrap = xc0 + DX >= CPR;
@@ -495,8 +416,7 @@ __global__ void __launch_bounds__(HalfPlanOf<MS>::T, HalfPlanOf<MS>::WPE) pc_hal
         d.x = __builtin_amdgcn_perm(vb, va, 0x05010400u);
         d.y = __builtin_amdgcn_perm(vb, va, 0x07030602u);
         const uint32_t lds0 = (uint32_t)((l0 + li0) * (P * 8) + 8 * xc0);
-        const uint32_t rsb = RSK != 0 ? (uint32_t)(8 * RSK * ((l0 + li) >> 3)) : 0u;  // (the row skew of line l0 + li)
-        *(lds_u2_ptr)(reinterpret_cast<unsigned char*>(z) + (lds0 + rsb + (uint32_t)(DL * (P * 8) + 8 * DX) + (wrap ? (uint32_t)(P * 8 - 8 * CPR) : 0u))) = d;
+        *(lds_u2_ptr)(reinterpret_cast<unsigned char*>(z) + (lds0 + (uint32_t)(DL * (P * 8) + 8 * DX) + (wrap ? (uint32_t)(P * 8 - 8 * CPR) : 0u))) = d;
       }
     } else {
       const int q = lane + 64 * k, li = q / CPR, x0 = 4 * (q % CPR), y = 2 * (l0 + li);
@@ -506,19 +426,11 @@ __global__ void __launch_bounds__(HalfPlanOf<MS>::T, HalfPlanOf<MS>::WPE) pc_hal
           if (y < n) *diff |= (va ^ pat) & inside;
           if (y + 1 < n) *diff |= (vb ^ pat) & inside;
         }
-        cf* line = z + (l0 + li) * P + RSK * ((l0 + li) >> 3);
-        if constexpr (MOF_HALF_RAW) {
-          u2 d;
-          d.x = __builtin_amdgcn_perm(vb, va, 0x05010400u);
-          d.y = __builtin_amdgcn_perm(vb, va, 0x07030602u);
-          *(lds_u2_ptr)(reinterpret_cast<unsigned char*>(line) + 2 * x0) = d;  // (a partial last chunk spills past 2 M bytes: inside the line, never read)
-        } else {
-#pragma unroll
-          for (int b = 0; b < 4; ++b) {
-            const int x = x0 + b;
-            if (x < M) line[x + ((x >> SH) & SKM)] = {(float)((va >> (8 * b)) & 0xffu), (float)((vb >> (8 * b)) & 0xffu)};
-          }
-        }
+        cf* line = z + (l0 + li) * P;
+        u2 d;
+        d.x = __builtin_amdgcn_perm(vb, va, 0x05010400u);
+        d.y = __builtin_amdgcn_perm(vb, va, 0x07030602u);
+        *(lds_u2_ptr)(reinterpret_cast<unsigned char*>(line) + 2 * x0) = d;  // (a partial last chunk spills past 2 M bytes: inside the line, never read)
       }
     }
   };
@@ -527,10 +439,7 @@ __global__ void __launch_bounds__(HalfPlanOf<MS>::T, HalfPlanOf<MS>::WPE) pc_hal
     if (__builtin_amdgcn_ballot_w64(diff != 0u) != 0ull && lane == 0) flags[which] = 1;
     if (tid == 0) flags[3 + which] = (int)first;
     wave_sync();
-    if (nl > 0 && MOF_HABL != 1) {
-      if constexpr (MOF_HALF_RAW) pass_lines_static<SP, 0, 1, NoSink, HalfRawSrc>(z, tw, rows, l0, nl, lane, false, NoSink{}, HalfRawSrc{P, RSK});
-      else pass_lines_static<SP>(z, tw, rows, l0, nl, lane, false);
-    }
+    if (nl > 0) pass_lines_static<SP, 0, 1, NoSink, HalfRawSrc>(z, tw, rows, l0, nl, lane, false, NoSink{}, HalfRawSrc{P});
     if constexpr (UFUSE) return;  // (the untangle rides the forward column pass: HalfUntangleSrc)
     // untangle: line j = rows 2j + i (2j + 1): R_2j[u] = (Z[u] + conj Z[M-u]) / 2, R_2j+1[u] = (Z[u] - conj Z[M-u]) / 2i, kept
     // DOUBLED; the real bins u = 0 and u = M/2 of a row share its column 0. Every read of a line before its first write.
@@ -619,11 +528,11 @@ __global__ void __launch_bounds__(HalfPlanOf<MS>::T, HalfPlanOf<MS>::WPE) pc_hal
   constexpr int NPV = XSINK ? NGL * NBL * RL : KE;  // XSINK: the last column stage's own outputs: (group, butterfly), output p
   constexpr int KV0 = (H + 1 + 63) / 64;      // XSINK: column 0's slots v and M - v (v <= M/2) of the previous image, lane v
   cf pv[NPV], pv0a[KV0], pv0b[KV0];
-  if constexpr (MOF_HABL != 4) load_and_rows(prev, 1);
+  load_and_rows(prev, 1);
   __syncthreads();
   // gray frames: the CURRENT image's pixels are requested here, before the previous image's column pass, and wait in 2 NCH registers
-  // (8 - 10) until the tile is free -- their memory latency runs under that pass instead of in front of the row pass (MOF_HALF_PREFETCH)
-  constexpr bool PREFETCH = MOF_HALF_PREFETCH != 0 && CH == 1 && !SEQ;  // (SEQ: once per run only, and its registers would be live across the run's loop: 39 spills at M = 120)
+  // (8 - 10) until the tile is free -- their memory latency runs under that pass instead of in front of the row pass
+  constexpr bool PREFETCH = CH == 1 && !SEQ;  // (SEQ: once per run only, and its registers would be live across the run's loop: 39 spills at M = 120)
   uint32_t ca[PREFETCH ? NCH : 1], cb[PREFETCH ? NCH : 1], cfirst = 0u;
   if constexpr (PREFETCH) {
     cfirst = fetch_px<1, CH>(cur, a.pitch, 0, 0);
@@ -638,17 +547,16 @@ __global__ void __launch_bounds__(HalfPlanOf<MS>::T, HalfPlanOf<MS>::WPE) pc_hal
   // forward column pass of the image in the tile (UFUSE: with the untangle as its source and a workgroup barrier inside its first stage)
   auto fwd_cols = [&](auto sink) {
     using Sink = decltype(sink);
-    if constexpr (MOF_HABL == 1) return;
     if constexpr (UFUSE)
       pass_lines_static<SP, 0, 1, Sink, HalfUntangleSrc, WorkgroupSync, NG0, (XSINK ? NGL : 0)>(z, tw, cols, l0, nl, lane, false, sink,
-                                                                                                HalfUntangleSrc{P, M, SKM, SH, RSK});
+                                                                                                HalfUntangleSrc{P, M, SKM, SH});
     else if (nl > 0)
       pass_lines_static<SP, 0, 1, Sink>(z, tw, cols, l0, nl, lane, false, sink);
   };
   if constexpr (XSINK) {
 #pragma unroll
     for (int i = 0; i < NPV; ++i) pv[i] = cf{1.f, 0.f};
-    if constexpr (MOF_HABL != 4) fwd_cols(HalfSaveSink{pv, RL});
+    fwd_cols(HalfSaveSink{pv, RL});
     if (wave == 0) {
       split_col0();
 #pragma unroll
@@ -723,8 +631,7 @@ have_current:
     return C;
   };
   if constexpr (XSINK) {
-    if constexpr (MOF_HABL == 2) fwd_cols(NoSink{});
-    else fwd_cols(HalfXpowSink<SEQ>{pv, RL, H, box_zeros, zq});
+    fwd_cols(HalfXpowSink<SEQ>{pv, RL, H, box_zeros, zq});
     if (wave == 0) {
       // column 0: apart, crossed with the previous image's slots (registers, lane v), together again -- G'[v] = conj C0[v] + i conj CH[v],
       // G'[M - v] = C0[v] + i CH[v] (C0, CH Hermitian in v) -- straight from the registers
@@ -760,19 +667,17 @@ have_current:
   } else {
   fwd_cols(NoSink{});
   if (wave == 0) split_col0();
-  if (MOF_HABL != 2) {
 #pragma unroll
-    for (int k = 0; k < KE; ++k) {
-      const int q = lane + 64 * k, r = q / LPW, c = q % LPW;
-      const bool on = r < M && c < nl;
-      const int rr = on ? r : 0, u = on ? l0 + c : l0;  // (lanes past the wave's elements repeat a bin: cross_power_ab's
-      const cf av = lds_read(&z[spec_at(rr, u)]);       //  wave-uniform branch wants every lane to take part)
-      const cf bv = on ? pv[k] : cf{1.f, 0.f};
-      cf C = u == 0 ? col0_bin(av, bv, rr, on) : cross_power_ab(av, bv, false);
-      if (box_zeros && u != 0 && (box_zero_line(rr, zq) || box_zero_line(u, zq))) C = {0.f, 0.f};
-      // conjugated for the inverse (a forward transform of conj C); column 0 keeps C itself until it is put together again below
-      if (on) z[spec_at(rr, u)] = u == 0 ? C : cf{C.x, -C.y};
-    }
+  for (int k = 0; k < KE; ++k) {
+    const int q = lane + 64 * k, r = q / LPW, c = q % LPW;
+    const bool on = r < M && c < nl;
+    const int rr = on ? r : 0, u = on ? l0 + c : l0;  // (lanes past the wave's elements repeat a bin: cross_power_ab's
+    const cf av = lds_read(&z[spec_at(rr, u)]);       //  wave-uniform branch wants every lane to take part)
+    const cf bv = on ? pv[k] : cf{1.f, 0.f};
+    cf C = u == 0 ? col0_bin(av, bv, rr, on) : cross_power_ab(av, bv, false);
+    if (box_zeros && u != 0 && (box_zero_line(rr, zq) || box_zero_line(u, zq))) C = {0.f, 0.f};
+    // conjugated for the inverse (a forward transform of conj C); column 0 keeps C itself until it is put together again below
+    if (on) z[spec_at(rr, u)] = u == 0 ? C : cf{C.x, -C.y};
   }
   wave_sync();
   if (wave == 0) {
@@ -803,46 +708,13 @@ have_current:
     wave_sync();
   }
   }  // (!XSINK)
-  if (nl > 0 && MOF_HABL != 1) pass_lines_static<SP>(z, tw, cols, l0, nl, lane, false);
+  if (nl > 0) pass_lines_static<SP>(z, tw, cols, l0, nl, lane, false);
   __syncthreads();
 
   // ---- Hermitian row pairs: line j carries rows y1 = 2j, y2 = 2j + 1: E[u] = D[y1][u] + i D[y2][u], D[y][M - u] = conj D[y][u];
-  //      column 0 holds (D[y][0], D[y][M/2]), both real. spec -> rows layout in place per line, every read before the first write.
-  if constexpr (!MOF_HALF_PAIR_SRC) {
-    constexpr int KU = (LPW * H + 63) / 64;
-    cf d1[KU], d2[KU];
-#pragma unroll
-    for (int k = 0; k < KU; ++k) {
-      const int q = lane + 64 * k, li = q / H, u = q % H;
-      d1[k] = d2[k] = cf{0.f, 0.f};
-      if (li < nl) {
-        d1[k] = lds_read(&z[spec_at(2 * (l0 + li), u)]);
-        d2[k] = lds_read(&z[spec_at(2 * (l0 + li) + 1, u)]);
-      }
-    }
-    wave_sync();
-#pragma unroll
-    for (int k = 0; k < KU; ++k) {
-      const int q = lane + 64 * k, li = q / H, u = q % H;
-      if (li < nl) {
-        if (u == 0) {
-          z[rows_at(l0 + li, 0)] = {d1[k].x, d2[k].x};
-          z[rows_at(l0 + li, H)] = {d1[k].y, d2[k].y};
-        } else {
-          z[rows_at(l0 + li, u)] = {d1[k].x - d2[k].y, d1[k].y + d2[k].x};
-          z[rows_at(l0 + li, M - u)] = {d1[k].x + d2[k].y, d2[k].x - d1[k].y};
-        }
-      }
-    }
-    wave_sync();
-  }
+  //      column 0 holds (D[y][0], D[y][M/2]), both real. spec -> rows layout on the way into the first stage (HalfPairSrc).
   Best best = {-__builtin_huge_valf(), 0x7fffffff};
-  if (nl > 0 && MOF_HABL != 1) {
-    if constexpr (MOF_HALF_PAIR_SRC)
-      pass_lines_static<SP, 0, 1, HalfScanSink, HalfPairSrc>(z, tw, rows, l0, nl, lane, false, HalfScanSink{&best, M, H}, HalfPairSrc{P2, M, SKM, SH, RSK});
-    else
-      pass_lines_static<SP, 0, 1, HalfScanSink>(z, tw, rows, l0, nl, lane, false, HalfScanSink{&best, M, H});
-  }
+  if (nl > 0) pass_lines_static<SP, 0, 1, HalfScanSink, HalfPairSrc>(z, tw, rows, l0, nl, lane, false, HalfScanSink{&best, M, H}, HalfPairSrc{P2, M, SKM, SH});
   best = wave_best(best);
   if (lane == 0) red[wave] = best;
   __syncthreads();

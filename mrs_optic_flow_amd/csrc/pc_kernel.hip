@@ -50,9 +50,6 @@ namespace mof {
 // CH = 3: the frames are interleaved BGR8 and the CV_RGB2GRAY conversion of the node's front end
 // (optic_flow.cpp:1622) is fused into the load, so raw camera frames are read from HBM exactly once.
 // PK = 1: the peak model of the reference's useOCL=true branch (cl/FftMethod.cl) instead of cv::phaseCorrelate's.
-#ifndef MOF_K1_FWD3
-#define MOF_K1_FWD3 1
-#endif
 #ifndef MOF_K1_MFMA_S1  // S1 of the three-stage forward transform on the matrix cores (pc_passes3.hpp)
 #define MOF_K1_MFMA_S1 0
 #endif
@@ -80,8 +77,8 @@ __global__ void __launch_bounds__(PcTraits<N>::T) pc_field_kernel(PcArgs a) {
   // than a static stride does, and the patch coordinates come from blockIdx without the integer divisions that
   // otherwise cost ~5 % of the kernel's VALU instructions.
   constexpr bool PERSIST = P::PERSIST;
-  constexpr bool FWD3 = MOF_K1_FWD3 && N == 64 && DS == 1 && !P::PERSIST && MOF_RAW_STAGE && T == 256;  // pc_passes3.hpp
-  constexpr bool RAW = MOF_RAW_STAGE && (N == 128 || N == 64) && DS == 1 && T == N * N / 16;  // raw pixel staging (pc_passes.hpp)  // raw pixel staging (pc_passes.hpp)
+  constexpr bool FWD3 = N == 64 && DS == 1;                  // the three-stage forward transform (pc_passes3.hpp)
+  constexpr bool RAW = (N == 128 || N == 64) && DS == 1;     // raw pixel staging (pc_passes.hpp)
   (void)patches;
   // (x0, y0) of a patch are in the units of the correlated image: full-res pixels, or quarter-res when DS = 4
   auto patch_base = [&](int p, const uint8_t* frames, size_t frame_stride) -> const uint8_t* {
@@ -143,16 +140,6 @@ __global__ void __launch_bounds__(PcTraits<N>::T) pc_field_kernel(PcArgs a) {
   lane &= 63;             // give the value ranges back to the optimiser (they fold the skew and the
   wave &= P::WAVES - 1;   // Hermitian row cases at compile time)
   const int tid = wave * 64 + lane;
-#ifdef MOF_EXTRA_VALU  // diagnostic build: MOF_EXTRA_VALU independent FMAs per wave and patch (is K1 VALU-issue bound?)
-  {
-    float d0 = (float)lane, d1 = 1.f, d2 = 2.f, d3 = 3.f;
-#pragma unroll
-    for (int i = 0; i < MOF_EXTRA_VALU / 4; ++i)
-      asm volatile("v_fma_f32 %0, %0, %0, %0\n\tv_fma_f32 %1, %1, %1, %1\n\tv_fma_f32 %2, %2, %2, %2\n\tv_fma_f32 %3, %3, %3, %3"
-                   : "+v"(d0), "+v"(d1), "+v"(d2), "+v"(d3));
-    if (d0 + d1 + d2 + d3 == 12345.678f) a.out[0] = d0;
-  }
-#endif
   // ---- the wave's own LPW rows: u8 -> f32 (exact), z = cur + i*prev  (convertTo, :1805-1806)
   {
     const int row = wave * LPW + ord1<N>(lane / CPR), col = (lane % CPR) * 16;
@@ -189,9 +176,6 @@ __global__ void __launch_bounds__(PcTraits<N>::T) pc_field_kernel(PcArgs a) {
         for (int q = 0; q < 4; ++q)
 #pragma unroll
           for (int b = 0; b < 4; ++b) {
-#ifdef MOF_ABLATE_NOLOADW  // diagnostic build: one tile store per lane instead of 16 (results wrong by design)
-            if (q + b) continue;
-#endif
             z[zaddr<N>(row, col + q * 4 + b)] = {(float)((cw[q] >> (8 * b)) & 0xffu), (float)((pw[q] >> (8 * b)) & 0xffu)};
           }
         if constexpr (PERSIST) {
@@ -231,7 +215,6 @@ __global__ void __launch_bounds__(PcTraits<N>::T) pc_field_kernel(PcArgs a) {
   }
 
   // ---- forward 2-D transform of z: rows (wave-local), barrier, columns (wave-local)  (dft x2, :1491-1493)
-#ifndef MOF_ABLATE_NOFWD
   if constexpr (FWD3) {
 #if MOF_K1_MFMA_S1
     fwd3_rows_mfma(z, wave, lane, a.twiddles);
@@ -247,7 +230,6 @@ __global__ void __launch_bounds__(PcTraits<N>::T) pc_field_kernel(PcArgs a) {
     __syncthreads();
     col_pass_fwd<N>(z, wave * LPW, lane, tw_col);
   }
-#endif
   __syncthreads();
 
   // ---- untangle A = FFT(cur), B = FFT(prev); P = A conj(B); C = P|P| / (|P|^2 + eps)
@@ -271,14 +253,9 @@ __global__ void __launch_bounds__(PcTraits<N>::T) pc_field_kernel(PcArgs a) {
   }
   // ---- inverse (unscaled) of the Hermitian spectrum: forward transforms of conj(C); rows 0..H-1 only,
   //      then column pairs  (idft :1497)
-#if MOF_XPOW_SPLIT
   if (wave == 0) row_pass_xpow<N, PK, true>(z, 0, lane, tw_row);
   else if (wave < P::WI) row_pass_xpow<N, PK, false>(z, wave * P::LI, lane, tw_row);
-#else
-  if (wave < P::WI) row_pass_xpow<N, PK, true>(z, wave * P::LI, lane, tw_row);
-#endif
   } else {
-#ifndef MOF_ABLATE_NOPW
   {
     // rows 1..H-1: every u; partner (N-v, N-u) lies in the untouched lower half. Fixed trip count, so every
     // address is a base plus a compile-time offset.
@@ -313,22 +290,15 @@ __global__ void __launch_bounds__(PcTraits<N>::T) pc_field_kernel(PcArgs a) {
       if (!self) z[zaddr<N>(0, um)] = {C0.x - Ch.y, Ch.x + C0.y};
     }
   }
-#endif
   __syncthreads();
 
   // ---- inverse (unscaled) of the Hermitian spectrum: forward transforms of conj(C); rows 0..H-1 only,
   //      then column pairs  (idft :1497)
-#ifndef MOF_ABLATE_NOINV
   if (wave < P::WI) row_pass<N, P::LI>(z, wave * P::LI, lane, tw_row);
-#endif
   }  // FUSE_XPOW
   __syncthreads();
   Best best = {-__builtin_huge_valf(), 0x7fffffff};
-#ifndef MOF_ABLATE_NOINV
   if (wave < P::WI) best = col_pass_inv<N, PK>(z, wave * P::LI, lane, tw_col, a.search_radius);
-#else
-  best = Best{z[zaddr<N>(lane, wave)].x, lane * N + wave};
-#endif
   best = wave_best(best);
   if (lane == 0) red[wave] = best;
   __syncthreads();
@@ -337,10 +307,6 @@ __global__ void __launch_bounds__(PcTraits<N>::T) pc_field_kernel(PcArgs a) {
   //      before a second barrier releases the other waves to overwrite the tile with the next patch.
   float wval = 0.f;
   bool degenerate = false;
-#ifdef MOF_ABLATE_NOTAIL
-  if (wave == 0 && lane == 0) { a.out[2 * (size_t)p] = best.v; a.out[2 * (size_t)p + 1] = (double)best.idx; }
-  continue;
-#endif
   if (wave == 0) {
     const int my_code = const_code[lane & 15];
     for (int w = 1; w < P::WAVES; ++w) best = better(best, red[w]);

@@ -42,24 +42,6 @@ struct ScanSink {
   }
 };
 
-// the conjugated normalised cross-power spectrum as the source of the inverse row pass (rows 1 .. H-1; row 0 holds the packed rows
-// 0 and H already): bin (v, u) from Z(v, u) and its partner Z(m - v, m - u) in the untouched lower half of the tile
-struct XpowSrc {
-  static constexpr bool active = true;
-  int m, H, pitch, skew_mask;
-  bool box_zeros;
-  int zq;  // box_zeros: the constant box's exact-zero lines are the multiples of zq (pc_common.hpp, box_zero_period)
-  __device__ __forceinline__ cf operator()(const cf* z, int v, int u) const {
-    const cf zk = lds_read(&z[v * pitch + u + ((u >> 3) & skew_mask)]);
-    if (v == 0) return zk;
-    const int um = u == 0 ? 0 : m - u;
-    const cf zm = lds_read(&z[(m - v) * pitch + um + ((um >> 3) & skew_mask)]);
-    cf C = cross_power<0>(zk, zm, false);
-    if (box_zeros && (box_zero_line(u, zq) || box_zero_line(v, zq))) C = {0.f, 0.f};
-    return {C.x, -C.y};
-  }
-};
-
 // MS > 0: the instantiation for ONE transform size, whose plan is a compile-time constant (pc_static_plan(MS) is what the host
 // builds for it; only n -- the unpadded size -- and the launch geometry stay run-time values): radices, strides, divisions and
 // loop counts fold away. MS = 0: the plan is read from the argument (sizes below 16, and the BGR / long-range / OpenCL-model
@@ -72,18 +54,6 @@ struct StaticPlanOf {
   static_assert(MS == 0 || P.threads > 0, "no static plan for this size");
 };
 
-#ifndef MOF_PLANNED_XPOW_FUSED  // 1: the cross-power spectrum formed on the way into the inverse row pass (XpowSrc). Measured r04, same box:
-                                // SLOWER (p96 753 -> 689 k, p60 1.05 -> 1.03 M pairs/s): it puts the whole cross-power on the waves that own
-                                // the H inverse rows, the sweep of its own spreads it over every thread (as K1 found at N = 128)
-#define MOF_PLANNED_XPOW_FUSED 0
-#endif
-#ifndef MOF_PLANNED_SCAN_FUSED  // 0: the arg-max as a sweep of its own (A/B)
-#define MOF_PLANNED_SCAN_FUSED 1
-#endif
-#ifndef MOF_GABL  // diagnostic builds (results wrong by design): 1 no transform passes, 2 no cross-power, 3 no arg-max scan, 4 no pixel loads,
-                  // 5 no centroid tail, 6 no load phase at all, 7 none of 1-6 (what is left: launch, twiddles, barriers)
-#define MOF_GABL 0
-#endif
 template <int DS, int CH, int PK, int MS>
 __global__ void __launch_bounds__(StaticPlanOf<MS>::T, StaticPlanOf<MS>::WPE) pc_generic_kernel(PcArgs a, PcPlan pl_arg) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_g[];
@@ -167,7 +137,7 @@ __global__ void __launch_bounds__(StaticPlanOf<MS>::T, StaticPlanOf<MS>::WPE) pc
         return y;
       };
 #pragma unroll 1
-      for (int q0 = tid; q0 < ((MOF_GABL == 6 || MOF_GABL == 7) ? 0 : nchunks); q0 += CMAX * T) {
+      for (int q0 = tid; q0 < nchunks; q0 += CMAX * T) {
         uint32_t cw[CMAX], pw[CMAX];
 #pragma unroll
         for (int k = 0; k < CMAX; ++k) {
@@ -175,7 +145,7 @@ __global__ void __launch_bounds__(StaticPlanOf<MS>::T, StaticPlanOf<MS>::WPE) pc
           int x0;
           const int y = coords(q, &x0);
           cw[k] = pw[k] = 0u;
-          if (MOF_GABL != 4 && q < nchunks && y < n && x0 < n) {
+          if (q < nchunks && y < n && x0 < n) {
             if (x0 + 3 < n) {
               cw[k] = fetch_px4<DS, CH>(cur, a.pitch, y, x0);
               pw[k] = fetch_px4<DS, CH>(prev, a.pitch, y, x0);
@@ -249,7 +219,6 @@ __global__ void __launch_bounds__(StaticPlanOf<MS>::T, StaticPlanOf<MS>::WPE) pc
   };
 
   auto run_pass = [&](const Walk& w, int l0, int nl, bool h) {
-    if (MOF_GABL == 1 || MOF_GABL == 7) return;
     if constexpr (MS > 0) pass_lines_static<StaticPlanOf<MS>>(z, tw, w, l0, nl, lane, h);
     else pass_lines<false, false>(z, tw, pl, w, l0, nl, lane, h);
   };
@@ -288,15 +257,12 @@ __global__ void __launch_bounds__(StaticPlanOf<MS>::T, StaticPlanOf<MS>::WPE) pc
     }
     return cross_power_ab<PK>(cf{2.f * A.x, 2.f * A.y}, cf{2.f * B.x, 2.f * B.y}, real_only);
   };
-  // Compile-time plan, even M, cv::phaseCorrelate's model, no closed-form box: rows 1 .. H-1 get their cross-power spectrum on the
-  // way INTO the inverse row pass (XpowSrc) -- one tile sweep (a write and a read of half the tile, its index arithmetic) less
-  constexpr bool XPOW_FUSABLE = MS > 0 && PK == 0 && (StaticPlanOf<MS>::P.m % 2 == 0) && MOF_PLANNED_XPOW_FUSED;
-  const bool xpow_fused = XPOW_FUSABLE && !one_box;
-  if (MOF_GABL == 2 || MOF_GABL == 7) {
-  } else if (herm) {
+  // A sweep of its own over every thread. (Formed on the way INTO the inverse row pass instead, it measured slower, p96 753 -> 689 k and
+  // p60 1.05 -> 1.03 M pairs/s, r04: that puts the whole cross-power on the waves that own the H inverse rows, as K1 found at N = 128.)
+  if (herm) {
     // rows 1 .. H-1, every u: the partner (m - v, m - u) lies in the untouched lower half
     // (a counted loop: with a compile-time plan the trip count is a constant and UNR trips are in flight)
-    const int xtrips = xpow_fused ? 0 : ((H - 1) * m + T - 1) / T;
+    const int xtrips = ((H - 1) * m + T - 1) / T;
     if (!one_box) {  // (the hot loop keeps the packed form alone: the closed-form branch inside it cost 4 % on every pair)
 #pragma clang loop unroll_count(UNR)
       for (int k = 0; k < xtrips; ++k) {
@@ -358,29 +324,19 @@ __global__ void __launch_bounds__(StaticPlanOf<MS>::T, StaticPlanOf<MS>::WPE) pc
 
   // Compile-time plan, even M, cv::phaseCorrelate's peak model: the first maximum of the shifted surface (fftShift :1257-1323,
   // minMaxLoc :1539) is taken from the registers of the inverse transform's last stage -- the separate sweep over the tile was 9 %
-  // of the kernel (p60, tools/ab_planned_phases.sh). Ties go to the smaller shifted index either way (better()).
-  constexpr bool SCAN_FUSED = MS > 0 && PK == 0 && (StaticPlanOf<MS>::P.m % 2 == 0) && MOF_PLANNED_SCAN_FUSED;
+  // of the kernel (p60). Ties go to the smaller shifted index either way (better()).
+  constexpr bool SCAN_FUSED = MS > 0 && PK == 0 && (StaticPlanOf<MS>::P.m % 2 == 0);
   Best best = {-__builtin_huge_valf(), 0x7fffffff};
   // ---- inverse (unscaled, idft :1497) as forward transforms of conj C
   {
     int l0, nl;
     my_lines(herm ? H : m, &l0, &nl);
-    if constexpr (XPOW_FUSABLE) {
-      if (xpow_fused) {
-        if (nl > 0 && MOF_GABL != 1 && MOF_GABL != 7)
-          pass_lines_static<StaticPlanOf<MS>, 0, 1, NoSink, XpowSrc>(z, tw, rows, l0, nl, lane, false, NoSink{},
-                                                                     XpowSrc{m, H, pl.pitch, pl.skew_mask, box_zeros, zq});
-      } else if (nl > 0) {
-        run_pass(rows, l0, nl, false);
-      }
-    } else {
-      if (nl > 0) run_pass(rows, l0, nl, false);
-    }
+    if (nl > 0) run_pass(rows, l0, nl, false);
     __syncthreads();
     // herm: column pairs (c, c + H), z(y, c) = (S[y][c], S[y][c + H]); else z(y, x).x = S[y][x]
     if constexpr (SCAN_FUSED) {
       // the arg-max rides the last stage: line c, element y carries the surface values at (y, c) and (y, c + H)
-      if (nl > 0 && MOF_GABL != 1 && MOF_GABL != 7)
+      if (nl > 0)
         pass_lines_static<StaticPlanOf<MS>, 0, 1, ScanSink>(z, tw, cols, l0, nl, lane, herm, ScanSink{&best, m, H});
     } else {
       if (nl > 0) run_pass(cols, l0, nl, herm);
@@ -405,7 +361,7 @@ __global__ void __launch_bounds__(StaticPlanOf<MS>::T, StaticPlanOf<MS>::WPE) pc
   // ---- first maximum of the fft-shifted surface in row-major order (fftShift :1257-1323: index i -> (i + (m >> 1)) mod m for
   //      even and odd m alike; minMaxLoc :1539)
 #pragma clang loop unroll_count(UNR)
-  for (int y = wave; y < ((SCAN_FUSED || MOF_GABL == 3 || MOF_GABL == 7) ? 0 : m); y += WAVES) {
+  for (int y = wave; y < (SCAN_FUSED ? 0 : m); y += WAVES) {
     const int ys = y + H >= m ? y + H - m : y + H;
 #pragma unroll 1
     for (int x = lane; x < m; x += 64) {
@@ -418,8 +374,7 @@ __global__ void __launch_bounds__(StaticPlanOf<MS>::T, StaticPlanOf<MS>::WPE) pc
   __syncthreads();
 
   // ---- weighted centroid in double + validity gate (:1337-1383, :1838-1856), wave 0
-  if ((MOF_GABL == 5 || MOF_GABL == 7) && tid == 0) a.out[2 * p] = a.out[2 * p + 1] = (double)best.v;
-  if (wave == 0 && MOF_GABL != 5 && MOF_GABL != 7) {
+  if (wave == 0) {
     for (int w = 1; w < WAVES; ++w) best = better(best, red[w]);
     int ys, xs;
     double val = 0.0;

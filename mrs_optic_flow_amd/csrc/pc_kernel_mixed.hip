@@ -29,33 +29,21 @@ constexpr int N = 120, H = 60, R1 = 15, R2 = 8, LPW = 8, WAVES = N / LPW, T = WA
 // Row pitch 136 = 8 (mod 32) complex elements: with the lane maps below every ds_read_b64 group (32 lanes, 64 banks)
 // and every ds_write_b64 group (16 lanes, 32 banks) of the transform passes hits distinct banks
 // (tools/design/lds_conflicts_120.py; pitch 121 cost 2.3x the conflict-free LDS cycles, SQ_LDS_BANK_CONFLICT = 53 %).
-#ifndef MOF_PITCH120
-#define MOF_PITCH120 136
-#endif
-constexpr int PITCH = MOF_PITCH120;
-#ifndef MOF_TW120_LDS  // 1: the 120 inter-stage twiddles live in LDS (one copy per persistent workgroup); 0: fetched from the L1-resident table (r01-r04)
-#define MOF_TW120_LDS 1
-#endif
-constexpr size_t LDS_BYTES_120 = sizeof(float) * 2 * (size_t)N * PITCH + 64 * sizeof(Best) + (MOF_TW120_LDS ? sizeof(float) * 2 * N : 0);
+constexpr int PITCH = 136;
+// the tile, the reduction slots and the 120 inter-stage twiddles (one LDS copy per persistent workgroup; r01-r04 fetched them from the
+// L1-resident table)
+constexpr size_t LDS_BYTES_120 = sizeof(float) * 2 * (size_t)N * PITCH + 64 * sizeof(Best) + sizeof(float) * 2 * N;
 
 __device__ __forceinline__ int za(int r, int c) { return r * PITCH + c; }
 
 __device__ __forceinline__ cf twiddle(const float* __restrict__ table, int idx) {  // W_120^idx, idx < 120
-#if MOF_TW120_LDS
   return lds_read(reinterpret_cast<const cf*>(table) + idx);  // (`table` points into LDS: the kernel copied the 120 entries there)
-#else
-  const float2 t = *reinterpret_cast<const float2*>(table + 2 * idx);
-  return {t.x, t.y};
-#endif
 }
 
 // ---- raw pixel staging (as pc_passes.hpp, raw_store): a chunk's 8 + 8 pixels leave as ONE ds_write_b128 of interleaved
 // bytes (c0 p0 c1 p1 ..) into a per-wave area that overlays the wave's own tile rows, and the first row stage reads its
 // operands with ds_read_u16 and converts them on the way into the butterfly -- 8 ds_write_b64 (48 cycles of the
 // VGPR -> LDS path) per chunk less. Slot = line within the wave, 272 B apart (four lines of a 32-lane group 16 B apart).
-#ifndef MOF_RAW_STAGE
-#define MOF_RAW_STAGE 1
-#endif
 constexpr int RAW_PITCH = 272;
 __device__ __forceinline__ unsigned char* raw_area(cf* z, int line0) { return reinterpret_cast<unsigned char*>(z + za(line0, 0)); }
 __device__ __forceinline__ void raw_store8(cf* z, int line0, int slot, int chunk, const uint32_t* c, const uint32_t* pv) {
@@ -257,7 +245,6 @@ __global__ void __launch_bounds__(T) pc_field_kernel_120(PcArgs a) {
 
   const int tid0 = threadIdx.x, lane0 = tid0 & 63, wave0 = tid0 >> 6;
   const int patches = a.grid_x * a.grid_y;
-#if MOF_TW120_LDS
   // r05: the second-stage twiddles W_120^{kx} (14 per lane and pass) were gathers from the L1-resident global table -- 64 lanes, up
   // to 8 cache lines per instruction through the texture addresser, ~1260 of them per patch and CU; one LDS copy per persistent
   // workgroup turns them into ds_read_b64
@@ -265,9 +252,6 @@ __global__ void __launch_bounds__(T) pc_field_kernel_120(PcArgs a) {
   for (int k = tid0; k < N; k += T) tw_lds[k] = {a.twiddles[2 * k], a.twiddles[2 * k + 1]};
   __syncthreads();
   const float* tw = reinterpret_cast<const float*>(tw_lds);
-#else
-  const float* tw = a.twiddles;
-#endif
   auto patch_ptr = [&](int pp, const uint8_t* frames, size_t frame_stride) -> const uint8_t* {
     const int pair = pp / patches, patch = pp % patches;
     const int x0 = a.origin_x + (patch % a.grid_x) * a.stride_x, y0 = a.origin_y + (patch / a.grid_x) * a.stride_y;
@@ -360,18 +344,9 @@ __global__ void __launch_bounds__(T) pc_field_kernel_120(PcArgs a) {
         asm volatile("");
         const_track(pv, 2, b == 0, fp, dp);
       }
-      if constexpr (MOF_RAW_STAGE) {
-        raw_store8(z, wave * LPW, q / (N / 8), q % (N / 8), c, pv);
-        continue;
-      }
-      // The 8 pixels of a chunk are stored in a per-lane rotated order: straight order puts the 16 lanes of a
-      // ds_write_b64 group on two banks (chunks are 8 elements apart), an 8-way conflict on every store.
-      const int rot = ((q % (N / 8)) >> 1) & 7;
-      const uint64_t cr = __builtin_rotateright64(((uint64_t)c[1] << 32) | c[0], 8 * rot);
-      const uint64_t pr = __builtin_rotateright64(((uint64_t)pv[1] << 32) | pv[0], 8 * rot);
-#pragma unroll
-      for (int i = 0; i < 8; ++i)  // byte i of the rotated word is pixel (i + rot) & 7
-        z[za(row, col + ((i + rot) & 7))] = {(float)((uint32_t)(cr >> (8 * i)) & 0xffu), (float)((uint32_t)(pr >> (8 * i)) & 0xffu)};
+      raw_store8(z, wave * LPW, q / (N / 8), q % (N / 8), c, pv);
+      continue;  // (redundant, kept: without it the compiler lays this unrolled loop out differently -- same arithmetic, other schedule;
+                 //  profiles/switch_retirement.txt, section 1)
     }
   }
   if (p + (int)gridDim.x < a.total) prefetch(p + (int)gridDim.x);
@@ -390,7 +365,7 @@ __global__ void __launch_bounds__(T) pc_field_kernel_120(PcArgs a) {
   wave_sync();
 
   // ---- forward 2-D transform: rows (wave-local), barrier, columns (wave-local)
-  row_pass<MOF_RAW_STAGE != 0>(z, wave * LPW, N, lane, tw);
+  row_pass<true>(z, wave * LPW, N, lane, tw);
   __syncthreads();
   col_pass_fwd(z, wave * LPW, lane, tw);
   __syncthreads();

@@ -49,26 +49,18 @@ constexpr size_t LDS_BYTES_Q64 = sizeof(cf) * TILE + sizeof(Best) * WAVES + size
 // skewed tile: rows 16 apart are shifted by 4 elements so that row-blocked column walks hit distinct banks
 __device__ __forceinline__ int zq(int v, int u) { return v * PITCH + u + 4 * (v >> 4); }
 
-// Value of lane quad_perm[q] of the same quad. MOF_QUAD_XCHG selects the carrier: 0 = DPP (a v_mov_b32_dpp on the
-// VALU; hipcc does not fold it into the consuming v_fmac), 1 = ds_swizzle_b32 in quad-perm mode (the LDS crossbar, no
-// memory access), 2 = v_fmac_f32 with a DPP operand, hand-written (see quad_radix4).
-#ifndef MOF_QUAD_XCHG
-#define MOF_QUAD_XCHG 2
-#endif
+// Value of lane quad_perm[q] of the same quad, by DPP (a v_mov_b32_dpp on the VALU; hipcc does not fold it into the consuming
+// v_fmac, so the radix-4 below carries v_fmac_f32 with a DPP operand hand-written; ds_swizzle_b32 in quad-perm mode -- the LDS
+// crossbar, no memory access -- was the third carrier tried).
 template <int CTRL>
 __device__ __forceinline__ float dpp(float x) {
-#if MOF_QUAD_XCHG == 1
-  return __builtin_bit_cast(float, __builtin_amdgcn_ds_swizzle(__builtin_bit_cast(int, x), 0x8000 | CTRL));
-#else
   return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), CTRL, 0xf, 0xf, true));
-#endif
 }
 constexpr int QP_XOR1 = 0xB1;  // quad_perm [1,0,3,2]
 constexpr int QP_XOR2 = 0x4E;  // quad_perm [2,3,0,1]
 constexpr int QP_0132 = 0xB4;  // quad_perm [0,1,3,2]
 
 // radix-4 across the quad: t = own + sa * partner(FIRST); lane 3 turns by +i; own + sb * partner(SECOND)
-#if MOF_QUAD_XCHG == 2
 // Hand-scheduled: v_fmac_f32 with a DPP operand does exchange and butterfly in ONE instruction (hipcc never folds the
 // v_mov_b32_dpp into the fmac). The compiler cannot see DPP reads inside inline asm, so the block provides the wait
 // states itself: s_nop 1 covers "VALU wrote the register a DPP operand reads" for whatever precedes the block, and
@@ -119,19 +111,6 @@ __device__ __forceinline__ void quad_radix4(cf* v, float sa, float sb, bool /*q3
     v[k + 3] = {t3, y3};
   }
 }
-#else
-template <int FIRST, int SECOND>
-__device__ __forceinline__ void quad_radix4(cf* v, float sa, float sb, bool q3) {
-#pragma unroll
-  for (int k = 0; k < 16; ++k) {
-    const float tx = __builtin_fmaf(dpp<FIRST>(v[k].x), sa, v[k].x);
-    const float ty = __builtin_fmaf(dpp<FIRST>(v[k].y), sa, v[k].y);
-    const float rx = q3 ? -ty : tx, ry = q3 ? tx : ty;
-    v[k].x = __builtin_fmaf(dpp<SECOND>(rx), sb, rx);
-    v[k].y = __builtin_fmaf(dpp<SECOND>(ry), sb, ry);
-  }
-}
-#endif
 
 struct QuadConst {
   float dit_sa, dit_sb, dif_sa, dif_sb;
@@ -235,13 +214,8 @@ __global__ void __launch_bounds__(T, 4) pc_quad64_kernel(PcArgs a) {
     MOF_QUAD_LANE();
     const int row = wave * 16 + g;
     float fc[16], fp[16];
-#ifdef MOF_QABL_NOLOAD  // diagnostic build: no HBM access
-#pragma unroll
-    for (int j = 0; j < 16; ++j) { fc[j] = (float)((lane * 7 + j * 13 + p) & 255); fp[j] = (float)((lane * 11 + j * 5 + p) & 255); }
-#else
     load16<DS, CH>(cur, a.pitch, row, 16 * q, fc);
     load16<DS, CH>(prev, a.pitch, row, 16 * q, fp);
-#endif
 #pragma unroll
     for (int j = 0; j < 16; ++j) v[j] = {fc[j], fp[j]};
     pass_blocked_in(v, c);
@@ -249,10 +223,6 @@ __global__ void __launch_bounds__(T, 4) pc_quad64_kernel(PcArgs a) {
     for (int k = 0; k < 16; ++k) z[zq(row, k1 + 4 * k)] = v[k];
   }
   __syncthreads();
-#if defined(MOF_QABL_STOP) && MOF_QABL_STOP == 1
-  if (tid == 0) a.out[2 * (size_t)p] = z[p & 1023].x;
-  return;
-#endif
 
   // ---- B: forward transform of the quad's column (dft x2, :1491-1493)
   {
@@ -265,10 +235,6 @@ __global__ void __launch_bounds__(T, 4) pc_quad64_kernel(PcArgs a) {
     for (int k = 0; k < 16; ++k) z[zq(k + 16 * q, u)] = v[k];
   }
   __syncthreads();
-#if defined(MOF_QABL_STOP) && MOF_QABL_STOP == 2
-  if (tid == 0) a.out[2 * (size_t)p] = z[p & 1023].x;
-  return;
-#endif
 
   // ---- C: untangle A = FFT(cur), B = FFT(prev); C = normalised cross-power (mulSpectrums :1494, magSpectrums :70-168,
   //      divSpectrums :1086-1251, real-only slots :107-109 / :1127-1129); column transform of D = conj(C) for columns
@@ -310,10 +276,6 @@ __global__ void __launch_bounds__(T, 4) pc_quad64_kernel(PcArgs a) {
     for (int k = 0; k < 16; ++k) z[zq(k1 + 4 * k, 0)] = v[k];
   }
   __syncthreads();
-#if defined(MOF_QABL_STOP) && MOF_QABL_STOP == 3
-  if (tid == 0) a.out[2 * (size_t)p] = z[p & 1023].x;
-  return;
-#endif
 
   // ---- D: rows y and y + 32 ride one complex transform: E[u] = G[y][u] + i G[y+32][u], E[N-u] = conj(G[y][u]) +
   //      i conj(G[y+32][u]) (idft :1497, unscaled); arg-max from registers (fftShift :1297-1305, minMaxLoc :1539)

@@ -8,19 +8,6 @@
 #include "mof_kernels.h"
 #include "pc_common.hpp"
 
-#ifndef MOF_FUSE_XPOW
-#define MOF_FUSE_XPOW 1  // 1: where it pays (PcTraits::FUSE_XPOW), the cross-power spectrum is formed inside the inverse row pass
-#endif
-#ifndef MOF_FUSE_XPOW_MAXN
-#define MOF_FUSE_XPOW_MAXN 64  // (128: measured again under the r03 layout)
-#endif
-#ifndef MOF_XPOW_SPLIT
-#define MOF_XPOW_SPLIT 1  // the inverse row pass of the waves that do not own row 0 carries no select for the packed row
-#endif
-#ifndef MOF_FUSED_TW
-#define MOF_FUSED_TW 1  // twiddles of the radix-8 second stage fused into its first layer (butterfly8_tw)
-#endif
-
 namespace mof {
 
 namespace {
@@ -35,18 +22,9 @@ template <>
 struct Cfg<64> {
   static constexpr int R1 = 8, R2 = 8, SK = 3, PITCH = 72;
 };
-#ifndef MOF_SK128
-#define MOF_SK128 4
-#endif
-#ifndef MOF_LAYOUT128
-#define MOF_LAYOUT128 1  // 1: pitch 140 + row skew + class-ordered lane maps (below); 0: the r01/r02 layout (pitch 136)
-#endif
-#ifndef MOF_PITCH128
-#define MOF_PITCH128 (MOF_LAYOUT128 ? 140 : 136)
-#endif
 template <>
-struct Cfg<128> {
-  static constexpr int R1 = 16, R2 = 8, SK = MOF_SK128, PITCH = MOF_PITCH128;
+struct Cfg<128> {  // pitch 140 + row skew + class-ordered lane maps (below); the r01/r02 layout was pitch 136, lines in order
+  static constexpr int R1 = 16, R2 = 8, SK = 4, PITCH = 140;
 };
 
 // ---- bank layout of the 128 x 128 tile (r03; model: tools/design/lds_conflicts_128.py, 1.44x -> 1.05x conflict-free) ----
@@ -63,26 +41,20 @@ struct Cfg<128> {
 // Rows 16 x + k of two lane-group neighbours x, x + 2 differ by 4480 = 0 (mod 16): the 8 (r >> 5) row skew separates them.
 template <int N>
 __device__ __forceinline__ int ord1(int j) {  // j = 0..7 -> 0 2 4 6 1 3 5 7
-  if constexpr (N == 128 && MOF_LAYOUT128) return 2 * (j & 3) + (j >> 2);
+  if constexpr (N == 128) return 2 * (j & 3) + (j >> 2);
   else return j;
 }
 template <int N>
 __device__ __forceinline__ int ord2(int j) {  // j = 0..7 -> 0 4 2 6 1 5 3 7
-  if constexpr (N == 128 && MOF_LAYOUT128) return ((j & 1) << 2) | (j & 2) | (j >> 2);
+  if constexpr (N == 128) return ((j & 1) << 2) | (j & 2) | (j >> 2);
   else return j;
 }
 
 }  // namespace
 
-#ifndef MOF_SKEW64
-#define MOF_SKEW64 1  // 64 x 64 tile: rows 8 x + k of lane-group neighbours x, x + 1 are 576 = 0 (mod 16) apart -> 8 (r >> 3) row skew
-#endif
 template <int N>
 struct PcTraits {
-#ifndef MOF_K1_T64
-#define MOF_K1_T64 256
-#endif
-  static constexpr int T = (N == 64) ? MOF_K1_T64 : N * N / 16;
+  static constexpr int T = N * N / 16;
   static constexpr int WAVES = T / 64;
   static constexpr int LPW = N / WAVES;  // lines (rows or columns) owned by a wave
   static constexpr int R1 = Cfg<N>::R1, R2 = Cfg<N>::R2, SK = Cfg<N>::SK, PITCH = Cfg<N>::PITCH;
@@ -91,28 +63,26 @@ struct PcTraits {
   static constexpr int LI = (LPW / 2 > 64 / BMIN) ? LPW / 2 : 64 / BMIN;
   static constexpr int WI = (N / 2) / LI;
   // complex elements of the tile, incl. the row skew (zaddr): 8 (r >> 5) at N = 128, 8 (r >> 3) at N = 64
-  static constexpr int TILE = N * PITCH + ((N == 128 && MOF_LAYOUT128) ? 24 : 0) + ((N == 64 && MOF_SKEW64) ? 56 : 0);
+  static constexpr int TILE = N * PITCH + (N == 128 ? 24 : 0) + (N == 64 ? 56 : 0);
   static constexpr size_t LDS_BYTES = sizeof(float) * 2 * (size_t)TILE + 64 * sizeof(Best);
-#ifndef MOF_PERSIST_MIN_N
-#define MOF_PERSIST_MIN_N 128
-#endif
-  static constexpr bool PERSIST = N >= MOF_PERSIST_MIN_N;  // see pc_field_kernel
+  static constexpr bool PERSIST = N >= 128;  // see pc_field_kernel
   // cross-power spectrum inside the inverse row pass (row_pass_xpow): one barrier and 1.5 tile passes fewer. Same-box
   // A/B: +4.4 % at N = 64 (several workgroups per CU, latency-bound), -4.4 % at N = 128 (one workgroup per CU: the
   // separate pass spreads the cross-power over all 16 waves, the fused one over the 8 that run the inverse)
-  static constexpr bool FUSE_XPOW = MOF_FUSE_XPOW && N <= MOF_FUSE_XPOW_MAXN;
+  static constexpr bool FUSE_XPOW = N <= 64;
   static_assert(R1 * R2 == N && T % 64 == 0 && 64 % R1 == 0 && 64 % R2 == 0, "bad plan");
 };
 
 // z(r, c): skewed tile address in complex units
 template <int N>
 __device__ __forceinline__ int zaddr(int r, int c) {
-  if constexpr (N == 128 && MOF_LAYOUT128) return r * PcTraits<N>::PITCH + 8 * (r >> 5) + c + (c >> PcTraits<N>::SK);
-  else if constexpr (N == 64 && MOF_SKEW64) return r * PcTraits<N>::PITCH + 8 * (r >> 3) + c + (c >> PcTraits<N>::SK);
+  if constexpr (N == 128) return r * PcTraits<N>::PITCH + 8 * (r >> 5) + c + (c >> PcTraits<N>::SK);
+  // 64 x 64 tile: rows 8 x + k of lane-group neighbours x, x + 1 are 576 = 0 (mod 16) apart -> 8 (r >> 3) row skew
+  else if constexpr (N == 64) return r * PcTraits<N>::PITCH + 8 * (r >> 3) + c + (c >> PcTraits<N>::SK);
   else return r * PcTraits<N>::PITCH + c + (c >> PcTraits<N>::SK);
 }
 
-// ---- raw pixel staging (MOF_RAW_STAGE, N = 128) -------------------------------------------------------------------
+// ---- raw pixel staging (N = 64 and 128) ---------------------------------------------------------------------------
 // ds_write_b64 costs 6 cycles of the VGPR -> LDS path per wave-instruction (MI355X_MICROARCH.md, LDS table) and that path,
 // not the arithmetic, is what the 128 x 128 kernel waits for. Converting a lane's 16 + 16 pixels to 16 complex floats
 // BEFORE the tile store is 16 such stores; instead the lane interleaves the raw bytes (c0 p0 c1 p1 ..: 8 v_perm) and
@@ -121,9 +91,6 @@ __device__ __forceinline__ int zaddr(int r, int c) {
 // Slot s = lane / CPR of the wave holds row line0 + ord1(s); a slot pitch of 2 N + 16 B puts the four slots of a 32-lane read
 // group 16 B apart (mod 128): conflict-free like the writes (8 lanes x 16 B at a 32-B stride; N = 64: two slots interleave).
 // N = 64 (c2): same-box A/B in DESIGN.md.
-#ifndef MOF_RAW_STAGE
-#define MOF_RAW_STAGE 1
-#endif
 template <int N>
 struct RawCfg {
   static constexpr int PITCH = 2 * N + 16, CPR = N / 16;  // bytes per slot (272 / 144), 16-pixel chunks per row
@@ -217,13 +184,9 @@ __device__ __forceinline__ void row_pass(cf* __restrict__ z, int line0, int lane
 #pragma unroll
       for (int k = 0; k < R2; ++k) {
         cf a = lds_read(&z[zaddr<N>(line, x + k * R1)]);
-#ifdef MOF_ABLATE_NOBFLY
-        v[b][k] = a;
-#else
-        v[b][k] = (k == 0 || (R2 == 8 && MOF_FUSED_TW)) ? a : cmul(a, tw_row[k - 1]);
-#endif
+        v[b][k] = (k == 0 || R2 == 8) ? a : cmul(a, tw_row[k - 1]);
       }
-      if constexpr (R2 == 8 && MOF_FUSED_TW) butterfly8_tw(v[b], tw_row);
+      if constexpr (R2 == 8) butterfly8_tw(v[b], tw_row);
       else butterfly<R2>(v[b]);
     }
     wave_sync();
@@ -238,7 +201,7 @@ __device__ __forceinline__ void row_pass(cf* __restrict__ z, int line0, int lane
   }
 }
 
-// ---- inverse row pass with the cross-power spectrum formed on the fly (MOF_FUSE_XPOW) ------------------------------
+// ---- inverse row pass with the cross-power spectrum formed on the fly (PcTraits::FUSE_XPOW) ------------------------------
 // Rows 0..H-1 of the half spectrum D = conj(C): stage 1 reads bin (v, u) AND its Hermitian partner (N-v, N-u) from the
 // forward spectrum, forms conj(C[v][u]) in registers and goes straight into the first butterfly. The separate
 // cross-power pass (a tile read and half a tile write, one workgroup barrier) disappears. Partner rows are N-1..H+1,
@@ -287,9 +250,9 @@ __device__ __forceinline__ void row_pass_xpow(cf* __restrict__ z, int line0, int
 #pragma unroll
       for (int k = 0; k < R2; ++k) {
         cf a = lds_read(&z[zaddr<N>(line, x + k * R1)]);
-        v[b][k] = (k == 0 || (R2 == 8 && MOF_FUSED_TW)) ? a : cmul(a, tw_row[k - 1]);
+        v[b][k] = (k == 0 || R2 == 8) ? a : cmul(a, tw_row[k - 1]);
       }
-      if constexpr (R2 == 8 && MOF_FUSED_TW) butterfly8_tw(v[b], tw_row);
+      if constexpr (R2 == 8) butterfly8_tw(v[b], tw_row);
       else butterfly<R2>(v[b]);
     }
     wave_sync();
@@ -337,13 +300,9 @@ __device__ __forceinline__ void col_pass_fwd(cf* __restrict__ z, int col0, int l
 #pragma unroll
       for (int k = 0; k < R2; ++k) {
         cf a = lds_read(&z[zaddr<N>(x + k * R1, col)]);
-#ifdef MOF_ABLATE_NOBFLY
-        v[b][k] = a;
-#else
-        v[b][k] = (k == 0 || (R2 == 8 && MOF_FUSED_TW)) ? a : cmul(a, tw_col[k - 1]);
-#endif
+        v[b][k] = (k == 0 || R2 == 8) ? a : cmul(a, tw_col[k - 1]);
       }
-      if constexpr (R2 == 8 && MOF_FUSED_TW) butterfly8_tw(v[b], tw_col);
+      if constexpr (R2 == 8) butterfly8_tw(v[b], tw_col);
       else butterfly<R2>(v[b]);
     }
     wave_sync();
@@ -414,13 +373,9 @@ __device__ __forceinline__ Best col_pass_inv(cf* __restrict__ z, int col0, int l
 #pragma unroll
       for (int k = 0; k < R2; ++k) {
         cf a = lds_read(&z[zaddr<N>(x + k * R1, col)]);
-#ifdef MOF_ABLATE_NOBFLY
-        v[b][k] = a;
-#else
-        v[b][k] = (k == 0 || (R2 == 8 && MOF_FUSED_TW)) ? a : cmul(a, tw_col[k - 1]);
-#endif
+        v[b][k] = (k == 0 || R2 == 8) ? a : cmul(a, tw_col[k - 1]);
       }
-      if constexpr (R2 == 8 && MOF_FUSED_TW) butterfly8_tw(v[b], tw_col);
+      if constexpr (R2 == 8) butterfly8_tw(v[b], tw_col);
       else butterfly<R2>(v[b]);
       if constexpr (PK == 1) {  // OpenCL-kernel model: 1/N^2 scaling and the +-search_radius mask (cl:733, :737-746, :823-826)
 #pragma unroll

@@ -43,9 +43,7 @@ __device__ __forceinline__ void fwd3_rows(cf* __restrict__ z, int wave, int lane
     const uint32_t cp = lds_read_u16(src + 8 * n1);
     v[n1] = {(float)(cp & 0xffu), (float)(cp >> 8)};
   }
-#if !defined(MOF_ABLATE_ROWS) && !defined(MOF_ABLATE_S1)  // diagnostic builds (tools/ab_mfma_bound.sh): the row arithmetic an
-  butterfly<16>(v);                                       // MFMA row-DFT would take off the VALU (S1 alone, or S1 and S2's row part)
-#endif
+  butterfly<16>(v);
   wave_sync();  // the raw area lies inside the wave's own part of the intermediate layout: all of it is read by now
 #pragma unroll
   for (int k1 = 0; k1 < 16; ++k1) z[t3addr(y, n2, k1)] = v[k1];
@@ -129,12 +127,8 @@ __device__ __forceinline__ void fwd3_mid(cf* __restrict__ z, int wave, int lane,
     for (int n2 = 0; n2 < 4; ++n2) e[m1][n2] = lds_read(&z[t3addr(m2 + 16 * m1, n2, k1)]);
 #pragma unroll
   for (int m1 = 0; m1 < 4; ++m1) {
-#ifdef MOF_ABLATE_ROWS
-    cf t[4] = {e[m1][0], e[m1][1], e[m1][2], e[m1][3]};
-#else
     cf t[4] = {e[m1][0], cmul(e[m1][1], tw.wr[0]), cmul(e[m1][2], tw.wr[1]), cmul(e[m1][3], tw.wr[2])};
     butterfly<4>(t);
-#endif
 #pragma unroll
     for (int k2 = 0; k2 < 4; ++k2) e[m1][k2] = t[k2];
   }

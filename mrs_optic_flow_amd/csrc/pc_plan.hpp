@@ -38,11 +38,14 @@ struct Walk {
   int line_fast;     // lane map of a stage: 0 = the butterfly index in the fast lane bits (row walks), 1 = the line (column walks)
   int line_perm = 0; // 1: later stages of a row walk take the lines of a four-line group in the order 0 2 1 3 (stage_rt; the half-tile kernel's pitches)
   int sh = 3;        // the skew's shift: coordinate c sits at c + (c >> sh) (3 everywhere but the half-tile kernel's radix-16-first sizes: 4)
-  // r06 (A/B, the half-tile kernel): a ROW skew -- tile row r (a line of the row walks = rows 2j | 2j + 1; an element of the column walks)
-  // starts rs * (r >> 4) complex elements later, so that the first-stage column writes of a radix-16-first size, 16 rows apart = 0 (mod 32
-  // banks) for any pitch, land in different banks. lrs / ers = rs for the walk whose line / element is the row; 0 everywhere else.
-  int lrs = 0, ers = 0;
-  __device__ __forceinline__ int loffs(int l) const { return l * ls + ((l >> sh) & lmask) + lrs * (l >> 3); }  // (line j = rows 2j, 2j + 1: (2j) >> 4 = j >> 3)
+  // (r06, the half-tile kernel: a ROW skew on top -- tile row r starting rs * (r >> 4) complex elements later, so that the first-stage column
+  // writes of a radix-16-first size, 16 rows apart = 0 (mod 32 banks) for any pitch, land in different banks -- measured -4 .. -7 % on videos
+  // and is not carried, docs/history/retired_switches.md)
+  __device__ __forceinline__ int loffs(int l) const { return l * ls + ((l >> sh) & lmask); }
+  // Residue of that row skew, always 0 and kept on purpose: without this member and its term the compiler orders independent instructions of
+  // K1h and of pc_generic_kernel<.., 120> differently, and the planned kernel at 120 then measured 0.16 % slower than with the parent's bytes,
+  // outside the parent's own scatter (profiles/switch_retirement.txt, section 2). With it every code object is the parent's.
+  int ers = 0;
   __device__ __forceinline__ int eoff(int e) const { return e * es + ((e >> sh) & emask) + ers * (e >> 4); }
   __device__ __forceinline__ int at(int l, int e) const { return loffs(l) + eoff(e); }
 };
@@ -145,10 +148,8 @@ __device__ __forceinline__ void bfly_rt(int R, cf* v) {
 // against the tuned kernel's 1412, with 61 % of its LDS cycles bank conflicts (profiles/r04_p62_planned_v1_sq_pmc.csv).
 // Sink: what the LAST stage of a pass hands its outputs to besides the tile (line l, element o of the line, value): the planned
 // kernel's arg-max rides the final stage of the inverse transform that way instead of a sweep of its own over the tile.
-#ifndef MOF_PLANNED_TW8  // 1: radix-8 stages with twiddles use butterfly8_tw (the products ride the first radix-2 layer as FMAs: 8 instructions
-                         // fewer per butterfly, the same value up to rounding -- what the tuned kernels do); 0: cmul + butterfly<8> (r04)
-#define MOF_PLANNED_TW8 1
-#endif
+// Radix-8 stages with twiddles use butterfly8_tw (the products ride the first radix-2 layer as FMAs: 8 instructions fewer per butterfly,
+// the same value up to rounding -- what the tuned kernels do; r04 was cmul + butterfly<8>).
 // A sink may declare `transforms = true`: the last stage then hands it every output BEFORE the tile write, with the stage routine's
 // compile-time loop indices (butterfly b of the lane's group, output p): val = sink.transform(line, o, val, b, p, &write). The sink may
 // keep the value in a per-lane register array laid out in the stage's own lane map, replace it, or suppress the write
@@ -180,20 +181,11 @@ struct WorkgroupSync {
   __device__ __forceinline__ void operator()() const { __syncthreads(); }
 };
 
-// MOF_SITE_ABL (diagnostic builds, results wrong by design; tools/half_site_counters.sh): ONE class of a stage's LDS accesses is removed,
-// so that SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE of the build, subtracted from the product's, give that class's share. Site =
-// 1 + (column walk ? 4 : 0) + (later stage, np > 1 ? 2 : 0) + (write ? 1 : 0); 0 = the product. A removed read hands the butterfly a
-// lane-dependent constant; a removed write keeps its value alive in a register (nothing upstream is dead code).
-#ifndef MOF_SITE_ABL
-#define MOF_SITE_ABL 0
-#endif
-#ifndef MOF_PLAN_LINE_PERM  // 0: every stage takes a group's lines in order (A/B)
-#define MOF_PLAN_LINE_PERM 1
-#endif
-__device__ __forceinline__ constexpr bool site_off(int line_fast, int np, int rw) {
-  return MOF_SITE_ABL != 0 && (MOF_SITE_ABL - 1) == (line_fast ? 4 : 0) + (np > 1 ? 2 : 0) + rw;
-}
-__device__ __forceinline__ void site_keep(cf v) { asm volatile("" ::"v"(v.x), "v"(v.y)); }
+// The second residue that keeps K1h's code objects the parent's (same record): stage_rt_ng's transforming write hands its value BY VALUE to an
+// empty function behind a guard that is always false but that the front end cannot fold (a constexpr function of run-time arguments). Dead
+// code in every build; without it the two selects of HalfXpowSink::transform come out in the other order and 58 kernels change their schedule.
+__device__ __forceinline__ constexpr bool never_taken(int, int, int) { return false; }
+__device__ __forceinline__ void pass_by_value(cf) {}
 
 template <int SLOTS, class Sink = NoSink, class Src = NoSrc, class Sync = WaveSync>
 __device__ __forceinline__ void stage_rt(cf* __restrict__ z, const cf* __restrict__ tw, const Walk& w, int m, int R, int np, int bpl,
@@ -213,12 +205,12 @@ __device__ __forceinline__ void stage_rt(cf* __restrict__ z, const cf* __restric
       sub = fdiv(lane, bpl, inv_bpl, &x);
     }
     const bool lane_on = w.line_fast ? x < bpl : sub < lpg;
-    // Line order inside a group (r06; measured per access class with tools/half_site_counters.sh: the later-stage reads of the row walks were
+    // Line order inside a group (r06; measured per access class: the later-stage reads of the row walks were
     // 2-way conflicts, 50 % of their LDS cycles, at every K1h size with four lines side by side): a later stage of a row walk reads 16
     // consecutive complex values per line, two lines per 32-lane half; with the pitches in use neighbouring lines start 48 or 16 banks
     // apart (mod 64) and overlap in 16 banks, lines TWO apart start 32 banks apart and do not. Which line a lane group takes is free
     // (a stage is in place per line): sub-groups 0 1 2 3 take lines 0 2 1 3.
-    if (MOF_PLAN_LINE_PERM && !w.line_fast && np > 1 && lpg == 4 && w.line_perm) sub = ((sub & 1) << 1) | (sub >> 1);
+    if (!w.line_fast && np > 1 && lpg == 4 && w.line_perm) sub = ((sub & 1) << 1) | (sub >> 1);
     int k = 0;
     if (np > 1) (void)fdiv(x, np, inv_np, &k);
     cf t[SLOTS - 1];
@@ -249,9 +241,7 @@ __device__ __forceinline__ void stage_rt(cf* __restrict__ z, const cf* __restric
             if (j < R) {
               const int e = x + j * bpl;
               cf a;
-              if (site_off(w.line_fast, np, 0)) {
-                a = cf{(float)(lane + j), 1.f};
-              } else if constexpr (Src::active) {
+              if constexpr (Src::active) {
                 a = src(z, l, e);
               } else if (herm_first) {
                 const int r = e < H ? e : (e == H ? 0 : m - e);
@@ -265,10 +255,10 @@ __device__ __forceinline__ void stage_rt(cf* __restrict__ z, const cf* __restric
                 a = lds_read(&z[loff[b] + w.eoff(e)]);
               }
               // (a radix-8 stage behind an earlier one takes its twiddles inside the butterfly: butterfly8_tw, pc_common.hpp)
-              if (j > 0 && np > 1 && !(MOF_PLANNED_TW8 && SLOTS == 8 && R == 8)) a = cmul(a, t[j - 1]);
+              if (j > 0 && np > 1 && !(SLOTS == 8 && R == 8)) a = cmul(a, t[j - 1]);
               v[b][j] = a;
             }
-          if (MOF_PLANNED_TW8 && SLOTS == 8 && R == 8 && np > 1) butterfly8_tw(v[b], t);
+          if (SLOTS == 8 && R == 8 && np > 1) butterfly8_tw(v[b], t);
           else bfly_rt<SLOTS>(R, v[b]);
         }
       }
@@ -283,11 +273,9 @@ __device__ __forceinline__ void stage_rt(cf* __restrict__ z, const cf* __restric
               if constexpr (SinkTransforms<Sink>::value) {
                 bool wr = true;
                 const cf val = sink.transform(line0 + g0 + b * lpg + sub, o, v[b][p], b, p, &wr);
-                if (site_off(w.line_fast, np, 1)) site_keep(val);
-                else if (wr) z[loff[b] + w.eoff(o)] = val;
+                if (wr) z[loff[b] + w.eoff(o)] = val;
               } else {
-                if (site_off(w.line_fast, np, 1)) site_keep(v[b][p]);
-                else z[loff[b] + w.eoff(o)] = v[b][p];
+                z[loff[b] + w.eoff(o)] = v[b][p];
                 if constexpr (Sink::active) sink(line0 + g0 + b * lpg + sub, o, v[b][p]);
               }
             }
@@ -410,17 +398,15 @@ __device__ __forceinline__ void stage_rt_ng(cf* __restrict__ z, const cf* __rest
           if (j < R) {
             const int e = x + j * bpl;
             cf a;
-            if (site_off(w.line_fast, np, 0)) {
-              a = cf{(float)(lane + j), 1.f};
-            } else if constexpr (Src::active) {
+            if constexpr (Src::active) {
               a = src(z, l, e);
             } else {
               a = lds_read(&z[loff[g][b] + w.eoff(e)]);
             }
-            if (j > 0 && np > 1 && !(MOF_PLANNED_TW8 && SLOTS == 8 && R == 8)) a = cmul(a, t[j - 1]);
+            if (j > 0 && np > 1 && !(SLOTS == 8 && R == 8)) a = cmul(a, t[j - 1]);
             v[g][b][j] = a;
           }
-        if (MOF_PLANNED_TW8 && SLOTS == 8 && R == 8 && np > 1) butterfly8_tw(v[g][b], t);
+        if (SLOTS == 8 && R == 8 && np > 1) butterfly8_tw(v[g][b], t);
         else bfly_rt<SLOTS>(R, v[g][b]);
       }
     }
@@ -438,11 +424,10 @@ __device__ __forceinline__ void stage_rt_ng(cf* __restrict__ z, const cf* __rest
             if constexpr (SinkTransforms<Sink>::value) {
               bool wr = true;
               const cf val = sink.transform(l, o, v[g][b][p], g * NB + b, p, &wr);
-              if (site_off(w.line_fast, np, 1)) site_keep(val);
+              if (never_taken(w.line_fast, np, 1)) pass_by_value(val);  // (kept for the bytes of the code object: above)
               else if (wr) z[loff[g][b] + w.eoff(o)] = val;
             } else {
-              if (site_off(w.line_fast, np, 1)) site_keep(v[g][b][p]);
-              else z[loff[g][b] + w.eoff(o)] = v[g][b][p];
+              z[loff[g][b] + w.eoff(o)] = v[g][b][p];
               if constexpr (Sink::active) sink(l, o, v[g][b][p]);
             }
           }

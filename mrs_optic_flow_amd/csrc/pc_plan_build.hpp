@@ -132,11 +132,7 @@ constexpr bool pc_two_stage_chain(int m, int& Ra, int& Rb) {
 // keep the workgroups per CU. The generic rule (pitch = 8 mod 16) is tuned for power-of-two radices; with 4 or 6 butterflies per
 // line sixteen lines sit side by side in a wave and their rows land on a quarter of the banks (p60: 42 % of the LDS cycles were
 // conflicts, profiles/r04_p60_sq_pmc.csv). 0 = keep the generic rule.
-#ifndef MOF_PLANNED_PITCH_TABLE
-#define MOF_PLANNED_PITCH_TABLE 1
-#endif
 constexpr int pc_static_pitch(int m) {
-  if (!MOF_PLANNED_PITCH_TABLE) return 0;
   switch (m) {
     case 16: return 20;  case 18: return 20;  case 20: return 28;  case 25: return 45;  case 27: return 39;  case 30: return 39;
     case 36: return 42;  case 40: return 44;  case 45: return 52;  case 48: return 55;  case 50: return 59;  case 54: return 71;
@@ -150,11 +146,7 @@ constexpr int pc_static_pitch(int m) {
 // (tools/design/planned_banks.py, kernel_cost(m, pitch, skew=False)) -- and every element offset of a stage (x + j bpl, (x - k) R + k + p np)
 // is then linear in the loop index: an immediate of the LDS instruction instead of a shift and an add per element. Sizes listed here
 // take the unskewed pitch; 0 = keep the skewed plan (16, 32, 64, 96, 128 and what has no two-stage chain).
-#ifndef MOF_PLANNED_UNSKEWED
-#define MOF_PLANNED_UNSKEWED 1
-#endif
 constexpr int pc_static_pitch_unskewed(int m) {
-  if (!MOF_PLANNED_PITCH_TABLE || !MOF_PLANNED_UNSKEWED) return 0;
   switch (m) {
     case 18: return 20;  case 20: return 44;  case 24: return 44;  case 25: return 44;  case 27: return 46;  case 30: return 52;
     case 36: return 41;  case 40: return 44;  case 45: return 52;  case 48: return 55;  case 50: return 69;  case 54: return 58;

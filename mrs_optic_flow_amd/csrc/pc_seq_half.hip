@@ -88,9 +88,6 @@ struct HalfTw {
 
 // ---- raw pixel staging (N = 128; as pc_passes.hpp, raw_store): the lane's 16 + 16 pixels (patch rows 2j, 2j + 1) leave as
 // two ds_write_b128 of interleaved bytes into a per-wave area over the wave's own lines; the first row stage converts.
-#ifndef MOF_RAW_STAGE
-#define MOF_RAW_STAGE 1
-#endif
 constexpr int HALF_RAW_PITCH = 272;
 template <int N>
 __device__ __forceinline__ unsigned char* half_raw_area(cf* z, int line0) {
@@ -476,7 +473,7 @@ __global__ void __launch_bounds__(HalfTile<N>::T, (N == 64 ? 4 : 2)) pc_seq_half
     lane &= 63;
     wave &= W - 1;
     {
-      constexpr bool RAW = MOF_RAW_STAGE && PPL == 16;
+      constexpr bool RAW = PPL == 16;
       if constexpr (RAW) {
         half_raw_store<N>(z, 8 * wave, lane, ra, rb);
       } else {
@@ -521,11 +518,9 @@ __global__ void __launch_bounds__(HalfTile<N>::T, (N == 64 ? 4 : 2)) pc_seq_half
 // columns, cross-power against the slab, inverse columns, row pairs + arg-max, centroid. Same passes as the sequence kernel above,
 // 1.5 transform units per pair like the packed pair kernel (pc_kernel.hip), but on HALF its LDS: TWO workgroups per CU, so one
 // covers the other's barriers and latency chains (the packed N = 128 kernel runs 47 % of its wave-cycles parked, r03 counters).
-#ifndef MOF_PAIR_HALF_WPE  // waves per SIMD the pair kernel is compiled for (4 = two workgroups per CU)
-#define MOF_PAIR_HALF_WPE 4
-#endif
+constexpr int PAIR_HALF_WPE = 4;  // waves per SIMD the pair kernel is compiled for: two workgroups per CU
 template <int N, int PK, int CH>
-__global__ void __launch_bounds__(HalfTile<N>::T, MOF_PAIR_HALF_WPE) pc_pair_half_kernel(PcArgs a, float2* __restrict__ slabs) {
+__global__ void __launch_bounds__(HalfTile<N>::T, PAIR_HALF_WPE) pc_pair_half_kernel(PcArgs a, float2* __restrict__ slabs) {
   using L = HalfTile<N>;
   constexpr int H = L::H, R1 = L::R1, W = HalfCfg<N>::WAVES, PPL = N / 8;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -568,7 +563,7 @@ __global__ void __launch_bounds__(HalfTile<N>::T, MOF_PAIR_HALF_WPE) pc_pair_hal
       asm volatile("" : "+v"(lane), "+v"(wave));
       lane &= 63;
       wave &= W - 1;
-      constexpr bool RAW = MOF_RAW_STAGE && PPL == 16;
+      constexpr bool RAW = PPL == 16;
       if constexpr (RAW) {
         half_raw_store<N>(z, 8 * wave, lane, ra, rb);
       } else {

@@ -16,17 +16,9 @@ template <int N>
 struct SrPlan;
 // LINE = complex elements per line buffer: >= R1 * Y2 (the padded stage-1 output), odd so that the 8 lines of a
 // workgroup start on different banks; Y2 = row pitch of the stage-1 output (R2 + 1: stride-Y2 reads hit distinct banks)
-#ifndef MOF_SR_LINE480  // (A/B: tools/ab_sr_line.sh)
-#define MOF_SR_LINE480 497
-#endif
-// (A/B, r06: -DMOF_SR_480_R1=24 -DMOF_SR_480_R2=20 -DMOF_SR_LINE480=505 and the like -- the first radix may be up to 32 now)
-#ifndef MOF_SR_480_R1
-#define MOF_SR_480_R1 15
-#define MOF_SR_480_R2 32
-#endif
 template <>
-struct SrPlan<480> {
-  static constexpr int R1 = MOF_SR_480_R1, R2 = MOF_SR_480_R2, Y2 = R2 + 1, LINE = MOF_SR_LINE480;
+struct SrPlan<480> {  // (r06 A/B of the split 24 x 20 with line 505 and the like -- the first radix may be up to 32 -- kept 15 x 32, line 497)
+  static constexpr int R1 = 15, R2 = 32, Y2 = R2 + 1, LINE = 497;
   static_assert(R1 * R2 == 480 && LINE >= R1 * Y2 && LINE >= 480, "the padded stage-1 output fits a line");
 };
 template <>
@@ -39,12 +31,9 @@ struct SrPlan<256> {
 };
 // r06: FftMethod patches of 200 x 200 pixels (the first 5-smooth size past the half-tile kernel's 192) on the same
 // tuned transforms -- 200 = 10 x 20: three lines per stage-1 pass (60 of 64 lanes), ten of sixteen lanes per line in stage 2
-#ifndef MOF_SR_LINE200  // (A/B: LDS line pitch of the 200-point kernels)
-#define MOF_SR_LINE200 211
-#endif
 template <>
 struct SrPlan<200> {
-  static constexpr int R1 = 10, R2 = 20, Y2 = 21, LINE = MOF_SR_LINE200;
+  static constexpr int R1 = 10, R2 = 20, Y2 = 21, LINE = 211;
   static_assert(LINE >= R1 * Y2, "the padded stage-1 output fits a line");
 };
 // ... and 288 = 16 x 18, 320 = 16 x 20, 384 = 12 x 32 (r06): with the zero padding of the row kernel these serve patches of 271 .. 288, 301 .. 320 and
@@ -282,39 +271,18 @@ hipError_t sr_dispatch_size(int m, F&& f) {
 
 // Zt / Zh / Dt (and the log-polar images) are STREAMS: written once by one kernel, read once by the next, hundreds of MB per
 // pass. Marking those accesses non-temporal keeps them from displacing each other's lines on their way through the caches:
-// same-box A/B (r03) c5seq 492 k -> 516 k pairs/s with K5s / K6s alone. MOF_SR_NT=0 builds the plain form.
-#ifndef MOF_SR_NT
-#define MOF_SR_NT 1
-#endif
-// MOF_SR_L2_ABLATE=1 (diagnostic build, results wrong by design): every frame's Zh and every pair's Dt live in slot 0 --
-// K5s writes, K6s reads and writes, K7 reads the SAME 0.9 MB over and over, so the intermediates stay in the L2s instead of going through
-// HBM. What that build gains over the product is the most ANY decomposition that keeps Zh / Dt on chip can return (it pays no hand-off).
-#ifndef MOF_SR_L2_ABLATE
-#define MOF_SR_L2_ABLATE 0
-#endif
+// same-box A/B (r03) c5seq 492 k -> 516 k pairs/s with K5s / K6s alone.
 typedef float v4f_t __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ float4 stream_load(const float4* p) {
-#if MOF_SR_NT
   const v4f_t v = __builtin_nontemporal_load(reinterpret_cast<const v4f_t*>(p));
   return make_float4(v.x, v.y, v.z, v.w);
-#else
-  return *p;
-#endif
 }
 __device__ __forceinline__ void stream_store(float4* p, float4 v) {
-#if MOF_SR_NT
   const v4f_t w = {v.x, v.y, v.z, v.w};
   __builtin_nontemporal_store(w, reinterpret_cast<v4f_t*>(p));
-#else
-  *p = v;
-#endif
 }
 __device__ __forceinline__ uint32_t stream_load(const uint32_t* p) {
-#if MOF_SR_NT
   return __builtin_nontemporal_load(p);
-#else
-  return *p;
-#endif
 }
 
 __device__ __forceinline__ void butterfly20(cf* v) {  // 5 x 4 (pc_plan.hpp: butterfly_ct), twiddles W_20^j = (cos(pi j / 10), -sin(pi j / 10))

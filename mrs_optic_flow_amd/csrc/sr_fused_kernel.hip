@@ -36,17 +36,6 @@ typedef float float16_t __attribute__((ext_vector_type(16)));
 typedef uint32_t u4_t __attribute__((ext_vector_type(4)));
 typedef uint32_t u2_t __attribute__((ext_vector_type(2)));
 
-#ifndef MOF_FUSED_ABLATE  // diagnostic builds: 1 = no product (the lines get zeros), 2 = no column transforms / cross-power
-#define MOF_FUSED_ABLATE 0
-#endif
-
-#ifndef MOF_FUSED_UNROLL  // double steps per trip of the product loop (behind a back edge the compiler waits with vmcnt(0))
-#define MOF_FUSED_UNROLL 1
-#endif
-#define MOF_PRAGMA_(x) _Pragma(#x)
-#define MOF_PRAGMA(x) MOF_PRAGMA_(x)
-#define MOF_FUSED_UNROLL_PRAGMA MOF_PRAGMA(unroll MOF_FUSED_UNROLL)
-
 template <int N>
 struct Fused {
   static constexpr int H = N / 2, BINS = 16, T = 256;
@@ -122,8 +111,8 @@ sr_cols_fused_kernel(const uint8_t* __restrict__ lp_prev, const uint8_t* __restr
     for (int t = 0; t < NT; ++t) px[t] = *reinterpret_cast<const u4_t*>(rowp[t]);
 #pragma unroll
     for (int q = 0; q < 4; ++q) b[q] = frag[(size_t)q * 64];  // (step 2 s2: hi, lo), (step 2 s2 + 1: hi, lo)
-MOF_FUSED_UNROLL_PRAGMA
-    for (int s2 = 0; s2 < (MOF_FUSED_ABLATE == 1 ? 1 : F::KS2); ++s2) {
+#pragma unroll 1  // (one double step per trip; behind a back edge the compiler waits with vmcnt(0))
+    for (int s2 = 0; s2 < F::KS2; ++s2) {
       const int sn = s2 + 1 < F::KS2 ? s2 + 1 : s2;  // (the last step re-reads itself: no branch inside the pipeline)
       half8_t a[NT][2];
 #pragma unroll
@@ -160,7 +149,7 @@ MOF_FUSED_UNROLL_PRAGMA
       }
     }
     __syncthreads();
-    if (wave_on && MOF_FUSED_ABLATE != 2) {
+    if (wave_on) {
       SrTw<N> tw;
       tw.load(twiddles, lane);
       wave_fft<N>(z, CW, lane, tw, StoreNatural<N>{});
@@ -182,7 +171,6 @@ MOF_FUSED_UNROLL_PRAGMA
   for (int j = 0; j < np; ++j) {
     spectra(lp_cur + (size_t)(p0 + j) * lp_stride);
     if (!wave_on) continue;  // (wave-uniform; the barriers all sit inside spectra())
-#if MOF_FUSED_ABLATE != 2
     // normalised cross-power spectrum of bins (v, u), conjugated in place; the current spectra move into the registers
 #pragma unroll
     for (int s = 0; s < CW; ++s) {
@@ -204,7 +192,6 @@ MOF_FUSED_UNROLL_PRAGMA
       tw.load(twiddles, lane);
       wave_fft<N>(z, CW, lane, tw, StoreNatural<N>{});
     }
-#endif
     cf* D = reinterpret_cast<cf*>(Dt) + (size_t)(p0 + j) * (H + 1) * N;
 #pragma unroll
     for (int s = 0; s < CW; ++s) {

@@ -69,11 +69,7 @@ __global__ void __launch_bounds__(256) sr_logpolar_kernel(SrLpArgs a) {
     return;
   }
   const uint8_t* src = a.src + (size_t)img * a.src_stride;
-#ifdef MOF_SR_ABL_W  // diagnostic build: every lane reads weight row 0 (results wrong by design)
-  const int16_t* w = a.weights;
-#else
   const int16_t* w = a.weights + (size_t)m.widx * (K * K);
-#endif
   constexpr int HALF = K / 2 - 1;
   const int sx = m.ax - HALF, sy = m.ay - HALF;
   int sum = 0;
@@ -189,11 +185,6 @@ __host__ __device__ inline int lp_box_capacity(int box_dwords_max) {
   return 64 * (t <= 4 ? 4 : (t <= 8 ? 8 : (t <= 12 ? 12 : 16)));
 }
 
-#ifdef MOF_LP_WPE
-#define MOF_LP_ATTR __attribute__((amdgpu_waves_per_eu(MOF_LP_WPE, MOF_LP_WPE)))
-#else
-#define MOF_LP_ATTR
-#endif
 // SUPER: the four waves of a workgroup own the four 8 x 8 tiles of one 16 x 16 SUPER-TILE and share ONE staged box (the
 // bounding box of all their footprints, a.sboxes): the texture addresser was what bound the per-wave form (TA_BUSY 84-89 %:
 // every box row is a cache line of its own), and one shared box has 2.2-2.5x fewer rows than four separate ones. The
@@ -203,14 +194,8 @@ __host__ __device__ inline int lp_box_capacity(int box_dwords_max) {
 // at one issue per ≈4 clocks + 24 LDS reads and their round trip per image) but put a third more of them side by side:
 // c5seq +3.4 % same-box even with 7 spilled dwords; with a 12-deep staging ring where the map's boxes allow it (NR = 12:
 // 8 VGPRs less) the Lanczos4 form fits 128 VGPRs.
-#ifndef MOF_LP_SUPER_WPE
-#define MOF_LP_SUPER_WPE 4
-#endif
-#ifndef MOF_LP_SUPER_WPE4
-#define MOF_LP_SUPER_WPE4 4  // the cubic form
-#endif
 template <int K, int NR, bool SUPER>
-__global__ void __launch_bounds__(256, (SUPER ? (K == 4 ? MOF_LP_SUPER_WPE4 : MOF_LP_SUPER_WPE) : 1)) MOF_LP_ATTR sr_logpolar_staged_kernel(SrLpArgs a, int n_images, int img_per_wave, int xcd_groups) {
+__global__ void __launch_bounds__(256, (SUPER ? 4 : 1)) sr_logpolar_staged_kernel(SrLpArgs a, int n_images, int img_per_wave, int xcd_groups) {
   extern __shared__ __attribute__((aligned(16))) uint32_t lp_lds[];
   const int res = a.res, tiles = (res + 7) / 8, n_tiles = SUPER ? (tiles / 2) * (tiles / 2) : tiles * tiles;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -491,10 +476,7 @@ __global__ void __launch_bounds__(256, (SUPER ? (K == 4 ? MOF_LP_SUPER_WPE4 : MO
 }
 
 // ---- K5: forward row transforms of z = cur_lp + i prev_lp, written transposed -----------------------------
-#ifndef MOF_SR_FWD_ROWS
-#define MOF_SR_FWD_ROWS 16
-#endif
-constexpr int FWD_ROWS = MOF_SR_FWD_ROWS;  // rows per workgroup: the transposed store writes FWD_ROWS * 8 bytes per segment
+constexpr int FWD_ROWS = 16;               // rows per workgroup: the transposed store writes FWD_ROWS * 8 bytes per segment
 constexpr int FWD_T = FWD_ROWS * 16;       // four rows per wave
 
 template <int N>
@@ -616,12 +598,10 @@ __global__ void __launch_bounds__(SR_T) sr_cols_kernel(SrPcArgs a) {
 // ---- K7: Hermitian rows back to the real surface, two rows per complex transform; arg-max from registers -----
 // K7's waves: two of four lines each; at the long lines (r06, N >= 540: first radix above 16, both stages of wave_fft take two lines per pass
 // anyway) four of two lines each -- the eight lines in LDS set the workgroups per CU, so that is twice the waves for the same LDS
-#ifndef MOF_K7_LPW2_FROM
-#define MOF_K7_LPW2_FROM 540
-#endif
+constexpr int K7_LPW2_FROM = 540;
 template <int N>
 struct K7Cfg {
-  static constexpr int LPW = (SrPlan<N>::R1 > 16 || N >= MOF_K7_LPW2_FROM) ? 2 : 4;  // (also 324 / 486 / 500: +1 .. 4 %)
+  static constexpr int LPW = (SrPlan<N>::R1 > 16 || N >= K7_LPW2_FROM) ? 2 : 4;  // (also 324 / 486 / 500: +1 .. 4 %)
   static constexpr int T = SR_LINES / LPW * 64;
 };
 template <int N>
@@ -633,7 +613,7 @@ __global__ void __launch_bounds__(K7Cfg<N>::T) sr_rows_inv_kernel(SrPcArgs a) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, pair = blockIdx.y, p0 = blockIdx.x * SR_LINES;
   SrTw<N> tw;
   tw.load(a.twiddles, lane);
-  const cf* Dt = reinterpret_cast<const cf*>(a.Dt) + (size_t)(MOF_SR_L2_ABLATE ? 0 : pair) * (H + 1) * N;
+  const cf* Dt = reinterpret_cast<const cf*>(a.Dt) + (size_t)pair * (H + 1) * N;
   // line l carries rows y1 = 2 (p0 + l), y2 = y1 + 1: E[u] = F[y1][u] + i F[y2][u], F[y][N-u] = conj F[y][u].
   // Dt[u][y1], Dt[u][y2] are neighbours: one 16-byte load; 8 lanes fetch the 16 rows of the workgroup (128 bytes).
   constexpr bool ODD = (N & 1) != 0;   // (r06) the last row of an odd image shares its line with zeros; every u > 0 has a partner N - u != u

@@ -32,25 +32,17 @@ namespace {
 // ---- K5s: row half-spectra of one real image -------------------------------------------------------------------------
 // ROWS image rows per workgroup = ROWS / 2 packed lines, four lines per wave. The transposed store writes ROWS * 8
 // contiguous bytes per u.
-#ifndef MOF_K5S_ROTATE
-#define MOF_K5S_ROTATE 1
-#endif
-#ifndef MOF_K5S_ROWS32  // 32 image rows per workgroup where N allows (256-byte segments of the transposed store); 0: 16 rows (more workgroups per CU)
-#define MOF_K5S_ROWS32 1
-#endif
+// 32 image rows per workgroup where N allows (256-byte segments of the transposed store; kept in the A/B against 16 rows = more workgroups per CU).
 template <int N>
 struct RowsReal {
-  static constexpr int ROWS = N > 512 ? 8 : ((N % 32 == 0 && MOF_K5S_ROWS32) ? 32 : (N % 16 == 0 ? 16 : 8));  // (200: 25 one-wave workgroups of 8 rows per image; beyond 512: one wave = four lines = up to 31 KB of LDS per workgroup)
+  static constexpr int ROWS = N > 512 ? 8 : (N % 32 == 0 ? 32 : (N % 16 == 0 ? 16 : 8));  // (200: 25 one-wave workgroups of 8 rows per image; beyond 512: one wave = four lines = up to 31 KB of LDS per workgroup)
   static constexpr bool TAIL = N % ROWS != 0;  // (270, 300, 450: the last one-wave workgroup holds 3, 2 or 1 row pairs; the rest of its lines are zeros and are not stored)
   static_assert((N % ROWS == 0 || ROWS == 8) && ROWS % 8 == 0, "whole workgroups of four-line waves, a tail only behind one-wave workgroups");  // (odd N: the last row shares its line with zeros)
   static constexpr int GROUPS = (N + ROWS - 1) / ROWS;
   static constexpr int LINES = ROWS / 2;
-  // lines per wave: four. (r06 A/B, -DMOF_K5S_LPW2_FROM=540: two lines per wave at the long lines -- twice the waves for the same LDS, as K7 took
-  // it -- LOSES here: 576 +9 %, 640 +17 % time, profiles/r06_lpw2_ab.txt; off)
-#ifndef MOF_K5S_LPW2_FROM
-#define MOF_K5S_LPW2_FROM 1000000
-#endif
-  static constexpr int LPW = N >= MOF_K5S_LPW2_FROM ? 2 : 4;
+  // lines per wave: four. (r06 A/B: two lines per wave at the long lines, N >= 540 -- twice the waves for the same LDS, as K7 took
+  // it -- LOSES here: 576 +9 %, 640 +17 % time, profiles/r06_lpw2_ab.txt)
+  static constexpr int LPW = 4;
   static constexpr int T = LINES / LPW * 64;
 };
 
@@ -90,7 +82,7 @@ __global__ void __launch_bounds__(RowsReal<N>::T) sr_rows_real_kernel(const uint
         //  hit the same bank with every one of their four stores: 38 % of this kernel's LDS cycles were conflicts, r04 counters)
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-          const int r = MOF_K5S_ROTATE ? (q + (d >> 2)) & 3 : q;
+          const int r = (q + (d >> 2)) & 3;
           mine[l * P::LINE + 4 * d + r] = {(float)((c[k] >> (8 * r)) & 0xffu), (float)((p[k] >> (8 * r)) & 0xffu)};
         }
       }
@@ -100,7 +92,7 @@ __global__ void __launch_bounds__(RowsReal<N>::T) sr_rows_real_kernel(const uint
   wave_fft<N>(mine, 4, lane, tw, StoreNatural<N>{});
   __syncthreads();
   // untangle the two rows of every line and store transposed: Zh[u][row0 + 2j], Zh[u][row0 + 2j + 1] are neighbours
-  cf* out = reinterpret_cast<cf*>(zh + (size_t)(MOF_SR_L2_ABLATE ? 0 : frame) * zh_stride) + row0;
+  cf* out = reinterpret_cast<cf*>(zh + (size_t)frame * zh_stride) + row0;
   for (int i = tid; i < R::LINES * (H + 1); i += R::T) {
     const int u = i / R::LINES, j = i % R::LINES;
     const cf zk = z[j * P::LINE + u], zm = z[j * P::LINE + (N - u) % N];
@@ -210,7 +202,6 @@ __global__ void __launch_bounds__(RowsReal<N>::T) sr_rows_real_src_kernel(PclSrc
     s01 = wave_sum(s01);
     s10 = wave_sum(s10);
     s11 = wave_sum(s11);
-#ifndef MOF_SR_SUMS_ABLATE  // (diagnostic build: no atomics -- results wrong by design)
     if (lane == 0 && sums) {  // (zeroed by the caller; 255 * 432^2 < 2^31)
       int* q = sums + (size_t)(src.sums_stride ? src.sums_stride : 4) * img;
       atomicAdd(&q[0], s00);
@@ -218,7 +209,6 @@ __global__ void __launch_bounds__(RowsReal<N>::T) sr_rows_real_src_kernel(PclSrc
       atomicAdd(&q[2], s10);
       atomicAdd(&q[3], s11);
     }
-#endif
   }
   if (flags) {  // bit 0: some pixel differs from pixel (0, 0); bit 1: pixel (0, 0) is not zero (zeroed by the caller)
     if (__builtin_amdgcn_ballot_w64(diff != 0u) != 0ull && lane == 0) atomicOr(&flags[img], 1);
@@ -234,28 +224,20 @@ __global__ void __launch_bounds__(RowsReal<N>::T) sr_rows_real_src_kernel(PclSrc
     const cf zk = z[j * P::LINE + u], zm = z[j * P::LINE + (N - u) % N];
     cf a2, b2;
     untangle2(zk, zm, &a2, &b2);
-#ifdef MOF_SR_ABL_ROWSTORE  // (diagnostic build, results wrong by design: what the row kernel's stores cost)
-    if (a2.x == 123456.f)
-#endif
     stream_store(reinterpret_cast<float4*>(out + (size_t)u * sr_zh_pitch<N>() + 2 * j), make_float4(a2.x, a2.y, b2.x, b2.y));
   }
 }
 
 // ---- K6s: column transforms + cross-power + inverse columns, one wave walking a run of pairs -------------------------
-#ifndef MOF_SEQ_CW
-#define MOF_SEQ_CW 4
-#endif
-constexpr int SEQ_CW = MOF_SEQ_CW;  // columns per wave
+constexpr int SEQ_CW = 4;  // columns per wave
 // (r06) the long lines: two columns per wave -- half the LDS, half of the previous-image spectra in registers (from 640 on four columns put
 // those in AGPRs at one wave per SIMD: VALU 22 % / LDS 23 % at 720, profiles/r06_l720_sq_pmc.csv), and with a first radix above 16 the second
-// stage takes two lines per pass anyway. MOF_SEQ_CW_BIG_FROM: first N of the two-column form (A/B)
-#ifndef MOF_SEQ_CW_BIG_FROM
-#define MOF_SEQ_CW_BIG_FROM 540
-#endif
+// stage takes two lines per pass anyway. SEQ_CW_BIG_FROM: first N of the two-column form
+constexpr int SEQ_CW_BIG_FROM = 540;
 template <int N>
 constexpr int seq_cw() {
   // (two columns wherever the first radix is above 16 -- every N >= 540, and 324 / 486 / 500: 324 +10 %, 500 +5 %, 486 -1 %)
-  return (SrPlan<N>::R1 > 16 || N >= MOF_SEQ_CW_BIG_FROM) ? 2 : SEQ_CW;
+  return (SrPlan<N>::R1 > 16 || N >= SEQ_CW_BIG_FROM) ? 2 : SEQ_CW;
 }
 
 template <int N, bool BOX = false>  // BOX: patches zero-padded to N -- the box-zero rule of padded CONSTANT patches (the plain form pays nothing for it)
@@ -302,11 +284,8 @@ __global__ void __launch_bounds__(64) sr_cols_seq_kernel(const float* __restrict
     wave_fft<N>(z, CW, lane, tw, StoreNatural<N>{});
   };
 
-#ifndef MOF_K6S_ABLATE  // diagnostic build (results wrong by design): 1 = every wave reads pair 0's lines (L2 hits instead of HBM reads)
-#define MOF_K6S_ABLATE 0
-#endif
   cf ap[CW][MV];  // column spectra of the previous frame (doubled): 2 B[v][u]
-  load_cols(zh_prev + (size_t)((MOF_K6S_ABLATE != 0 || MOF_SR_L2_ABLATE != 0) ? 0 : p0) * zh_stride);
+  load_cols(zh_prev + (size_t)p0 * zh_stride);
 #pragma unroll
   for (int s = 0; s < CW; ++s)
 #pragma unroll
@@ -321,7 +300,7 @@ __global__ void __launch_bounds__(64) sr_cols_seq_kernel(const float* __restrict
   // rule of pcl_cols_kernel (pc_large_kernel.hip) and of the in-LDS kernels (pc_common.hpp)
   const int zq = BOX ? box_zero_period(n, N) : N + 1;
   for (int j = 0; j < np; ++j) {
-    load_cols(zh_cur + (size_t)((MOF_K6S_ABLATE != 0 || MOF_SR_L2_ABLATE != 0) ? 0 : p0 + j) * zh_stride);
+    load_cols(zh_cur + (size_t)(p0 + j) * zh_stride);
     bool box_zeros = false;
     if constexpr (BOX) box_zeros = __builtin_amdgcn_readfirstlane((int)(((flags[2 * (p0 + j)] & 1) == 0) || ((flags[2 * (p0 + j) + 1] & 1) == 0))) != 0;
     // normalised cross-power spectrum of bins (v, u), conjugated in place; the current spectra move into the registers
@@ -354,7 +333,7 @@ __global__ void __launch_bounds__(64) sr_cols_seq_kernel(const float* __restrict
     }
     wave_sync();
     wave_fft<N>(z, CW, lane, tw, StoreNatural<N>{});
-    cf* D = reinterpret_cast<cf*>(Dt) + (size_t)(MOF_SR_L2_ABLATE ? 0 : p0 + j) * (H + 1) * N;
+    cf* D = reinterpret_cast<cf*>(Dt) + (size_t)(p0 + j) * (H + 1) * N;
     if constexpr (ODD) {  // rows of N complex start on odd multiples of 8 bytes: element stores
 #pragma unroll
       for (int s = 0; s < CW; ++s) {
@@ -374,10 +353,7 @@ __global__ void __launch_bounds__(64) sr_cols_seq_kernel(const float* __restrict
           const int q = lane + 64 * m;
           if (q < N / 2 && u <= H) {
             const cf a0 = z[s * P::LINE + 2 * q], a1 = z[s * P::LINE + 2 * q + 1];
-            // (MOF_SR_L2_ABLATE = 2: Dt is not stored at all -- thousands of waves storing to the SAME aliased lines serialise in the L2 and
-            //  made the aliased build's K6s 44 % slower; dropping the store bounds the write side from above instead)
-            if (MOF_SR_L2_ABLATE == 2) asm volatile("" ::"v"(a0.x), "v"(a0.y), "v"(a1.x), "v"(a1.y));
-            else stream_store(reinterpret_cast<float4*>(D + (size_t)u * N + 2 * q), make_float4(a0.x, a0.y, a1.x, a1.y));
+            stream_store(reinterpret_cast<float4*>(D + (size_t)u * N + 2 * q), make_float4(a0.x, a0.y, a1.x, a1.y));
           }
         }
       }
@@ -400,11 +376,9 @@ __global__ void __launch_bounds__(64) sr_cols_seq_kernel(const float* __restrict
 //             -> LDS [line][k1][m2];  lane (line, m2) reads k1 = 0..14, twiddle W480^{k1 m2} (the SAME per-lane table), radix 15:
 //             S[32 m1 + m2] -> Dt (256 contiguous bytes per line and store).
 // 8 KB of LDS and ~half the registers per wave: four waves per SIMD.
-#ifndef MOF_K6P_WPE
-#define MOF_K6P_WPE 3
-#endif
+constexpr int K6P_WPE = 3;  // waves per SIMD the split-lane kernel is compiled for
 template <int N>
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MOF_K6P_WPE, MOF_K6P_WPE))) sr_cols_split_kernel(const float* __restrict__ zh_prev, const float* __restrict__ zh_cur,
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(K6P_WPE, K6P_WPE))) sr_cols_split_kernel(const float* __restrict__ zh_prev, const float* __restrict__ zh_cur,
                                                            size_t zh_stride, const float* __restrict__ twiddles,
                                                            float* __restrict__ Dt, int n_pairs, int run) {
   static_assert(N == 480, "15 x 32 only");

@@ -4,7 +4,7 @@
 # MOF_LIB_PATH; the product library and its object files are never touched (ablation variants may compute wrong results
 # by design -- nothing of them can leak into a later build).
 #   usage (on the GPU box):  tools/ab_variants.sh <source.hip> "<bench args>" "<flags variant 0>" "<flags variant 1>" ...
-#   e.g. tools/ab_variants.sh sr_kernel.hip "--workload c5" "-DMOF_SR_FWD_ROWS=8" "-DMOF_SR_FWD_ROWS=16"
+#   e.g. tools/ab_variants.sh pc_kernel.hip "--workload c2" "" "-DMOF_K1_TAIL_BARRIER=0"
 set -e
 R=${GRAFT_REPO_ROOT:-/root/repo}
 SRC=$1; BENCH_ARGS=$2; shift 2

@@ -1,11 +1,16 @@
 #!/usr/bin/env python3
-"""The static record of a libmof_hip.so: every kernel of every gfx950 code object with the numeric fields of its metadata note.
+"""The static record of a libmof_hip.so: every kernel of every gfx950 code object with the numeric fields of its metadata note and
+`code`, a SHA-256 over the bytes of the kernel's symbol in .text followed by its 64-byte descriptor <name>.kd.
 
   tools/kernel_static.py LIB             one line per kernel, sorted by name
-  tools/kernel_static.py compare A B     the names only in A, the names only in B, and the fields that changed
+  tools/kernel_static.py compare A B     whether each whole gfx950 code object is byte-identical, then the names only in A, the names
+                                         only in B, and the fields (code included) that changed
 
-Reads metadata only (llvm-readelf --notes on the unbundled code objects): no disassembly, no instruction is looked at.
+Reads metadata, the symbol table and the section headers (llvm-readelf --notes / --symbols / --section-headers on the unbundled code
+objects) and slices the symbols' bytes out of the file: no disassembly, no instruction is looked at. `code` covers the kernel's own
+symbol only: a change in a device function it calls (none is left un-inlined in this library) shows in the whole-object line alone.
 """
+import hashlib
 import os
 import re
 import shutil
@@ -63,6 +68,20 @@ def kernels_of(notes):
     return out
 
 
+def code_hashes(co, sections, symbols):
+    """{mangled name: sha256 hex of the symbol's bytes + its .kd descriptor} from the text of llvm-readelf -S and -s of code object `co`."""
+    sec = {}  # index -> (address, file offset)
+    for m in re.finditer(r"^\s*\[\s*(\d+)\]\s+\S+\s+(?:PROGBITS)\s+([0-9a-f]+)\s+([0-9a-f]+)\s+[0-9a-f]+", sections, re.M):
+        sec[int(m.group(1))] = (int(m.group(2), 16), int(m.group(3), 16))
+    sym = {}  # name -> bytes
+    for m in re.finditer(r"^\s*\d+:\s+([0-9a-f]+)\s+(\d+)\s+(?:FUNC|OBJECT)\s+\S+\s+\S+\s+(\d+)\s+(\S+)\s*$", symbols, re.M):
+        addr, size, ndx, name = int(m.group(1), 16), int(m.group(2)), int(m.group(3)), m.group(4)
+        if ndx in sec:
+            off = sec[ndx][1] + addr - sec[ndx][0]
+            sym[name] = co[off:off + size]
+    return {n: hashlib.sha256(b + sym[n + ".kd"]).hexdigest() for n, b in sym.items() if n + ".kd" in sym}
+
+
 def record(lib):
     readelf = tool("llvm-readelf")
     if not readelf:
@@ -73,7 +92,12 @@ def record(lib):
             path = os.path.join(tmp, f"co{i}.elf")
             with open(path, "wb") as f:
                 f.write(co)
+            code = code_hashes(co, subprocess.check_output([readelf, "-S", "-W", path], text=True),
+                               subprocess.check_output([readelf, "--symbols", "-W", path], text=True))
             for name, fields in kernels_of(subprocess.check_output([readelf, "--notes", path], text=True)).items():
+                if name not in code:
+                    sys.exit(f"{lib}: no symbol or no descriptor {name}.kd found for kernel {name} (llvm-readelf --symbols)")
+                fields["code"] = code[name]
                 while name in rec:  # (kernels of unnamed namespaces in two translation units may share a name)
                     name += "'"
                 rec[name] = fields
@@ -87,7 +111,7 @@ def record(lib):
 
 
 def row(fields):
-    return " ".join(f"{s} {fields.get(k, 0)}" for s, k in zip(SHORT, FIELDS))
+    return " ".join(f"{s} {fields.get(k, 0)}" for s, k in zip(SHORT, FIELDS)) + f" code {fields['code'][:16]}"
 
 
 def main(argv):
@@ -98,6 +122,11 @@ def main(argv):
         print(f"kernels: {len(rec)}")
         return 0
     if len(argv) == 4 and argv[1] == "compare":
+        ca, cb = [[hashlib.sha256(co).hexdigest() for co in code_objects(lib)] for lib in (argv[2], argv[3])]
+        same = sum(x == y for x, y in zip(ca, cb))
+        print(f"gfx950 code objects: A {len(ca)}, B {len(cb)}; byte-identical {same}" + ("" if len(ca) != len(cb) else f", differing {len(ca) - same}"))
+        for i, (x, y) in enumerate(zip(ca, cb)):
+            print(f"  code object {i}: {'identical' if x == y else f'DIFFERS {x[:16]} -> {y[:16]}'}")
         a, b = record(argv[2]), record(argv[3])
         only_a, only_b = sorted(set(a) - set(b)), sorted(set(b) - set(a))
         print(f"kernels: A {len(a)}, B {len(b)}; library {os.path.getsize(argv[2])} -> {os.path.getsize(argv[3])} bytes")
@@ -106,6 +135,8 @@ def main(argv):
         changed = 0
         for name in sorted(set(a) & set(b)):
             diff = [f"{s} {a[name].get(k, 0)} -> {b[name].get(k, 0)}" for s, k in zip(SHORT, FIELDS) if a[name].get(k, 0) != b[name].get(k, 0)]
+            if a[name]["code"] != b[name]["code"]:
+                diff.append(f"code {a[name]['code'][:16]} -> {b[name]['code'][:16]}")
             if diff:
                 changed += 1
                 print(f"{name}: {', '.join(diff)}")
