@@ -1,6 +1,7 @@
-// mfma_frag.hpp -- host-side helpers for the f16 operand tables of the matrix-core kernels (pc_passes3.hpp: fwd3_rows_mfma;
-// sr_fused_kernel.hip). A DFT matrix entry w (fp32) is split w = hi + lo into two halves: u8 pixels are exact in f16, both
-// products are exact in the f32 accumulator, so the matrix pass is as accurate as an fp32 one.
+// mfma_frag.hpp -- host-side helpers for the f16 operand tables of the matrix-core kernels (pc_passes3.hpp: fwd3_rows_mfma, the `make mfma`
+// library; the estimator's fused K56 used them until it was retired, docs/history/retired_switches.md). A DFT matrix entry w (fp32) is split
+// w = hi + lo into two halves: u8 pixels are exact in f16, both products are exact in the f32 accumulator, so the matrix pass is as accurate
+// as an fp32 one.
 #pragma once
 
 #include <cmath>

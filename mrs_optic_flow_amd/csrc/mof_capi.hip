@@ -100,8 +100,6 @@ struct FftRoute {
   int m = 0;                // transform size: the patch size (TUNED) or the size cv::phaseCorrelate pads it to
   int half_m = 0;           // > 0: full-resolution pair launches run the fused half-tile kernel of this size instead (pc_half_kernel.hip;
                             //      cv::phaseCorrelate model only)
-  int pair_half_wgs = 0;    // != 0: full-resolution pair launches run the pair kernel on the half tile (pc_seq_half.hip), this many
-                            //       workgroups per CU
   Video video = PAIRS;      // a video: the pair form on consecutive frames, K1s (pc_seq_kernel.hip), pc_seq_half.hip, or the half-tile
   int video_m = 0;          // kernel's sequence form at transform size video_m
   bool large_tuned = false; // LARGE, full resolution: the estimator's tuned K5s / K6s / K7 instead of L5 / L6 / L7
@@ -111,8 +109,8 @@ struct FftRoute {
 
 // The MOF_FFT_* knobs that select kernels (README), read once per process
 struct FftKnobs {
-  int half, pair_half_wgs;  // MOF_FFT_HALF: -1 unset
-  bool force_planned, force_large, pair_half, seq_pairs, seq_half64, seq_half128, half_seq_off, large_tuned, large_video;
+  int half;  // MOF_FFT_HALF: -1 unset
+  bool force_planned, force_large, seq_pairs, seq_half128, half_seq_off, large_tuned, large_video;
 };
 
 // The route of a configuration (validated by validate_fft); *plan receives the plan of the planned families. False: no plan.
@@ -123,10 +121,7 @@ bool fft_route(const mof_fft_config& c, mof::PcPlan* plan, FftRoute* r) {
     r.half = (v = getenv("MOF_FFT_HALF")) ? atoi(v) : -1;
     r.force_planned = getenv("MOF_FFT_FORCE_PLANNED") != nullptr;
     r.force_large = getenv("MOF_FFT_FORCE_LARGE") != nullptr;
-    r.pair_half = (v = getenv("MOF_FFT_PAIR_HALF")) && atoi(v) != 0;
-    r.pair_half_wgs = (v = getenv("MOF_FFT_PAIR_HALF_WGS")) ? atoi(v) : 2;
     r.seq_pairs = getenv("MOF_FFT_SEQ_PAIRS") != nullptr;
-    r.seq_half64 = getenv("MOF_FFT_SEQ_HALF64") != nullptr;
     r.seq_half128 = getenv("MOF_FFT_SEQ_HALF128") != nullptr;
     r.half_seq_off = (v = getenv("MOF_FFT_HALF_SEQ")) && atoi(v) == 0;
     r.large_tuned = !(v = getenv("MOF_FFT_LARGE_TUNED")) || atoi(v) != 0;
@@ -159,9 +154,6 @@ bool fft_route(const mof_fft_config& c, mof::PcPlan* plan, FftRoute* r) {
       (r->family == FftRoute::LARGE || k.half == 1 || (tuned && m == 120) ||
        (planned && (m == 60 || m == 72 || m == 90 || m == 96 || m == 100 || m == 120))))
     r->half_m = m;
-  // A/B (r05): independent pairs of 128 x 128 patches through the pair kernel on the HALF tile, two workgroups per CU (it has
-  // MOF_PEAK_OCL instantiations too)
-  if (tuned && r->half_m == 0 && k.pair_half && mof::pc_pair_half_supported(m)) r->pair_half_wgs = k.pair_half_wgs;
   // The video form. The half-tile kernel's sequence form: every size it serves by default but 162 (MOF_FFT_HALF_SEQ=0 keeps the pair form);
   // 128 x 128 patches, whose pair form stays on the tuned kernel -- there it beats the older half-tile sequence kernel (pc_seq_half.hip: one
   // 8-wave workgroup per CU, 192 VGPRs), c4seq 93.3 k -> 112 k pairs/s, MOF_FFT_SEQ_HALF128=1 keeps that one; and the planned sizes where only
@@ -172,7 +164,7 @@ bool fft_route(const mof_fft_config& c, mof::PcPlan* plan, FftRoute* r) {
   if (kh_m > 0 && ocv && !k.seq_pairs && !k.half_seq_off && mof::pc_half_sequence_supported(kh_m)) {
     r->video = FftRoute::HALF_SEQ;
     r->video_m = kh_m;
-  } else if (tuned && !k.seq_pairs && mof::pc_sequence_half_supported(m) && (m != 64 || k.seq_half64)) {
+  } else if (tuned && !k.seq_pairs && mof::pc_sequence_half_supported(m)) {
     r->video = FftRoute::SEQ_HALF;
   } else if (tuned && !k.seq_pairs && mof::pc_sequence_supported(m)) {
     r->video = FftRoute::SEQ;
@@ -211,8 +203,6 @@ struct mof_fft_engine {
   bool first = true;                      // FftMethod.cpp:1761
   FftRoute route;
   mof::PcPlan plan{};                     // route.family PLANNED / LARGE
-  mof::DevMem<float> d_pair_slabs;        // route.pair_half_wgs: slabs of the pair kernel on the half tile, one per workgroup
-  int n_pair_slabs = 0;
   // scratch of the large-patch pipeline, for `cap` patch pairs per pass: row half-spectra of 2 cap patches, Dt, peak
   // candidates, constant-patch flags, C_dc. Grown by a batch that needs more (never under a graph capture, never while pinned).
   mof::DevMem<float> d_zh, d_dt, d_cdc;
@@ -354,10 +344,6 @@ static int launch_field(mof_fft_engine* e, const mof::PcArgs& a, int n_pairs, hi
     return MOF_OK;
   }
   if (r.family == FftRoute::LARGE) return launch_large(e, a, n_pairs, stream);
-  if (r.pair_half_wgs != 0 && a.downscale == 1) {
-    HIP_TRY(mof::launch_pc_pair_half(a, e->cfg.patch_size, n_pairs, e->d_pair_slabs, e->n_pair_slabs, stream));
-    return MOF_OK;
-  }
   HIP_TRY(r.family == FftRoute::PLANNED ? mof::launch_pc_generic(a, e->plan, n_pairs, stream)
                                         : mof::launch_pc_field(a, e->cfg.patch_size, n_pairs, stream));
   return MOF_OK;
@@ -538,11 +524,6 @@ int mof_fft_create(const mof_fft_config* cfg, mof_fft_engine** out) try {
   }
   if (r.video == FftRoute::SEQ) HIP_TRY(mof::pc_configure_sequence());
   if (r.video == FftRoute::SEQ_HALF) HIP_TRY(mof::pc_configure_sequence_half(r.m));
-  if (r.pair_half_wgs != 0) {
-    e->n_pair_slabs = r.pair_half_wgs * mof::pc_cu_count();
-    HIP_TRY(mof::pc_configure_pair_half(r.m));
-    HIP_TRY(e->d_pair_slabs.alloc((size_t)e->n_pair_slabs * mof::pc_pair_half_slab_floats(r.m)));
-  }
   *out = e.release();
   return MOF_OK;
 } catch (const std::bad_alloc&) {

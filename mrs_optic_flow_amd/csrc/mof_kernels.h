@@ -117,16 +117,10 @@ hipError_t launch_pc_field(const PcArgs& a, int patch_size, int n_pairs, hipStre
 bool pc_sequence_supported(int patch_size);
 hipError_t pc_configure_sequence();
 hipError_t launch_pc_sequence(const PcArgs& a, int n_pairs, int run, hipStream_t stream);
-// The same on a half-size tile (pc_seq_half.hip): 128 x 128 patches (two workgroups per CU); 64 x 64 for A/B only
+// The same on a half-size tile (pc_seq_half.hip): 128 x 128 patches, two workgroups per CU
 bool pc_sequence_half_supported(int patch_size);
 hipError_t pc_configure_sequence_half(int patch_size);
 hipError_t launch_pc_sequence_half(const PcArgs& a, int patch_size, int n_pairs, int run, hipStream_t stream);
-// The PAIR form on the half tile (pc_seq_half.hip, r05; 128 x 128 patches): persistent workgroups, two per CU, the previous image's
-// spectrum parked in a per-workgroup slab of device memory (n_slabs slabs of pc_pair_half_slab_floats floats, owned by the engine)
-bool pc_pair_half_supported(int patch_size);
-size_t pc_pair_half_slab_floats(int patch_size);
-hipError_t pc_configure_pair_half(int patch_size);
-hipError_t launch_pc_pair_half(const PcArgs& a, int patch_size, int n_pairs, float* slabs, int n_slabs, hipStream_t stream);
 // N = 64, quad-per-line formulation (pc_kernel_quad.hip)
 hipError_t pc_configure_quad64();
 hipError_t launch_pc_field_quad64(const PcArgs& a, int n_pairs, hipStream_t stream);
@@ -186,18 +180,22 @@ struct SrLpArgs {
   int box_dwords_max;      // dwords of the largest box
 };
 
+// Residue, kept on purpose: lp_cur, lp_prev, lp_stride, Zt and degen were read by the retired packed pair kernels K5 / K6 only
+// (docs/history/retired_switches.md) and are always zero now. K7 and K8 take this struct by value: without the five fields their kernel
+// arguments move and both kernels come out with other SGPR counts and other code; with them -- and K8's read of the null `degen` -- every
+// instantiation is the one measured so far (profiles/runtime_forms_retirement.txt).
 struct SrPcArgs {
-  const uint8_t* lp_cur;   // pair k at + k*lp_stride, res*res u8 each
-  const uint8_t* lp_prev;
-  size_t lp_stride;
+  const uint8_t* lp_cur;   // (residue)
+  const uint8_t* lp_prev;  // (residue)
+  size_t lp_stride;        // (residue)
   const float* twiddles;   // res (cos, -sin) pairs
-  float* Zt;               // scratch [pairs][res u][res v] complex: row transforms, stored transposed
+  float* Zt;               // (residue)
   float* Dt;               // scratch [pairs][res/2+1 u][res y] complex: half spectrum after the column passes
   float2* cand;            // scratch [pairs][n_cand] (value, shifted index)
   int n_cand;
   double M;                // log-polar magnitude
   double* out;             // [pairs][4] = scale, rot, pt.x, pt.y
-  int* degen;              // pair pipeline only (else null): [pairs], K6 -> K8: one of the two log-polar images is all zero
+  int* degen;              // (residue: null)
 };
 
 // host-side tables of cv::logPolar / cv::remap (mof_sr.hip); exposed so that the CPU suite can compare them with the oracle
@@ -211,14 +209,12 @@ std::vector<uint32_t> sr_weight_planes(const std::vector<int16_t>& weights, int 
 // tile = 8 (per-wave boxes) or 16 (super-tile boxes shared by a workgroup)
 std::vector<SrTileBox> sr_tile_boxes(const std::vector<SrMapEntry>& map, int res, int ksize, int* lds_per_wave, int tile_px);
 
-bool sr_pair_kernels_supported(int res);    // the packed pair kernels K5 / K6 (and K6p) exist for this resolution: 240, 256, 480
+bool sr_always_tuned(int res);             // 240, 256, 480: on the tuned transforms whatever MOF_SR_TUNED_ALL says
 bool sr_transform_size_tuned(int m, bool* exact_nyquist);  // the tuned transforms K5s / K6s / K7 exist for transform size m (sr_common.hpp: MOF_SR_TUNED_SIZES)
 
 // The MOF_SR_* knobs of the estimator's engine (README), read once per process (mof_sr.hip: sr_knobs)
 struct SrKnobs {
   bool tuned_all = true;  // MOF_SR_TUNED_ALL=0: tuned transforms at 240 / 256 / 480 only, every other resolution on the planned pipeline
-  bool pair_seq = true;   // MOF_SR_PAIR_SEQ=0: independent pairs of 240 / 256 / 480 through the packed pair kernels K5 / K6
-  bool fused = false;     // MOF_SR_FUSED=1: K56 for the independent pairs of the resolutions it is built for
   bool verbose = false;   // MOF_SR_VERBOSE
   int seq_run = 0;        // MOF_SR_SEQ_RUN in 1 .. 4096: the fixed run of K6s; 0: chosen per pass
   int chunk = 0;          // MOF_SR_CHUNK: pairs per pass over mof_sr_config.batch_chunk (a value outside 1 .. 4096: the default); 0: unset
@@ -227,7 +223,6 @@ struct SrKnobs {
 // Which kernels an estimator launches and how large its buffers are, decided once at create (sr_route)
 struct SrRoute {
   enum Family { TUNED, TUNED_PAD, PLANNED };
-  enum Pairs { FRAMES, PACKED, FUSED };
   Family family = TUNED;  // TUNED: K5s / K6s / K7 + K8 on the resolution itself; the resolution padded to m = getOptimalDFTSize: TUNED_PAD, the
                           // zero-padding frame form of K5s, K6s, K7 and the planned pipeline's final kernel -- or PLANNED, L5 - L8 (pc_large_kernel.hip)
   int m = 0;              // transform size
@@ -235,7 +230,6 @@ struct SrRoute {
   size_t sums_off = 0;    // behind the padded rows), so they travel wherever the slot is copied
   size_t zh_floats = 0;   // floats of one image's row half-spectra (Dt has the same shape)
   int candidates = 0;     // peak candidates per pair
-  Pairs pairs = FRAMES;   // the batch entry's independent pairs: the frame kernels, the packed K5 / K6, or the fused K56
   int seq_run = 0;        // pairs one wave of K6s walks in time: 0 = chosen per pass, MOF_SR_SEQ_RUN fixes it (r05: 16)
 };
 // Pure host code (no HIP call): the route of an even resolution >= 16; *plan receives the line plan of the padded families. False: the
@@ -243,7 +237,6 @@ struct SrRoute {
 bool sr_route(int resolution, const SrKnobs& k, PcPlan* plan, SrRoute* r);
 int sr_candidates(int res);
 hipError_t launch_sr_logpolar(const SrLpArgs& a, int interp /*2 cubic, 4 lanczos4*/, int n_images, hipStream_t stream);
-hipError_t launch_sr_phase_correlate(const SrPcArgs& a, int res, int n_pairs, hipStream_t stream);
 // K7 + K8 alone (uses a.Dt, a.cand, a.twiddles, a.M, a.out)
 hipError_t launch_sr_peak(const SrPcArgs& a, int res, int n_pairs, hipStream_t stream);
 // Sequence pipeline (sr_seq_kernel.hip). Zh = the row half-spectra of ONE log-polar image, doubled and transposed:
@@ -289,12 +282,6 @@ struct SrColsSeq {
 };
 hipError_t launch_sr_cols_seq(const SrColsSeq& a, int n_pairs, hipStream_t stream);
 int sr_seq_columns_per_wave(int res);  // K6s's columns per wave at transform size res; 0: no K6s there
-// K56 (sr_fused_kernel.hip): K5s + K6s in one kernel, the row transforms as a dense product on the matrix cores -- reads the u8
-// log-polar images instead of Zh. `frags` = sr_fused_fragments(res) on the device. Same pair / run semantics as K6s.
-bool sr_fused_supported(int res);
-std::vector<uint32_t> sr_fused_fragments(int res);
-hipError_t launch_sr_cols_fused(const uint8_t* lp_prev, const uint8_t* lp_cur, size_t lp_stride, const uint32_t* frags,
-                                const float* twiddles, float* Dt, int res, int n_pairs, int run, hipStream_t stream);
 
 // ---- the camera front end (fe_kernel.hip): cv::resize by an exact integer factor, crop, CV_RGB2GRAY -> gray crops ----
 struct FeArgs {

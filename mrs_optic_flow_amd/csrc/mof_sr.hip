@@ -48,8 +48,6 @@ const mof::SrKnobs& sr_knobs() {
     mof::SrKnobs r;
     const char* v;
     r.tuned_all = !(v = getenv("MOF_SR_TUNED_ALL")) || atoi(v) != 0;
-    r.pair_seq = !(v = getenv("MOF_SR_PAIR_SEQ")) || atoi(v) != 0;
-    r.fused = (v = getenv("MOF_SR_FUSED")) && atoi(v) != 0;
     r.verbose = (v = getenv("MOF_SR_VERBOSE")) && atoi(v) != 0;
     if ((v = getenv("MOF_SR_SEQ_RUN")) && atoi(v) >= 1 && atoi(v) <= 4096) r.seq_run = atoi(v);
     if ((v = getenv("MOF_SR_CHUNK"))) r.chunk = atoi(v) >= 1 && atoi(v) <= 4096 ? atoi(v) : kChunkDefault;
@@ -242,16 +240,13 @@ std::vector<SrTileBox> sr_tile_boxes(const std::vector<SrMapEntry>& map, int res
 bool sr_route(int res, const SrKnobs& k, PcPlan* plan, SrRoute* r) {
   *r = SrRoute{};
   bool exact = false;
-  if (sr_pair_kernels_supported(res) || (k.tuned_all && res % 2 == 0 && sr_transform_size_tuned(res, &exact) && exact)) {
+  if (sr_always_tuned(res) || (k.tuned_all && res % 2 == 0 && sr_transform_size_tuned(res, &exact) && exact)) {
     r->m = res;
     r->zh_floats = sr_zh_floats(res);
     r->candidates = sr_candidates(res);
     // Independent pairs run the FRAME kernels too (sr_seq_kernel.hip): each of the 2n log-polar images gets its own real row transform, K6s
-    // correlates slot 2p against 2p + 1, one pair per wave-run. Same-box c5: 360 k pairs/s against 354 k for the packed pair kernels (K5 / K6
-    // of sr_kernel.hip, MOF_SR_PAIR_SEQ=0; 240 / 256 / 480 only), and the batch entry computes exactly what the stateful entry computes for a
-    // fresh estimator fed (prev, cur): same bits. MOF_SR_FUSED: K56, K5s + K6s in one kernel.
-    if (!k.pair_seq && sr_pair_kernels_supported(res)) r->pairs = SrRoute::PACKED;
-    else if (k.fused && sr_fused_supported(res)) r->pairs = SrRoute::FUSED;
+    // correlates slot 2p against 2p + 1, one pair per wave-run, and the batch entry computes exactly what the stateful entry computes for a
+    // fresh estimator fed (prev, cur): same bits. (The packed pair kernels and the fused K56 lost to them: docs/history/retired_switches.md.)
   } else {
     if (!pc_build_line_plan(res, plan)) return false;
     r->family = SrRoute::PLANNED;
@@ -297,7 +292,6 @@ struct mof_sr_engine {
   mof::DevMem<float> d_twiddles;
   mof::DevMem<uint8_t> d_frame;    // staging for the stateful path (res*res)
   mof::DevMem<uint8_t> d_temp_im;  // tempIm, :27
-  mof::DevMem<uint32_t> d_wfrag;   // K56 (sr_fused_kernel.hip): f16 hi / lo fragments of the row-DFT matrix, tuned resolutions only
   mof::DevMem<float> d_zh_prev;    // prevIm_F32 (:48, :128), kept as what the correlation needs of it: its row half-spectra
                                    // (sr_seq_kernel.hip, K5s) -- each frame is remapped and row-transformed ONCE
   // the pipeline scratch (scratch_alloc). A batch call captured into a HIP graph bakes raw pointers into it into the graph's kernel
@@ -306,7 +300,6 @@ struct mof_sr_engine {
   mof::DevMem<float> d_Zt, d_Dt;
   mof::DevMem<float2> d_cand;
   mof::DevMem<double> d_out;       // [kChunk][4]
-  mof::DevMem<int> d_degen;        // [kChunk]: K6 -> K8 flag of the pair pipeline (an all-zero log-polar image)
   mof::PinnedMem<uint8_t> h_stage;
   mof::PinnedMem<double> h_out;
   mof::PinnedMem<double> h_seq;    // [chunk][4]: a pass's results, read back when a sequence call resolves the gate
@@ -346,10 +339,6 @@ hipError_t rows_real(const mof_sr_engine* e, const uint8_t* lp, size_t lp_stride
     if (err != hipSuccess) return err;
   }
   return mof::launch_sr_rows_real_src(mof::SrRowsSrc{src, e->d_twiddles, zh, zh_stride, nullptr, r.m, 1, res, sums}, n_frames, s);
-}
-// K56: K5s + K6s in one kernel on the u8 log-polar images (route.pairs FUSED; the fragments exist only then)
-hipError_t cols_fused(const mof_sr_engine* e, const uint8_t* lp_prev, const uint8_t* lp_cur, size_t lp_stride, int n_pairs, int run, hipStream_t s) {
-  return mof::launch_sr_cols_fused(lp_prev, lp_cur, lp_stride, e->d_wfrag, e->d_twiddles, e->d_Dt, e->cfg.resolution, n_pairs, run, s);
 }
 // Run length of K6s for a pass of m consecutive pairs (r06; tools/video_probe.py showed the same shape on the FFT engine's video kernel): a
 // wave walks `run` pairs one after the other, so a short video in runs of 16 leaves most of the chip idle -- 64 frames of 480^2 are 61 column
@@ -403,13 +392,12 @@ hipError_t peak(const mof_sr_engine* e, const mof::SrPcArgs& a, int n_pairs, hip
 hipError_t scratch_alloc(mof_sr_engine* e, int pairs) {
   mof::RelaxedCapture relaxed;  // allocation / release must not invalidate a capture on another thread
   const size_t nn = (size_t)e->cfg.resolution * e->cfg.resolution, zhf = e->route.zh_floats, n = (size_t)pairs;
-  // d_Zt: the pair pipeline's packed row spectra, nn complex per pair; the sequence pipeline's (pairs + 1) frames of half spectra;
-  // pairs through the frame kernels: 2 * pairs frames of half spectra
-  const size_t zt = e->route.family == SrRoute::TUNED ? n * nn * 2 : 0, zh = (n + 1 > 2 * n ? n + 1 : 2 * n) * zhf;
+  // d_Zt: the sequence pipeline's (pairs + 1) frames of half spectra; independent pairs: 2 * pairs frames of half spectra
+  const size_t zh = (n + 1 > 2 * n ? n + 1 : 2 * n) * zhf;
   e->scratch_pairs = 0;
   // d_lp holds two passes: remap of pass k+1 beside the transforms of pass k; Dt has Zh's shape
-  const hipError_t err = mof::alloc_all(e->d_lp, 2 * n * 2 * nn, e->d_Zt, zt > zh ? zt : zh, e->d_Dt, n * zhf, e->d_cand, n * e->route.candidates,
-                                        e->d_out, n * 4, e->d_degen, n);
+  const hipError_t err = mof::alloc_all(e->d_lp, 2 * n * 2 * nn, e->d_Zt, zh, e->d_Dt, n * zhf, e->d_cand, n * e->route.candidates,
+                                        e->d_out, n * 4);
   if (err == hipSuccess) e->scratch_pairs = pairs;
   return err;
 }
@@ -542,8 +530,6 @@ int mof_sr_create(const mof_sr_config* cfg, mof_sr_engine** out) try {
   HIP_TRY(mof::upload(e->d_wp[0], mof::sr_weight_planes(wc, 4), e->stream));
   HIP_TRY(mof::upload(e->d_wp[1], mof::sr_weight_planes(wl, 8), e->stream));
   HIP_TRY(mof::upload(e->d_twiddles, tw, e->stream));
-  if (route.pairs == SrRoute::FUSED)  // (1 MB of f16 matrix fragments at 480: only for the opt-in path)
-    HIP_TRY(mof::upload(e->d_wfrag, mof::sr_fused_fragments(res), e->stream));
   HIP_TRY(mof::alloc_all(e->d_frame, nn, e->d_temp_im, nn, e->d_zh_prev, route.zh_floats));
   HIP_TRY(mof::fill_on(e->stream, e->d_temp_im, 0, nn));  // tempIm = cv::Mat::zeros, :27
   HIP_TRY(mof::fill_on(e->stream, e->d_zh_prev, 0, route.zh_floats * sizeof(float)));
@@ -577,14 +563,9 @@ static void lp_tables(const mof_sr_engine* e, int interp, mof::SrLpArgs* lp) {
   lp->box_dwords_max = e->lds_per_wave[k] / 4;
 }
 
-static mof::SrPcArgs pc_args(const mof_sr_engine* e, const uint8_t* lp_cur, const uint8_t* lp_prev, size_t lp_stride,
-                             double* out) {
+static mof::SrPcArgs pc_args(const mof_sr_engine* e, double* out) {
   mof::SrPcArgs a{};
-  a.lp_cur = lp_cur;
-  a.lp_prev = lp_prev;
-  a.lp_stride = lp_stride;
   a.twiddles = e->d_twiddles;
-  a.Zt = e->d_Zt;
   a.Dt = e->d_Dt;
   a.cand = e->d_cand;
   a.n_cand = e->route.candidates;
@@ -597,7 +578,7 @@ static mof::SrPcArgs pc_args(const mof_sr_engine* e, const uint8_t* lp_cur, cons
 static hipError_t seq_one_pair(mof_sr_engine* e, const float* zh_prev, const float* zh_cur, double* out, hipStream_t s) {
   hipError_t err = cols_seq(e, zh_prev, zh_cur, 0, 1, 1, s);
   if (err != hipSuccess) return err;
-  mof::SrPcArgs a = pc_args(e, nullptr, nullptr, 0, out);
+  mof::SrPcArgs a = pc_args(e, out);
   return peak(e, a, 1, s);
 }
 
@@ -716,7 +697,7 @@ int mof_sr_process_sequence_device(mof_sr_engine* e, const uint8_t* d_frames, si
         HIP_TRY(mof::launch_sr_logpolar(lp, 4, m, s));  // INTER_LANCZOS4, :112 -- every frame once
         HIP_TRY(rows_real(e, e->d_lp + nn, nn, zh + zhf, zhf, m, s));
         HIP_TRY(cols_seq(e, zh, zh + zhf, zhf, m, seq_run_for(e, m), s));
-        mof::SrPcArgs a = pc_args(e, nullptr, nullptr, 0, d_out + 4 * (size_t)done);
+        mof::SrPcArgs a = pc_args(e, d_out + 4 * (size_t)done);
         HIP_TRY(peak(e, a, m, s));
         carry = m;
         if (n_gated) {
@@ -850,20 +831,11 @@ int mof_sr_process_batch_device(mof_sr_engine* e, const uint8_t* d_cur, size_t c
       HIP_TRY(hipEventRecord(e->ev_lp[b], sr));
       HIP_TRY(hipStreamWaitEvent(s, e->ev_lp[b], 0));  // also the join: every remap precedes a wait on the caller's stream
     }
-    mof::SrPcArgs a = pc_args(e, lp_buf, lp_buf + nn, 2 * nn, d_out + 4 * (size_t)k0);
-    if (e->route.pairs == SrRoute::PACKED) {
-      a.degen = e->d_degen;
-      HIP_TRY(mof::launch_sr_phase_correlate(a, res, n, s));
-    } else {
-      const size_t zhf = e->route.zh_floats;
-      if (e->route.pairs == SrRoute::FUSED) {
-        HIP_TRY(cols_fused(e, lp_buf + nn, lp_buf, 2 * nn, n, 1, s));
-      } else {  // the frame kernels: image 2p = cur of pair p, 2p + 1 = prev
-        HIP_TRY(rows_real(e, lp_buf, nn, e->d_Zt, zhf, 2 * n, s));
-        HIP_TRY(cols_seq(e, e->d_Zt + zhf, e->d_Zt, 2 * zhf, n, 1, s));
-      }
-      HIP_TRY(peak(e, a, n, s));
-    }
+    // the frame kernels: image 2p = cur of pair p, 2p + 1 = prev
+    const size_t zhf = e->route.zh_floats;
+    HIP_TRY(rows_real(e, lp_buf, nn, e->d_Zt, zhf, 2 * n, s));
+    HIP_TRY(cols_seq(e, e->d_Zt + zhf, e->d_Zt, 2 * zhf, n, 1, s));
+    HIP_TRY(peak(e, pc_args(e, d_out + 4 * (size_t)k0), n, s));
     if (two_lanes) HIP_TRY(hipEventRecord(e->ev_fft[b], s));
   }
   HIP_TRY(e->fence.release(s));

@@ -13,7 +13,9 @@
 // Per frame: rows (wave-local) -> barrier -> columns forward, cross-power against the previous frame's spectrum held in
 // registers (16 complex bins per lane), columns inverse -> barrier -> row pairs + arg-max -> barrier -> centroid -> barrier.
 // R1 = 16 != R2 = 8, so unlike N = 64 the cross-power result passes through LDS once on its way into the inverse transform.
-// Template on N: the N = 64 instantiation exists for A/B against pc_seq_kernel.hip's full-tile form (MOF_FFT_SEQ_HALF64=1).
+// This file serves ONE size, 128: the default video kernel there under MOF_PEAK_OCL, the MOF_FFT_SEQ_HALF128=1 form otherwise. N stays a
+// template parameter because the kernel's name carries it; HalfCfg<128> is its only configuration (the 64 x 64 instantiation and the pair
+// form on this tile lost their A/Bs: docs/history/retired_switches.md).
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -29,10 +31,6 @@ namespace {
 
 template <int N>
 struct HalfCfg;
-template <>
-struct HalfCfg<64> {
-  static constexpr int R1 = 8, R2 = 8, SK = 3, GAP = 4, PITCH = 80, WAVES = 4;
-};
 template <>
 struct HalfCfg<128> {
   static constexpr int R1 = 16, R2 = 8, SK = 4, GAP = 8, PITCH = 152, WAVES = 8;
@@ -50,38 +48,23 @@ struct HalfTile {
   static __device__ __forceinline__ int out(int y1, int c) { return c < H ? spec(y1, c) : spec(y1 + H, c - H); }
 };
 
-// Second-stage twiddles W_N^{k x}, k = 1..7. N = 64: held in registers for the whole kernel (as K1). N = 128: fetched from
-// the L1-resident table right before each second stage -- the 28 VGPRs of two resident sets do not fit beside the 32 of the
-// previous frame's spectrum at four waves per SIMD (72 spilled registers otherwise).
+// Second-stage twiddles W_N^{k x}, k = 1..7, fetched from the L1-resident table right before each second stage -- the 28 VGPRs of two
+// resident sets do not fit beside the 32 of the previous frame's spectrum at four waves per SIMD (72 spilled registers otherwise).
 template <int N>
 struct HalfTw {
-  static constexpr bool IN_REGS = N == 64;
-  cf row[IN_REGS ? 7 : 1], col[IN_REGS ? 7 : 1];
   const float* table;
   int xr, xc;
   __device__ __forceinline__ void init(const float* t, int lane) {
     table = t;
     xr = lane % HalfCfg<N>::R1;
     xc = lane / (64 / HalfCfg<N>::R1);
-    if constexpr (IN_REGS) {
-#pragma unroll
-      for (int k = 1; k < 8; ++k) {
-        row[k - 1] = {t[2 * (k * xr)], t[2 * (k * xr) + 1]};
-        col[k - 1] = {t[2 * (k * xc)], t[2 * (k * xc) + 1]};
-      }
-    }
   }
   __device__ __forceinline__ void get(bool is_row, cf* out) const {
-    if constexpr (IN_REGS) {
+    const int x = is_row ? xr : xc;
 #pragma unroll
-      for (int k = 0; k < 7; ++k) out[k] = is_row ? row[k] : col[k];
-    } else {
-      const int x = is_row ? xr : xc;
-#pragma unroll
-      for (int k = 1; k < 8; ++k) {
-        const float2 t = *reinterpret_cast<const float2*>(table + 2 * (k * x));
-        out[k - 1] = {t.x, t.y};
-      }
+    for (int k = 1; k < 8; ++k) {
+      const float2 t = *reinterpret_cast<const float2*>(table + 2 * (k * x));
+      out[k - 1] = {t.x, t.y};
     }
   }
 };
@@ -112,24 +95,19 @@ __device__ __forceinline__ void half_raw_store(cf* z, int line0, int lane, const
 }
 
 // ---- transforms along x of the wave's 8 lines, then the wave-local untangle into the two half-spectrum rows per line ----
-template <int N, bool RAW = false>
+template <int N>
 __device__ __forceinline__ void half_rows(cf* __restrict__ z, int line0, int lane, const HalfTw<N>& tw) {
   using L = HalfTile<N>;
   constexpr int R1 = L::R1, R2 = L::R2, H = L::H;
   {
     const int ln = line0 + (lane >> 3), x = lane & 7;
     cf v[R1];
-    if constexpr (RAW) {
-      typedef const volatile uint16_t __attribute__((address_space(3))) * lds_u16_ptr;
-      const unsigned char* src = half_raw_area<N>(z, line0) + (lane >> 3) * HALF_RAW_PITCH + 2 * x;
+    typedef const volatile uint16_t __attribute__((address_space(3))) * lds_u16_ptr;
+    const unsigned char* src = half_raw_area<N>(z, line0) + (lane >> 3) * HALF_RAW_PITCH + 2 * x;
 #pragma unroll
-      for (int k = 0; k < R1; ++k) {
-        const uint32_t ab = *(lds_u16_ptr)(src + 2 * k * R2);
-        v[k] = {(float)(ab & 0xffu), (float)(ab >> 8)};
-      }
-    } else {
-#pragma unroll
-      for (int k = 0; k < R1; ++k) v[k] = lds_read(&z[L::line(ln, x + k * R2)]);
+    for (int k = 0; k < R1; ++k) {  // the raw bytes of half_raw_store: this stage converts
+      const uint32_t ab = *(lds_u16_ptr)(src + 2 * k * R2);
+      v[k] = {(float)(ab & 0xffu), (float)(ab >> 8)};
     }
     butterfly<R1>(v);
     wave_sync();
@@ -187,29 +165,10 @@ __device__ __forceinline__ void half_rows(cf* __restrict__ z, int line0, int lan
 }
 
 // ---- the wave's 8 columns: forward along y, cross-power against `prev`, inverse along y ------------------------------
-// Where the previous image's column spectra wait between the two images of a PAIR (pc_pair_half_kernel): in the sequence kernel they
-// stay in the registers `prev`; the pair kernel parks them in a per-workgroup slab of global memory (L2 / Infinity Cache resident:
-// written and re-read by the same lanes a few microseconds apart), so that the 32 registers are free while the current image's
-// rows and columns are transformed -- what lets the 128 x 128 form fit 128 VGPRs = two workgroups per CU.
-struct PrevInRegs {
-  static constexpr bool parked = false;
-  __device__ __forceinline__ void store(int, cf) const {}
-  __device__ __forceinline__ cf load(int) const { return cf{0.f, 0.f}; }
-};
-struct PrevInSlab {
-  static constexpr bool parked = true;
-  float2* slab;  // [elements per lane][threads], this lane's column
-  int threads;
-  __device__ __forceinline__ void store(int i, cf v) const { slab[(size_t)i * threads] = make_float2(v.x, v.y); }
-  __device__ __forceinline__ cf load(int i) const {
-    const float2 t = slab[(size_t)i * threads];
-    return cf{t.x, t.y};
-  }
-};
-
-template <int N, int PK, class Park = PrevInRegs>
+// (the previous frame's column spectra stay in the registers `prev`, `prev0`, `prevH`; prime: the run's first frame only fills them)
+template <int N, int PK>
 __device__ __forceinline__ void half_cols(cf* __restrict__ z, int col0, int lane, const HalfTw<N>& tw, cf (*prev)[8], cf* prev0,
-                                          cf* prevH, bool prime, bool has_col0, Park park = Park{}) {
+                                          cf* prevH, bool prime, bool has_col0) {
   using L = HalfTile<N>;
   constexpr int R1 = L::R1, R2 = L::R2, H = L::H, PER = 8 * R1 / 64, CW = 64 / R1;
   auto stage1 = [&](bool load) {
@@ -285,60 +244,28 @@ __device__ __forceinline__ void half_cols(cf* __restrict__ z, int col0, int lane
 #pragma unroll
     for (int b = 0; b < PER; ++b)
 #pragma unroll
-      for (int k = 0; k < R2; ++k) {
-        if constexpr (Park::parked) park.store(b * R2 + k, v[b][k]);
-        else prev[b][k] = v[b][k];
-      }
+      for (int k = 0; k < R2; ++k) prev[b][k] = v[b][k];
     return;
   }
-  if constexpr (Park::parked) {
-    cf pv[PER][R2];
 #pragma unroll
-    for (int b = 0; b < PER; ++b)
+  for (int b = 0; b < PER; ++b)
 #pragma unroll
-      for (int k = 0; k < R2; ++k) pv[b][k] = park.load(b * R2 + k);
-#pragma unroll
-    for (int b = 0; b < PER; ++b)
-#pragma unroll
-      for (int k = 0; k < R2; ++k) {
-        const cf C = cross_power_ab<PK>(v[b][k], pv[b][k], false);
-        v[b][k] = {C.x, -C.y};
-      }
-  } else {
-#pragma unroll
-    for (int b = 0; b < PER; ++b)
-#pragma unroll
-      for (int k = 0; k < R2; ++k) {
-        const cf C = cross_power_ab<PK>(v[b][k], prev[b][k], false);
-        prev[b][k] = v[b][k];
-        v[b][k] = {C.x, -C.y};
-      }
-  }
-  if constexpr (R1 == R2) {
-    // 64 = 8 x 8: the second-stage output distribution IS the first-stage input distribution: registers go straight on
-    const int col = col0 + (lane & 7), x = lane >> 3;
-    if (holder) {
-#pragma unroll
-      for (int k = 0; k < R2; ++k) v[0][k] = lds_read(&z[L::spec(x + k * R1, 0)]);
+    for (int k = 0; k < R2; ++k) {
+      const cf C = cross_power_ab<PK>(v[b][k], prev[b][k], false);
+      prev[b][k] = v[b][k];
+      v[b][k] = {C.x, -C.y};
     }
-    butterfly<R1>(v[0]);
-    wave_sync();
+  // conj(C) back to its natural place (column 0 is already there), then the first stage reads its own distribution
 #pragma unroll
-    for (int k = 0; k < R1; ++k) z[L::spec(x * R1 + k, col)] = v[0][k];
-    wave_sync();
-  } else {
-    // conj(C) back to its natural place (column 0 is already there), then the first stage reads its own distribution
+  for (int b = 0; b < PER; ++b) {
+    const int col = col0 + lane % CW + CW * b, x = lane / CW;
+    if (!(holder && b == 0)) {
 #pragma unroll
-    for (int b = 0; b < PER; ++b) {
-      const int col = col0 + lane % CW + CW * b, x = lane / CW;
-      if (!(holder && b == 0)) {
-#pragma unroll
-        for (int k = 0; k < R2; ++k) z[L::spec(x + k * R1, col)] = v[b][k];
-      }
+      for (int k = 0; k < R2; ++k) z[L::spec(x + k * R1, col)] = v[b][k];
     }
-    wave_sync();
-    stage1(false);
   }
+  wave_sync();
+  stage1(false);
   {
     cf tw_col[7];
     tw.get(false, tw_col);
@@ -429,9 +356,10 @@ __device__ __forceinline__ Best half_row_pairs(cf* __restrict__ z, int row0, int
 
 // CH = 3: interleaved BGR8 frames, CV_RGB2GRAY in the load (as pc_seq_kernel.hip)
 template <int N, int PK, int CH>
-__global__ void __launch_bounds__(HalfTile<N>::T, (N == 64 ? 4 : 2)) pc_seq_half_kernel(PcArgs a, int n_pairs, int run) {
+__global__ void __launch_bounds__(HalfTile<N>::T, 2) pc_seq_half_kernel(PcArgs a, int n_pairs, int run) {
   using L = HalfTile<N>;
   constexpr int H = L::H, R1 = L::R1, W = HalfCfg<N>::WAVES, PPL = N / 8;  // pixels per lane and row
+  static_assert(PPL == 16, "half_raw_store stages 16 + 16 pixels per lane");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   cf* z = reinterpret_cast<cf*>(smem);
   Best* red = reinterpret_cast<Best*>(z + H * HalfCfg<N>::PITCH);
@@ -458,12 +386,9 @@ __global__ void __launch_bounds__(HalfTile<N>::T, (N == 64 ? 4 : 2)) pc_seq_half
     if constexpr (CH == 1) {
       __builtin_memcpy(ra, s, PPL);
       __builtin_memcpy(rb, s + a.pitch, PPL);
-    } else if constexpr (PPL == 16) {
+    } else {
       gray16_from_bgr48(s, ra);
       gray16_from_bgr48(s + a.pitch, rb);
-    } else {
-      gray8_from_bgr24(s, ra);
-      gray8_from_bgr24(s + a.pitch, rb);
     }
   };
   fetch(p0);
@@ -472,20 +397,10 @@ __global__ void __launch_bounds__(HalfTile<N>::T, (N == 64 ? 4 : 2)) pc_seq_half
     asm volatile("" : "+v"(lane), "+v"(wave));
     lane &= 63;
     wave &= W - 1;
-    {
-      constexpr bool RAW = PPL == 16;
-      if constexpr (RAW) {
-        half_raw_store<N>(z, 8 * wave, lane, ra, rb);
-      } else {
-        const int lr = 8 * wave + (lane >> 3), c0 = PPL * (lane & 7);
-#pragma unroll
-        for (int i = 0; i < PPL; ++i)
-          z[L::line(lr, c0 + i)] = {(float)((ra[i >> 2] >> (8 * (i & 3))) & 0xffu), (float)((rb[i >> 2] >> (8 * (i & 3))) & 0xffu)};
-      }
-      if (f < np) fetch(p0 + f + 1);
-      wave_sync();
-      half_rows<N, RAW>(z, 8 * wave, lane, tw);
-    }
+    half_raw_store<N>(z, 8 * wave, lane, ra, rb);
+    if (f < np) fetch(p0 + f + 1);
+    wave_sync();
+    half_rows<N>(z, 8 * wave, lane, tw);
     __syncthreads();
     half_cols<N, PK>(z, 8 * wave, lane, tw, prev, prev0, prevH, f == 0, wave == 0);
     if (f == 0) {
@@ -513,100 +428,6 @@ __global__ void __launch_bounds__(HalfTile<N>::T, (N == 64 ? 4 : 2)) pc_seq_half
   }
 }
 
-// ---- the PAIR form on the half tile (r05): independent frame pairs (BASELINE c4), a persistent workgroup per slab walks patch pairs
-// p = blockIdx.x, + gridDim.x, ...: previous image -> rows, columns, spectrum parked in the workgroup's slab; current image -> rows,
-// columns, cross-power against the slab, inverse columns, row pairs + arg-max, centroid. Same passes as the sequence kernel above,
-// 1.5 transform units per pair like the packed pair kernel (pc_kernel.hip), but on HALF its LDS: TWO workgroups per CU, so one
-// covers the other's barriers and latency chains (the packed N = 128 kernel runs 47 % of its wave-cycles parked, r03 counters).
-constexpr int PAIR_HALF_WPE = 4;  // waves per SIMD the pair kernel is compiled for: two workgroups per CU
-template <int N, int PK, int CH>
-__global__ void __launch_bounds__(HalfTile<N>::T, PAIR_HALF_WPE) pc_pair_half_kernel(PcArgs a, float2* __restrict__ slabs) {
-  using L = HalfTile<N>;
-  constexpr int H = L::H, R1 = L::R1, W = HalfCfg<N>::WAVES, PPL = N / 8;
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  cf* z = reinterpret_cast<cf*>(smem);
-  Best* red = reinterpret_cast<Best*>(z + H * HalfCfg<N>::PITCH);
-  const int lane0 = threadIdx.x & 63, wave0 = threadIdx.x >> 6;
-  const int patches = a.grid_x * a.grid_y;
-  HalfTw<N> tw;
-  tw.init(a.twiddles, lane0);
-  constexpr int PER = 8 * R1 / 64, NC0 = (H + 64) / 64;
-  const PrevInSlab park{slabs + (size_t)blockIdx.x * (PER * 8) * L::T + threadIdx.x, L::T};
-  // this lane's 2 x PPL pixels of a patch: rows 2j, 2j + 1 (j = 8 wave + lane / 8), columns PPL (lane % 8) .. + PPL - 1
-  const size_t lane_off = (size_t)(2 * (8 * wave0 + (lane0 >> 3))) * a.pitch + CH * PPL * (lane0 & 7);
-  auto patch_off = [&](int pp, size_t frame_stride) -> size_t {
-    const int pair = pp / patches, patch = pp - pair * patches, by = patch / a.grid_x, bx = patch - by * a.grid_x;
-    return (size_t)pair * frame_stride + (size_t)(a.origin_y + by * a.stride_y) * a.pitch + (size_t)CH * (a.origin_x + bx * a.stride_x) + lane_off;
-  };
-  uint32_t ra[PPL / 4], rb[PPL / 4];
-  auto fetch = [&](const uint8_t* s) {
-    if constexpr (CH == 1) {
-      __builtin_memcpy(ra, s, PPL);
-      __builtin_memcpy(rb, s + a.pitch, PPL);
-    } else if constexpr (PPL == 16) {
-      gray16_from_bgr48(s, ra);
-      gray16_from_bgr48(s + a.pitch, rb);
-    } else {
-      gray8_from_bgr24(s, ra);
-      gray8_from_bgr24(s + a.pitch, rb);
-    }
-  };
-  int p = blockIdx.x;
-  if (p < a.total) fetch(a.prev + patch_off(p, a.prev_stride));
-  for (; p < a.total; p += gridDim.x) {
-    cf prev[PER][8], prev0[NC0], prevH[NC0];  // (prev itself is never live in this form: the slab holds it)
-#pragma unroll
-    for (int i = 0; i < NC0; ++i) prev0[i] = prevH[i] = {0.f, 0.f};
-#pragma unroll
-    for (int f = 0; f < 2; ++f) {  // f = 0: the previous image, f = 1: the current one
-      int lane = lane0, wave = wave0;
-      asm volatile("" : "+v"(lane), "+v"(wave));
-      lane &= 63;
-      wave &= W - 1;
-      constexpr bool RAW = PPL == 16;
-      if constexpr (RAW) {
-        half_raw_store<N>(z, 8 * wave, lane, ra, rb);
-      } else {
-        const int lr = 8 * wave + (lane >> 3), c0 = PPL * (lane & 7);
-#pragma unroll
-        for (int i = 0; i < PPL; ++i)
-          z[L::line(lr, c0 + i)] = {(float)((ra[i >> 2] >> (8 * (i & 3))) & 0xffu), (float)((rb[i >> 2] >> (8 * (i & 3))) & 0xffu)};
-      }
-      // the next image's pixels are requested before this one is transformed: the current image of this pair, then the previous
-      // image of the workgroup's next pair
-      if (f == 0) fetch(a.cur + patch_off(p, a.cur_stride));
-      else if (p + (int)gridDim.x < a.total) fetch(a.prev + patch_off(p + (int)gridDim.x, a.prev_stride));
-      wave_sync();
-      half_rows<N, RAW>(z, 8 * wave, lane, tw);
-      __syncthreads();
-      half_cols<N, PK, PrevInSlab>(z, 8 * wave, lane, tw, prev, prev0, prevH, f == 0, wave == 0, park);
-      __syncthreads();
-    }
-    int lane = lane0, wave = wave0;
-    asm volatile("" : "+v"(lane), "+v"(wave));
-    lane &= 63;
-    wave &= W - 1;
-    // (no constant-patch rule: the images are transformed separately with power-of-two butterflies, so a constant patch has the exactly
-    //  zero spectrum the reference's transforms give it and the flat surface produces the degenerate answer by itself, as in the
-    //  sequence kernel above)
-    Best best = half_row_pairs<N, PK>(z, 8 * wave, lane, tw, a.search_radius);
-    best = wave_best(best);
-    if (lane == 0) red[wave] = best;
-    __syncthreads();
-    float wval = 0.f;
-    if (wave == 0) {
-      for (int w = 1; w < W; ++w) best = better(best, red[w]);
-      wval = centroid_window_value<N, PK>(best, lane, [&](int ys, int xs) {
-        const int y = (ys + H) & (N - 1), x = (xs + H) & (N - 1);
-        const cf s = z[L::out(y & (H - 1), x)];
-        return y < H ? s.x : s.y;
-      });
-    }
-    __syncthreads();
-    if (wave == 0) centroid_gate_store<N, PK>(best, wval, lane, a.max_px_speed_sq, a.out + 2 * (size_t)p, a.quality ? a.quality + 2 * (size_t)p : nullptr);
-  }
-}
-
 template <int N>
 hipError_t configure_half() {
   const size_t lds = HalfTile<N>::LDS_BYTES + pc_extra_lds();
@@ -625,48 +446,18 @@ hipError_t launch_half(const PcArgs& a, int n_pairs, int run, hipStream_t stream
   });
 }
 
-template <int N>
-hipError_t launch_pair_half(const PcArgs& a_in, int n_pairs, float* slabs, int n_slabs, hipStream_t stream) {
-  if ((a_in.channels != 1 && a_in.channels != 3) || a_in.downscale != 1 || !slabs || n_slabs < 1) return hipErrorInvalidValue;
-  PcArgs a = a_in;
-  a.total = n_pairs * a.grid_x * a.grid_y;
-  const unsigned blocks = (unsigned)(a.total < n_slabs ? a.total : n_slabs);
-  const size_t lds = HalfTile<N>::LDS_BYTES + pc_extra_lds();
-  float2* sl = reinterpret_cast<float2*>(slabs);
-  return pc_dispatch_form<PC_FORMS_CH_PK>(a, [&](auto, auto ch, auto pk) {
-    hipLaunchKernelGGL((pc_pair_half_kernel<N, pk, ch>), dim3(blocks), dim3(HalfTile<N>::T), lds, stream, a, sl);
-    return hipGetLastError();
-  });
-}
-
-template <int N>
-hipError_t configure_pair_half() {
-  const size_t lds = HalfTile<N>::LDS_BYTES + pc_extra_lds();
-  return pc_each_form<PC_FORMS_CH_PK>([&](auto, auto ch, auto pk) { return pc_raise_lds(&pc_pair_half_kernel<N, pk, ch>, lds); });
-}
-
 }  // namespace
 
-// The pair form on the half tile (N = 128): slabs = n_slabs * pc_pair_half_slab_floats() floats of device memory owned by the engine
-bool pc_pair_half_supported(int patch_size) { return patch_size == 128; }
-size_t pc_pair_half_slab_floats(int patch_size) { return patch_size == 128 ? (size_t)2 * (8 * HalfCfg<128>::R1 / 64) * 8 * HalfTile<128>::T : 0; }
-hipError_t pc_configure_pair_half(int patch_size) { return patch_size == 128 ? configure_pair_half<128>() : hipErrorInvalidValue; }
-hipError_t launch_pc_pair_half(const PcArgs& a, int patch_size, int n_pairs, float* slabs, int n_slabs, hipStream_t stream) {
-  if (n_pairs <= 0) return hipSuccess;
-  return patch_size == 128 ? launch_pair_half<128>(a, n_pairs, slabs, n_slabs, stream) : hipErrorInvalidValue;
-}
-
-bool pc_sequence_half_supported(int patch_size) { return patch_size == 64 || patch_size == 128; }
+bool pc_sequence_half_supported(int patch_size) { return patch_size == 128; }
 
 hipError_t pc_configure_sequence_half(int patch_size) {
-  return patch_size == 64 ? configure_half<64>() : patch_size == 128 ? configure_half<128>() : hipErrorInvalidValue;
+  return patch_size == 128 ? configure_half<128>() : hipErrorInvalidValue;
 }
 
 hipError_t launch_pc_sequence_half(const PcArgs& a, int patch_size, int n_pairs, int run, hipStream_t stream) {
   if (n_pairs <= 0) return hipSuccess;
   if (run < 1) run = 1;
-  return patch_size == 64 ? launch_half<64>(a, n_pairs, run, stream)
-                          : patch_size == 128 ? launch_half<128>(a, n_pairs, run, stream) : hipErrorInvalidValue;
+  return patch_size == 128 ? launch_half<128>(a, n_pairs, run, stream) : hipErrorInvalidValue;
 }
 
 }  // namespace mof

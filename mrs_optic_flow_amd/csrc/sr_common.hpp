@@ -384,9 +384,7 @@ __device__ __forceinline__ void bfly(cf* v) {
   else butterfly<R>(v);
 }
 
-constexpr int SR_LINES = 8;      // lines per workgroup in K5 / K7 (8 rows, 8 row pairs) and in K6 (4 columns + 4 mirrors)
-constexpr int SR_T = 128;        // two waves, four lines each
-constexpr int COLS_CW = SR_LINES / 2;
+constexpr int SR_LINES = 8;      // lines per workgroup in K7 (8 row pairs)
 
 // Inter-stage twiddles of the lane's stage-1 slot: W_N^{n2 k1}, k1 = 1..R1-1, n2 = lane % R2 (the same for every line
 // the lane ever transforms, so they are fetched once per kernel).

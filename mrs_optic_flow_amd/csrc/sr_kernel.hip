@@ -6,11 +6,9 @@
 // The res x res complex tile (480^2 x 8 B = 1.8 MB) fits neither the LDS nor the registers of a CU, so unlike K1 the
 // whole-frame correlation has to cross CUs twice (after the row pass and after the column pass); everything between
 // those two hand-overs stays on chip:
-//   K5 sr_rows_fwd   : u8 log-polar rows of cur/prev packed as cur + i*prev, row FFTs in LDS, written TRANSPOSED
-//                      (Zt[u][v], 64-byte segments) so that the column pass reads whole lines                  -> Zt
-//   K6 sr_cols       : column FFTs of a column group AND its mirror, untangle + normalised cross-power
-//                      spectrum (same rules as K1, incl. the real-only slots), inverse column FFTs of the
-//                      half spectrum, written line by line                                                    -> Dt (N/2+1 lines of N)
+//   K5s, K6s         : sr_seq_kernel.hip: real row FFTs of every log-polar image, written TRANSPOSED as half spectra   -> Zh
+//                      column FFTs, normalised cross-power spectrum (same rules as K1, incl. the real-only slots),
+//                      inverse column FFTs of the half spectrum, written line by line                         -> Dt (N/2+1 lines of N)
 //   K7 sr_rows_inv   : Hermitian rows, two per complex transform; the real surface is NEVER written: the arg-max is
 //                      taken from the registers of the last stage                                             -> candidates
 //   K8 sr_final      : first-maximum reduction; the 5x5 window around the peak is re-evaluated from Dt (25 dot products
@@ -475,126 +473,6 @@ __global__ void __launch_bounds__(256, (SUPER ? 4 : 1)) sr_logpolar_staged_kerne
   else if constexpr (NR >= 16) pipeline(std::integral_constant<int, 16>{});
 }
 
-// ---- K5: forward row transforms of z = cur_lp + i prev_lp, written transposed -----------------------------
-constexpr int FWD_ROWS = 16;               // rows per workgroup: the transposed store writes FWD_ROWS * 8 bytes per segment
-constexpr int FWD_T = FWD_ROWS * 16;       // four rows per wave
-
-template <int N>
-__global__ void __launch_bounds__(FWD_T) sr_rows_fwd_kernel(SrPcArgs a) {
-  using P = SrPlan<N>;
-  extern __shared__ __attribute__((aligned(16))) unsigned char fwd_lds[];
-  cf* z = reinterpret_cast<cf*>(fwd_lds);  // [FWD_ROWS][LINE]
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, pair = blockIdx.y, row0 = blockIdx.x * FWD_ROWS;
-  SrTw<N> tw;
-  tw.load(a.twiddles, lane);
-  // wave w owns rows row0 + 4w .. +3: it loads them (4 px of cur and prev per lane and step), transforms them ...
-  const uint8_t* cur = a.lp_cur + (size_t)pair * a.lp_stride + (size_t)(row0 + 4 * wave) * N;
-  const uint8_t* prev = a.lp_prev + (size_t)pair * a.lp_stride + (size_t)(row0 + 4 * wave) * N;
-  cf* mine = z + 4 * wave * P::LINE;
-  {
-    // all loads first (a load-use loop would pay the memory latency once per trip), then the conversion
-    constexpr int NL = (N + 63) / 64;  // dwords per lane: four rows of N bytes
-    uint32_t c[NL], p[NL];
-#pragma unroll
-    for (int k = 0; k < NL; ++k) {
-      const int i = lane + 64 * k;
-      if (i < N) {
-        c[k] = stream_load(reinterpret_cast<const uint32_t*>(cur + 4 * i));
-        p[k] = stream_load(reinterpret_cast<const uint32_t*>(prev + 4 * i));
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < NL; ++k) {
-      const int i = lane + 64 * k;
-      if (i < N) {
-        const int l = (4 * i) / N, x = (4 * i) % N;
-#pragma unroll
-        for (int q = 0; q < 4; ++q)  // convertTo CV_32FC1, :115
-          mine[l * P::LINE + x + q] = {(float)((c[k] >> (8 * q)) & 0xffu), (float)((p[k] >> (8 * q)) & 0xffu)};
-      }
-    }
-  }
-  wave_sync();
-  wave_fft<N>(mine, 4, lane, tw, StoreNatural<N>{});
-  __syncthreads();
-  // ... and the workgroup stores its rows transposed: Zt[u][row0 .. row0 + FWD_ROWS) is one contiguous segment per u
-  cf* Zt = reinterpret_cast<cf*>(a.Zt) + (size_t)pair * N * N + row0;
-  // (two neighbouring rows per lane: 16-byte non-temporal stores, as K5s -- the 8-byte form cost 16 % more on this kernel)
-  static_assert(FWD_ROWS % 2 == 0, "row pairs");
-  for (int i = tid; i < FWD_ROWS / 2 * N; i += FWD_T) {
-    const int u = i / (FWD_ROWS / 2), dv = 2 * (i % (FWD_ROWS / 2));
-    const cf a0 = z[dv * P::LINE + u], a1 = z[(dv + 1) * P::LINE + u];
-    stream_store(reinterpret_cast<float4*>(&Zt[(size_t)u * N + dv]), make_float4(a0.x, a0.y, a1.x, a1.y));
-  }
-}
-
-// ---- K6: column transforms, cross-power spectrum, inverse column transforms of the half spectrum -----------
-template <int N>
-__global__ void __launch_bounds__(SR_T) sr_cols_kernel(SrPcArgs a) {
-  using P = SrPlan<N>;
-  constexpr int H = N / 2, CW = COLS_CW;
-  __shared__ cf z[2 * CW * P::LINE];  // lines 0..CW-1: columns u0+s ; lines CW..2CW-1: their mirrors (N - u) % N
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, pair = blockIdx.y, u0 = blockIdx.x * CW;
-  SrTw<N> tw;
-  tw.load(a.twiddles, lane);
-  const cf* Zt = reinterpret_cast<const cf*>(a.Zt) + (size_t)pair * N * N;
-  // wave 0 loads and transforms the columns, wave 1 their mirrors: whole lines of N complex, 16 bytes per lane
-  {
-    cf* mine = z + wave * CW * P::LINE;
-    constexpr int NL = (CW * N / 2 + 63) / 64;  // 16-byte loads per lane, all in flight before the first LDS write
-    float4 t[NL];
-#pragma unroll
-    for (int k = 0; k < NL; ++k) {
-      const int i = lane + 64 * k;
-      if (i < CW * N / 2) {
-        const int s = (2 * i) / N, v = (2 * i) % N;
-        int u = u0 + s;
-        if (u > H) u = H;  // tail group: clamp (results of clamped lines are never stored)
-        const int col = wave == 0 ? u : (N - u) % N;
-        t[k] = stream_load(reinterpret_cast<const float4*>(Zt + (size_t)col * N + v));
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < NL; ++k) {
-      const int i = lane + 64 * k;
-      if (i < CW * N / 2) {
-        const int s = (2 * i) / N, v = (2 * i) % N;
-        mine[s * P::LINE + v] = {t[k].x, t[k].y};
-        mine[s * P::LINE + v + 1] = {t[k].z, t[k].w};
-      }
-    }
-    wave_sync();
-    wave_fft<N>(mine, CW, lane, tw, StoreNatural<N>{});
-  }
-  __syncthreads();
-  // normalised cross-power spectrum of bins (v, u), conjugated in place (see K1 for the rules)
-  for (int i = tid; i < CW * N; i += SR_T) {
-    const int s = i / N, v = i % N;
-    int u = u0 + s;
-    if (u > H) u = H;
-    const cf zk = z[s * P::LINE + v], zm = z[(CW + s) * P::LINE + (N - v) % N];
-    const bool real_only = (v == 0 || v == H) && (u == 0 || u == H);
-    // The DC bin is exact in the packed transform: (sum cur, sum prev). A sum of zero = an all-zero (black) image, whose
-    // spectrum is exactly zero in the reference's separate transforms: P = 0 everywhere, flat zero surface, pt = (N/2, N/2).
-    // The packed form would leak rounding noise of the other image into it (see pc_common.hpp, degenerate pairs): tell K8.
-    if (u0 == 0 && i == 0 && a.degen) a.degen[pair] = (zk.x == 0.f || zk.y == 0.f) ? 1 : 0;
-    const cf C = cross_power(zk, zm, real_only);
-    z[s * P::LINE + v] = {C.x, -C.y};
-  }
-  __syncthreads();
-  // the CW lines of the half spectrum: two per wave
-  wave_fft<N>(z + 2 * wave * P::LINE, 2, lane, tw, StoreNatural<N>{});
-  __syncthreads();
-  cf* Dt = reinterpret_cast<cf*>(a.Dt) + (size_t)pair * (H + 1) * N;
-  for (int i = tid; i < CW * N / 2; i += SR_T) {
-    const int s = (2 * i) / N, y = (2 * i) % N, u = u0 + s;
-    if (u <= H) {
-      const cf a0 = z[s * P::LINE + y], a1 = z[s * P::LINE + y + 1];
-      stream_store(reinterpret_cast<float4*>(Dt + (size_t)u * N + y), make_float4(a0.x, a0.y, a1.x, a1.y));
-    }
-  }
-}
-
 // ---- K7: Hermitian rows back to the real surface, two rows per complex transform; arg-max from registers -----
 // K7's waves: two of four lines each; at the long lines (r06, N >= 540: first radix above 16, both stages of wave_fft take two lines per pass
 // anyway) four of two lines each -- the eight lines in LDS set the workgroups per CU, so that is twice the waves for the same LDS
@@ -683,7 +561,7 @@ __global__ void __launch_bounds__(64) sr_final_kernel(SrPcArgs a) {
   peak_window<0>(best, lane, N, &ys, &xs);
   double cx = (double)xs * val, cy = (double)ys * val, sum = val;
   wave_sum3<16>(cx, cy, sum);
-  if (lane == 0) sr_finish(cx, cy, sum, N, N, a.M, a.degen && a.degen[pair], a.out + 4 * pair);
+  if (lane == 0) sr_finish(cx, cy, sum, N, N, a.M, a.degen && a.degen[pair], a.out + 4 * pair);  // (degen: null, the residue of SrPcArgs)
 }
 
 // (the list: MOF_SR_TUNED_SIZES, sr_common.hpp)
@@ -693,7 +571,7 @@ bool sr_transform_size_tuned(int m, bool* exact_nyquist) {
     return hipSuccess;
   }) == hipSuccess;
 }
-bool sr_pair_kernels_supported(int res) { return res == 240 || res == 256 || res == 480; }  // K5 / K6 (packed pairs), K56, K6p
+bool sr_always_tuned(int res) { return res == 240 || res == 256 || res == 480; }  // (these stay tuned under MOF_SR_TUNED_ALL=0)
 
 template <int K>
 static hipError_t launch_lp_lds(const SrLpArgs& a, int n_images, hipStream_t stream) {
@@ -778,20 +656,6 @@ hipError_t launch_sr_logpolar(const SrLpArgs& a, int interp, int n_images, hipSt
   return hipGetLastError();
 }
 
-template <int N>
-static hipError_t launch_sr_pc_n(const SrPcArgs& a, int n_pairs, hipStream_t stream) {
-  constexpr int H = N / 2;
-  static_assert(N % FWD_ROWS == 0 && H % SR_LINES == 0, "rows and row pairs divide evenly over the workgroups");
-  constexpr size_t fwd_lds = sizeof(cf) * FWD_ROWS * SrPlan<N>::LINE;
-  const hipError_t e = pc_raise_lds_beyond_default(&sr_rows_fwd_kernel<N>, fwd_lds);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(sr_rows_fwd_kernel<N>, dim3(N / FWD_ROWS, (unsigned)n_pairs), dim3(FWD_T), fwd_lds, stream, a);
-  hipLaunchKernelGGL(sr_cols_kernel<N>, dim3((H + 1 + COLS_CW - 1) / COLS_CW, (unsigned)n_pairs), dim3(SR_T), 0, stream, a);
-  hipLaunchKernelGGL(sr_rows_inv_kernel<N>, dim3(H / SR_LINES, (unsigned)n_pairs), dim3(K7Cfg<N>::T), 0, stream, a);
-  hipLaunchKernelGGL(sr_final_kernel<N>, dim3((unsigned)n_pairs), dim3(64), 0, stream, a);
-  return hipGetLastError();
-}
-
 int sr_candidates(int res) { return ((res + 1) / 2 + SR_LINES - 1) / SR_LINES; }  // (one per workgroup of K7: eight row pairs)
 
 // K7 + K8 alone: from a Dt that somebody else produced (the sequence pipeline, sr_seq_kernel.hip) to (scale, rot, pt)
@@ -832,15 +696,6 @@ hipError_t launch_sr_rows_inv(const float* Dt, const float* twiddles, float2* ca
   a.cand = cand;
   a.n_cand = sr_candidates(res);
   return sr_dispatch_size(res, [&](auto n) { return launch_sr_rows_inv_n<decltype(n)::value>(a, n_pairs, stream); });
-}
-
-hipError_t launch_sr_phase_correlate(const SrPcArgs& a, int res, int n_pairs, hipStream_t stream) {
-  switch (res) {
-    case 240: return launch_sr_pc_n<240>(a, n_pairs, stream);
-    case 256: return launch_sr_pc_n<256>(a, n_pairs, stream);
-    case 480: return launch_sr_pc_n<480>(a, n_pairs, stream);
-    default: return hipErrorInvalidValue;
-  }
 }
 
 }  // namespace mof

@@ -168,28 +168,21 @@ int main() {
         CHECK(std::strcmp(fam, "unsupported") == 0 && !ok);
       } else {
         CHECK(ok && std::strcmp(fam, families[r.family]) == 0 && r.m == m && r.sums == (sums != 0) && r.sums_off == off);
-        CHECK(r.zh_floats == zh && r.candidates == cand && r.pairs == mof::SrRoute::FRAMES && r.seq_run == 0);
+        CHECK(r.zh_floats == zh && r.candidates == cand && r.seq_run == 0);
         CHECK(r.family == mof::SrRoute::TUNED || (plan.n == res && plan.m == m));
       }
       ++rows;
     }
     std::fclose(f);
     CHECK(rows == 2 * 493);  // even resolutions 16 .. 1000, MOF_SR_TUNED_ALL unset and 0
-    // the pair form of the batch entry and the fixed K6s run follow their knobs
+    // the fixed K6s run follows its knob
     for (int res = 16; res <= 1000; res += 2) {
       mof::SrKnobs k;
       mof::PcPlan plan{};
       mof::SrRoute r;
-      k.pair_seq = false;
-      k.fused = true;
       k.seq_run = 7;
       if (!mof::sr_route(res, k, &plan, &r)) continue;
-      const bool tuned = r.family == mof::SrRoute::TUNED;
-      const mof::SrRoute::Pairs want = mof::sr_pair_kernels_supported(res) ? mof::SrRoute::PACKED
-                                       : tuned && mof::sr_fused_supported(res) ? mof::SrRoute::FUSED : mof::SrRoute::FRAMES;
-      CHECK(r.pairs == want && r.seq_run == 7);
-      k.pair_seq = true;
-      CHECK(mof::sr_route(res, k, &plan, &r) && r.pairs == (tuned && mof::sr_fused_supported(res) ? mof::SrRoute::FUSED : mof::SrRoute::FRAMES));
+      CHECK(r.seq_run == 7);
     }
     // one list of tuned transform sizes, whoever is asked
     int listed = 0;

@@ -99,8 +99,8 @@ def test_the_older_forms(gpu):
 
 def test_the_half_tile_everywhere(gpu):
     """MOF_FFT_HALF=1: 64 and 128 through the half-tile kernel, pairs (the tiled 128 frames: 512 patches) and its sequence form on the
-    long videos (fft_route takes the half tile's video form before it looks at MOF_FFT_SEQ_HALF64 / 128, so those have a child of
-    their own); the constant and zero patches. Evidence: kernel_variant 'planned-half' at 64 and 128 ('stockham' by default); the
+    long videos (fft_route takes the half tile's video form before it looks at MOF_FFT_SEQ_HALF128, so that one has a child of
+    its own); the constant and zero patches. Evidence: kernel_variant 'planned-half' at 64 and 128 ('stockham' by default); the
     video entry has the pair entry's bits at 64 and 128 (the half tile's two forms share their arithmetic, as at 120 by default).
     The front-end forms: gray and BGR8 pairs and videos at 64 and 128 on the half tile; the OpenCL model, which the half tile does
     not have, stays on K1 ('stockham'), and so does the long-range mode (kernel_variant names the full-resolution route)."""
@@ -114,15 +114,13 @@ def test_the_half_tile_everywhere(gpu):
 
 
 def test_the_older_half_tile_sequence_kernels(gpu):
-    """MOF_FFT_SEQ_HALF64=1, MOF_FFT_SEQ_HALF128=1, MOF_FFT_SEQ_RUN=3: pc_seq_half.hip's sequence kernel at 64 and 128 in runs of three
-    (it takes 16 by default, which the 10 pairs at 128 would not fill: both instantiations must see a second run), and a constant and
-    a zero frame in its stream at 64. Nothing exposes the route: kernel_variant names the pair kernels, 'stockham' either way, and
-    the video entry has not the pair entry's bits with or without the knobs. The front-end forms: gray and BGR8 videos under both peak
-    models at 64 and 128 -- the four instantiations of pc_seq_half_kernel at either size."""
-    _child({"MOF_FFT_SEQ_HALF64": "1", "MOF_FFT_SEQ_HALF128": "1", "MOF_FFT_SEQ_RUN": "3"},
-           "test_sequence_runs or test_constant_and_zero_frames_in_a_video",
-           videos=[("long-video-64", "own"), ("long-video-128", "own"), ("video-64", "own"), ("video-128", "own")],
-           forms=_forms("stockham", *(f"video-{n}-{f}-{m}" for n in (64, 128) for f in ("gray", "bgr") for m in ("cv", "ocl"))))
+    """MOF_FFT_SEQ_HALF128=1, MOF_FFT_SEQ_RUN=3: pc_seq_half.hip's sequence kernel at 128, the one size it serves, in runs of three (it
+    takes 16 by default, which the 10 pairs would not fill: the kernel must see a second run). Nothing exposes the route: kernel_variant
+    names the pair kernel, 'stockham' either way, and the video entry has not the pair entry's bits with or without the knob. The
+    front-end forms: gray and BGR8 videos under both peak models -- the four instantiations of pc_seq_half_kernel."""
+    _child({"MOF_FFT_SEQ_HALF128": "1", "MOF_FFT_SEQ_RUN": "3"}, "test_sequence_runs",
+           videos=[("long-video-128", "own"), ("video-128", "own")],
+           forms=_forms("stockham", *(f"video-128-{f}-{m}" for f in ("gray", "bgr") for m in ("cv", "ocl"))))
 
 
 def test_forced_planned_kernel(gpu):
@@ -153,16 +151,6 @@ def test_videos_on_the_pair_form_of_their_family(gpu):
     twice). The video entry must keep the pair entry's bits; it has them by default too at these sizes, so nothing exposes the route."""
     _child({"MOF_FFT_LARGE_VIDEO": "0", "MOF_FFT_HALF_SEQ": "0"}, "test_sequence_runs",
            videos=[("long-video-200", "pair"), ("long-video-120", "pair"), ("video-200", "pair"), ("video-120", "pair")])
-
-
-def test_pair_kernel_on_the_half_tile_at_128(gpu):
-    """MOF_FFT_PAIR_HALF=1: pc_pair_half_kernel on THREE tiled 128 frames -- 768 patch pairs against one slab per workgroup, two
-    workgroups per CU (512 on 256 CUs), so half of the workgroups walk a second patch pair: the prefetch of the next previous image,
-    the slab's reuse, the store at a.quality + 2 p for p >= gridDim.x -- and on the 36 pairs alone. Nothing exposes the route:
-    kernel_variant stays 'stockham'. The front-end forms: gray and BGR8 under both peak models, the four instantiations of
-    pc_pair_half_kernel; the long-range mode stays on K1."""
-    _child({"MOF_FFT_PAIR_HALF": "1"}, "test_pair_entry_on_its_route", pairs=[("tiled-128x3", "stockham"), ("circular-128", "stockham")],
-           forms=_forms("stockham", "k1-128-gray-cv", "k1-128-bgr-cv", "k1-128-gray-ocl", "k1-128-bgr-ocl", "k1-128-lr-cv"))
 
 
 def test_forced_pass_run_and_chunk_boundaries(gpu):

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """The static record of a libmof_hip.so: every kernel of every gfx950 code object with the numeric fields of its metadata note and
-`code`, a SHA-256 over the bytes of the kernel's symbol in .text followed by its 64-byte descriptor <name>.kd.
+`code`, a SHA-256 over the bytes of the kernel's symbol in .text followed by its 64-byte descriptor <name>.kd -- without the descriptor's
+kernel_code_entry_byte_offset (bytes 16 .. 23), the distance from the descriptor to the entry, which moves whenever another kernel joins
+or leaves the code object.
 
   tools/kernel_static.py LIB             one line per kernel, sorted by name
   tools/kernel_static.py compare A B     whether each whole gfx950 code object is byte-identical, then the names only in A, the names
@@ -69,7 +71,8 @@ def kernels_of(notes):
 
 
 def code_hashes(co, sections, symbols):
-    """{mangled name: sha256 hex of the symbol's bytes + its .kd descriptor} from the text of llvm-readelf -S and -s of code object `co`."""
+    """{mangled name: sha256 hex of the symbol's bytes + its .kd descriptor, entry offset zeroed} from the text of llvm-readelf -S and -s
+    of code object `co`."""
     sec = {}  # index -> (address, file offset)
     for m in re.finditer(r"^\s*\[\s*(\d+)\]\s+\S+\s+(?:PROGBITS)\s+([0-9a-f]+)\s+([0-9a-f]+)\s+[0-9a-f]+", sections, re.M):
         sec[int(m.group(1))] = (int(m.group(2), 16), int(m.group(3), 16))
@@ -79,7 +82,7 @@ def code_hashes(co, sections, symbols):
         if ndx in sec:
             off = sec[ndx][1] + addr - sec[ndx][0]
             sym[name] = co[off:off + size]
-    return {n: hashlib.sha256(b + sym[n + ".kd"]).hexdigest() for n, b in sym.items() if n + ".kd" in sym}
+    return {n: hashlib.sha256(b + sym[n + ".kd"][:16] + bytes(8) + sym[n + ".kd"][24:]).hexdigest() for n, b in sym.items() if n + ".kd" in sym}
 
 
 def record(lib):

@@ -36,8 +36,6 @@ FACTORS = {
     "pcl_rows_kernel": (2.0, "reads 480*480 B of u8 per image = 235.9 MB per 1024-image launch; FETCH_SIZE 118.8 MB = 0.50x"),
     "pcl_cols_kernel": (2.0, "reads the Zh of both images once: 2 * 925,440 B per pair = 947.6 MB per 512-pair launch; FETCH_SIZE 474.1 MB = 0.50x"),
     "pcl_rows_inv_kernel": (2.0, "reads Dt once: 925,440 B per pair = 473.8 MB per 512-pair launch; FETCH_SIZE 237.1 MB = 0.50x"),
-    "sr_cols_fused_kernel": (2.0, "r04, K56: every log-polar image comes from HBM once (TCC_HIT 96 %): 2*480*480 B per pair = 471.9 MB per 1024-pair "
-                                  "launch; FETCH_SIZE 234.5 MB = 0.50x (profiles/r04_sr_fused_pmc.csv)"),
     "sr_cols_seq_kernel": (2.0, "reads 17 frames of Zh (925,440 B) per 16-pair run = 503.4 MB per 512-pair launch; FETCH_SIZE 251.5 MB = 0.50x"),
     # r05: the half-tile kernel reads every pixel of every patch exactly once with one unaligned dword per four pixels. At l160 (160-byte
     # patch rows) FETCH_SIZE reads BELOW the bytes that must be fetched -- 189.29 MB against 2*480*480*512 B = 235.93 MB per launch
