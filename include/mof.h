@@ -229,8 +229,8 @@ int mof_fft_process_batch_host(mof_fft_engine* e, const uint8_t* cur, size_t cur
  * the corner is clamped to 3 x 3; both 0 for an all-zero patch); under MOF_PEAK_OCL (NaN, NaN), as the shift.
  * quality / d_quality may be null: the call is then the entry without _q (which is this code with a null pointer; every output keeps
  * its bits either way). The device entries allocate nothing and may be captured into a HIP graph under the rules above. channels:
- * 1 gray, 3 BGR8 (pitch in bytes); long_range 0 | 1, not together with channels == 3 (MOF_ERR_BAD_ARG). Out of scope: the estimator's
- * response (mof_sr_*) and the sharded entries. */
+ * 1 gray, 3 BGR8 (pitch in bytes); long_range 0 | 1, not together with channels == 3 (MOF_ERR_BAD_ARG). The estimator has the same
+ * outputs and a gate on them (mof_sr_*_q, mof_sr_set_min_response below). Out of scope: the sharded entries. */
 int mof_fft_process_q(mof_fft_engine* e, const uint8_t* frame, size_t pitch, double* out_xy, double* quality, int* n_invalid);
 int mof_fft_process_long_range_q(mof_fft_engine* e, const uint8_t* frame, size_t pitch, double* out_xy, double* quality, int* n_invalid);
 int mof_fft_process_batch_device_q(mof_fft_engine* e, const uint8_t* d_cur, size_t cur_stride, const uint8_t* d_prev, size_t prev_stride,
@@ -475,6 +475,36 @@ int mof_sr_process_sequence_device(mof_sr_engine* e, const uint8_t* d_frames, si
  * CHUNK left it (the frames before it have been consumed). */
 int mof_sr_process_sequence_host(mof_sr_engine* e, const uint8_t* frames, size_t frame_stride, size_t pitch, int n_frames,
                                  double* out, int* n_gated);
+
+/* Correlation quality of the estimator: the *_q forms of the four entries above hand out, beside every result, (response, peak) of the
+ * surface of pt = cv::phaseCorrelate(current, previous) (:117) -- exactly the MOF_PEAK_OPENCV definition of "Per-patch correlation
+ * quality" above with M = getOptimalDFTSize(resolution): quality[2 k + {0, 1}] for frame (or pair) k. Matched consecutive views give a
+ * response of 0.8 .. 1, a frame of noise against a view below 0.25 -- with pt.x well inside the reference's gate, which checks nothing else.
+ *   - A frame for which no correlation ran -- the first one of a fresh or reset estimator (:36-74) -- reports (NaN, NaN).
+ *   - An all-zero log-polar image (flat zero surface) reports exactly (0, 0).
+ *   - The value does not depend on either gate: a gated frame reports the quality of the correlation that gated it; a frame the
+ *     sequence entry re-ran against an older partner reports the quality of that pair.
+ * quality / d_quality may be null: the call is then the entry without _q, which is this code with a null pointer -- every output keeps
+ * its bits either way. The device entries allocate nothing and stay capturable under the rules of the entries above.
+ *
+ * The response gate. mof_sr_set_min_response(e, v): v = 0, the default, switches it off -- the reference's behaviour, bit for bit. v must
+ * be finite and >= 0 (MOF_ERR_BAD_ARG). With v > 0 a frame with !(response >= v) -- a NaN response included -- is treated exactly as one
+ * that fails the reference's |pt.x| > resolution/2 rule: (scale, rot) = (1, 0), pt still reported, and the frame does NOT replace the
+ * previous image. A caller cannot apply such a threshold afterwards: by then the bad frame is the partner of the next one. It holds in
+ * every entry: the stateful call; the batch entry (pairs are independent: only the output changes); the sequence entries with
+ * n_gated != NULL, which resolve partners behind a gated frame as for the reference's gate; and the asynchronous form (n_gated == NULL),
+ * where the output is gated and every frame is correlated with its immediate predecessor. *n_gated counts frames gated by either rule.
+ * The kernel and the host decide from the same stored double. The setter fails with MOF_ERR_BUSY while a call is in flight and while the
+ * engine is graph-pinned (a captured kernel holds the old value as an argument: mof_sr_release_graphs first). mof_sr_reset keeps the value. */
+int mof_sr_set_min_response(mof_sr_engine* e, double min_response);
+double mof_sr_min_response(const mof_sr_engine* e);
+int mof_sr_process_q(mof_sr_engine* e, const uint8_t* frame, size_t pitch, double* out_scale_rot, double* quality /* 2 */);
+int mof_sr_process_batch_device_q(mof_sr_engine* e, const uint8_t* d_cur, size_t cur_stride, const uint8_t* d_prev, size_t prev_stride,
+                                  size_t pitch, int n_pairs, double* d_out, double* d_quality /* n_pairs x 2 */, void* stream);
+int mof_sr_process_sequence_device_q(mof_sr_engine* e, const uint8_t* d_frames, size_t frame_stride, size_t pitch, int n_frames,
+                                     double* d_out, double* d_quality /* n_frames x 2 */, void* stream, int* n_gated);
+int mof_sr_process_sequence_host_q(mof_sr_engine* e, const uint8_t* frames, size_t frame_stride, size_t pitch, int n_frames, double* out,
+                                   double* quality /* n_frames x 2 */, int* n_gated);
 
 /* The remap stage alone: cv::logPolar(src, dst, Point2f(res/2, res/2), M, interpolation) (scaleRotationEstimator.cpp:45
  * INTER_CUBIC, :112 INTER_LANCZOS4) on n_images res x res CV_8UC1 crops (image i at d_src + i*src_stride, `pitch` bytes

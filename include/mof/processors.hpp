@@ -378,9 +378,16 @@ class scaleRotationEstimator {
   Point2d processImage(ImageView imCurr, bool /*gui*/, bool /*debug*/) {
     if (imCurr.rows != res_ || imCurr.cols != res_) throw std::runtime_error("scaleRotationEstimator: accepts only res x res images");
     double out[2] = {1.0, 0.0};
-    detail::check(mof_sr_process(engine_, imCurr.data, imCurr.step, out), "mof_sr_process");
+    detail::check(mof_sr_process_q(engine_, imCurr.data, imCurr.step, out, &last_quality_.response), "mof_sr_process_q");
     return Point2d{out[0], out[1]};
   }
+  // (response, peak) of the surface the last processImage call read pt from (include/mof.h, "Correlation quality of the estimator");
+  // (NaN, NaN) after the first frame of a fresh estimator, where no correlation ran. A gated frame still carries its quality.
+  PatchQuality lastQuality() const { return last_quality_; }
+  // The response gate (no reference counterpart; 0 = off): a frame whose response is not >= min_response returns (1, 0) and does not
+  // become the previous image, like one that fails the reference's |pt.x| rule (:119-121). Throws while a captured graph pins the engine.
+  void setMinResponse(double min_response) { detail::check(mof_sr_set_min_response(engine_, min_response), "mof_sr_set_min_response"); }
+  double minResponse() const { return mof_sr_min_response(engine_); }
   // A video on the DEVICE: what n_frames consecutive processImage calls return (scale, rot, pt.x, pt.y per frame), continuing
   // and updating this estimator's state (first frame INTER_CUBIC, the gate of :119-121 resolved). d_frames: top-left pixel of
   // the res x res crop of frame 0, frame i at + i * frame_stride, `pitch` bytes per row; d_out4: n_frames * 4 doubles.
@@ -399,11 +406,26 @@ class scaleRotationEstimator {
     detail::check(mof_sr_process_sequence_host(engine_, frames, frame_stride, pitch, n_frames, out4, &gated), "mof_sr_process_sequence_host");
     return gated;
   }
+  // The two video entries with the quality beside the results: d_quality / quality = n_frames * 2 doubles, (response, peak) per frame
+  int processSequenceDeviceQ(const uint8_t* d_frames, size_t frame_stride, size_t pitch, int n_frames, double* d_out4, double* d_quality,
+                             void* stream = nullptr) {
+    int gated = 0;
+    detail::check(mof_sr_process_sequence_device_q(engine_, d_frames, frame_stride, pitch, n_frames, d_out4, d_quality, stream, &gated),
+                  "mof_sr_process_sequence_device_q");
+    return gated;
+  }
+  int processVideoQ(const uint8_t* frames, size_t frame_stride, size_t pitch, int n_frames, double* out4, double* quality) {
+    int gated = 0;
+    detail::check(mof_sr_process_sequence_host_q(engine_, frames, frame_stride, pitch, n_frames, out4, quality, &gated),
+                  "mof_sr_process_sequence_host_q");
+    return gated;
+  }
   mof_sr_engine* handle() { return engine_; }
 
  private:
   mof_sr_engine* engine_ = nullptr;
   int res_ = 0;
+  PatchQuality last_quality_{0.0, 0.0};
 };
 
 // The node's camera front end (optic_flow.cpp:1603-1622; include/mof.h, mof_frontend_*): cv::resize by the integer scale_factor,

@@ -139,6 +139,12 @@ SYMBOLS = {
     "mof_sr_process_batch_device": (_I, [_VP, _VP, _SZ, _VP, _SZ, _SZ, _I, _VP, _VP]),
     "mof_sr_process_sequence_device": (_I, [_VP, _VP, _SZ, _SZ, _I, _VP, _VP, C.POINTER(_I)]),
     "mof_sr_process_sequence_host": (_I, [_VP, _VP, _SZ, _SZ, _I, _VP, C.POINTER(_I)]),
+    "mof_sr_set_min_response": (_I, [_VP, C.c_double]),
+    "mof_sr_min_response": (C.c_double, [_VP]),
+    "mof_sr_process_q": (_I, [_VP, _VP, _SZ, _VP, _VP]),
+    "mof_sr_process_batch_device_q": (_I, [_VP, _VP, _SZ, _VP, _SZ, _SZ, _I, _VP, _VP, _VP]),
+    "mof_sr_process_sequence_device_q": (_I, [_VP, _VP, _SZ, _SZ, _I, _VP, _VP, _VP, C.POINTER(_I)]),
+    "mof_sr_process_sequence_host_q": (_I, [_VP, _VP, _SZ, _SZ, _I, _VP, _VP, C.POINTER(_I)]),
     "mof_sr_logpolar_batch_device": (_I, [_VP, _VP, _SZ, _SZ, _I, _I, _VP, _VP]),
     "mof_frontend_config_reference": (_I, [C.POINTER(FrontendConfig), _I, _I, _I, _I, _I, C.c_double]),
     "mof_frontend_validate": (_I, [C.POINTER(FrontendConfig)]),

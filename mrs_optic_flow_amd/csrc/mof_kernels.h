@@ -82,7 +82,8 @@ struct PclFinal {
   const float* cdc;        // mode 1, with flags: [pairs] DC bin of the cross-power spectrum
   int peak_model;          // mode 1: 0 = cv::phaseCorrelate, 1 = the OpenCL kernel's model (m == n; L7 + L8 of the planned pipeline only)
   int search_radius;       // peak_model 1
-  double* quality;         // mode 1, nullable: [pairs] (response, peak), as PcArgs::quality
+  double* quality;         // nullable: [pairs] (response, peak), as PcArgs::quality (mode 0: as SrPcArgs::quality)
+  double min_response;     // mode 0: the estimator's response gate, as SrPcArgs::min_response
 };
 size_t pcl_zh_floats(const PcPlan& pl);  // floats of one image's row half-spectra Zh: (m/2 + 1) * m complex
 int pcl_candidates(const PcPlan& pl);    // peak candidates per pair
@@ -92,7 +93,7 @@ hipError_t launch_pcl_rows(const PclSrc& src, const PcPlan& pl, const float* twi
 // L6: pair p = (cur: zh_cur + p * zh_stride, prev: zh_prev + p * zh_stride) -> Dt[p]; cdc nullable; peak_model as PclFinal
 hipError_t launch_pcl_cols(const float* zh_prev, const float* zh_cur, size_t zh_stride, const PcPlan& pl, const float* twiddles,
                            float* Dt, float* cdc, const int* flags, int n_pairs, hipStream_t stream, int peak_model = 0);
-// L7 + L8 (a.Dt, a.cand, a.twiddles, a.mode, a.out [, a.M_log | a.max_px_speed_sq, a.flags, a.cdc, a.peak_model, a.search_radius])
+// L7 + L8 (a.Dt, a.cand, a.twiddles, a.mode, a.out, a.quality [, a.M_log, a.min_response | a.max_px_speed_sq, a.flags, a.cdc, a.peak_model, a.search_radius])
 hipError_t launch_pcl_peak(const PclFinal& a, const PcPlan& pl, int n_pairs, hipStream_t stream, bool candidates_done = false);
 // C_dc of every pair from its row spectra (for pipelines whose column kernel does not hand it out)
 hipError_t launch_pcl_cdc(const float* zh_prev, const float* zh_cur, size_t zh_stride, int m, float* cdc, int n_pairs, hipStream_t stream);
@@ -180,14 +181,15 @@ struct SrLpArgs {
   int box_dwords_max;      // dwords of the largest box
 };
 
-// Residue, kept on purpose: lp_cur, lp_prev, lp_stride, Zt and degen were read by the retired packed pair kernels K5 / K6 only
-// (docs/history/retired_switches.md) and are always zero now. K7 and K8 take this struct by value: without the five fields their kernel
-// arguments move and both kernels come out with other SGPR counts and other code; with them -- and K8's read of the null `degen` -- every
-// instantiation is the one measured so far (profiles/runtime_forms_retirement.txt).
+// Residue, kept on purpose: lp_cur, lp_prev and Zt were read by the retired packed pair kernels K5 / K6 only
+// (docs/history/retired_switches.md) and are always zero now. K7 and K8 take this struct by value: without the fields K7's kernel
+// arguments move and it comes out with another SGPR count and other code; with them it is the instantiation measured so far
+// (profiles/runtime_forms_retirement.txt). min_response and quality, read by K8 alone, sit in the eight-byte slots of two more such
+// fields (lp_stride, degen), so K7's arguments keep their size and offsets (profiles/sr_quality_static.txt).
 struct SrPcArgs {
   const uint8_t* lp_cur;   // (residue)
   const uint8_t* lp_prev;  // (residue)
-  size_t lp_stride;        // (residue)
+  double min_response;     // 0: no response gate; > 0: !(response >= min_response) -> (1, 0) (pc_common.hpp, sr_finish)
   const float* twiddles;   // res (cos, -sin) pairs
   float* Zt;               // (residue)
   float* Dt;               // scratch [pairs][res/2+1 u][res y] complex: half spectrum after the column passes
@@ -195,7 +197,7 @@ struct SrPcArgs {
   int n_cand;
   double M;                // log-polar magnitude
   double* out;             // [pairs][4] = scale, rot, pt.x, pt.y
-  int* degen;              // (residue: null)
+  double* quality;         // nullable: [pairs][2] = response, peak of the surface pt was read from (pc_common.hpp, quality_store)
 };
 
 // host-side tables of cv::logPolar / cv::remap (mof_sr.hip); exposed so that the CPU suite can compare them with the oracle
@@ -242,7 +244,8 @@ hipError_t launch_sr_peak(const SrPcArgs& a, int res, int n_pairs, hipStream_t s
 // Sequence pipeline (sr_seq_kernel.hip). Zh = the row half-spectra of ONE log-polar image, doubled and transposed:
 // [(res/2 + 1) u][res v] complex floats = sr_zh_floats(res) floats.
 size_t sr_zh_floats(int res);
-hipError_t launch_sr_identity(double* out4, hipStream_t stream);  // (1, 0, 0, 0): the first frame's result (:74)
+// (1, 0, 0, 0): the first frame's result (:74); quality2 (nullable): (NaN, NaN), no correlation ran
+hipError_t launch_sr_identity(double* out4, double* quality2, hipStream_t stream);
 // K5s: images lp + f * lp_stride (res * res u8, tightly packed rows) -> zh + f * zh_stride (strides: bytes / floats)
 hipError_t launch_sr_rows_real(const uint8_t* lp, size_t lp_stride, const float* twiddles, float* zh, size_t zh_stride, int res,
                                int n_frames, hipStream_t stream);

@@ -300,19 +300,22 @@ struct mof_sr_engine {
   mof::DevMem<float> d_Zt, d_Dt;
   mof::DevMem<float2> d_cand;
   mof::DevMem<double> d_out;       // [kChunk][4]
+  mof::DevMem<double> d_q;         // [kChunk][2]: a pass's (response, peak) where the host walks the response gate and the caller asked for no quality
   mof::PinnedMem<uint8_t> h_stage;
-  mof::PinnedMem<double> h_out;
-  mof::PinnedMem<double> h_seq;    // [chunk][4]: a pass's results, read back when a sequence call resolves the gate
+  mof::PinnedMem<double> h_out;    // [4 + 2]: one result and its quality
+  mof::PinnedMem<double> h_seq;    // [chunk][4] + [chunk][2]: a pass's results and their quality, read back when a sequence call resolves the gates
   int chunk = 0;                 // frame pairs per pipeline pass
   int scratch_pairs = 0;         // pairs per pass the scratch holds now (1 after create, `chunk` after the first batch)
   bool two_lanes = false;        // remap of pass k+1 beside the transforms of pass k (mof_sr_config.pipeline_lanes == 2)
   bool first = true;             // :31
+  double min_response = 0.0;     // mof_sr_set_min_response: 0 = the reference's gate alone
   SrRoute route;                 // which transforms every launch runs (sr_route)
   mof::PcPlan plan{};            // route.family TUNED_PAD / PLANNED: the line plan of the padded size route.m
   std::atomic<bool> busy{false};
   std::atomic<bool> graph_pinned{false};  // a batch call was captured into a HIP graph
   std::mutex host_mu;  // mof_sr_process_sequence_host: the upload pipeline (host_pipe.hpp), made by its first call
   std::unique_ptr<mof::HostPipe> host_pipe;
+  std::unique_ptr<mof::HostPipe> host_pipe_q;  // mof_sr_process_sequence_host_q with a quality output: the same pipeline with a second output
 };
 
 namespace {
@@ -382,13 +385,15 @@ hipError_t peak(const mof_sr_engine* e, const mof::SrPcArgs& a, int n_pairs, hip
   f.mode = 0;
   f.M_log = a.M;
   f.out = a.out;
+  f.quality = a.quality;
+  f.min_response = a.min_response;
   if (r.family == SrRoute::PLANNED) return mof::launch_pcl_peak(f, e->plan, n_pairs, s);
   // K7 forms the candidates; L8 (the planned pipeline's final kernel: it knows the padded geometry) reads them
   const hipError_t err = mof::launch_sr_rows_inv(a.Dt, a.twiddles, a.cand, r.m, n_pairs, s);
   return err != hipSuccess ? err : mof::launch_pcl_peak(f, e->plan, n_pairs, s, true);
 }
 
-// The pipeline scratch (log-polar images of two passes, Zt, Dt, peak candidates, results) for `pairs` pairs per pass.
+// The pipeline scratch (log-polar images of two passes, Zt, Dt, peak candidates, results, their quality) for `pairs` pairs per pass.
 hipError_t scratch_alloc(mof_sr_engine* e, int pairs) {
   mof::RelaxedCapture relaxed;  // allocation / release must not invalidate a capture on another thread
   const size_t nn = (size_t)e->cfg.resolution * e->cfg.resolution, zhf = e->route.zh_floats, n = (size_t)pairs;
@@ -397,7 +402,7 @@ hipError_t scratch_alloc(mof_sr_engine* e, int pairs) {
   e->scratch_pairs = 0;
   // d_lp holds two passes: remap of pass k+1 beside the transforms of pass k; Dt has Zh's shape
   const hipError_t err = mof::alloc_all(e->d_lp, 2 * n * 2 * nn, e->d_Zt, zh, e->d_Dt, n * zhf, e->d_cand, n * e->route.candidates,
-                                        e->d_out, n * 4);
+                                        e->d_out, n * 4, e->d_q, n * 2);
   if (err == hipSuccess) e->scratch_pairs = pairs;
   return err;
 }
@@ -534,7 +539,7 @@ int mof_sr_create(const mof_sr_config* cfg, mof_sr_engine** out) try {
   HIP_TRY(mof::fill_on(e->stream, e->d_temp_im, 0, nn));  // tempIm = cv::Mat::zeros, :27
   HIP_TRY(mof::fill_on(e->stream, e->d_zh_prev, 0, route.zh_floats * sizeof(float)));
   HIP_TRY(scratch_alloc(e.get(), 1));  // the stateful call needs one pair; a batch grows it to a whole pass (scratch_reserve)
-  HIP_TRY(mof::alloc_all(e->h_stage, nn, e->h_out, 4, e->h_seq, (size_t)e->chunk * 4));
+  HIP_TRY(mof::alloc_all(e->h_stage, nn, e->h_out, 6, e->h_seq, (size_t)e->chunk * 6));
   *out = e.release();
   return MOF_OK;
 } catch (const std::bad_alloc&) {
@@ -552,6 +557,19 @@ int mof_sr_reset(mof_sr_engine* e) {
   return MOF_OK;
 }
 
+int mof_sr_set_min_response(mof_sr_engine* e, double min_response) {
+  if (!e) return mof::capi_fail(MOF_ERR_NOT_INIT, "null engine");
+  if (!std::isfinite(min_response) || min_response < 0.0) return mof::capi_fail(MOF_ERR_BAD_ARG, "min_response must be finite and >= 0");
+  BusyGuard g(e->busy);
+  if (!g.owned) return mof::capi_fail(MOF_ERR_BUSY, "engine busy");
+  // a captured final kernel holds the old value as an argument: a replay would gate by it while the host walks by the new one
+  if (e->graph_pinned.load()) return mof::capi_fail(MOF_ERR_BUSY, "min_response is baked into a captured graph: mof_sr_release_graphs first");
+  e->min_response = min_response;
+  return MOF_OK;
+}
+
+double mof_sr_min_response(const mof_sr_engine* e) { return e ? e->min_response : 0.0; }
+
 static void lp_tables(const mof_sr_engine* e, int interp, mof::SrLpArgs* lp) {
   const int k = interp == 2 ? 0 : 1;
   lp->weights = k == 0 ? e->d_w_cubic : e->d_w_lanczos;
@@ -563,7 +581,7 @@ static void lp_tables(const mof_sr_engine* e, int interp, mof::SrLpArgs* lp) {
   lp->box_dwords_max = e->lds_per_wave[k] / 4;
 }
 
-static mof::SrPcArgs pc_args(const mof_sr_engine* e, double* out) {
+static mof::SrPcArgs pc_args(const mof_sr_engine* e, double* out, double* quality) {
   mof::SrPcArgs a{};
   a.twiddles = e->d_twiddles;
   a.Dt = e->d_Dt;
@@ -571,18 +589,30 @@ static mof::SrPcArgs pc_args(const mof_sr_engine* e, double* out) {
   a.n_cand = e->route.candidates;
   a.M = e->cfg.magnitude;
   a.out = out;
+  a.quality = quality;
+  a.min_response = e->min_response;
   return a;
 }
 
-// One pair through the sequence kernels: (cur spectra, prev spectra) -> Dt slot 0 -> (scale, rot, pt) at `out`
-static hipError_t seq_one_pair(mof_sr_engine* e, const float* zh_prev, const float* zh_cur, double* out, hipStream_t s) {
+// both gates on the host, from the doubles the final kernel stored and decided by (pc_common.hpp, sr_finish): the reference's |pt.x| > res / 2
+// (:119-121) and, armed by min_response > 0, !(response >= min_response)
+static bool sr_gated(const mof_sr_engine* e, double ptx, double response) {
+  return std::fabs(ptx) > (double)(e->cfg.resolution / 2) || (e->min_response > 0.0 && !(response >= e->min_response));
+}
+
+// One pair through the sequence kernels: (cur spectra, prev spectra) -> Dt slot 0 -> (scale, rot, pt) at `out`, (response, peak) at `quality` (nullable)
+static hipError_t seq_one_pair(mof_sr_engine* e, const float* zh_prev, const float* zh_cur, double* out, double* quality, hipStream_t s) {
   hipError_t err = cols_seq(e, zh_prev, zh_cur, 0, 1, 1, s);
   if (err != hipSuccess) return err;
-  mof::SrPcArgs a = pc_args(e, out);
+  mof::SrPcArgs a = pc_args(e, out, quality);
   return peak(e, a, 1, s);
 }
 
 int mof_sr_process(mof_sr_engine* e, const uint8_t* frame, size_t pitch, double* out_scale_rot) {
+  return mof_sr_process_q(e, frame, pitch, out_scale_rot, nullptr);
+}
+
+int mof_sr_process_q(mof_sr_engine* e, const uint8_t* frame, size_t pitch, double* out_scale_rot, double* quality) {
   if (!e) return mof::capi_fail(MOF_ERR_NOT_INIT, "null engine");
   const int res = e->cfg.resolution;
   if (!frame || !out_scale_rot || pitch < (size_t)res) return mof::capi_fail(MOF_ERR_BAD_ARG, "bad frame/pitch/out");
@@ -613,15 +643,22 @@ int mof_sr_process(mof_sr_engine* e, const uint8_t* frame, size_t pitch, double*
     e->first = false;  // :73
     out_scale_rot[0] = 1.0;
     out_scale_rot[1] = 0.0;  // :74
+    if (quality) quality[0] = quality[1] = std::nan("");  // no correlation ran
     return MOF_OK;
   }
-  HIP_TRY(seq_one_pair(e, e->d_zh_prev, e->d_Zt, e->d_out, e->stream));  // :117
+  const bool want_q = quality || e->min_response > 0.0;  // (the response gate is walked from the stored double)
+  HIP_TRY(seq_one_pair(e, e->d_zh_prev, e->d_Zt, e->d_out, want_q ? e->d_q.get() : nullptr, e->stream));  // :117
   HIP_TRY(hipMemcpyAsync(e->h_out, e->d_out, 4 * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+  if (want_q) HIP_TRY(hipMemcpyAsync(e->h_out + 4, e->d_q, 2 * sizeof(double), hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));
   out_scale_rot[0] = e->h_out[0];
   out_scale_rot[1] = e->h_out[1];
+  if (quality) {
+    quality[0] = e->h_out[4];
+    quality[1] = e->h_out[5];
+  }
   // the reference returns early on the gate, BEFORE prevIm_F32 = tempIm_F32.clone() (:119-121 vs :128)
-  if (!(std::fabs(e->h_out[2]) > (double)(res / 2)))
+  if (!sr_gated(e, e->h_out[2], want_q ? e->h_out[4] : 0.0))
     HIP_TRY(hipMemcpyAsync(e->d_zh_prev, e->d_Zt, zh_bytes, hipMemcpyDeviceToDevice, e->stream));
   HIP_TRY(e->fence.release(e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));
@@ -632,6 +669,11 @@ int mof_sr_process(mof_sr_engine* e, const uint8_t* frame, size_t pitch, double*
 // scratch holds slot 0 = the spectra the first new frame is correlated with, slots 1..m = the new frames.
 int mof_sr_process_sequence_device(mof_sr_engine* e, const uint8_t* d_frames, size_t frame_stride, size_t pitch, int n_frames,
                                    double* d_out, void* stream, int* n_gated) {
+  return mof_sr_process_sequence_device_q(e, d_frames, frame_stride, pitch, n_frames, d_out, nullptr, stream, n_gated);
+}
+
+int mof_sr_process_sequence_device_q(mof_sr_engine* e, const uint8_t* d_frames, size_t frame_stride, size_t pitch, int n_frames,
+                                     double* d_out, double* d_quality, void* stream, int* n_gated) {
   if (!e) return mof::capi_fail(MOF_ERR_NOT_INIT, "null engine");
   const int res = e->cfg.resolution;
   if (n_gated) *n_gated = 0;
@@ -680,7 +722,7 @@ int mof_sr_process_sequence_device(mof_sr_engine* e, const uint8_t* d_frames, si
         lp_tables(e, 2, &lp);
         HIP_TRY(mof::launch_sr_logpolar(lp, 2, 1, s));
         HIP_TRY(rows_real(e, e->d_lp, nn, zh, zhf, 1, s));
-        HIP_TRY(mof::launch_sr_identity(d_out + 4 * (size_t)done, s));
+        HIP_TRY(mof::launch_sr_identity(d_out + 4 * (size_t)done, d_quality ? d_quality + 2 * (size_t)done : nullptr, s));
         first = false;  // :73
         ++done;
       } else if (carry < 0) {
@@ -697,26 +739,33 @@ int mof_sr_process_sequence_device(mof_sr_engine* e, const uint8_t* d_frames, si
         HIP_TRY(mof::launch_sr_logpolar(lp, 4, m, s));  // INTER_LANCZOS4, :112 -- every frame once
         HIP_TRY(rows_real(e, e->d_lp + nn, nn, zh + zhf, zhf, m, s));
         HIP_TRY(cols_seq(e, zh, zh + zhf, zhf, m, seq_run_for(e, m), s));
-        mof::SrPcArgs a = pc_args(e, d_out + 4 * (size_t)done);
+        // the pass's quality: the caller's array, or -- where the host walks the response gate below and needs it all the same -- the engine's
+        double* q = d_quality ? d_quality + 2 * (size_t)done : (n_gated && e->min_response > 0.0 ? e->d_q.get() : nullptr);
+        mof::SrPcArgs a = pc_args(e, d_out + 4 * (size_t)done, q);
         HIP_TRY(peak(e, a, m, s));
         carry = m;
         if (n_gated) {
-          // The gate (:119-121): a frame whose |pt.x| > res/2 returns (1, 0) and does NOT become prev. The pass above
-          // correlated every frame with its immediate predecessor; behind a gated frame that is the wrong partner, so
+          // The gates (:119-121, and the response gate that acts like it): a gated frame returns (1, 0) and does NOT become prev. The pass
+          // above correlated every frame with its immediate predecessor; behind a gated frame that is the wrong partner, so
           // walk the results in order and redo the (rare) pairs whose reference partner is an older frame.
+          double* hq = e->h_seq + 4 * (size_t)e->chunk;
           HIP_TRY(hipMemcpyAsync(e->h_seq, d_out + 4 * (size_t)done, (size_t)m * 4 * sizeof(double), hipMemcpyDeviceToHost, s));
+          if (q) HIP_TRY(hipMemcpyAsync(hq, q, (size_t)m * 2 * sizeof(double), hipMemcpyDeviceToHost, s));
           HIP_TRY(hipStreamSynchronize(s));
           int prev_slot = 0;
           for (int i = 1; i <= m; ++i) {
-            double ptx = e->h_seq[4 * (size_t)(i - 1) + 2];
+            double ptx = e->h_seq[4 * (size_t)(i - 1) + 2], response = q ? hq[2 * (size_t)(i - 1)] : 0.0;
             if (prev_slot != i - 1) {
               double* o = d_out + 4 * (size_t)(done + i - 1);
-              HIP_TRY(seq_one_pair(e, zh + (size_t)prev_slot * zhf, zh + (size_t)i * zhf, o, s));
+              double* oq = q ? q + 2 * (size_t)(i - 1) : nullptr;  // the redone frame's quality is that of the pair that now stands
+              HIP_TRY(seq_one_pair(e, zh + (size_t)prev_slot * zhf, zh + (size_t)i * zhf, o, oq, s));
               HIP_TRY(hipMemcpyAsync(e->h_out, o, 4 * sizeof(double), hipMemcpyDeviceToHost, s));
+              if (oq) HIP_TRY(hipMemcpyAsync(e->h_out + 4, oq, 2 * sizeof(double), hipMemcpyDeviceToHost, s));
               HIP_TRY(hipStreamSynchronize(s));
               ptx = e->h_out[2];
+              response = oq ? e->h_out[4] : 0.0;
             }
-            if (std::fabs(ptx) > (double)(res / 2)) ++gated_total;
+            if (sr_gated(e, ptx, response)) ++gated_total;
             else prev_slot = i;
           }
           carry = prev_slot;
@@ -742,7 +791,12 @@ int mof_sr_process_sequence_device(mof_sr_engine* e, const uint8_t* d_frames, si
 }
 
 int mof_sr_process_sequence_host(mof_sr_engine* e, const uint8_t* frames, size_t frame_stride, size_t pitch, int n_frames,
-                                 double* out, int* n_gated) try {
+                                 double* out, int* n_gated) {
+  return mof_sr_process_sequence_host_q(e, frames, frame_stride, pitch, n_frames, out, nullptr, n_gated);
+}
+
+int mof_sr_process_sequence_host_q(mof_sr_engine* e, const uint8_t* frames, size_t frame_stride, size_t pitch, int n_frames,
+                                   double* out, double* quality, int* n_gated) try {
   if (!e) return mof::capi_fail(MOF_ERR_NOT_INIT, "null engine");
   if (n_gated) *n_gated = 0;
   if (n_frames == 0) return MOF_OK;
@@ -750,21 +804,24 @@ int mof_sr_process_sequence_host(mof_sr_engine* e, const uint8_t* frames, size_t
   if (!frames || !out || n_frames < 0 || pitch < (size_t)res) return mof::capi_fail(MOF_ERR_BAD_ARG, "bad video arguments");
   HIP_TRY(hipSetDevice(e->cfg.device));
   mof::RelaxedCapture relaxed;
-  const size_t bpp = 4 * sizeof(double);
+  const size_t bpp[2] = {4 * sizeof(double), 2 * sizeof(double)};
   {
     std::lock_guard<std::mutex> lock(e->host_mu);
-    if (!e->host_pipe) e->host_pipe.reset(new mof::HostPipe((size_t)res * res, &bpp, 1));
+    if (!e->host_pipe) e->host_pipe.reset(new mof::HostPipe((size_t)res * res, bpp, 1));
+    if (quality && !e->host_pipe_q) e->host_pipe_q.reset(new mof::HostPipe((size_t)res * res, bpp, 2));
   }
-  const mof::HostPipe::Out o{out, bpp};
+  const mof::HostPipe::Out o[2] = {{out, bpp[0]}, {quality, bpp[1]}};
+  mof::HostPipe* pipe = (quality ? e->host_pipe_q : e->host_pipe).get();
   hipError_t he = hipSuccess;
   int gated_total = 0;
   // the frames go up in chunks on the pipe's copy stream, each chunk runs through the DEVICE video entry -- stateful, so chunk k + 1
   // continues where chunk k stopped, and with the gate resolved (n_gated != NULL there), i.e. exactly the frame-by-frame calls
-  const int rc = e->host_pipe->process_frames(
-      frames, frame_stride, pitch, res, res, n_frames, &o, e->stream,
-      [e, &gated_total](const mof::HostPipe::Chunk& c, hipStream_t s) {
+  const int rc = pipe->process_frames(
+      frames, frame_stride, pitch, res, res, n_frames, o, e->stream,
+      [e, quality, &gated_total](const mof::HostPipe::Chunk& c, hipStream_t s) {
         int g = 0;
-        const int r = mof_sr_process_sequence_device(e, c.d_cur, c.stride, (size_t)e->cfg.resolution, c.count, static_cast<double*>(c.d_out[0]), s, &g);
+        const int r = mof_sr_process_sequence_device_q(e, c.d_cur, c.stride, (size_t)e->cfg.resolution, c.count, static_cast<double*>(c.d_out[0]),
+                                                       quality ? static_cast<double*>(c.d_out[1]) : nullptr, s, &g);
         gated_total += g;
         return r;
       },
@@ -778,6 +835,11 @@ int mof_sr_process_sequence_host(mof_sr_engine* e, const uint8_t* frames, size_t
 
 int mof_sr_process_batch_device(mof_sr_engine* e, const uint8_t* d_cur, size_t cur_stride, const uint8_t* d_prev,
                                 size_t prev_stride, size_t pitch, int n_pairs, double* d_out, void* stream) {
+  return mof_sr_process_batch_device_q(e, d_cur, cur_stride, d_prev, prev_stride, pitch, n_pairs, d_out, nullptr, stream);
+}
+
+int mof_sr_process_batch_device_q(mof_sr_engine* e, const uint8_t* d_cur, size_t cur_stride, const uint8_t* d_prev, size_t prev_stride,
+                                  size_t pitch, int n_pairs, double* d_out, double* d_quality, void* stream) {
   if (!e) return mof::capi_fail(MOF_ERR_NOT_INIT, "null engine");
   const int res = e->cfg.resolution;
   if (n_pairs == 0) return MOF_OK;  // an empty batch carries no pointers to check
@@ -835,7 +897,7 @@ int mof_sr_process_batch_device(mof_sr_engine* e, const uint8_t* d_cur, size_t c
     const size_t zhf = e->route.zh_floats;
     HIP_TRY(rows_real(e, lp_buf, nn, e->d_Zt, zhf, 2 * n, s));
     HIP_TRY(cols_seq(e, e->d_Zt + zhf, e->d_Zt, 2 * zhf, n, 1, s));
-    HIP_TRY(peak(e, pc_args(e, d_out + 4 * (size_t)k0), n, s));
+    HIP_TRY(peak(e, pc_args(e, d_out + 4 * (size_t)k0, d_quality ? d_quality + 2 * (size_t)k0 : nullptr), n, s));
     if (two_lanes) HIP_TRY(hipEventRecord(e->ev_fft[b], s));
   }
   HIP_TRY(e->fence.release(s));

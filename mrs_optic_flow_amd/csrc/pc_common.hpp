@@ -611,14 +611,24 @@ __device__ __forceinline__ void centroid_gate_store(Best best, float wval, int l
 
 // The estimator's finish, by lane 0: pt = cv::phaseCorrelate(cur_lp, prev_lp) = center - t, NOT negated (scaleRotationEstimator.cpp:117);
 // |pt.x| > resolution / 2 (int division) -> (1, 0) (:119-121); scale = exp(pt.x / M), rot = (pt.y / Ky) pi/180, Ky = resolution / 360
-// (:123-124). flat_zero: an all-zero log-polar image -- flat zero surface: first index, centroid 0 / (0 + eps). out4 = scale, rot, pt.x, pt.y
-__device__ __forceinline__ void sr_finish(double cx, double cy, double sum, int m, int n, double M_log, bool flat_zero, double* out4) {
+// (:123-124). An all-zero log-polar image has an exactly zero spectrum -- flat zero surface: first index, centroid 0 / (0 + eps), pt = (m / 2, m / 2),
+// quality (0, 0) -- and needs no special case here. out4 = scale, rot, pt.x, pt.y
+// The quality of that surface (quality_store<0>: response, peak; `best` = its first maximum) goes to `quality` when that is non-null, whatever
+// the gates decide. min_response > 0 arms the response gate, which acts as the reference's: !(response >= min_response) -> (1, 0), pt still
+// reported. It reads the very double that is stored, so a host that reads `quality` back decides as this code did.
+__device__ __forceinline__ void sr_finish(double cx, double cy, double sum, Best best, int m, int n, double M_log, double* out4, double* quality,
+                                          double min_response) {
+  double q[2] = {0.0, 0.0};
+  if (quality || min_response > 0.0) quality_store<0>(q, sum, best.v, (double)m * (double)m, best.idx != 0x7fffffff, false, 0.f);
+  if (quality) {
+    quality[0] = q[0];
+    quality[1] = q[1];
+  }
   sum += 2.220446049250313e-16;
   const double half_m = (double)m / 2.0;
-  double ptx = half_m - cx / sum, pty = half_m - cy / sum;
-  if (flat_zero) ptx = pty = half_m;
+  const double ptx = half_m - cx / sum, pty = half_m - cy / sum;
   double scale = 1.0, rot = 0.0;
-  if (!(fabs(ptx) > (double)(n / 2))) {
+  if (!(fabs(ptx) > (double)(n / 2)) && !(min_response > 0.0 && !(q[0] >= min_response))) {
     scale = exp(ptx / M_log);
     rot = (pty / ((double)n / 360.0)) * (3.14159265358979323846 / 180.0);
   }

@@ -317,7 +317,7 @@ __global__ void __launch_bounds__(64) pcl_final_kernel(PclFinal a) {
   wave_sum3<(WW > 32 ? 32 : 16)>(cx, cy, sum);
   if (lane != 0) return;
   if (PK == 0 && a.mode == 0) {  // scaleRotationEstimator
-    sr_finish(cx, cy, sum, m, a.n, a.M_log, false, a.out + 4 * pair);
+    sr_finish(cx, cy, sum, best, m, a.n, a.M_log, a.out + 4 * pair, a.quality ? a.quality + 2 * pair : nullptr, a.min_response);
   } else {  // FftMethod
     bool degenerate = false;
     if (a.flags) {  // a constant patch (pc_common.hpp, degenerate pairs); padded, only the all-zero patch stays constant
@@ -461,7 +461,7 @@ hipError_t launch_pcl_peak(const PclFinal& a_in, const PcPlan& pl, int n_pairs, 
     a.Dt = a_in.Dt + (size_t)p0 * NU * pl.m * 2;
     a.cand = a_in.cand + (size_t)p0 * n_cand;
     a.out = a_in.out + (size_t)p0 * (a.mode == 0 ? 4 : 2);
-    a.quality = (a.mode == 1 && a_in.quality) ? a_in.quality + (size_t)p0 * 2 : nullptr;
+    a.quality = a_in.quality ? a_in.quality + (size_t)p0 * 2 : nullptr;
     if (a.flags) a.flags = a_in.flags + 2 * (size_t)p0;
     if (a.cdc) a.cdc = a_in.cdc + p0;
     if (!candidates_done)  // (else L7 was run by somebody else: the tuned K7 for patches of 240 / 256 / 480 pixels)

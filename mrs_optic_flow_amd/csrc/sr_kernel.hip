@@ -548,7 +548,8 @@ __global__ void __launch_bounds__(K7Cfg<N>::T) sr_rows_inv_kernel(SrPcArgs a) {
 
 // ---- K8: peak, centroid, (scale, rot) ----------------------------------------------------------------------
 // out[pair] = {scale, rot, pt.x, pt.y} (pc_common.hpp, sr_finish). K7 keeps no surface: the 25 values of the window are re-evaluated from the
-// half spectrum of their rows (Dt), in double (spectrum_window).
+// half spectrum of their rows (Dt), in double (spectrum_window). Their sum and the first maximum are the correlation quality: stored at
+// a.quality[pair] when that is non-null, and what the response gate (a.min_response > 0) reads.
 template <int N>
 __global__ void __launch_bounds__(64) sr_final_kernel(SrPcArgs a) {
   __shared__ double part[25][65];
@@ -561,7 +562,7 @@ __global__ void __launch_bounds__(64) sr_final_kernel(SrPcArgs a) {
   peak_window<0>(best, lane, N, &ys, &xs);
   double cx = (double)xs * val, cy = (double)ys * val, sum = val;
   wave_sum3<16>(cx, cy, sum);
-  if (lane == 0) sr_finish(cx, cy, sum, N, N, a.M, a.degen && a.degen[pair], a.out + 4 * pair);  // (degen: null, the residue of SrPcArgs)
+  if (lane == 0) sr_finish(cx, cy, sum, best, N, N, a.M, a.out + 4 * pair, a.quality ? a.quality + 2 * pair : nullptr, a.min_response);
 }
 
 // (the list: MOF_SR_TUNED_SIZES, sr_common.hpp)

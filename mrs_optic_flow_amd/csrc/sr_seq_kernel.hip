@@ -361,9 +361,11 @@ __global__ void __launch_bounds__(64) sr_cols_seq_kernel(const float* __restrict
   }
 }
 
-// what processImage returns for the very first frame of a sequence (scaleRotationEstimator.cpp:74): (1, 0), no pt
-__global__ void sr_identity_kernel(double* __restrict__ out) {
+// what processImage returns for the very first frame of a sequence (scaleRotationEstimator.cpp:74): (1, 0), no pt -- and, where the call
+// asked for quality, (NaN, NaN): no correlation ran
+__global__ void sr_identity_kernel(double* __restrict__ out, double* __restrict__ quality) {
   if (threadIdx.x < 4) out[threadIdx.x] = threadIdx.x == 0 ? 1.0 : 0.0;
+  else if (threadIdx.x < 6 && quality) quality[threadIdx.x - 4] = __builtin_nan("");
 }
 
 template <int N>
@@ -422,8 +424,8 @@ hipError_t launch_cols_seq_n(const float* zh_prev, const float* zh_cur, size_t z
 
 size_t sr_zh_floats(int res) { return (size_t)(res / 2 + 1) * (((res + 7) & ~7) + 8) * 2; }  // (pitch: sr_zh_pitch)
 
-hipError_t launch_sr_identity(double* out, hipStream_t stream) {
-  hipLaunchKernelGGL(sr_identity_kernel, dim3(1), dim3(64), 0, stream, out);
+hipError_t launch_sr_identity(double* out, double* quality, hipStream_t stream) {
+  hipLaunchKernelGGL(sr_identity_kernel, dim3(1), dim3(64), 0, stream, out, quality);
   return hipGetLastError();
 }
 

@@ -500,14 +500,27 @@ class ScaleRotationEstimator:
     returns (scale, rotation [rad]) like :34-148."""
 
     def __init__(self, resolution: int, m: float = 49.9, storeVideo: bool = False, videoPath=None, videoFPS: int = 30,
-                 device: int = 0, logpolar_variant: int = 0, batch_chunk: int = 0, pipeline_lanes: int = 0):
+                 device: int = 0, logpolar_variant: int = 0, batch_chunk: int = 0, pipeline_lanes: int = 0, min_response: float = 0.0):
         """logpolar_variant: LOGPOLAR_CV4 (cv::logPolar of OpenCV 4.x, ROS Noetic) or LOGPOLAR_CV3 (cvLogPolar of OpenCV 3.2,
         ROS Melodic) -- the two calls scaleRotationEstimator.cpp:41-46 compiles. batch_chunk / pipeline_lanes: batched mode
-        only (frame pairs per pipeline pass, one or two stream lanes; 0 = the library's defaults, see mof.h)."""
+        only (frame pairs per pipeline pass, one or two stream lanes; 0 = the library's defaults, see mof.h). min_response: the
+        response gate (mof_sr_set_min_response; 0 = off, the reference's behaviour): a frame whose correlation response is not
+        >= min_response is gated like one that fails the reference's |pt.x| rule. No reference counterpart."""
         self._lib = _capi.load()
         self.cfg = SrConfig(resolution, float(m), device, int(logpolar_variant), int(batch_chunk), int(pipeline_lanes))
         self._h = C.c_void_p()
         check(self._lib.mof_sr_create(C.byref(self.cfg), C.byref(self._h)))
+        self.last_quality = None
+        if min_response != 0.0:
+            self.set_min_response(min_response)
+
+    def set_min_response(self, min_response: float) -> None:
+        """MofError(MOF_ERR_BUSY) while a captured graph pins the engine, MOF_ERR_BAD_ARG unless finite and >= 0."""
+        check(self._lib.mof_sr_set_min_response(self._h, float(min_response)))
+
+    @property
+    def min_response(self) -> float:
+        return float(self._lib.mof_sr_min_response(self._h))
 
     def reset(self) -> None:
         check(self._lib.mof_sr_reset(self._h))
@@ -521,27 +534,32 @@ class ScaleRotationEstimator:
         if f.shape != (self.cfg.resolution, self.cfg.resolution):
             raise ValueError("scaleRotationEstimator accepts only square images of its resolution")
         out = np.zeros(2, np.float64)
-        check(self._lib.mof_sr_process(self._h, f.ctypes.data, f.strides[0], out.ctypes.data))
+        quality = np.zeros(2, np.float64)
+        check(self._lib.mof_sr_process_q(self._h, f.ctypes.data, f.strides[0], out.ctypes.data, quality.ctypes.data))
+        self.last_quality = quality  # (response, peak) of this call's correlation surface; (NaN, NaN) for the first frame (include/mof.h)
         return float(out[0]), float(out[1])
 
-    def process_sequence_host(self, frames) -> np.ndarray:
+    def process_sequence_host(self, frames, return_quality=False):
         """frames: numpy uint8 [n, res, res] video in HOST memory (any frame stride / row pitch; pinned_empty() memory is DMA'd in place)
         -> float64 [n, 4] = what n consecutive processImage calls return (scale, rot, pt.x, pt.y), continuing and updating the engine's
-        state; ``self.last_gated`` = gated frames. Synchronous (mof_sr_process_sequence_host)."""
+        state; ``self.last_gated`` = gated frames. Synchronous (mof_sr_process_sequence_host). ``return_quality``: (results, quality),
+        quality float64 [n, 2] = (response, peak) per frame -- as on the device entries below."""
         f = np.asarray(frames)
         if f.ndim != 3 or tuple(f.shape[1:]) != (self.cfg.resolution, self.cfg.resolution):
             raise ValueError("scaleRotationEstimator accepts only square images of its resolution")
         if not (f.dtype == np.uint8 and f.strides[2] == 1 and f.strides[1] >= f.shape[2] and (f.shape[0] < 2 or f.strides[0] > 0)):
             f = np.ascontiguousarray(f, dtype=np.uint8)
         out = np.zeros((f.shape[0], 4), np.float64)
+        quality = np.zeros((f.shape[0], 2), np.float64) if return_quality else None
         gated = C.c_int(0)
-        check(self._lib.mof_sr_process_sequence_host(self._h, f.ctypes.data, max(f.strides[0], 0), f.strides[1], f.shape[0], out.ctypes.data,
-                                                     C.byref(gated)))
+        check(self._lib.mof_sr_process_sequence_host_q(self._h, f.ctypes.data, max(f.strides[0], 0), f.strides[1], f.shape[0], out.ctypes.data,
+                                                       quality.ctypes.data if return_quality else None, C.byref(gated)))
         self.last_gated = gated.value
-        return out
+        return (out, quality) if return_quality else out
 
-    def process_batch_device(self, cur, prev, stream=None):
-        """cur, prev: torch uint8 [n, res, res] views (any pitch/stride) -> float64 [n, 4] = scale, rot, pt.x, pt.y."""
+    def process_batch_device(self, cur, prev, stream=None, return_quality=False):
+        """cur, prev: torch uint8 [n, res, res] views (any pitch/stride) -> float64 [n, 4] = scale, rot, pt.x, pt.y; with
+        ``return_quality`` (results, quality), quality a float64 tensor [n, 2] = (response, peak) of each pair's surface."""
         import torch
 
         _check_device_batch(cur, prev, (self.cfg.resolution, self.cfg.resolution), self.cfg.device)
@@ -549,15 +567,17 @@ class ScaleRotationEstimator:
         out = torch.empty((n, 4), dtype=torch.float64, device=cur.device)
         s = stream if stream is not None else torch.cuda.current_stream(cur.device)
         _pin_if_capturing(self, s)
-        check(self._lib.mof_sr_process_batch_device(self._h, cur.data_ptr(), cur.stride(0), prev.data_ptr(),
-                                                    prev.stride(0), cur.stride(1), n, out.data_ptr(), _stream_ptr(s)))
-        return out
+        quality = torch.empty((n, 2), dtype=torch.float64, device=cur.device) if return_quality else None
+        check(self._lib.mof_sr_process_batch_device_q(self._h, cur.data_ptr(), cur.stride(0), prev.data_ptr(), prev.stride(0), cur.stride(1), n,
+                                                      out.data_ptr(), quality.data_ptr() if return_quality else None, _stream_ptr(s)))
+        return (out, quality) if return_quality else out
 
-    def process_sequence_device(self, frames, resolve_gate: bool = True, stream=None):
+    def process_sequence_device(self, frames, resolve_gate: bool = True, stream=None, return_quality=False):
         """frames: torch uint8 [n, res, res] view of a video (any pitch / frame stride) -> float64 [n, 4] = what n consecutive
         processImage calls return (scale, rot, pt.x, pt.y; the first frame of a fresh estimator: 1, 0, 0, 0), continuing
         and updating the engine's stateful sequence. resolve_gate=True is synchronous and exact under the gate of
-        scaleRotationEstimator.cpp:119-121 (``self.last_gated`` = gated frames); False is asynchronous / capturable."""
+        scaleRotationEstimator.cpp:119-121 and the response gate (``self.last_gated`` = gated frames); False is asynchronous /
+        capturable. ``return_quality``: (results, quality), quality [n, 2] = (response, peak); (NaN, NaN) where no correlation ran."""
         import torch
 
         _check_device_batch(frames, frames, (self.cfg.resolution, self.cfg.resolution), self.cfg.device)
@@ -566,11 +586,12 @@ class ScaleRotationEstimator:
         s = stream if stream is not None else torch.cuda.current_stream(frames.device)
         _pin_if_capturing(self, s)
         gated = C.c_int(0)
-        check(self._lib.mof_sr_process_sequence_device(self._h, frames.data_ptr(), frames.stride(0), frames.stride(1), n,
-                                                       out.data_ptr(), _stream_ptr(s),
-                                                       C.byref(gated) if resolve_gate else None))
+        quality = torch.empty((n, 2), dtype=torch.float64, device=frames.device) if return_quality else None
+        check(self._lib.mof_sr_process_sequence_device_q(self._h, frames.data_ptr(), frames.stride(0), frames.stride(1), n,
+                                                         out.data_ptr(), quality.data_ptr() if return_quality else None, _stream_ptr(s),
+                                                         C.byref(gated) if resolve_gate else None))
         self.last_gated = gated.value if resolve_gate else None
-        return out
+        return (out, quality) if return_quality else out
 
     def logpolar_batch_device(self, src, interpolation: int = INTER_LANCZOS4, dst=None, stream=None):
         """cv::logPolar of n res x res crops (torch uint8 [n, res, res], any pitch/stride) -> uint8 [n, res, res].
