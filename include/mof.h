@@ -241,6 +241,25 @@ int mof_fft_process_sequence_device_q(mof_fft_engine* e, const uint8_t* d_frames
 int mof_fft_process_batch_host_q(mof_fft_engine* e, const uint8_t* cur, size_t cur_stride, const uint8_t* prev, size_t prev_stride,
                                  size_t pitch, int n_pairs, double* out_xy, double* quality);
 
+/* The response gate (no reference counterpart; off by default): with min_response > 0 a patch whose response -- the first quality slot
+ * above, under either peak model and on that model's own scale -- is not >= min_response returns (NaN, NaN), exactly as a patch that
+ * fails the reference's validity rule (|s| <= max_px_speed, |s_x|, |s_y| <= patch_size / 2); a NaN response counts as below the
+ * threshold. Every entry of the engine sees the one value: the stateful calls (n_invalid counts gated patches), the batch, video, BGR8,
+ * long-range and host entries; mof_geom_get_rt / mof_geom_get_2dt skip non-finite shifts as they always did. What the gate does NOT
+ * change: the quality outputs (a gated patch reports the response that gated it), the bits of every shift that passes, and the frame
+ * chain -- unlike the estimator's gate (mof_sr_set_min_response) a gated frame still becomes the previous one (FftMethod.cpp:1872).
+ * The decision is made on the device from the very double the quality output holds (csrc/pc_gate_kernel.hip, one small kernel enqueued on
+ * the call's stream behind the field's kernels), so a host that reads `quality` back decides as the engine did.
+ * A batched call without a quality pointer stores the responses in a buffer of the engine's own (n_pairs * patches * 2 doubles), which
+ * follows the rules of the large-patch scratch (mof_fft_create above): it grows with the first call that needs more, never inside a HIP
+ * graph capture (MOF_ERR_BAD_ARG, nothing is launched: run the largest batch once before capturing) and never while a captured graph
+ * pins the engine (MOF_ERR_BUSY); calls on different streams are ordered through it. With min_response == 0 nothing is launched and
+ * nothing is allocated: the engine is the one without this function.
+ * min_response must be finite and >= 0 (else MOF_ERR_BAD_ARG). MOF_ERR_BUSY while a call is in flight and while the engine is graph-pinned
+ * (a captured gate kernel holds the old value: mof_fft_release_graphs first). mof_fft_reset keeps the value. */
+int mof_fft_set_min_response(mof_fft_engine* e, double min_response);
+double mof_fft_min_response(const mof_fft_engine* e);
+
 /* Pinned (page-locked) host memory for callers that do not link HIP themselves: hipHostMalloc / hipHostFree / hipHostRegister /
  * hipHostUnregister behind the C ABI. Frames handed to the *_batch_host entries from such memory skip the staging copy. */
 int mof_host_alloc(size_t bytes, void** out);
@@ -293,6 +312,11 @@ int mof_shard_fft_process_batch_device(mof_shard_fft* g, const uint8_t* const* d
                                        const uint8_t* const* d_prev, size_t prev_stride, size_t pitch, int n_pairs,
                                        double* const* d_out, int gather);
 int mof_shard_fft_sync(mof_shard_fft* g);
+/* mof_fft_set_min_response on every engine of the group: all of them or none -- MOF_ERR_BUSY (nothing changes) if any engine has a call
+ * in flight or is graph-pinned. mof_shard_fft_min_response: the group's value (0 for a null group). The sharded entries have no
+ * quality outputs; each engine reads the responses from its own buffer. */
+int mof_shard_fft_set_min_response(mof_shard_fft* g, double min_response);
+double mof_shard_fft_min_response(const mof_shard_fft* g);
 
 /* ------------------------------------------------------------------------------------------ */
 /* SAD block matching (BlockMethod / FastSpacedBMMethod)                                      */

@@ -166,6 +166,11 @@ class FftMethod {
   // (response, peak) of every patch of the last processImage / processImageLongRange call, indexed as its vectors; a gated patch
   // (NaN vector) still carries its quality
   const std::vector<PatchQuality>& lastQuality() const { return last_quality_; }
+  // The response gate (no reference counterpart; 0 = off): a patch whose response is not >= min_response returns (NaN, NaN) on every entry,
+  // like one that fails the reference's validity rule; invalidPatches() counts it, lastQuality() still carries the response that gated it,
+  // and the frame still becomes the previous one. Throws while a call is in flight or a captured graph pins the engine.
+  void setMinResponse(double min_response) { detail::check(mof_fft_set_min_response(engine_, min_response), "mof_fft_set_min_response"); }
+  double minResponse() const { return mof_fft_min_response(engine_); }
   const mof_fft_config& config() const { return cfg_; }
   mof_fft_engine* handle() { return engine_; }
 
@@ -215,6 +220,9 @@ class ShardedFftMethod {
   // the asynchronous batch call never builds communicators itself (it throws with MOF_ERR_NOT_INIT's text instead).
   void initGather() { detail::check(mof_shard_fft_init_gather(group_), "mof_shard_fft_init_gather"); }
   bool gatherReady() const { return mof_shard_fft_gather_ready(group_) != 0; }
+  // FftMethod::setMinResponse on every engine of the group, all or none (throws if any is busy or pinned)
+  void setMinResponse(double min_response) { detail::check(mof_shard_fft_set_min_response(group_, min_response), "mof_shard_fft_set_min_response"); }
+  double minResponse() const { return mof_shard_fft_min_response(group_); }
 
  private:
   mof_fft_config cfg_{};
@@ -513,6 +521,9 @@ class MofFftMethod final : public OpticFlowCalc {
     imPrev = imPrev_t;
     impl_.setImPrev(mof::ImageView{imPrev_t.data, imPrev_t.rows, imPrev_t.cols, imPrev_t.step});
   }
+  // the response gate of mof::FftMethod (no reference counterpart; 0 = off)
+  void setMinResponse(double min_response) { impl_.setMinResponse(min_response); }
+  double minResponse() const { return impl_.minResponse(); }
 
  private:
   mof::FftMethod impl_;

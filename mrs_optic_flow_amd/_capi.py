@@ -92,6 +92,10 @@ SYMBOLS = {
     "mof_fft_process_batch_device_q": (_I, [_VP, _VP, _SZ, _VP, _SZ, _SZ, _I, _I, _I, _VP, _VP, _VP]),
     "mof_fft_process_sequence_device_q": (_I, [_VP, _VP, _SZ, _SZ, _I, _I, _VP, _VP, _VP]),
     "mof_fft_process_batch_host_q": (_I, [_VP, _VP, _SZ, _VP, _SZ, _SZ, _I, _VP, _VP]),
+    "mof_fft_set_min_response": (_I, [_VP, C.c_double]),
+    "mof_fft_min_response": (C.c_double, [_VP]),
+    "mof_shard_fft_set_min_response": (_I, [_VP, C.c_double]),
+    "mof_shard_fft_min_response": (C.c_double, [_VP]),
     "mof_host_alloc": (_I, [_SZ, C.POINTER(_VP)]),
     "mof_host_free": (_I, [_VP]),
     "mof_host_register": (_I, [_VP, _SZ]),

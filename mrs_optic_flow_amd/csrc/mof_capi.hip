@@ -24,6 +24,10 @@
 #include "mof_kernels.h"
 #include "pc_launch.hpp"
 
+// The response gate's kernel and its launcher (mof::launch_pc_response_gate): no translation unit of its own -- this file is its only
+// caller and held no device code before, so the gate adds one code object to the library and changes none.
+#include "pc_gate_kernel.hip"
+
 namespace {
 thread_local char g_err[512] = "";
 }  // namespace
@@ -191,6 +195,7 @@ struct mof_fft_engine {
   mof_fft_config cfg{};
   mof::Stream stream;
   mof::ScratchFence fence;                // cross-stream ordering of the large-patch scratch
+  mof::ScratchFence gate_fence;           // ... and of the response gate's quality buffer (d_gate_q; created with it)
   mof::DevMem<float> d_twiddles;
   mof::DevMem<uint8_t> d_frames[2];       // [cur_slot], [1-cur_slot] = previous
   int prev_slot = 0;
@@ -209,6 +214,11 @@ struct mof_fft_engine {
   mof::DevMem<float2> d_cand;
   mof::DevMem<int> d_flags;
   int cap = 0;
+  // the response gate (mof_fft_set_min_response; 0 = off): where a batched call brings no quality buffer the kernels store the response
+  // the gate reads into d_gate_q, for gate_cap patches -- made and grown as the large-patch scratch is, ordered by a fence of its own
+  std::atomic<double> min_response{0.0};  // (mof_fft_min_response reads it without the busy flag)
+  mof::DevMem<double> d_gate_q;
+  size_t gate_cap = 0;
   std::atomic<bool> busy{false};
   std::atomic<bool> graph_pinned{false};  // a batch call was captured into a HIP graph (capi_graph.hpp)
   std::mutex host_mu;                     // mof_fft_process_batch_host: upload / run / download pipeline (host_pipe.hpp), made by its first call
@@ -354,6 +364,44 @@ static int launch_field(mof_fft_engine* e, const mof::PcArgs& a, int n_pairs, hi
     if (_rc != MOF_OK) return _rc; \
   } while (0)
 
+// The response gate of the batched entries (mof_fft_set_min_response), in two steps around the field's launches on stream s.
+// gate_begin, before anything is launched and before a capturing call pins the engine: where the gate is armed and the caller brought no
+// quality buffer, *quality becomes the engine's own, grown to n_patches patches by the rules of the large-patch scratch (grow_scratch: not
+// while pinned, not inside a capture) and acquired for s. gate_end, behind the last launch: the gate kernel over the call's patches, reading
+// the doubles the field's kernels stored. Disarmed, neither does anything.
+// A launch that fails between the two leaves the fence unreleased for the kernels already enqueued, as launch_large's error path leaves
+// its own: the call has failed, its outputs are void, and every later user of the buffer on another stream is still ordered behind the
+// last release; the buffer is freed only after the stream and the fence have been waited for (fft_destroy_now, grow_scratch's drain).
+static int gate_begin(mof_fft_engine* e, size_t n_patches, hipStream_t s, double** quality, bool* own) {
+  *own = false;
+  if (!(e->min_response > 0.0) || *quality) return MOF_OK;
+  const int rc = mof::grow_scratch(e->graph_pinned.load(), e->gate_fence, {e->stream}, mof::stream_capturing(s),
+                                   "the response gate's quality buffer (patches)", (long)e->gate_cap, (long)n_patches, 0, [e](long cap) {
+                                     mof::RelaxedCapture relaxed;
+                                     e->gate_cap = 0;
+                                     e->d_gate_q.reset();
+                                     if (cap == 0) return hipSuccess;
+                                     if (!e->gate_fence.ev) {
+                                       const hipError_t err = e->gate_fence.create();
+                                       if (err != hipSuccess) return err;
+                                     }
+                                     const hipError_t err = e->d_gate_q.alloc(2 * (size_t)cap);
+                                     if (err == hipSuccess) e->gate_cap = (size_t)cap;
+                                     return err;
+                                   });
+  if (rc != MOF_OK) return rc;
+  HIP_TRY(e->gate_fence.acquire(s));
+  *quality = e->d_gate_q;
+  *own = true;
+  return MOF_OK;
+}
+static int gate_end(mof_fft_engine* e, double* out, const double* quality, size_t n_patches, hipStream_t s, bool own) {
+  if (!(e->min_response > 0.0)) return MOF_OK;
+  HIP_TRY(mof::launch_pc_response_gate(out, quality, n_patches, e->min_response, s));
+  if (own) HIP_TRY(e->gate_fence.release(s));
+  return MOF_OK;
+}
+
 // (member order = teardown order in reverse, as mof_fft_engine: stream, buffers, host pipe)
 struct mof_bm_engine {
   mof_bm_config cfg{};
@@ -476,6 +524,7 @@ static void fft_destroy_now(void* p) {
   (void)hipSetDevice(e->cfg.device);
   if (e->stream) (void)hipStreamSynchronize(e->stream);
   e->fence.wait_idle();
+  e->gate_fence.wait_idle();
   delete e;
 }
 struct FftDestroyNow {
@@ -590,9 +639,22 @@ int mof_fft_reset(mof_fft_engine* e) {
   if (!e) return fail(MOF_ERR_NOT_INIT, "null engine");
   BusyGuard g(e->busy);
   if (!g.owned) return fail(MOF_ERR_BUSY, "engine busy");
-  e->first = true;
+  e->first = true;  // (min_response stays: it is a setting, not state of the frame chain)
   return MOF_OK;
 }
+
+int mof_fft_set_min_response(mof_fft_engine* e, double min_response) {
+  if (!e) return fail(MOF_ERR_NOT_INIT, "null engine");
+  if (!std::isfinite(min_response) || min_response < 0.0) return fail(MOF_ERR_BAD_ARG, "min_response must be finite and >= 0");
+  BusyGuard g(e->busy);
+  if (!g.owned) return fail(MOF_ERR_BUSY, "engine busy");
+  // a captured graph holds the gate kernel with the old value as an argument, or no gate kernel at all: its replays would not follow
+  if (e->graph_pinned.load()) return fail(MOF_ERR_BUSY, "min_response is baked into a captured graph: mof_fft_release_graphs first");
+  e->min_response = min_response;
+  return MOF_OK;
+}
+
+double mof_fft_min_response(const mof_fft_engine* e) { return e ? e->min_response.load() : 0.0; }
 
 // Long-range geometry (FftMethod.cpp:1685, :1720): same patch size on the quarter-resolution frame,
 // sqNum_lr = sqNum / 4 patches per side. Only defined for the reference's own tiling.
@@ -631,13 +693,15 @@ static int fft_process_frame(mof_fft_engine* e, const uint8_t* frame, size_t pit
   HIP_TRY(upload_frame(e, cur_slot, frame, pitch));
   // `first`: the frame is correlated with itself (FftMethod.cpp:1791-1793, :1920-1922)
   const uint8_t* prev = e->first ? e->d_frames[cur_slot] : e->d_frames[e->prev_slot];
-  mof::PcArgs a = fft_args(e, e->d_frames[cur_slot], 0, prev, 0, (size_t)e->cfg.frame_width, e->d_out, quality ? e->d_quality.get() : nullptr);
+  const bool armed = e->min_response > 0.0;  // (the gate reads the engine's d_quality whether or not the caller asked for it)
+  mof::PcArgs a = fft_args(e, e->d_frames[cur_slot], 0, prev, 0, (size_t)e->cfg.frame_width, e->d_out, quality || armed ? e->d_quality.get() : nullptr);
   if (long_range) {
     int rc = long_range_args(e, &a);
     if (rc) return rc;
   }
   FIELD_TRY(launch_field(e, a, 1, e->stream));
   const size_t res = (size_t)a.grid_x * a.grid_y * 2;
+  if (armed) HIP_TRY(mof::launch_pc_response_gate(e->d_out, e->d_quality, res / 2, e->min_response, e->stream));
   HIP_TRY(hipMemcpyAsync(e->h_out, e->d_out, res * sizeof(double), hipMemcpyDeviceToHost, e->stream));
   if (quality) HIP_TRY(hipMemcpyAsync(e->h_quality, e->d_quality, res * sizeof(double), hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));
@@ -688,9 +752,12 @@ static int fft_batch(mof_fft_engine* e, const uint8_t* d_cur, size_t cur_stride,
     int rc = long_range_args(e, &a);
     if (rc) return rc;
   }
+  const size_t n_patches = (size_t)n_pairs * a.grid_x * a.grid_y;
+  bool own_q = false;
+  FIELD_TRY(gate_begin(e, n_patches, (hipStream_t)stream, &a.quality, &own_q));
   if (mof::stream_capturing((hipStream_t)stream)) e->graph_pinned.store(true);
   FIELD_TRY(launch_field(e, a, n_pairs, (hipStream_t)stream));
-  return MOF_OK;
+  return gate_end(e, a.out, a.quality, n_patches, (hipStream_t)stream, own_q);
 }
 
 int mof_fft_process_batch_device(mof_fft_engine* e, const uint8_t* d_cur, size_t cur_stride, const uint8_t* d_prev,
@@ -735,11 +802,15 @@ static int fft_sequence(mof_fft_engine* e, const uint8_t* d_frames, size_t frame
   HIP_TRY(hipSetDevice(e->cfg.device));
   mof::PcArgs a = fft_args(e, d_frames + frame_stride, frame_stride, d_frames, frame_stride, pitch, d_out_xy, d_quality);
   a.channels = channels;
+  const size_t n_patches = (size_t)n_pairs * a.grid_x * a.grid_y;
+  bool own_q = false;
+  FIELD_TRY(gate_begin(e, n_patches, (hipStream_t)stream, &a.quality, &own_q));
+  d_quality = a.quality;
   if (mof::stream_capturing((hipStream_t)stream)) e->graph_pinned.store(true);
   const FftRoute& r = e->route;
   if (r.video == FftRoute::PAIRS) {
     FIELD_TRY(launch_field(e, a, n_pairs, (hipStream_t)stream));
-    return MOF_OK;
+    return gate_end(e, a.out, a.quality, n_patches, (hipStream_t)stream, own_q);
   }
   // MOF_FFT_SEQ_RUN: pairs a workgroup walks in time (0: the launchers pick the run length; pc_seq_half.hip takes 16)
   static const int run_knob = [] { const char* v = getenv("MOF_FFT_SEQ_RUN"); const int r = v ? atoi(v) : 0; return r >= 1 ? r : 0; }();
@@ -756,7 +827,7 @@ static int fft_sequence(mof_fft_engine* e, const uint8_t* d_frames, size_t frame
     else if (r.video == FftRoute::SEQ_HALF) HIP_TRY(mof::launch_pc_sequence_half(c, e->cfg.patch_size, nk, run_knob ? run_knob : 16, (hipStream_t)stream));
     else HIP_TRY(mof::launch_pc_sequence(c, nk, run_knob, (hipStream_t)stream));
   }
-  return MOF_OK;
+  return gate_end(e, a.out, a.quality, n_patches, (hipStream_t)stream, own_q);
 }
 
 int mof_fft_process_sequence_device(mof_fft_engine* e, const uint8_t* d_frames, size_t frame_stride, size_t pitch, int n_frames,

@@ -128,6 +128,9 @@ hipError_t launch_pc_field_quad64(const PcArgs& a, int n_pairs, hipStream_t stre
 // N = 120 (15 x 8) lives in pc_kernel_mixed.hip
 hipError_t pc_configure_120();
 hipError_t launch_pc_field_120(const PcArgs& a, int n_pairs, hipStream_t stream);
+// The response gate behind any of the above (pc_gate_kernel.hip): patch i < n_patches with !(quality[2 i] >= min_response) gets (NaN, NaN)
+// at out[2 i], every other patch is left as it is
+hipError_t launch_pc_response_gate(double* out, const double* quality, size_t n_patches, double min_response, hipStream_t stream);
 
 // ---- K2/K3: SAD block scan + histogram mode -------------------------------------------------
 struct BmArgs {

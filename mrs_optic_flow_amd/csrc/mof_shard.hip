@@ -339,6 +339,26 @@ int mof_shard_fft_sync(mof_shard_fft* g) {
   return g->core.sync();
 }
 
+// all engines or none: a pinned engine is seen before anything changes; one that turns busy under the loop (a call in flight on another
+// thread) undoes the engines already set
+int mof_shard_fft_set_min_response(mof_shard_fft* g, double min_response) {
+  if (!g) return mof::capi_fail(MOF_ERR_NOT_INIT, "null shard group");
+  for (size_t i = 0; i < g->engines.size(); ++i)
+    if (mof_fft_graph_pinned(g->engines[i]))
+      return mof::capi_fail(MOF_ERR_BUSY, "shard %d is pinned by a captured graph: release the graphs first", (int)i);
+  const double old = mof_shard_fft_min_response(g);
+  for (size_t i = 0; i < g->engines.size(); ++i) {
+    const int rc = mof_fft_set_min_response(g->engines[i], min_response);  // (its error text stays the thread's last error)
+    if (rc != MOF_OK) {
+      for (size_t j = 0; j < i; ++j) (void)mof_fft_set_min_response(g->engines[j], old);
+      return rc;
+    }
+  }
+  return MOF_OK;
+}
+
+double mof_shard_fft_min_response(const mof_shard_fft* g) { return g && !g->engines.empty() ? mof_fft_min_response(g->engines[0]) : 0.0; }
+
 /* ---- BlockMethod / FastSpacedBMMethod --------------------------------------------------------------------------------- */
 
 void mof_shard_bm_destroy(mof_shard_bm* g) {

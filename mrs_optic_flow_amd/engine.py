@@ -140,7 +140,10 @@ class FftMethod:
     def __init__(self, frame_size: int | None = None, sample_point_size: int = 64, max_px_speed: float = 80.0, *,
                  frame_shape: tuple[int, int] | None = None, grid: tuple[int, int] | None = None,
                  origin: tuple[int, int] = (0, 0), stride: tuple[int, int] | None = None, device: int = 0,
-                 peak_model: int = 0, search_radius: int = 55):
+                 peak_model: int = 0, search_radius: int = 55, min_response: float = 0.0):
+        """min_response: the response gate (mof_fft_set_min_response; 0 = off, the reference's behaviour): a patch whose
+        correlation response is not >= min_response returns (NaN, NaN) on every entry, like one that fails the reference's
+        validity rule. No reference counterpart."""
         lib = _capi.load()
         cfg = FftConfig()
         if frame_shape is None:
@@ -161,6 +164,21 @@ class FftMethod:
         self._lib = lib
         self._h = C.c_void_p()
         check(lib.mof_fft_create(C.byref(cfg), C.byref(self._h)))
+        if min_response != 0.0:
+            self.set_min_response(min_response)
+
+    def set_min_response(self, min_response: float) -> None:
+        """MofError(MOF_ERR_BUSY) while a call is in flight or a captured graph pins the engine (release_captured first),
+        MOF_ERR_BAD_ARG unless finite and >= 0. 0 switches the gate off."""
+        check(self._lib.mof_fft_set_min_response(self._h, float(min_response)))
+
+    @property
+    def min_response(self) -> float:
+        return float(self._lib.mof_fft_min_response(self._h))
+
+    @property
+    def graph_pinned(self) -> bool:
+        return bool(self._lib.mof_fft_graph_pinned(self._h))
 
     @property
     def kernel_variant(self) -> str:

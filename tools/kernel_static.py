@@ -5,8 +5,9 @@ kernel_code_entry_byte_offset (bytes 16 .. 23), the distance from the descriptor
 or leaves the code object.
 
   tools/kernel_static.py LIB             one line per kernel, sorted by name
-  tools/kernel_static.py compare A B     whether each whole gfx950 code object is byte-identical, then the names only in A, the names
-                                         only in B, and the fields (code included) that changed
+  tools/kernel_static.py compare A B     whether each whole gfx950 code object is byte-identical (by position, and by content: a new
+                                         translation unit shifts the positions behind it), then the names only in A, the names only
+                                         in B, and the fields (code included) that changed
 
 Reads metadata, the symbol table and the section headers (llvm-readelf --notes / --symbols / --section-headers on the unbundled code
 objects) and slices the symbols' bytes out of the file: no disassembly, no instruction is looked at. `code` covers the kernel's own
@@ -130,6 +131,10 @@ def main(argv):
         print(f"gfx950 code objects: A {len(ca)}, B {len(cb)}; byte-identical {same}" + ("" if len(ca) != len(cb) else f", differing {len(ca) - same}"))
         for i, (x, y) in enumerate(zip(ca, cb)):
             print(f"  code object {i}: {'identical' if x == y else f'DIFFERS {x[:16]} -> {y[:16]}'}")
+        # (the linker places a translation unit's bundle where it likes: one more unit shifts the positions behind it, so also by content)
+        gone, new = [x for x in ca if x not in cb], [y for y in cb if y not in ca]
+        print(f"by content: {len(ca) - len(gone)} of A's {len(ca)} code objects are byte-identical in B; only in A {[x[:16] for x in gone]}, "
+              f"only in B {[y[:16] for y in new]}")
         a, b = record(argv[2]), record(argv[3])
         only_a, only_b = sorted(set(a) - set(b)), sorted(set(b) - set(a))
         print(f"kernels: A {len(a)}, B {len(b)}; library {os.path.getsize(argv[2])} -> {os.path.getsize(argv[3])} bytes")
