@@ -133,9 +133,8 @@ typedef struct mof_fft_engine mof_fft_engine;
 int mof_fft_create(const mof_fft_config* cfg, mof_fft_engine** out);
 /* Diagnostics: name of the kernel formulation the engine launches for cv::phaseCorrelate-model batches on full-resolution frames:
  * "stockham" (pc_kernel.hip / pc_kernel_mixed.hip), "planned-half", "planned" or "planned-large" (above) in the product library;
- * MOF_PEAK_OCL engines name theirs the same way ("planned-large" for every patch size from 136 on);
- * "quad" only in the A/B build csrc/ab/libmof_hip_quad.so with MOF_PC_QUAD=1 (pc_kernel_quad.hip, a measured-slower alternative kept
- * for comparison, not shipped). MOF_FFT_HALF=0 / 1 (environment, read once) keeps every size off / forces the instantiated sizes
+ * MOF_PEAK_OCL engines name theirs the same way ("planned-large" for every patch size from 136 on).
+ * MOF_FFT_HALF=0 / 1 (environment, read once) keeps every size off / forces the instantiated sizes
  * onto the half-tile kernel (A/B and the tests of either family). */
 const char* mof_fft_kernel_variant(const mof_fft_engine* e);
 void mof_fft_destroy(mof_fft_engine* e);

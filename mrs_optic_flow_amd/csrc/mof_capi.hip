@@ -547,13 +547,7 @@ int mof_fft_create(const mof_fft_config* cfg, mof_fft_engine** out) try {
   if (!fft_route(*cfg, &e->plan, &e->route))  // (validate_fft has checked that a plan exists)
     return fail(MOF_ERR_UNSUPPORTED, "no plan for patch_size %d", cfg->patch_size);
   const FftRoute& r = e->route;
-  std::vector<float> tw = mof::twiddle_table(r.m);
-  if (r.family == FftRoute::TUNED && r.m == 64) {  // the tuned N = 64 kernel's matrix-core stage reads its DFT-16 fragments from behind the twiddles
-    std::vector<uint32_t> frag(1024, 0u);
-    mof::pc_mfma_s1_fragments(frag.data());
-    tw.resize(128 + 1024);
-    std::memcpy(tw.data() + 128, frag.data(), 4096);
-  }
+  const std::vector<float> tw = mof::twiddle_table(r.m);
   HIP_TRY(e->stream.create());
   HIP_TRY(mof::upload(e->d_twiddles, tw, e->stream));
   for (auto& frame : e->d_frames) {
@@ -584,7 +578,7 @@ const char* mof_fft_kernel_variant(const mof_fft_engine* e) {
   const FftRoute& r = e->route;
   return r.half_m > 0 ? "planned-half"
                       : (r.family == FftRoute::LARGE ? "planned-large"
-                                                     : (r.family == FftRoute::PLANNED ? "planned" : mof::pc_kernel_variant(e->cfg.patch_size)));
+                                                     : (r.family == FftRoute::PLANNED ? "planned" : "stockham"));
 }
 
 void mof_fft_destroy(mof_fft_engine* e) {

@@ -31,9 +31,6 @@ struct PcArgs {
   double* quality;        // device, nullable: [pair][patch] (response, peak) of the correlation surface (pc_common.hpp, quality_store)
 };
 
-// 1024 dwords behind the 64 twiddles of an N = 64 engine: the f16 hi / lo fragments of the radix-16 DFT matrix, in the lane order
-// of v_mfma_f32_32x32x16_f16's A operand (pc_passes3.hpp, fwd3_rows_mfma)
-void pc_mfma_s1_fragments(uint32_t* out);
 // twiddles W_n^k = exp(-2 pi i k / n), k < n, as (re, im) float pairs (mof_capi.hip; both engines' d_twiddles)
 std::vector<float> twiddle_table(int n);
 
@@ -110,7 +107,6 @@ bool pc_half_sequence_supported(int m);
 hipError_t launch_pc_half_sequence(const PcArgs& a, int m, int n, int n_pairs, int run, hipStream_t stream);
 
 bool pc_patch_size_supported(int n);  // the hand-tuned instantiations: 32, 64, 120, 128
-const char* pc_kernel_variant(int patch_size);
 hipError_t pc_configure(int patch_size);  // once per device before the first launch
 hipError_t launch_pc_field(const PcArgs& a, int patch_size, int n_pairs, hipStream_t stream);
 // Frame sequences (pc_seq_kernel.hip; 64 x 64 patches): a.cur = frame 0, a.cur_stride = bytes between frames, pair k =
@@ -122,9 +118,6 @@ hipError_t launch_pc_sequence(const PcArgs& a, int n_pairs, int run, hipStream_t
 bool pc_sequence_half_supported(int patch_size);
 hipError_t pc_configure_sequence_half(int patch_size);
 hipError_t launch_pc_sequence_half(const PcArgs& a, int patch_size, int n_pairs, int run, hipStream_t stream);
-// N = 64, quad-per-line formulation (pc_kernel_quad.hip)
-hipError_t pc_configure_quad64();
-hipError_t launch_pc_field_quad64(const PcArgs& a, int n_pairs, hipStream_t stream);
 // N = 120 (15 x 8) lives in pc_kernel_mixed.hip
 hipError_t pc_configure_120();
 hipError_t launch_pc_field_120(const PcArgs& a, int n_pairs, hipStream_t stream);

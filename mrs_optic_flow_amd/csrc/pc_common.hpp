@@ -423,8 +423,8 @@ __device__ __forceinline__ cf cross_power_ab(cf A, cf B, bool real_only) {
   }
   // |P'|^2 >= 2^10: 16 eps / q < 2^-30 is below half an ulp of the unit-magnitude result, so C = P' rsq(q) (one
   // transcendental); the general form only runs for (numerically) empty bins such as constant patches
-  // -- taken as a wave-uniform branch: a per-lane one costs exec-mask juggling around every bin and, in the quad
-  // kernel, 48 spilled VGPRs.
+  // -- taken as a wave-uniform branch: a per-lane one costs exec-mask juggling around every bin (and cost the retired
+  // quad-per-line kernel 48 spilled VGPRs).
   float s = __builtin_amdgcn_rsqf(q);
   if (__builtin_amdgcn_ballot_w64(!(q >= 1024.f)) != 0)
     s = (q >= 1024.f) ? s : __builtin_amdgcn_sqrtf(q) * __builtin_amdgcn_rcpf(q + eps16);

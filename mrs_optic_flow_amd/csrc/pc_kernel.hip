@@ -34,7 +34,6 @@
 #include <stdint.h>
 #include <stdlib.h>
 
-#include "mfma_frag.hpp"
 #include "mof_kernels.h"
 #include "pc_common.hpp"
 #include "pc_launch.hpp"
@@ -50,12 +49,6 @@ namespace mof {
 // CH = 3: the frames are interleaved BGR8 and the CV_RGB2GRAY conversion of the node's front end
 // (optic_flow.cpp:1622) is fused into the load, so raw camera frames are read from HBM exactly once.
 // PK = 1: the peak model of the reference's useOCL=true branch (cl/FftMethod.cl) instead of cv::phaseCorrelate's.
-#ifndef MOF_K1_MFMA_S1  // S1 of the three-stage forward transform on the matrix cores (pc_passes3.hpp)
-#define MOF_K1_MFMA_S1 0
-#endif
-#ifndef MOF_K1_TAIL_BARRIER  // 0: no barrier between the window read and the centroid where a workgroup runs ONE patch
-#define MOF_K1_TAIL_BARRIER 1
-#endif
 template <int N, int DS, int CH, int PK>
 __global__ void __launch_bounds__(PcTraits<N>::T) pc_field_kernel(PcArgs a) {
   static_assert(CH == 1 || (CH == 3 && DS == 1), "BGR front end only for the full-resolution path");
@@ -216,11 +209,7 @@ __global__ void __launch_bounds__(PcTraits<N>::T) pc_field_kernel(PcArgs a) {
 
   // ---- forward 2-D transform of z: rows (wave-local), barrier, columns (wave-local)  (dft x2, :1491-1493)
   if constexpr (FWD3) {
-#if MOF_K1_MFMA_S1
-    fwd3_rows_mfma(z, wave, lane, a.twiddles);
-#else
     fwd3_rows(z, wave, lane);
-#endif
     __syncthreads();
     fwd3_mid(z, wave, lane, tw3);
     wave_sync();
@@ -317,8 +306,8 @@ __global__ void __launch_bounds__(PcTraits<N>::T) pc_field_kernel(PcArgs a) {
     });
     degenerate = const_codes_degenerate<P::WAVES>(my_code, lane);
   }
-  // (needed by the persistent form only; -DMOF_K1_TAIL_BARRIER=0 drops it where a workgroup runs one patch: A/B in DESIGN 8)
-  if constexpr (PERSIST || MOF_K1_TAIL_BARRIER) __syncthreads();
+  // (only the persistent form needs it; the one-patch forms without it were never measured: docs/history/retired_switches.md)
+  __syncthreads();
   if (wave == 0)
     centroid_gate_store<N, PK>(best, wval, lane, a.max_px_speed_sq, a.out + 2 * (size_t)p, a.quality ? a.quality + 2 * (size_t)p : nullptr, degenerate,
                                degenerate ? *reinterpret_cast<const float*>(const_code + 16) : 0.f);
@@ -361,45 +350,10 @@ static hipError_t launch_n(const PcArgs& a_in, int n_pairs, hipStream_t stream) 
   }
 }
 
-// The quad-per-line formulation of pc_kernel_quad.hip (an evaluated alternative: a third of the LDS traffic, 35 % more
-// VALU instructions, 8 % slower on MI355X -- DESIGN.md section 4, K1) is NOT part of the product library: only the A/B
-// build `make quad` (-DMOF_WITH_QUAD -> csrc/ab/libmof_hip_quad.so, loaded through MOF_LIB_PATH) links it, and there
-// MOF_PC_QUAD=1 routes N = 64 to it.
-#ifdef MOF_WITH_QUAD
-static bool classic64() {
-  static const bool v = [] { const char* e = getenv("MOF_PC_QUAD"); return !(e && atoi(e) != 0); }();
-  return v;
-}
-#endif
-
-void pc_mfma_s1_fragments(uint32_t* out) {
-  // step s = (hi | lo, n1 half ks); lane l = (row r = l % 32 = (k1, re | im), h = l / 32); slot j = 2 q + (cur | prev), n1 = 8 ks + 4 h + q
-  for (int s = 0; s < 4; ++s)
-    for (int l = 0; l < 64; ++l)
-      for (int j = 0; j < 8; ++j) {
-        const int ks = s & 1, lo = s >> 1, r = l & 31, h = l >> 5, q = j >> 1, c = j & 1;
-        const int k1 = r >> 1, part = r & 1, n1 = 8 * ks + 4 * h + q, idx = (k1 * n1) & 15;
-        double cs, sn;
-        unit_root(idx, 16, &cs, &sn);
-        const float w = (float)(part == 0 ? (c == 0 ? cs : sn) : (c == 0 ? -sn : cs));
-        uint16_t hi, lw;
-        f16_split(w, &hi, &lw);
-        const uint16_t v = lo ? lw : hi;
-        uint32_t& d = out[(64 * s + l) * 4 + (j >> 1)];
-        d = (j & 1) ? (d & 0xffffu) | ((uint32_t)v << 16) : (d & 0xffff0000u) | v;
-      }
-}
-
 hipError_t pc_configure(int patch_size) {
   switch (patch_size) {
     case 32: return configure_n<32>();
-    case 64: {
-      hipError_t e = configure_n<64>();
-#ifdef MOF_WITH_QUAD
-      if (e == hipSuccess) e = pc_configure_quad64();
-#endif
-      return e;
-    }
+    case 64: return configure_n<64>();
     case 128: return configure_n<128>();
     case 120: return pc_configure_120();
     default: return hipErrorInvalidValue;
@@ -409,22 +363,11 @@ hipError_t pc_configure(int patch_size) {
 hipError_t launch_pc_field(const PcArgs& a, int patch_size, int n_pairs, hipStream_t stream) {
   switch (patch_size) {
     case 32: return launch_n<32>(a, n_pairs, stream);
-    case 64:
-#ifdef MOF_WITH_QUAD
-      if (!classic64()) return launch_pc_field_quad64(a, n_pairs, stream);
-#endif
-      return launch_n<64>(a, n_pairs, stream);
+    case 64: return launch_n<64>(a, n_pairs, stream);
     case 128: return launch_n<128>(a, n_pairs, stream);
     case 120: return launch_pc_field_120(a, n_pairs, stream);
     default: return hipErrorInvalidValue;
   }
-}
-
-const char* pc_kernel_variant(int patch_size) {
-#ifdef MOF_WITH_QUAD
-  if (patch_size == 64 && !classic64()) return "quad";
-#endif
-  return "stockham";
 }
 
 bool pc_patch_size_supported(int n) { return n == 32 || n == 64 || n == 128 || n == 120; }

@@ -182,7 +182,7 @@ class FftMethod:
 
     @property
     def kernel_variant(self) -> str:
-        """'stockham' or 'quad' (diagnostics, include/mof.h)."""
+        """'stockham', 'planned', 'planned-half' or 'planned-large' (diagnostics, include/mof.h)."""
         return self._lib.mof_fft_kernel_variant(self._h).decode()
 
     # -- reference surface --------------------------------------------------------------------

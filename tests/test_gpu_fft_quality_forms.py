@@ -163,22 +163,3 @@ def test_forced_pass_run_and_chunk_boundaries(gpu):
            pairs=[("passes-200", "planned-large"), ("ocl-passes-144", "planned-large"), ("padded-246", "planned-large")],
            videos=[("long-video-64", "own"), ("long-video-120", "pair"), ("long-video-128", "own"), ("long-video-200", "pair")])
 
-
-@pytest.mark.parametrize("target", ["mfma", "quad"])
-def test_ab_library_of_k1(gpu, target):
-    """The A/B libraries of K1 at 64 (`make mfma`; `make quad`, whose kernel MOF_PC_QUAD=1 selects there), loaded through MOF_LIB_PATH:
-    the 64-pixel batches and the long video; on the MFMA library, which is K1 with another first stage, the constant patches too.
-    The quad formulation (pc_kernel_quad.hip) never carried the constant-patch rule of pc_common.hpp -- it detects no constant patch,
-    so shift AND quality of one are the noise that rule exists to replace (its shift tests select no such pair either): the constant
-    answer is not part of what that library is held to, here or there. Skipped with a message where the library is not built, as
-    the shift tests of these libraries are. Evidence: kernel_variant 'quad' for the quad library; nothing exposes the MFMA stage.
-    The quad library also runs the six front-end forms of pc_quad64_kernel (gray, BGR8, long-range under both peak models)."""
-    lib = os.path.join(ROOT, "mrs_optic_flow_amd", "csrc", "ab", f"libmof_hip_{target}.so")
-    if not os.path.exists(lib):
-        pytest.skip(f"csrc/ab/libmof_hip_{target}.so not built (`make -C mrs_optic_flow_amd/csrc {target}`)")
-    pairs = [("circular-64", "stockham"), ("crops-64", "stockham"), ("grid-64", "stockham")]
-    if target == "quad":
-        _child({"MOF_LIB_PATH": lib, "MOF_PC_QUAD": "1"}, ROUTES, pairs=[(name, "quad") for name, _ in pairs], videos=[("long-video-64", "own")],
-               forms=_forms("quad", *(f"k1-64-{f}-{m}" for f in ("gray", "bgr", "lr") for m in ("cv", "ocl"))))
-    else:
-        _child({"MOF_LIB_PATH": lib}, f"{ROUTES} or (test_constant_and_zero_patches and 64)", pairs=pairs, videos=[("long-video-64", "own")])

@@ -1,6 +1,6 @@
-"""GPU tests of the kernel forms that are NOT the default route (A/B knobs and A/B libraries): each must pass the parity tests of
-the form it replaces -- remap ring / super-tile / staged forms, the MFMA first stage of K1. (Forms whose A/B is closed are not kept
-correct here: they leave the library, docs/history/retired_switches.md.)"""
+"""GPU tests of the kernel forms that are NOT the default route (A/B knobs): each must pass the parity tests of the form it
+replaces -- remap ring / super-tile / staged forms. (Forms whose A/B is closed are not kept correct here: they leave the library,
+docs/history/retired_switches.md.)"""
 import os
 import subprocess
 import sys
@@ -51,7 +51,6 @@ for res, M in ((480, 49.9), (256, 45.0)):
             hard += 1
 print("hard remap ok", hard)
 """
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.mark.parametrize("env", [{"MOF_SR_LP_RING": "16"}, {"MOF_SR_LP_SUPER": "0"}, {"MOF_SR_LP_STAGED": "0"}, {"MOF_SR_LP_GLOBAL": "1"}])
@@ -65,21 +64,3 @@ def test_remap_other_kernel_forms_are_byte_exact(gpu, env):
     assert r.returncode == 0 and "remap ok 36" in r.stdout, (env, r.stdout[-1500:], r.stderr[-1500:])
     assert "hard remap ok 104" in r.stdout, (env, r.stdout[-1500:], r.stderr[-1500:])
 
-
-def test_mfma_first_stage_variant_of_k1_passes_the_parity_tests(gpu):
-    """VERDICT r03 item 5: K1 (N = 64) with S1 of its forward transform on the matrix cores (pc_passes3.hpp, fwd3_rows_mfma;
-    f16 hi + lo split of the DFT-16 matrix, f32 accumulation) is an A/B library (`make mfma`), measured slower than the product
-    (profiles/r04_mfma_s1_ab.txt) and therefore not shipped -- but it has to stay correct for that comparison to mean anything:
-    a child process re-runs the N = 64 parity cases of test_gpu_fft.py on it."""
-    import subprocess
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    lib = os.path.join(root, "mrs_optic_flow_amd", "csrc", "ab", "libmof_hip_mfma.so")
-    if not os.path.exists(lib):
-        pytest.skip("csrc/ab/libmof_hip_mfma.so not built (`make -C mrs_optic_flow_amd/csrc mfma`)")
-    env = dict(os.environ, MOF_LIB_PATH=lib)
-    sel = "golden or seeded or ocl_peak or bgr or long_range or gating or circular or expected_variant"
-    out = subprocess.run([sys.executable, "-m", "pytest", os.path.join(root, "tests", "test_gpu_fft.py"), "-q", "-x", "-k", sel,
-                          "-p", "no:cacheprovider"], env=env, capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-2000:]
-    assert " passed" in out.stdout

@@ -4,13 +4,13 @@
 # MOF_LIB_PATH; the product library and its object files are never touched (ablation variants may compute wrong results
 # by design -- nothing of them can leak into a later build).
 #   usage (on the GPU box):  tools/ab_variants.sh <source.hip> "<bench args>" "<flags variant 0>" "<flags variant 1>" ...
-#   e.g. tools/ab_variants.sh pc_kernel.hip "--workload c2" "" "-DMOF_K1_TAIL_BARRIER=0"
+#   e.g. tools/ab_variants.sh pc_kernel.hip "--workload c2" "" "-DMY_NEW_SWITCH=1"   (a switch of the branch that carries the A/B)
 set -e
 R=${GRAFT_REPO_ROOT:-/root/repo}
 SRC=$1; BENCH_ARGS=$2; shift 2
 cd $R/mrs_optic_flow_amd/csrc
 BASE="-O3 -std=c++17 -fPIC -fno-slp-vectorize -Wno-unused-parameter -Wno-unused-function"
-OTHERS=$(ls *.hip | grep -v "^$SRC$" | grep -v "^pc_kernel_quad.hip$" | sed 's/\.hip$/.o/')
+OTHERS=$(ls *.hip | grep -v "^$SRC$" | sed 's/\.hip$/.o/')
 for o in $OTHERS; do [ -f $o ] || { echo "missing $o: build the product library first"; exit 1; }; done
 EXTRA=""; [ "$SRC" == "mof_geom.hip" ] && EXTRA="-ffp-contract=off"
 i=0

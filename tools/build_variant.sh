@@ -7,7 +7,7 @@ NAME=$1; SRC=$2; FLAGS=$3
 mkdir -p $R/tmp_ab
 cd $R/mrs_optic_flow_amd/csrc
 BASE="-O3 -std=c++17 -fPIC -fno-slp-vectorize -Wno-unused-parameter -Wno-unused-function"
-OTHERS=$(ls *.hip | grep -v "^pc_kernel_quad.hip$")
+OTHERS=$(ls *.hip)
 VAR=""
 for S in ${SRC//,/ }; do
   EXTRA=""; [ "$S" == "mof_geom.hip" ] && EXTRA="-ffp-contract=off"
