@@ -379,6 +379,40 @@ int mof_bm_process_batch_host(mof_bm_engine* e, const uint8_t* cur, size_t cur_s
                               size_t prev_stride, size_t pitch, int n_pairs, int8_t* dx, int8_t* dy, int8_t* mode);
 int mof_bm_sync(mof_bm_engine* e);
 
+/* Match quality per block and the match gate (no reference counterpart; the gate is off by default).
+ * quality[pair][by * grid_x + bx][3] = {min_sad, zero_sad, max_sad}, three uint32 per block: the SAD at the reported first minimum, the
+ * SAD at shift (0, 0) (abssum[r][r] of the low-contrast rule) and the largest SAD over the (2r + 1)^2 candidates -- the raw integers of
+ * the scan, exact as the shifts are; neither the low-contrast rule nor the gate alters them. n_invalid[pair] (int32): the blocks the gate
+ * rejected. Every new pointer may be null; the entries without _q are these with null pointers, and with the gate off they launch the
+ * kernels they always launched.
+ * The gate, mof_bm_set_gate(e, max_min_sad, min_sad_range): a block is VALID iff min_sad <= max_min_sad and max_sad - min_sad >=
+ * min_sad_range; the default (UINT32_MAX, 0) is off. Both thresholds are whole-block SADs: scale a per-pixel figure by block_size^2. While
+ * armed, on EVERY entry of the engine (stateful, batch device gray and BGR8, batch host, the sharded group), with or without quality
+ * pointers: an invalid block reports dx = dy = MOF_BM_INVALID (-128, outside every scan range since scan_radius <= 48) and casts no vote;
+ * the low-contrast rule is applied first, as always, and a block it zeroed still votes when it is valid; the six mode entries are the
+ * top three per axis of the valid blocks' histogram, and a pair without a valid block reports MOF_BM_INVALID in all six (mode[6..7] stay
+ * 0; the stateful entry's mode_xy is then (MOF_BM_INVALID, MOF_BM_INVALID) -- do not hand that to mof_bm_refine, which has no cut-out at
+ * such an offset). The frame chain (previous <- current) is untouched. The decision is made in the scan kernel from the integers the
+ * quality output holds; the engine owns no buffer for it, so block-matching batches still never pin.
+ * mof_bm_set_gate: MOF_ERR_BUSY (nothing changes) while a call is in flight. mof_bm_gate reads the pair back (either pointer may be
+ * null). mof_bm_refine is unchanged. */
+#define MOF_BM_INVALID (-128)
+int mof_bm_set_gate(mof_bm_engine* e, uint32_t max_min_sad, uint32_t min_sad_range);
+int mof_bm_gate(const mof_bm_engine* e, uint32_t* max_min_sad, uint32_t* min_sad_range);
+int mof_bm_process_q(mof_bm_engine* e, const uint8_t* frame, size_t pitch, int8_t* dx, int8_t* dy, int8_t* mode_xy, uint32_t* quality,
+                     int* n_invalid);
+int mof_bm_process_batch_device_q(mof_bm_engine* e, const uint8_t* d_cur, size_t cur_stride, const uint8_t* d_prev, size_t prev_stride,
+                                  size_t pitch, int n_pairs, int8_t* d_dx, int8_t* d_dy, int8_t* d_mode, uint32_t* d_quality,
+                                  int32_t* d_n_invalid, void* stream);
+int mof_bm_process_batch_device_bgr_q(mof_bm_engine* e, const uint8_t* d_cur, size_t cur_stride, const uint8_t* d_prev, size_t prev_stride,
+                                      size_t pitch, int n_pairs, int8_t* d_dx, int8_t* d_dy, int8_t* d_mode, uint32_t* d_quality,
+                                      int32_t* d_n_invalid, void* stream);
+int mof_bm_process_batch_host_q(mof_bm_engine* e, const uint8_t* cur, size_t cur_stride, const uint8_t* prev, size_t prev_stride,
+                                size_t pitch, int n_pairs, int8_t* dx, int8_t* dy, int8_t* mode, uint32_t* quality, int32_t* n_invalid);
+/* Diagnostics, no device needed: the launch shape of the block scan for a geometry, out4 = {1 if the 16 x 16 fast path, blocks per
+ * workgroup, threads, dynamic LDS bytes}; quality != 0: of the form that carries the quality outputs / the gate. grid_x = 0: any. */
+int mof_bm_scan_plan(int block_size, int step_size, int scan_radius, int grid_x, int quality, int* out4);
+
 /* The same group for the block matchers (BlockMethod / FastSpacedBMMethod): shard g runs mof_bm_process_batch_device on its
  * pairs, and the per-block shifts AND the per-pair histogram modes -- the pair FastSpacedBMMethod returns,
  * /root/reference/src/FastSpacedBMMethod_OCL.cpp:172-175 -- ride in ONE slab per rank ("BM mode vectors ride in the same slab",
@@ -401,6 +435,11 @@ int mof_shard_bm_process_batch_device(mof_shard_bm* g, const uint8_t* const* d_c
                                       const uint8_t* const* d_prev, size_t prev_stride, size_t pitch, int n_pairs,
                                       int8_t* const* d_out, int gather);
 int mof_shard_bm_sync(mof_shard_bm* g);
+/* mof_bm_set_gate on every engine of the group: all of them or none -- MOF_ERR_BUSY (nothing changes) if any engine has a call in flight.
+ * mof_shard_bm_gate: the group's pair. The slab layout does not change: gated blocks hold MOF_BM_INVALID in the dx / dy planes, the
+ * mode plane follows the rules above. The sharded entries have no quality or n_invalid outputs. */
+int mof_shard_bm_set_gate(mof_shard_bm* g, uint32_t max_min_sad, uint32_t min_sad_range);
+int mof_shard_bm_gate(const mof_shard_bm* g, uint32_t* max_min_sad, uint32_t* min_sad_range);
 
 /* ------------------------------------------------------------------------------------------ */
 /* Scale / rotation estimator (scaleRotationEstimator, BASELINE config c5)                    */

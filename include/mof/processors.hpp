@@ -264,6 +264,13 @@ class ShardedBlockMatcher {
                                                     d_out.data(), gather ? 1 : 0), "mof_shard_bm_process_batch_device");
   }
   void sync() { detail::check(mof_shard_bm_sync(group_), "mof_shard_bm_sync"); }
+  // The match gate on every engine of the group, all of them or none (BlockMatcherBase::setGate); the slab keeps its layout
+  void setGate(uint32_t max_min_sad, uint32_t min_sad_range) {
+    detail::check(mof_shard_bm_set_gate(group_, max_min_sad, min_sad_range), "mof_shard_bm_set_gate");
+  }
+  void gate(uint32_t* max_min_sad, uint32_t* min_sad_range) const {
+    detail::check(mof_shard_bm_gate(group_, max_min_sad, min_sad_range), "mof_shard_bm_gate");
+  }
   void initGather() { detail::check(mof_shard_bm_init_gather(group_), "mof_shard_bm_init_gather"); }
   bool gatherReady() const { return mof_shard_bm_gather_ready(group_) != 0; }
 
@@ -271,6 +278,12 @@ class ShardedBlockMatcher {
   mof_bm_config cfg_{};
   mof_shard_bm* group_ = nullptr;
 };
+
+// The three raw SADs of one block's scan (include/mof.h): at the reported first minimum, at shift (0, 0), the largest of the scan
+struct BlockQuality {
+  uint32_t min_sad, zero_sad, max_sad;
+};
+static_assert(sizeof(BlockQuality) == 3 * sizeof(uint32_t), "BlockQuality is the ABI's three uint32");
 
 // Integer stage of both block matchers behind one engine.
 class BlockMatcherBase {
@@ -287,25 +300,43 @@ class BlockMatcherBase {
   const std::vector<int8_t>& flowX() const { return dx_; }
   const std::vector<int8_t>& flowY() const { return dy_; }
   const mof_bm_config& config() const { return cfg_; }
+  // The match gate (no reference counterpart; off by default = (UINT32_MAX, 0)): a block is valid iff min_sad <= max_min_sad and
+  // max_sad - min_sad >= min_sad_range, whole-block SADs. An invalid block reports MOF_BM_INVALID in flowX / flowY and casts no vote;
+  // a frame without a valid block has the mode (MOF_BM_INVALID, MOF_BM_INVALID) and processImage returns no vector.
+  void setGate(uint32_t max_min_sad, uint32_t min_sad_range) { detail::check(mof_bm_set_gate(engine_, max_min_sad, min_sad_range), "mof_bm_set_gate"); }
+  void gate(uint32_t* max_min_sad, uint32_t* min_sad_range) const { detail::check(mof_bm_gate(engine_, max_min_sad, min_sad_range), "mof_bm_gate"); }
+  // per-block quality and the gated-block count of the last processImage call
+  const std::vector<BlockQuality>& lastQuality() const { return quality_; }
+  int invalidBlocks() const { return n_invalid_; }
+  // mof_bm_process_batch_device_q: device pointers, asynchronous on `stream`; d_quality (3 uint32 per block) and d_n_invalid may be null
+  void processBatchDeviceQ(const uint8_t* d_cur, size_t cur_stride, const uint8_t* d_prev, size_t prev_stride, size_t pitch, int n_pairs,
+                           int8_t* d_dx, int8_t* d_dy, int8_t* d_mode, uint32_t* d_quality, int32_t* d_n_invalid, void* stream) {
+    detail::check(mof_bm_process_batch_device_q(engine_, d_cur, cur_stride, d_prev, prev_stride, pitch, n_pairs, d_dx, d_dy, d_mode, d_quality,
+                                                d_n_invalid, stream), "mof_bm_process_batch_device_q");
+  }
 
  protected:
   explicit BlockMatcherBase(const mof_bm_config& cfg) : cfg_(cfg) {
     detail::check(mof_bm_create(&cfg_, &engine_), "mof_bm_create");
     dx_.resize((size_t)cfg_.grid_x * cfg_.grid_y);
     dy_.resize(dx_.size());
+    quality_.resize(dx_.size());
   }
   // returns false when the engine was busy
   bool run(ImageView im, int8_t mode[2]) {
     if (im.rows != cfg_.frame_height || im.cols != cfg_.frame_width)
       throw std::runtime_error("processImage: frame size does not match the engine geometry");
-    const int rc = mof_bm_process(engine_, im.data, im.step, dx_.data(), dy_.data(), mode);
+    const int rc = mof_bm_process_q(engine_, im.data, im.step, dx_.data(), dy_.data(), mode, reinterpret_cast<uint32_t*>(quality_.data()),
+                                    &n_invalid_);
     if (rc == MOF_ERR_BUSY) return false;
-    detail::check(rc, "mof_bm_process");
+    detail::check(rc, "mof_bm_process_q");
     return true;
   }
   mof_bm_config cfg_{};
   mof_bm_engine* engine_ = nullptr;
   std::vector<int8_t> dx_, dy_;
+  std::vector<BlockQuality> quality_;
+  int n_invalid_ = 0;
 };
 
 class BlockMethod : public BlockMatcherBase {
@@ -324,6 +355,7 @@ class BlockMethod : public BlockMatcherBase {
     int8_t mode[2] = {0, 0};
     if (!run(imCurr, mode)) return {};
     mode_ = Point2i{mode[0], mode[1]};
+    if (mode[0] == MOF_BM_INVALID) return {};  // the gate left no valid block (Refine has no cut-out at such an offset)
     if (refine_ == kNoRefine) return {Point2d{(double)mode[0], (double)mode[1]}};
     double r[2] = {0, 0};
     detail::check(mof_bm_refine(engine_, mode[0], mode[1], 2, refine_ == kFaithful ? 1 : 0, r), "mof_bm_refine");
@@ -354,6 +386,7 @@ class FastSpacedBMMethod : public BlockMatcherBase {
                                     double /*yaw_angle*/, Point2d /*tiltCorr*/) {
     int8_t mode[2] = {0, 0};
     if (!run(imCurr, mode)) return {};
+    if (mode[0] == MOF_BM_INVALID) return {};  // the gate left no valid block
     return {Point2f{(float)mode[0], (float)mode[1]}};
   }
 

@@ -22,6 +22,7 @@ MOF_ERR_NOT_INIT = -4
 MOF_ERR_UNSUPPORTED = -5
 MOF_ERR_NO_DEVICE = -6
 MOF_ERR_NO_MEMORY = -7
+MOF_BM_INVALID = -128  # dx / dy / mode of a block (a pair) the match gate rejected
 
 
 class MofLibraryError(RuntimeError):
@@ -135,6 +136,15 @@ SYMBOLS = {
     "mof_bm_process_batch_device_bgr": (_I, [_VP, _VP, _SZ, _VP, _SZ, _SZ, _I, _VP, _VP, _VP, _VP]),
     "mof_bm_process_batch_host": (_I, [_VP, _VP, _SZ, _VP, _SZ, _SZ, _I, _VP, _VP, _VP]),
     "mof_bm_sync": (_I, [_VP]),
+    "mof_bm_set_gate": (_I, [_VP, C.c_uint32, C.c_uint32]),
+    "mof_bm_gate": (_I, [_VP, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "mof_bm_process_q": (_I, [_VP, _VP, _SZ, _VP, _VP, _VP, _VP, C.POINTER(_I)]),
+    "mof_bm_process_batch_device_q": (_I, [_VP, _VP, _SZ, _VP, _SZ, _SZ, _I, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "mof_bm_process_batch_device_bgr_q": (_I, [_VP, _VP, _SZ, _VP, _SZ, _SZ, _I, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "mof_bm_process_batch_host_q": (_I, [_VP, _VP, _SZ, _VP, _SZ, _SZ, _I, _VP, _VP, _VP, _VP, _VP]),
+    "mof_bm_scan_plan": (_I, [_I, _I, _I, _I, _I, C.POINTER(_I)]),
+    "mof_shard_bm_set_gate": (_I, [_VP, C.c_uint32, C.c_uint32]),
+    "mof_shard_bm_gate": (_I, [_VP, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "mof_sr_create": (_I, [C.POINTER(SrConfig), C.POINTER(_VP)]),
     "mof_sr_destroy": (None, [_VP]),
     "mof_sr_reset": (_I, [_VP]),

@@ -10,6 +10,9 @@
 //    differences per lane-op, exact integer arithmetic). Packed u16 partial sums are widened to u32 every <=256
 //    pixels so no block size can overflow. The arg-min (first occurrence in row-major order) is a 64-bit LDS
 //    atomic min over (sad, index) keys.
+// Both have a compile-time Q form (launch_bm_scan picks it iff a quality pointer was given or the match gate is armed): a running maximum
+// beside the arg-min, the three raw SADs {min, zero, max} per block, and BM_INVALID in dx / dy for a block that fails the gate -- decided
+// in the lane that finishes the block, from a second kernel argument. Q = false is the kernel without any of it.
 //
 // Replaces
 //   BlockMethod::processImage's scan          /root/reference/src/BlockMethod.cpp:43-66
@@ -55,6 +58,22 @@ __device__ __forceinline__ void static_for(F&& f) {
   }
 }
 
+// The Q forms' second kernel argument: BmQArgs for Q = true, nothing for Q = false (whose kernarg layout and code stay as they were)
+struct BmNoQ {};
+template <bool Q>
+using BmQ = std::conditional_t<Q, BmQArgs, BmNoQ>;
+
+// a finished block's outputs in the Q form: the three raw SADs when asked for, the match gate
+__device__ __forceinline__ bool bm_finish_q(const BmQArgs& q, size_t o, uint32_t min_sad, uint32_t zero_sad, uint32_t max_sad) {
+  if (q.quality) {
+    uint32_t* out = q.quality + 3 * o;
+    out[0] = min_sad;
+    out[1] = zero_sad;
+    out[2] = max_sad;
+  }
+  return min_sad <= q.max_min_sad && max_sad - min_sad >= q.min_sad_range;  // the default (UINT32_MAX, 0) passes every block
+}
+
 }  // namespace
 
 // LDS layout per block slot (dwords): window rows [WW][WPD], current block [sps][sps/4]; then per slot one 64-bit
@@ -68,11 +87,18 @@ __device__ __forceinline__ void static_for(F&& f) {
 // five address / move VALU instructions per v_qsad (24 of every 40 issue cycles) and sat at 38-41 % of the ceiling.
 // Exact i / d for i * d < 2^32 with m = ceil(2^32 / d), m = 0 standing for d = 1 (the staging loops index at most
 // 40 K dwords).
+// Q = true (quality outputs and / or the match gate, launch_bm_scan): a running maximum beside the arg-min, taken on the widened acc[][]
+// (the packed partial sums pass 2^16 at large blocks) and only over x-shifts < D (the padded ones are sums of LDS dwords nobody wrote);
+// the per-block maximum is an LDS atomicMax in one more dword per slot behind `centre`. Those 4 * bpw bytes are not in the plan's
+// 12 * bpw: bm_plan_q takes one block fewer per workgroup where they would pass the 160 KB. A host sweep of every supported
+// (block, radius) at grid_x = 0 .. 64 finds no geometry whose searched plan reaches that case, and four under a knob: block 100 /
+// radius 4 with MOF_BM_XB=2 at grid_x = 7, 13, 14, 28 (7 blocks in 163 828 bytes; tests/test_bm_quality_host.py holds the arithmetic,
+// test_gpu_bm_quality.py runs it). The smaller plan is also there because grid_x has no upper limit.
 __device__ __forceinline__ uint32_t fast_div(uint32_t i, uint32_t m) { return m ? __umulhi(i, m) : i; }
 __device__ __forceinline__ uint32_t div_magic(uint32_t d) { return d == 1 ? 0u : (uint32_t)((0x100000000ull + d - 1) / d); }
 
-template <int XB, int G>
-__global__ void __launch_bounds__(BM_THREADS_MAX) bm_scan_kernel(BmArgs a, int bpw, int groups_per_row, int WPD, int slot_dwords) {
+template <int XB, int G, bool Q>
+__global__ void __launch_bounds__(BM_THREADS_MAX) bm_scan_kernel(BmArgs a, int bpw, int groups_per_row, int WPD, int slot_dwords, BmQ<Q> q) {
   extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
   const int tid = threadIdx.x, nthreads = blockDim.x;
   const int r = a.radius, sps = a.block, S = a.block + a.step, D = 2 * r + 1;
@@ -82,6 +108,7 @@ __global__ void __launch_bounds__(BM_THREADS_MAX) bm_scan_kernel(BmArgs a, int b
   const int CPD = sps / 4;              // current-block row pitch in dwords
   unsigned long long* keys = reinterpret_cast<unsigned long long*>(lds + (size_t)bpw * slot_dwords);  // slot_dwords is even
   uint32_t* centre = reinterpret_cast<uint32_t*>(keys + bpw);
+  [[maybe_unused]] uint32_t* maxs = centre + bpw;  // Q only
 
   const int blocks = a.grid_x * a.grid_y;
   const int grp = blockIdx.x % groups_per_row;
@@ -124,7 +151,10 @@ __global__ void __launch_bounds__(BM_THREADS_MAX) bm_scan_kernel(BmArgs a, int b
     stage(prev0, WW, WW, WPD, 0);
     stage(cur0, sps, sps, CPD, win_dwords);
   }
-  if (tid < nb) keys[tid] = ~0ull;
+  if (tid < nb) {
+    keys[tid] = ~0ull;
+    if constexpr (Q) maxs[tid] = 0u;
+  }
   __syncthreads();
 
   // ---- SAD scan: item = (slot, ys, lane group) -> x-shifts 4 (xl XB) .. 4 (xl XB + XB) - 1 of block bx0 + slot at ys
@@ -141,7 +171,7 @@ __global__ void __launch_bounds__(BM_THREADS_MAX) bm_scan_kernel(BmArgs a, int b
 #pragma unroll
     for (int k = 0; k < XB; ++k)
 #pragma unroll
-      for (int q = 0; q < 4; ++q) acc[k][q] = 0u;
+      for (int f = 0; f < 4; ++f) acc[k][f] = 0u;
     for (int j0 = 0; j0 < sps; j0 += rows_per_flush) {
       uint64_t pk[XB];
 #pragma unroll
@@ -202,18 +232,21 @@ __global__ void __launch_bounds__(BM_THREADS_MAX) bm_scan_kernel(BmArgs a, int b
     }
     // arg-min, first occurrence in row-major order (BlockMethod.cpp:63; .cl:50-56, :66-73): min over (sad, index) keys
     unsigned long long best = ~0ull;
+    [[maybe_unused]] uint32_t worst = 0u;
 #pragma unroll
     for (int k = 0; k < XB; ++k)
 #pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int xs = 4 * (xg0 + k) + q;
+      for (int f = 0; f < 4; ++f) {
+        const int xs = 4 * (xg0 + k) + f;
         if (xs < D) {
-          const unsigned long long key = ((unsigned long long)acc[k][q] << 32) | (uint32_t)(ys * D + xs);
+          const unsigned long long key = ((unsigned long long)acc[k][f] << 32) | (uint32_t)(ys * D + xs);
           best = key < best ? key : best;
-          if (ys == r && xs == r) centre[s] = acc[k][q];  // SAD(0, 0), FastSpacedBMMethod.cl:77
+          if constexpr (Q) worst = acc[k][f] > worst ? acc[k][f] : worst;
+          if (ys == r && xs == r) centre[s] = acc[k][f];  // SAD(0, 0), FastSpacedBMMethod.cl:77
         }
       }
     atomicMin(&keys[s], best);
+    if constexpr (Q) atomicMax(&maxs[s], worst);
   }
   __syncthreads();
   if (tid < nb) {
@@ -229,6 +262,9 @@ __global__ void __launch_bounds__(BM_THREADS_MAX) bm_scan_kernel(BmArgs a, int b
       }
     }
     const size_t o = (size_t)pair * blocks + (size_t)by * a.grid_x + bx0 + tid;
+    if constexpr (Q) {
+      if (!bm_finish_q(q, o, best_sad, centre[tid], maxs[tid])) mx = my = BM_INVALID + r;
+    }
     a.dx[o] = (int8_t)(mx - r);
     a.dy[o] = (int8_t)(my - r);
   }
@@ -268,6 +304,49 @@ __global__ void __launch_bounds__(256) bm_mode_kernel(BmArgs a) {
   }
 }
 
+// K3 behind the Q scans: the same histogram and the same top-3 over the VALID blocks only (a gated block holds BM_INVALID in dx and dy and
+// casts no vote); n_invalid[pair] = the gated blocks when asked for; a pair without a valid block reports BM_INVALID in all six entries.
+// Without a gated block this writes bm_mode_kernel's bytes.
+__global__ void __launch_bounds__(256) bm_mode_gated_kernel(BmArgs a, int32_t* __restrict__ n_invalid) {
+  __shared__ int hist[2][128];
+  __shared__ int gated;
+  const int tid = threadIdx.x;
+  const int pair = blockIdx.x;
+  const int blocks = a.grid_x * a.grid_y;
+  const int r = a.radius, D = 2 * r + 1;
+  if (tid < 128) {
+    hist[0][tid] = 0;
+    hist[1][tid] = 0;
+  }
+  if (tid == 0) gated = 0;
+  __syncthreads();
+  const int8_t* dx = a.dx + (size_t)pair * blocks;
+  const int8_t* dy = a.dy + (size_t)pair * blocks;
+  for (int i = tid; i < blocks; i += 256) {
+    const int x = dx[i], y = dy[i];
+    if (x == BM_INVALID || y == BM_INVALID) {
+      atomicAdd(&gated, 1);
+    } else {
+      atomicAdd(&hist[0][x + r], 1);
+      atomicAdd(&hist[1][y + r], 1);
+    }
+  }
+  __syncthreads();
+  const int n_gated = gated;
+  if (tid == 0 && n_invalid) n_invalid[pair] = n_gated;
+  if (tid < 2) {
+    int* h = hist[tid];
+    int8_t* out = a.mode + (size_t)pair * 8;
+    for (int rank = 0; rank < 3; ++rank) {
+      int bi = -1;
+      for (int i = 0; i < D; ++i)
+        if (h[i] >= 0 && (bi < 0 || h[i] > h[bi])) bi = i;
+      out[2 * rank + tid] = n_gated == blocks ? (int8_t)BM_INVALID : (bi >= 0) ? (int8_t)(bi - r) : (int8_t)0;
+      if (bi >= 0) h[bi] = -1;  // taken
+    }
+    out[6 + tid] = 0;
+  }
+}
 
 // ------------------------------------------------------------------------------------------------
 // K2 fast path: 16x16 blocks, one workgroup per ROW of blocks, one lane per (block, group of 4
@@ -277,9 +356,19 @@ __global__ void __launch_bounds__(256) bm_mode_kernel(BmArgs a) {
 // block-row) pairs x 4 v_qsad_pk_u16_u8. LDS traffic drops to 5 dwords per 64 SAD instructions and the
 // VALU stream is >80 % v_qsad. The strip of the previous frame shared by the whole block row is staged
 // in LDS once (windows of neighbouring blocks overlap by 50 %).
+// Q = true: the four sums of a completed y-shift also feed a running packed maximum (two v_pk_max_u16: UNSIGNED 16-bit fields, a sum
+// reaches 255 * 256 = 65280), the last x-shift's v_sad_u8 sums a scalar one; the block's lanes meet in a second 64-entry LDS array.
 // ------------------------------------------------------------------------------------------------
-template <int R>
-__global__ void __launch_bounds__(64) bm_scan16_kernel(BmArgs a, int strip_dwords, int bpw, int waves_per_row) {
+// (as an instruction, not as a vector umax: the compiler rebalances the chain of 2R + 1 maxima into a tree and keeps the completed
+// accumulators alive for it -- 134 / 142 / 150 VGPRs at R = 12 / 14 / 16 where this form stays at the Q = false kernels' 126)
+__device__ __forceinline__ uint32_t pk_max_u16(uint32_t x, uint32_t y) {
+  uint32_t r;
+  asm("v_pk_max_u16 %0, %1, %2" : "=v"(r) : "v"(x), "v"(y));
+  return r;
+}
+
+template <int R, bool Q>
+__global__ void __launch_bounds__(64) bm_scan16_kernel(BmArgs a, int strip_dwords, int bpw, int waves_per_row, BmQ<Q> q) {
   // ONE wave per workgroup: `bpw` consecutive blocks of one block row; no workgroup barrier anywhere.
   // 2R+1 = 4*(R/2) + 1 x-shifts: R/2 lanes per block take four each through v_qsad, the last x-shift (2R) is
   // shared out over the same lanes by y-shift and done with v_sad_u8 (same 1 byte-difference / lane / cycle rate)
@@ -296,6 +385,7 @@ __global__ void __launch_bounds__(64) bm_scan16_kernel(BmArgs a, int strip_dword
   const int nb = (gx - b0 < bpw) ? gx - b0 : bpw;        // blocks of this wave (>= 1)
   uint32_t* strip = lds;                                 // [WW][strip_dwords]
   uint32_t* keys = strip + WW * strip_dwords;            // [64]
+  [[maybe_unused]] uint32_t* maxs = keys + 64;           // [64], Q only
   const int CH = a.channels;  // 3: BGR8 frames, gray conversion inside the loads
   const uint8_t* prev = a.prev + (size_t)pair * a.prev_stride + (size_t)(by * S) * a.pitch + (size_t)(b0 * S) * CH;
   const uint8_t* cur = a.cur + (size_t)pair * a.cur_stride + (size_t)(by * S + R) * a.pitch + (size_t)(R + b0 * S) * CH;
@@ -373,6 +463,7 @@ __global__ void __launch_bounds__(64) bm_scan16_kernel(BmArgs a, int strip_dword
   // complete once window row ys + 15 has been consumed: it is folded into the running first-minimum key
   // ((sad << 16) | row-major index) right away, so at most 16 accumulators are live.
   uint32_t kmin = 0xffffffffu, centre = 0;
+  [[maybe_unused]] uint32_t pmax = 0u, smax = 0u;  // Q: packed maximum of the v_qsad sums, maximum of the last x-shift's
   static_for<0, WW>([&](auto wy_c) {
     constexpr int wy = decltype(wy_c)::value;
     uint32_t w[5];
@@ -397,6 +488,7 @@ __global__ void __launch_bounds__(64) bm_scan16_kernel(BmArgs a, int strip_dword
       uint32_t k2 = (hi << 16) | (idx0 + 2u);
       uint32_t k3 = (hi & 0xffff0000u) | (idx0 + 3u);
       kmin = min(kmin, min(min(k0, k1), min(k2, k3)));
+      if constexpr (Q) pmax = pk_max_u16(pmax, pk_max_u16(lo, hi));
       if constexpr (done == R) centre = (uint32_t)(acc[R] >> (16 * (R % 4))) & 0xffffu;
     }
     // keep the scheduler from hoisting every row's LDS reads to the top (it would spill ~130 VGPRs)
@@ -414,10 +506,12 @@ __global__ void __launch_bounds__(64) bm_scan16_kernel(BmArgs a, int strip_dword
     }
     const uint32_t key = (acc1 << 16) | (uint32_t)(ys * D + 2 * R);
     kmin = min(kmin, key);
+    if constexpr (Q) smax = max(smax, acc1);
   }
 
   // ---- per block: first minimum over its XG lanes (wave-local through LDS), low-contrast rule, store
   keys[lane] = kmin;
+  if constexpr (Q) maxs[lane] = max(smax, max(pmax & 0xffffu, pmax >> 16));
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -433,6 +527,12 @@ __global__ void __launch_bounds__(64) bm_scan16_kernel(BmArgs a, int strip_dword
       my = R;
     }
     const size_t o = (size_t)pair * (gx * a.grid_y) + (size_t)by * gx + b0 + b;
+    if constexpr (Q) {
+      uint32_t worst = 0u;
+#pragma unroll
+      for (int i = 0; i < XG; ++i) worst = max(worst, maxs[b * XG + i]);
+      if (!bm_finish_q(q, o, (uint32_t)best, centre, worst)) mx = my = BM_INVALID + R;
+    }
     a.dx[o] = (int8_t)(mx - R);
     a.dy[o] = (int8_t)(my - R);
   }
@@ -450,13 +550,25 @@ static void scan16_plan(const BmArgs& a, int* bpw, int* waves_per_row, int* stri
   *lds = sizeof(uint32_t) * ((size_t)WW * *strip_dwords + 64);
 }
 
+constexpr size_t SCAN16_Q_LDS = 64 * sizeof(uint32_t);  // the Q form's second reduce array
+
 template <int R>
-static hipError_t launch_scan16(const BmArgs& a, int n_pairs, hipStream_t stream) {
+static hipError_t launch_scan16(const BmArgs& a, const BmQArgs* q, int n_pairs, hipStream_t stream) {
   int bpw, wpr, sd;
   size_t lds;
   scan16_plan<R>(a, &bpw, &wpr, &sd, &lds);
   if (lds > 64 * 1024) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(bm_scan16_kernel<R>, dim3((unsigned)n_pairs * a.grid_y * wpr), dim3(64), lds, stream, a, sd, bpw, wpr);
+  const dim3 grid((unsigned)n_pairs * a.grid_y * wpr);
+  if (q) {
+    lds += SCAN16_Q_LDS;
+    if (lds > 64 * 1024) {
+      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&bm_scan16_kernel<R, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL((bm_scan16_kernel<R, true>), grid, dim3(64), lds, stream, a, sd, bpw, wpr, *q);
+  } else {
+    hipLaunchKernelGGL((bm_scan16_kernel<R, false>), grid, dim3(64), lds, stream, a, sd, bpw, wpr, BmNoQ{});
+  }
   return hipGetLastError();
 }
 
@@ -655,36 +767,61 @@ bool bm_config_supported(int block, int radius) {
   return block >= 4 && block <= 128 && (block % 4) == 0 && radius >= 1 && radius <= 48 && bm_plan(block, radius, 0).xb > 0;
 }
 
-template <int XB, int G>
-static hipError_t launch_bm_generic(const BmArgs& a, int n_pairs, const BmPlan& p, hipStream_t stream) {
+// The Q form's plan: the searched plan with 4 more bytes per slot (the per-block maximum), one block fewer per workgroup where that would
+// pass the LDS (bpw = 1 always fits: a slot is a multiple of 8 bytes, so 8 k + 12 <= 160 KB implies 8 k + 16 <= 160 KB).
+static BmPlan bm_plan_q(BmPlan p, int radius) {
+  if (p.xb == 0) return p;
+  if (p.lds + 4 * (size_t)p.bpw > BM_LDS_MAX && p.bpw > 1) {
+    const int D = 2 * radius + 1, XGL = ((D + 3) / 4 + p.xb - 1) / p.xb;
+    --p.bpw;
+    p.threads = ((p.bpw * D * XGL + 63) / 64) * 64;
+  }
+  p.lds = sizeof(uint32_t) * (size_t)p.bpw * p.slot_dwords + 16 * (size_t)p.bpw;
+  return p;
+}
+
+template <int XB, int G, bool Q>
+static hipError_t launch_bm_generic(const BmArgs& a, BmQ<Q> q, int n_pairs, const BmPlan& p, hipStream_t stream) {
   if (p.lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&bm_scan_kernel<XB, G>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&bm_scan_kernel<XB, G, Q>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
     if (e != hipSuccess) return e;
   }
   const int groups_per_row = (a.grid_x + p.bpw - 1) / p.bpw;
   const unsigned wgs = (unsigned)n_pairs * (unsigned)(groups_per_row * a.grid_y);
-  hipLaunchKernelGGL((bm_scan_kernel<XB, G>), dim3(wgs), dim3(p.threads), p.lds, stream, a, p.bpw, groups_per_row, p.wpd, p.slot_dwords);
+  hipLaunchKernelGGL((bm_scan_kernel<XB, G, Q>), dim3(wgs), dim3(p.threads), p.lds, stream, a, p.bpw, groups_per_row, p.wpd, p.slot_dwords, q);
   return hipGetLastError();
 }
 
-template <int XB>
-static hipError_t launch_bm_generic_g(const BmArgs& a, int n_pairs, const BmPlan& p, hipStream_t stream) {
+template <int XB, bool Q>
+static hipError_t launch_bm_generic_g(const BmArgs& a, BmQ<Q> q, int n_pairs, const BmPlan& p, hipStream_t stream) {
   switch (p.g) {
-    case 6: return launch_bm_generic<XB, 6>(a, n_pairs, p, stream);
-    case 7: return launch_bm_generic<XB, 7>(a, n_pairs, p, stream);
-    case 10: return launch_bm_generic<XB, 10>(a, n_pairs, p, stream);
-    default: return launch_bm_generic<XB, 8>(a, n_pairs, p, stream);
+    case 6: return launch_bm_generic<XB, 6, Q>(a, q, n_pairs, p, stream);
+    case 7: return launch_bm_generic<XB, 7, Q>(a, q, n_pairs, p, stream);
+    case 10: return launch_bm_generic<XB, 10, Q>(a, q, n_pairs, p, stream);
+    default: return launch_bm_generic<XB, 8, Q>(a, q, n_pairs, p, stream);
   }
 }
 
-hipError_t launch_bm_scan(const BmArgs& a, int n_pairs, hipStream_t stream) {
+template <bool Q>
+static hipError_t launch_bm_generic_xb(const BmArgs& a, BmQ<Q> q, int n_pairs, const BmPlan& p, hipStream_t stream) {
+  switch (p.xb) {
+    case 1: return launch_bm_generic_g<1, Q>(a, q, n_pairs, p, stream);
+    case 2: return launch_bm_generic_g<2, Q>(a, q, n_pairs, p, stream);
+    default: return launch_bm_generic_g<3, Q>(a, q, n_pairs, p, stream);
+  }
+}
+
+// Q form iff a quality pointer was given or the gate is armed; with neither, the launch of the engine without them
+hipError_t launch_bm_scan(const BmArgs& a, const BmQArgs& qa, int n_pairs, hipStream_t stream) {
+  const bool Q = qa.quality != nullptr || bm_gate_armed(qa);
   if (fast16_ok(a) && !getenv("MOF_BM_GENERIC")) {
     hipError_t err = hipErrorInvalidValue;
-    scan16_dispatch(a.radius, [&](auto r) { err = launch_scan16<decltype(r)::value>(a, n_pairs, stream); });
+    scan16_dispatch(a.radius, [&](auto r) { err = launch_scan16<decltype(r)::value>(a, Q ? &qa : nullptr, n_pairs, stream); });
     return err;
   }
   BmPlan p = bm_plan(a.block, a.radius, a.grid_x);
   if (p.xb == 0) return hipErrorInvalidValue;
+  if (Q) p = bm_plan_q(p, a.radius);
   // row chunk: the length in {10, 8, 6, 7} that leaves the shortest ragged tail, longer on ties
   const int CPD = a.block / 4, cand[4] = {10, 8, 6, 7};
   int best_tail = 1 << 30;
@@ -696,15 +833,33 @@ hipError_t launch_bm_scan(const BmArgs& a, int n_pairs, hipStream_t stream) {
   if (const int fg = bm_env_int("MOF_BM_G")) p.g = fg;
   if (getenv("MOF_BM_VERBOSE"))
     fprintf(stderr, "mof: block scan plan xb %d g %d bpw %d wpd %d threads %d lds %zu cost %.1f\n", p.xb, p.g, p.bpw, p.wpd, p.threads, p.lds, p.cost);
-  switch (p.xb) {
-    case 1: return launch_bm_generic_g<1>(a, n_pairs, p, stream);
-    case 2: return launch_bm_generic_g<2>(a, n_pairs, p, stream);
-    default: return launch_bm_generic_g<3>(a, n_pairs, p, stream);
-  }
+  return Q ? launch_bm_generic_xb<true>(a, qa, n_pairs, p, stream) : launch_bm_generic_xb<false>(a, BmNoQ{}, n_pairs, p, stream);
 }
 
-hipError_t launch_bm_mode(const BmArgs& a, int n_pairs, hipStream_t stream) {
-  hipLaunchKernelGGL(bm_mode_kernel, dim3((unsigned)n_pairs), dim3(256), 0, stream, a);
+// the launch shape launch_bm_scan would use, without a device (host tests of the LDS arithmetic): {scan16, blocks per workgroup, threads, LDS bytes}
+bool bm_scan_plan(int block, int step, int radius, int grid_x, bool quality, int out[4]) {
+  BmArgs a{};
+  a.block = block, a.step = step, a.radius = radius, a.grid_x = grid_x, a.grid_y = 1;
+  if (grid_x > 0 && fast16_ok(a) && !getenv("MOF_BM_GENERIC")) {
+    int bpw = 0, wpr = 0, sd = 0;
+    size_t lds = 0;
+    scan16_dispatch(radius, [&](auto r) { scan16_plan<decltype(r)::value>(a, &bpw, &wpr, &sd, &lds); });
+    out[0] = 1, out[1] = bpw, out[2] = 64, out[3] = (int)(lds + (quality ? SCAN16_Q_LDS : 0));
+    return true;
+  }
+  BmPlan p = bm_plan_search(block, radius, grid_x);
+  if (p.xb == 0) return false;
+  if (quality) p = bm_plan_q(p, radius);
+  out[0] = 0, out[1] = p.bpw, out[2] = p.threads, out[3] = (int)p.lds;
+  return true;
+}
+
+// the gated kernel whenever the gate is armed or the count is asked for
+hipError_t launch_bm_mode(const BmArgs& a, const BmQArgs& qa, int32_t* n_invalid, int n_pairs, hipStream_t stream) {
+  if (bm_gate_armed(qa) || n_invalid)
+    hipLaunchKernelGGL(bm_mode_gated_kernel, dim3((unsigned)n_pairs), dim3(256), 0, stream, a, n_invalid);
+  else
+    hipLaunchKernelGGL(bm_mode_kernel, dim3((unsigned)n_pairs), dim3(256), 0, stream, a);
   return hipGetLastError();
 }
 

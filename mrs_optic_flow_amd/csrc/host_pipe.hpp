@@ -34,9 +34,9 @@ inline bool host_pointer_is_pinned(const void* p) {
 
 class HostPipe {
  public:
-  static constexpr int SLOTS = 3, MAX_OUTS = 3;
+  static constexpr int SLOTS = 3, MAX_OUTS = 5;
   struct Out {
-    void* user = nullptr;       // host destination of the whole batch
+    void* user = nullptr;       // host destination of the whole batch; null (pair form only): an optional output nobody asked for, not read back
     size_t bytes_per_pair = 0;
   };
   struct Chunk {  // what the engine's device entry is called with
@@ -102,7 +102,7 @@ class HostPipe {
       rc = run(ch, compute);
       if (rc != 0) break;
       for (int i = 0; i < n_outs_ && *err == hipSuccess; ++i)
-        *err = hipMemcpyAsync(s.h_out[i], s.d_out[i], out_bpp_[i] * (size_t)c, hipMemcpyDeviceToHost, compute);
+        if (outs[i].user) *err = hipMemcpyAsync(s.h_out[i], s.d_out[i], out_bpp_[i] * (size_t)c, hipMemcpyDeviceToHost, compute);
       if (*err == hipSuccess) *err = hipEventRecord(s.done, compute);
       if (*err != hipSuccess) { rc = -1; break; }
       s.first = k0;
@@ -256,13 +256,14 @@ class HostPipe {
     s.busy = false;
     if (e != hipSuccess) return e;
     for (int i = 0; i < n_outs_; ++i)
-      std::memcpy(static_cast<uint8_t*>(outs[i].user) + outs[i].bytes_per_pair * (size_t)s.first, s.h_out[i], outs[i].bytes_per_pair * (size_t)s.count);
+      if (outs[i].user)
+        std::memcpy(static_cast<uint8_t*>(outs[i].user) + outs[i].bytes_per_pair * (size_t)s.first, s.h_out[i], outs[i].bytes_per_pair * (size_t)s.count);
     return hipSuccess;
   }
 
   std::mutex mu_;
   size_t fb_;
-  size_t out_bpp_[MAX_OUTS] = {0, 0, 0};
+  size_t out_bpp_[MAX_OUTS] = {};
   int n_outs_, chunk_ = 1, threads_ = 4;
   bool video_on_ = true, ready_ = false, staged_ = false;
   Stream copy_;  // (declared before the slots: they are released first)

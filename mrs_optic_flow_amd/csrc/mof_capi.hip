@@ -411,6 +411,11 @@ struct mof_bm_engine {
   size_t frame_bytes = 0;
   mof::DevMem<int8_t> d_dx, d_dy, d_mode;
   mof::PinnedMem<int8_t> h_res;  // dx | dy | mode
+  // the stateful _q entry's outputs (allocated by the first call that asks for one): 3 uint32 per block, then the gated-block count
+  mof::DevMem<uint32_t> d_q;
+  mof::PinnedMem<uint32_t> h_q;
+  // the match gate (mof_bm_set_gate): kernel arguments, no buffer -- block-matching batches keep "never pin"
+  uint32_t max_min_sad = 0xffffffffu, min_sad_range = 0u;
   mof::PinnedMem<uint8_t> h_stage;
   // BlockMethod::Refine scratch (allocated on first use): the two 2x images, nine SADs
   mof::DevMem<uint8_t> d_up[2];
@@ -420,7 +425,7 @@ struct mof_bm_engine {
   std::atomic<bool> busy{false};
   std::atomic<bool> graph_pinned{false};
   std::mutex host_mu;          // mof_bm_process_batch_host's pipeline (host_pipe.hpp)
-  std::unique_ptr<mof::HostPipe> host_pipe;
+  std::unique_ptr<mof::HostPipe> host_pipe, host_pipe_q;  // (_q: with the quality and count slots, built by the first call that asks for one)
 };
 
 static void pack_frame(uint8_t* dst, const uint8_t* src, size_t pitch, int w, int h) {
@@ -1042,7 +1047,38 @@ int mof_bm_reset(mof_bm_engine* e) {
   return MOF_OK;
 }
 
-int mof_bm_process(mof_bm_engine* e, const uint8_t* frame, size_t pitch, int8_t* dx, int8_t* dy, int8_t* mode_xy) {
+static mof::BmQArgs bm_qargs(const mof_bm_engine* e, uint32_t* quality) {
+  mof::BmQArgs q;
+  q.quality = quality;
+  q.max_min_sad = e->max_min_sad;
+  q.min_sad_range = e->min_sad_range;
+  return q;
+}
+
+int mof_bm_set_gate(mof_bm_engine* e, uint32_t max_min_sad, uint32_t min_sad_range) {
+  if (!e) return fail(MOF_ERR_NOT_INIT, "null engine");
+  BusyGuard g(e->busy);
+  if (!g.owned) return fail(MOF_ERR_BUSY, "engine busy");
+  e->max_min_sad = max_min_sad;
+  e->min_sad_range = min_sad_range;
+  return MOF_OK;
+}
+
+int mof_bm_gate(const mof_bm_engine* e, uint32_t* max_min_sad, uint32_t* min_sad_range) {
+  if (!e) return fail(MOF_ERR_NOT_INIT, "null engine");
+  if (max_min_sad) *max_min_sad = e->max_min_sad;
+  if (min_sad_range) *min_sad_range = e->min_sad_range;
+  return MOF_OK;
+}
+
+int mof_bm_scan_plan(int block_size, int step_size, int scan_radius, int grid_x, int quality, int* out4) {
+  if (!out4 || grid_x < 0 || step_size < 0 || !mof::bm_config_supported(block_size, scan_radius))
+    return fail(MOF_ERR_BAD_ARG, "mof_bm_scan_plan: unsupported geometry or null output");
+  return mof::bm_scan_plan(block_size, step_size, scan_radius, grid_x, quality != 0, out4) ? MOF_OK : fail(MOF_ERR_UNSUPPORTED, "no plan");
+}
+
+int mof_bm_process_q(mof_bm_engine* e, const uint8_t* frame, size_t pitch, int8_t* dx, int8_t* dy, int8_t* mode_xy, uint32_t* quality,
+                     int* n_invalid) {
   if (!e) return fail(MOF_ERR_NOT_INIT, "null engine");
   if (!frame || !dx || !dy || pitch < (size_t)e->cfg.frame_width) return fail(MOF_ERR_BAD_ARG, "bad arguments");
   BusyGuard g(e->busy);
@@ -1050,17 +1086,27 @@ int mof_bm_process(mof_bm_engine* e, const uint8_t* frame, size_t pitch, int8_t*
   HIP_TRY(hipSetDevice(e->cfg.device));
   const int cur_slot = 1 - e->prev_slot;
   const size_t nb = (size_t)e->cfg.grid_x * e->cfg.grid_y;
+  const bool want_q = quality || n_invalid;
+  if (want_q && !e->d_q) {
+    mof::RelaxedCapture relaxed;
+    HIP_TRY(mof::alloc_all(e->h_q, 3 * nb + 1, e->d_q, 3 * nb + 1));  // (d_q, the test above, last)
+  }
   HIP_TRY(upload_frame(e, cur_slot, frame, pitch));
   mof::BmArgs a = bm_args(e, e->d_frames[cur_slot], 0, e->d_frames[e->prev_slot], 0, (size_t)e->cfg.frame_width,
                           e->d_dx, e->d_dy, e->d_mode);
-  HIP_TRY(mof::launch_bm_scan(a, 1, e->stream));
-  HIP_TRY(mof::launch_bm_mode(a, 1, e->stream));
+  const mof::BmQArgs q = bm_qargs(e, quality ? e->d_q.get() : nullptr);
+  HIP_TRY(mof::launch_bm_scan(a, q, 1, e->stream));
+  HIP_TRY(mof::launch_bm_mode(a, q, n_invalid ? reinterpret_cast<int32_t*>(e->d_q + 3 * nb) : nullptr, 1, e->stream));
   HIP_TRY(hipMemcpyAsync(e->h_res, e->d_dx, nb, hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(hipMemcpyAsync(e->h_res + nb, e->d_dy, nb, hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(hipMemcpyAsync(e->h_res + 2 * nb, e->d_mode, 8, hipMemcpyDeviceToHost, e->stream));
+  if (quality) HIP_TRY(hipMemcpyAsync(e->h_q, e->d_q, 3 * nb * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+  if (n_invalid) HIP_TRY(hipMemcpyAsync(e->h_q + 3 * nb, e->d_q + 3 * nb, sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));
   std::memcpy(dx, e->h_res, nb);
   std::memcpy(dy, e->h_res + nb, nb);
+  if (quality) std::memcpy(quality, e->h_q, 3 * nb * sizeof(uint32_t));
+  if (n_invalid) *n_invalid = (int)e->h_q[3 * nb];
   if (mode_xy) {
     mode_xy[0] = e->h_res[2 * nb];
     mode_xy[1] = e->h_res[2 * nb + 1];
@@ -1068,6 +1114,10 @@ int mof_bm_process(mof_bm_engine* e, const uint8_t* frame, size_t pitch, int8_t*
   e->prev_slot = cur_slot;  // imPrev = imCurr.clone(), BlockMethod.cpp:89
   e->have_pair = true;
   return MOF_OK;
+}
+
+int mof_bm_process(mof_bm_engine* e, const uint8_t* frame, size_t pitch, int8_t* dx, int8_t* dy, int8_t* mode_xy) {
+  return mof_bm_process_q(e, frame, pitch, dx, dy, mode_xy, nullptr, nullptr);
 }
 
 int mof_bm_refine(mof_bm_engine* e, int fullpix_x, int fullpix_y, int passes, int faithful, double* out_xy) {
@@ -1120,7 +1170,8 @@ int mof_bm_refine(mof_bm_engine* e, int fullpix_x, int fullpix_y, int passes, in
 
 // The device batch entries: n_pairs frame pairs of `channels` interleaved channels (1 gray, 3 BGR8)
 static int bm_batch(mof_bm_engine* e, const uint8_t* d_cur, size_t cur_stride, const uint8_t* d_prev, size_t prev_stride, size_t pitch,
-                    int n_pairs, int8_t* d_dx, int8_t* d_dy, int8_t* d_mode, void* stream, int channels) {
+                    int n_pairs, int8_t* d_dx, int8_t* d_dy, int8_t* d_mode, uint32_t* d_quality, int32_t* d_n_invalid, void* stream,
+                    int channels) {
   if (!e) return fail(MOF_ERR_NOT_INIT, "null engine");
   if (n_pairs == 0) return MOF_OK;  // an empty batch carries no pointers to check
   if (!d_cur || !d_prev || !d_dx || !d_dy || !d_mode || n_pairs < 0 || pitch < (size_t)channels * (size_t)e->cfg.frame_width)
@@ -1132,25 +1183,39 @@ static int bm_batch(mof_bm_engine* e, const uint8_t* d_cur, size_t cur_stride, c
   HIP_TRY(hipSetDevice(e->cfg.device));
   hipStream_t s = (hipStream_t)stream;  // (a captured block-matching batch reads no engine-owned memory: no pin)
   mof::BmArgs a = bm_args(e, d_cur, cur_stride, d_prev, prev_stride, pitch, d_dx, d_dy, d_mode, channels);
-  HIP_TRY(mof::launch_bm_scan(a, n_pairs, s));
-  HIP_TRY(mof::launch_bm_mode(a, n_pairs, s));
+  const mof::BmQArgs q = bm_qargs(e, d_quality);
+  HIP_TRY(mof::launch_bm_scan(a, q, n_pairs, s));
+  HIP_TRY(mof::launch_bm_mode(a, q, d_n_invalid, n_pairs, s));
   return MOF_OK;
+}
+
+int mof_bm_process_batch_device_q(mof_bm_engine* e, const uint8_t* d_cur, size_t cur_stride, const uint8_t* d_prev, size_t prev_stride,
+                                  size_t pitch, int n_pairs, int8_t* d_dx, int8_t* d_dy, int8_t* d_mode, uint32_t* d_quality,
+                                  int32_t* d_n_invalid, void* stream) {
+  return bm_batch(e, d_cur, cur_stride, d_prev, prev_stride, pitch, n_pairs, d_dx, d_dy, d_mode, d_quality, d_n_invalid, stream, 1);
+}
+
+int mof_bm_process_batch_device_bgr_q(mof_bm_engine* e, const uint8_t* d_cur, size_t cur_stride, const uint8_t* d_prev, size_t prev_stride,
+                                      size_t pitch, int n_pairs, int8_t* d_dx, int8_t* d_dy, int8_t* d_mode, uint32_t* d_quality,
+                                      int32_t* d_n_invalid, void* stream) {
+  return bm_batch(e, d_cur, cur_stride, d_prev, prev_stride, pitch, n_pairs, d_dx, d_dy, d_mode, d_quality, d_n_invalid, stream, 3);
 }
 
 int mof_bm_process_batch_device(mof_bm_engine* e, const uint8_t* d_cur, size_t cur_stride, const uint8_t* d_prev,
                                 size_t prev_stride, size_t pitch, int n_pairs, int8_t* d_dx, int8_t* d_dy,
                                 int8_t* d_mode, void* stream) {
-  return bm_batch(e, d_cur, cur_stride, d_prev, prev_stride, pitch, n_pairs, d_dx, d_dy, d_mode, stream, 1);
+  return bm_batch(e, d_cur, cur_stride, d_prev, prev_stride, pitch, n_pairs, d_dx, d_dy, d_mode, nullptr, nullptr, stream, 1);
 }
 
 int mof_bm_process_batch_device_bgr(mof_bm_engine* e, const uint8_t* d_cur, size_t cur_stride, const uint8_t* d_prev,
                                     size_t prev_stride, size_t pitch, int n_pairs, int8_t* d_dx, int8_t* d_dy,
                                     int8_t* d_mode, void* stream) {
-  return bm_batch(e, d_cur, cur_stride, d_prev, prev_stride, pitch, n_pairs, d_dx, d_dy, d_mode, stream, 3);
+  return bm_batch(e, d_cur, cur_stride, d_prev, prev_stride, pitch, n_pairs, d_dx, d_dy, d_mode, nullptr, nullptr, stream, 3);
 }
 
-int mof_bm_process_batch_host(mof_bm_engine* e, const uint8_t* cur, size_t cur_stride, const uint8_t* prev,
-                              size_t prev_stride, size_t pitch, int n_pairs, int8_t* dx, int8_t* dy, int8_t* mode) try {
+// (the _q pipe's slots carry all five outputs; one the caller did not ask for is neither computed nor read back)
+int mof_bm_process_batch_host_q(mof_bm_engine* e, const uint8_t* cur, size_t cur_stride, const uint8_t* prev, size_t prev_stride,
+                                size_t pitch, int n_pairs, int8_t* dx, int8_t* dy, int8_t* mode, uint32_t* quality, int32_t* n_invalid) try {
   if (!e) return fail(MOF_ERR_NOT_INIT, "null engine");
   if (n_pairs == 0) return MOF_OK;  // an empty batch carries no pointers to check
   if (!cur || !prev || !dx || !dy || !mode || n_pairs < 0 || pitch < (size_t)e->cfg.frame_width)
@@ -1158,24 +1223,33 @@ int mof_bm_process_batch_host(mof_bm_engine* e, const uint8_t* cur, size_t cur_s
   HIP_TRY(hipSetDevice(e->cfg.device));
   mof::RelaxedCapture relaxed;
   const size_t nb = (size_t)e->cfg.grid_x * e->cfg.grid_y;
-  const size_t bpp[3] = {nb, nb, 8};
+  const size_t bpp[5] = {nb, nb, 8, 3 * nb * sizeof(uint32_t), sizeof(int32_t)};
   {
     std::lock_guard<std::mutex> lock(e->host_mu);
     if (!e->host_pipe) e->host_pipe.reset(new mof::HostPipe(e->frame_bytes, bpp, 3));
+    if ((quality || n_invalid) && !e->host_pipe_q) e->host_pipe_q.reset(new mof::HostPipe(e->frame_bytes, bpp, 5));
   }
-  const mof::HostPipe::Out outs[3] = {{dx, nb}, {dy, nb}, {mode, 8}};
+  mof::HostPipe* pipe = (quality || n_invalid ? e->host_pipe_q : e->host_pipe).get();
+  const mof::HostPipe::Out outs[5] = {{dx, nb}, {dy, nb}, {mode, 8}, {quality, bpp[3]}, {n_invalid, bpp[4]}};
   hipError_t he = hipSuccess;
-  const int rc = e->host_pipe->process(
+  const int rc = pipe->process(
       cur, cur_stride, prev, prev_stride, pitch, e->cfg.frame_width, e->cfg.frame_height, n_pairs, outs, e->stream,
-      [e](const mof::HostPipe::Chunk& c, hipStream_t s) {
-        return mof_bm_process_batch_device(e, c.d_cur, c.stride, c.d_prev, c.stride, (size_t)e->cfg.frame_width, c.count,
-                                           static_cast<int8_t*>(c.d_out[0]), static_cast<int8_t*>(c.d_out[1]), static_cast<int8_t*>(c.d_out[2]), s);
+      [e, quality, n_invalid](const mof::HostPipe::Chunk& c, hipStream_t s) {
+        return mof_bm_process_batch_device_q(e, c.d_cur, c.stride, c.d_prev, c.stride, (size_t)e->cfg.frame_width, c.count,
+                                             static_cast<int8_t*>(c.d_out[0]), static_cast<int8_t*>(c.d_out[1]), static_cast<int8_t*>(c.d_out[2]),
+                                             quality ? static_cast<uint32_t*>(c.d_out[3]) : nullptr,
+                                             n_invalid ? static_cast<int32_t*>(c.d_out[4]) : nullptr, s);
       },
       &he);
   if (rc == -1) return fail(MOF_ERR_HIP, "host batch pipeline: %s", hipGetErrorString(he));
   return rc;
 } catch (const std::bad_alloc&) {
   return fail(MOF_ERR_NO_MEMORY, "mof_bm_process_batch_host: out of host memory");
+}
+
+int mof_bm_process_batch_host(mof_bm_engine* e, const uint8_t* cur, size_t cur_stride, const uint8_t* prev,
+                              size_t prev_stride, size_t pitch, int n_pairs, int8_t* dx, int8_t* dy, int8_t* mode) {
+  return mof_bm_process_batch_host_q(e, cur, cur_stride, prev, prev_stride, pitch, n_pairs, dx, dy, mode, nullptr, nullptr);
 }
 
 int mof_bm_sync(mof_bm_engine* e) {

@@ -139,9 +139,19 @@ struct BmArgs {
   int8_t* mode;  // [pair][8]
 };
 
+// What the scans' Q forms get beside BmArgs: the per-block quality output {min_sad, zero_sad, max_sad} (may be null) and the match
+// gate -- a block is valid iff min_sad <= max_min_sad and max_sad - min_sad >= min_sad_range; an invalid one reports BM_INVALID twice
+struct BmQArgs {
+  uint32_t* quality = nullptr;  // [pair][by*grid_x+bx][3]
+  uint32_t max_min_sad = 0xffffffffu, min_sad_range = 0u;
+};
+constexpr int BM_INVALID = -128;  // MOF_BM_INVALID: outside every scan range (radius <= 48)
+inline bool bm_gate_armed(const BmQArgs& q) { return q.max_min_sad != 0xffffffffu || q.min_sad_range != 0u; }
+
 bool bm_config_supported(int block, int radius);
-hipError_t launch_bm_scan(const BmArgs& a, int n_pairs, hipStream_t stream);
-hipError_t launch_bm_mode(const BmArgs& a, int n_pairs, hipStream_t stream);
+bool bm_scan_plan(int block, int step, int radius, int grid_x, bool quality, int out[4]);
+hipError_t launch_bm_scan(const BmArgs& a, const BmQArgs& q, int n_pairs, hipStream_t stream);
+hipError_t launch_bm_mode(const BmArgs& a, const BmQArgs& q, int32_t* n_invalid, int n_pairs, hipStream_t stream);
 // BlockMethod::Refine building blocks (K9 2x resize, K10 nine cut-out SADs)
 hipError_t launch_bm_resize2x(const uint8_t* src, size_t pitch, int w, int h, uint8_t* dst, hipStream_t stream);
 hipError_t launch_bm_refine_sad(const uint8_t* A, const uint8_t* B, int W2, int spx, int spy, int cw, int ch,

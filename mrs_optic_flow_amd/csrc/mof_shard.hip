@@ -465,6 +465,26 @@ int mof_shard_bm_process_batch_device(mof_shard_bm* g, const uint8_t* const* d_c
   return rc;
 }
 
+// mof_bm_set_gate on every engine of the group, all of them or none (as mof_shard_fft_set_min_response; the block matchers never pin)
+int mof_shard_bm_set_gate(mof_shard_bm* g, uint32_t max_min_sad, uint32_t min_sad_range) {
+  if (!g) return mof::capi_fail(MOF_ERR_NOT_INIT, "null shard group");
+  uint32_t old_a = 0xffffffffu, old_b = 0u;
+  (void)mof_shard_bm_gate(g, &old_a, &old_b);
+  for (size_t i = 0; i < g->engines.size(); ++i) {
+    const int rc = mof_bm_set_gate(g->engines[i], max_min_sad, min_sad_range);  // (its error text stays the thread's last error)
+    if (rc != MOF_OK) {
+      for (size_t j = 0; j < i; ++j) (void)mof_bm_set_gate(g->engines[j], old_a, old_b);
+      return rc;
+    }
+  }
+  return MOF_OK;
+}
+
+int mof_shard_bm_gate(const mof_shard_bm* g, uint32_t* max_min_sad, uint32_t* min_sad_range) {
+  if (!g || g->engines.empty()) return mof::capi_fail(MOF_ERR_NOT_INIT, "null shard group");
+  return mof_bm_gate(g->engines[0], max_min_sad, min_sad_range);
+}
+
 int mof_shard_bm_sync(mof_shard_bm* g) {
   if (!g) return mof::capi_fail(MOF_ERR_NOT_INIT, "null shard group");
   DeviceRestore restore;

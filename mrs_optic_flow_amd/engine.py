@@ -383,13 +383,36 @@ class FftMethod:
             pass
 
 
+_BM_GATE_OFF = (0xFFFFFFFF, 0)  # mof_bm_set_gate's default: no bound on min_sad, no range asked for
+
+
 class _BmBase:
-    def __init__(self, cfg: BmConfig, device: int):
+    def __init__(self, cfg: BmConfig, device: int, max_min_sad=None, min_sad_range: int = 0):
         self._lib = _capi.load()
         cfg.device = device
         self.cfg = cfg
         self._h = C.c_void_p()
         check(self._lib.mof_bm_create(C.byref(cfg), C.byref(self._h)))
+        self.last_quality = None    # [gy, gx, 3] uint32 {min_sad, zero_sad, max_sad} of the last processBlocks / processImage
+        self.last_n_invalid = None  # blocks the match gate rejected in that call
+        if max_min_sad is not None or min_sad_range:
+            self.set_gate(max_min_sad, min_sad_range)
+
+    def set_gate(self, max_min_sad=None, min_sad_range: int = 0) -> None:
+        """The match gate (include/mof.h): a block is valid iff min_sad <= max_min_sad and max_sad - min_sad >= min_sad_range, both
+        whole-block SADs (per-pixel figure x block_size^2). max_min_sad=None: no bound; (None, 0) switches the gate off.
+        MofError(MOF_ERR_BUSY) while a call is in flight."""
+        a = _BM_GATE_OFF[0] if max_min_sad is None else int(max_min_sad)
+        if not (0 <= a <= _BM_GATE_OFF[0] and 0 <= int(min_sad_range) <= _BM_GATE_OFF[0]):
+            raise ValueError("gate thresholds are uint32 whole-block SADs")
+        check(self._lib.mof_bm_set_gate(self._h, a, int(min_sad_range)))
+
+    @property
+    def gate(self):
+        """(max_min_sad, min_sad_range); max_min_sad is None when unbounded, so (None, 0) is the gate switched off."""
+        a, b = C.c_uint32(), C.c_uint32()
+        check(self._lib.mof_bm_gate(self._h, C.byref(a), C.byref(b)))
+        return (None if a.value == _BM_GATE_OFF[0] else int(a.value)), int(b.value)
 
     @property
     def n_blocks(self) -> int:
@@ -415,8 +438,11 @@ class _BmBase:
         dx = np.empty(self.n_blocks, np.int8)
         dy = np.empty(self.n_blocks, np.int8)
         mode = np.zeros(2, np.int8)
-        check(self._lib.mof_bm_process(self._h, f.ctypes.data, f.strides[0], dx.ctypes.data, dy.ctypes.data,
-                                       mode.ctypes.data))
+        quality = np.empty((self.cfg.grid_y, self.cfg.grid_x, 3), np.uint32)
+        n_invalid = C.c_int(0)
+        check(self._lib.mof_bm_process_q(self._h, f.ctypes.data, f.strides[0], dx.ctypes.data, dy.ctypes.data,
+                                         mode.ctypes.data, quality.ctypes.data, C.byref(n_invalid)))
+        self.last_quality, self.last_n_invalid = quality, int(n_invalid.value)
         g = (self.cfg.grid_y, self.cfg.grid_x)
         return dx.reshape(g), dy.reshape(g), (int(mode[0]), int(mode[1]))
 
@@ -430,50 +456,60 @@ class _BmBase:
         """One output vector. refine=None: the histogram mode (FastSpacedBMMethod_OCL.cpp:172-175; BlockMethod before
         :79). refine="faithful"/"fixed": BlockMethod's full return value, Refine(mode, 2) (BlockMethod.cpp:79)."""
         _, _, mode = self.processBlocks(imCurr)
+        if mode[0] == _capi.MOF_BM_INVALID:  # the gate left no valid block: no vector (and Refine has no cut-out at -128)
+            return np.array([[np.nan, np.nan]])
         if refine is None:
             return np.array([[float(mode[0]), float(mode[1])]])
         return np.array([self.refine(mode, 2, refine == "faithful")])
 
-    def process_batch_host(self, cur: np.ndarray, prev: np.ndarray):
+    def process_batch_host(self, cur: np.ndarray, prev: np.ndarray, return_quality=False):
+        """return_quality: additionally (quality [n, gy, gx, 3] uint32, n_invalid [n] int32)."""
         cur, prev, cs, ps, pitch = _host_batch_views(cur, prev)
         self._check_shape(cur)
         n = cur.shape[0]
         dx = np.empty((n, self.cfg.grid_y, self.cfg.grid_x), np.int8)
         dy = np.empty_like(dx)
         mode = np.empty((n, 8), np.int8)
-        check(self._lib.mof_bm_process_batch_host(self._h, cur.ctypes.data, cs, prev.ctypes.data, ps, pitch, n,
-                                                  dx.ctypes.data, dy.ctypes.data, mode.ctypes.data))
-        return dx, dy, mode
+        if not return_quality:
+            check(self._lib.mof_bm_process_batch_host(self._h, cur.ctypes.data, cs, prev.ctypes.data, ps, pitch, n,
+                                                      dx.ctypes.data, dy.ctypes.data, mode.ctypes.data))
+            return dx, dy, mode
+        quality = np.empty((n, self.cfg.grid_y, self.cfg.grid_x, 3), np.uint32)
+        n_invalid = np.empty(n, np.int32)
+        check(self._lib.mof_bm_process_batch_host_q(self._h, cur.ctypes.data, cs, prev.ctypes.data, ps, pitch, n, dx.ctypes.data,
+                                                    dy.ctypes.data, mode.ctypes.data, quality.ctypes.data, n_invalid.ctypes.data))
+        return dx, dy, mode, (quality, n_invalid)
 
-    def process_batch_device(self, cur, prev, stream=None):
+    def _batch_device(self, cur, prev, stream, return_quality, channels):
         import torch
 
-        _check_device_batch(cur, prev, (self.cfg.frame_height, self.cfg.frame_width), self.cfg.device)
+        _check_device_batch(cur, prev, (self.cfg.frame_height, self.cfg.frame_width), self.cfg.device, channels=channels)
         n = cur.shape[0]
         dx = torch.empty((n, self.cfg.grid_y, self.cfg.grid_x), dtype=torch.int8, device=cur.device)
         dy = torch.empty_like(dx)
         mode = torch.empty((n, 8), dtype=torch.int8, device=cur.device)
         s = stream if stream is not None else torch.cuda.current_stream(cur.device)
-        check(self._lib.mof_bm_process_batch_device(self._h, cur.data_ptr(), cur.stride(0), prev.data_ptr(),
-                                                    prev.stride(0), cur.stride(1), n, dx.data_ptr(), dy.data_ptr(),
-                                                    mode.data_ptr(), _stream_ptr(s)))
-        return dx, dy, mode
+        args = (self._h, cur.data_ptr(), cur.stride(0), prev.data_ptr(), prev.stride(0), cur.stride(1), n, dx.data_ptr(),
+                dy.data_ptr(), mode.data_ptr())
+        if not return_quality:
+            fn = self._lib.mof_bm_process_batch_device if channels == 1 else self._lib.mof_bm_process_batch_device_bgr
+            check(fn(*args, _stream_ptr(s)))
+            return dx, dy, mode
+        # (uint32 as int32 storage: torch has no arithmetic on uint32; a SAD stays below 2^22)
+        quality = torch.empty((n, self.cfg.grid_y, self.cfg.grid_x, 3), dtype=torch.int32, device=cur.device)
+        n_invalid = torch.empty((n,), dtype=torch.int32, device=cur.device)
+        fn = self._lib.mof_bm_process_batch_device_q if channels == 1 else self._lib.mof_bm_process_batch_device_bgr_q
+        check(fn(*args, quality.data_ptr(), n_invalid.data_ptr(), _stream_ptr(s)))
+        return dx, dy, mode, (quality, n_invalid)
 
-    def process_batch_device_bgr(self, cur, prev, stream=None):
+    def process_batch_device(self, cur, prev, stream=None, return_quality=False):
+        """return_quality: additionally (quality [n, gy, gx, 3] {min_sad, zero_sad, max_sad}, n_invalid [n]), int32 tensors."""
+        return self._batch_device(cur, prev, stream, return_quality, 1)
+
+    def process_batch_device_bgr(self, cur, prev, stream=None, return_quality=False):
         """cur, prev: torch uint8 [n, H, W, 3] BGR8 views (W-stride 3, any row pitch): CV_RGB2GRAY (as the node applies it to
         BGR data) is fused into the kernels' staging loads; same bits as the gray entry on the converted frames."""
-        import torch
-
-        _check_device_batch(cur, prev, (self.cfg.frame_height, self.cfg.frame_width), self.cfg.device, channels=3)
-        n = cur.shape[0]
-        dx = torch.empty((n, self.cfg.grid_y, self.cfg.grid_x), dtype=torch.int8, device=cur.device)
-        dy = torch.empty_like(dx)
-        mode = torch.empty((n, 8), dtype=torch.int8, device=cur.device)
-        s = stream if stream is not None else torch.cuda.current_stream(cur.device)
-        check(self._lib.mof_bm_process_batch_device_bgr(self._h, cur.data_ptr(), cur.stride(0), prev.data_ptr(),
-                                                        prev.stride(0), cur.stride(1), n, dx.data_ptr(), dy.data_ptr(),
-                                                        mode.data_ptr(), _stream_ptr(s)))
-        return dx, dy, mode
+        return self._batch_device(cur, prev, stream, return_quality, 3)
 
     def _release_graphs(self) -> None:
         if getattr(self, "_h", None) and self._h.value:
@@ -495,10 +531,10 @@ class BlockMethod(_BmBase):
     """BlockMethod(frameSize, samplePointSize, scanRadius, ...) -- /root/reference/src/BlockMethod.cpp:3-22."""
 
     def __init__(self, frameSize: int, samplePointSize: int, scanRadius: int, scanDiameter: int | None = None,
-                 scanCount: int | None = None, stepSize: int = 0, device: int = 0):
+                 scanCount: int | None = None, stepSize: int = 0, device: int = 0, max_min_sad=None, min_sad_range: int = 0):
         cfg = BmConfig()
         check(_capi.load().mof_bm_config_block_method(C.byref(cfg), frameSize, samplePointSize, scanRadius))
-        super().__init__(cfg, device)
+        super().__init__(cfg, device, max_min_sad, min_sad_range)
 
 
 class FastSpacedBMMethod(_BmBase):
@@ -506,11 +542,11 @@ class FastSpacedBMMethod(_BmBase):
     /root/reference/src/FastSpacedBMMethod_OCL.cpp:5-6, :81-97."""
 
     def __init__(self, samplePointSize: int, scanRadius: int, stepSize: int, frame_shape: tuple[int, int],
-                 device: int = 0):
+                 device: int = 0, max_min_sad=None, min_sad_range: int = 0):
         cfg = BmConfig()
         h, w = frame_shape
         check(_capi.load().mof_bm_config_fast_spaced(C.byref(cfg), w, h, samplePointSize, stepSize, scanRadius))
-        super().__init__(cfg, device)
+        super().__init__(cfg, device, max_min_sad, min_sad_range)
 
 
 class ScaleRotationEstimator:

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""The static record of a libmof_hip.so: every kernel of every gfx950 code object with the numeric fields of its metadata note and
-`code`, a SHA-256 over the bytes of the kernel's symbol in .text followed by its 64-byte descriptor <name>.kd -- without the descriptor's
+"""The static record of a libmof_hip.so: every kernel of every gfx950 code object with the numeric fields of its metadata note, `bytes`,
+the size of the kernel's symbol in .text, and `code`, a SHA-256 over the bytes of the kernel's symbol in .text followed by its 64-byte descriptor <name>.kd -- without the descriptor's
 kernel_code_entry_byte_offset (bytes 16 .. 23), the distance from the descriptor to the entry, which moves whenever another kernel joins
 or leaves the code object.
 
@@ -83,7 +83,7 @@ def code_hashes(co, sections, symbols):
         if ndx in sec:
             off = sec[ndx][1] + addr - sec[ndx][0]
             sym[name] = co[off:off + size]
-    return {n: hashlib.sha256(b + sym[n + ".kd"][:16] + bytes(8) + sym[n + ".kd"][24:]).hexdigest() for n, b in sym.items() if n + ".kd" in sym}
+    return {n: (hashlib.sha256(b + sym[n + ".kd"][:16] + bytes(8) + sym[n + ".kd"][24:]).hexdigest(), len(b)) for n, b in sym.items() if n + ".kd" in sym}
 
 
 def record(lib):
@@ -101,7 +101,7 @@ def record(lib):
             for name, fields in kernels_of(subprocess.check_output([readelf, "--notes", path], text=True)).items():
                 if name not in code:
                     sys.exit(f"{lib}: no symbol or no descriptor {name}.kd found for kernel {name} (llvm-readelf --symbols)")
-                fields["code"] = code[name]
+                fields["code"], fields["code_bytes"] = code[name]
                 while name in rec:  # (kernels of unnamed namespaces in two translation units may share a name)
                     name += "'"
                 rec[name] = fields
@@ -115,7 +115,7 @@ def record(lib):
 
 
 def row(fields):
-    return " ".join(f"{s} {fields.get(k, 0)}" for s, k in zip(SHORT, FIELDS)) + f" code {fields['code'][:16]}"
+    return " ".join(f"{s} {fields.get(k, 0)}" for s, k in zip(SHORT, FIELDS)) + f" bytes {fields['code_bytes']} code {fields['code'][:16]}"
 
 
 def main(argv):
