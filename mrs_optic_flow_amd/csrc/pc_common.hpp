@@ -421,10 +421,12 @@ __device__ __forceinline__ cf cross_power_ab(cf A, cf B, bool real_only) {
     const float s = __builtin_amdgcn_rsqf(q + eps16);
     return {pr * s, pim * s};
   }
-  // |P'|^2 >= 2^10: 16 eps / q < 2^-30 is below half an ulp of the unit-magnitude result, so C = P' rsq(q) (one
-  // transcendental); the general form only runs for (numerically) empty bins such as constant patches
-  // -- taken as a wave-uniform branch: a per-lane one costs exec-mask juggling around every bin (and cost the retired
-  // quad-per-line kernel 48 spilled VGPRs).
+  // |P'|^2 >= 2^10: 16 eps / q < 2^-30 is below half an ulp of the unit-magnitude result, so C = P' rsq(q); the general
+  // form is only needed for (numerically) empty bins such as constant patches. What the compiler makes of the test
+  // below is NOT a branch (profiles/xpow_batch_static.txt): it if-converts it, and every bin executes v_rsq_f32,
+  // v_sqrt_f32 and v_rcp_f32 (quarter rate each) plus the compare and two selects. That is accepted at the sites that
+  // keep this scalar form -- single bins, the real-only slots, lanes that repeat a bin -- and is what
+  // cross_power_ab_batch (below) removes where a lane holds several bins in registers.
   float s = __builtin_amdgcn_rsqf(q);
   if (__builtin_amdgcn_ballot_w64(!(q >= 1024.f)) != 0)
     s = (q >= 1024.f) ? s : __builtin_amdgcn_sqrtf(q) * __builtin_amdgcn_rcpf(q + eps16);
@@ -442,6 +444,62 @@ __device__ __forceinline__ cf cross_power(cf zk, cf zm, bool real_only) {
   cf A, B;
   untangle2(zk, zm, &A, &B);
   return cross_power_ab<PK>(A, B, real_only);
+}
+
+// R bins of one lane at once (none of them a real-only slot), bin by bin the arithmetic of cross_power_ab: P', q and
+// s = rsq(q) for every bin, the per-bin tests !(q >= 1024) OR-ed into ONE flag and ONE ballot per batch, and the general
+// form for all R bins behind one branch that a textured patch never takes. The empty asm keeps that branch a branch (as
+// for the constant-patch codes of pc_kernel.hip): the main path then carries R v_rsq_f32 and no v_sqrt_f32 / v_rcp_f32,
+// and -- one basic block for the whole batch -- the loads that feed it can all be in flight before the first bin is
+// worked on (ISA evidence: profiles/xpow_batch_static.txt). PK = 1 has no rare path.
+//
+// The sums of two products are spelled as the fused multiply-adds the compiler made of cross_power_ab's expressions at the
+// site the batch replaces -- it contracted them differently in the pair kernels (operands fresh from untangle2) and in the
+// sequence kernel (spectra in registers) --, so that every bin keeps the bits it had: XPOW_PAIR / XPOW_SEQ.
+enum { XPOW_PAIR = 0, XPOW_SEQ = 1 };
+template <int PK, int R, int FORM>
+__device__ __forceinline__ void cross_power_ab_batch(const cf* A, const cf* B, cf* C) {
+  const float eps16 = 16.f * 1.1920928955078125e-07f;  // 16 * FLT_EPSILON, as cross_power_ab
+  float pr[R], pim[R], q[R], s[R];
+  bool rare = false;
+#pragma unroll
+  for (int k = 0; k < R; ++k) {
+    if constexpr (FORM == XPOW_PAIR) {
+      pr[k] = __builtin_fmaf(A[k].y, B[k].y, A[k].x * B[k].x);
+      pim[k] = __builtin_fmaf(-A[k].x, B[k].y, A[k].y * B[k].x);
+      q[k] = __builtin_fmaf(pim[k], pim[k], pr[k] * pr[k]);
+    } else {
+      pr[k] = __builtin_fmaf(A[k].x, B[k].x, A[k].y * B[k].y);
+      pim[k] = __builtin_fmaf(A[k].y, B[k].x, -(A[k].x * B[k].y));
+      q[k] = __builtin_fmaf(pr[k], pr[k], pim[k] * pim[k]);
+    }
+    if constexpr (PK == 1) {
+      s[k] = __builtin_amdgcn_rsqf(q[k] + eps16);
+    } else {
+      s[k] = __builtin_amdgcn_rsqf(q[k]);
+      rare |= !(q[k] >= 1024.f);
+    }
+  }
+  if constexpr (PK != 1) {
+    if (__builtin_expect(__builtin_amdgcn_ballot_w64(rare) != 0, 0)) {
+      asm volatile("");
+#pragma unroll
+      for (int k = 0; k < R; ++k) s[k] = (q[k] >= 1024.f) ? s[k] : __builtin_amdgcn_sqrtf(q[k]) * __builtin_amdgcn_rcpf(q[k] + eps16);
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < R; ++k) C[k] = {pr[k] * s[k], pim[k] * s[k]};
+}
+
+// ... from the packed transform's bins zk[k] = Z[k], zm[k] = Z[-k], conjugated for the Hermitian inverse
+template <int PK, int R>
+__device__ __forceinline__ void cross_power_batch(const cf* zk, const cf* zm, cf* out_conj) {
+  cf A[R], B[R];
+#pragma unroll
+  for (int k = 0; k < R; ++k) untangle2(zk[k], zm[k], &A[k], &B[k]);
+  cross_power_ab_batch<PK, R, XPOW_PAIR>(A, B, out_conj);
+#pragma unroll
+  for (int k = 0; k < R; ++k) out_conj[k].y = -out_conj[k].y;
 }
 
 // ---- degenerate pairs: a CONSTANT patch ----------------------------------------------------------------------------

@@ -207,6 +207,32 @@ __device__ __forceinline__ void row_pass(cf* __restrict__ z, int line0, int lane
 // cross-power pass (a tile read and half a tile write, one workgroup barrier) disappears. Partner rows are N-1..H+1,
 // which nobody writes in this phase; row 0 (packed with row H by the owning wave beforehand) is taken as it is.
 // HAS_ROW0: the wave that owns row 0 (wave 0); the others never meet the packed row and carry no per-element select for it.
+//
+// Stage 1's addresses. A lane holds the bins u = x + k R2 (x = lane % R2 < R2 <= 8, k < R1) of its line. In the skewed row, column c
+// sits at c + (c >> SK), so its own bins are own_off(k) behind the first one, and the partner columns (N - u) % N -- for the lanes
+// with x > 0 -- at off(k) - x: N - k R2 is a multiple of R2, R2 divides 8, so the columns N - k R2 - 1 .. N - k R2 - (R2 - 1) share
+// one skew block. The lanes with x == 0 differ from that by delta(cls(k)): the partner of column 0 is column 0 (class 0), and a
+// multiple of 8 sits one skew block further (class 2; N = 64: every k > 0, 32: the even k). Three per-lane bases at the most, formed
+// once; every bin then is a base plus a compile-time offset, which goes into the read's offset field.
+template <int N>
+struct XpowPartner {
+  static constexpr int R1 = Cfg<N>::R1, R2 = Cfg<N>::R2, SK = Cfg<N>::SK;
+  static constexpr int col(int c) { return c + (c >> SK); }
+  static constexpr int own_off(int k) { return col(k * R2); }
+  static constexpr int off(int k) { return N - k * R2 + ((N - 1 - k * R2) >> SK); }
+  static constexpr int cls(int k) { return k == 0 ? 0 : (col(N - k * R2) == off(k) ? 1 : 2); }
+  static constexpr int delta(int c) { return c == 0 ? -off(0) : c - 1; }
+  static constexpr bool holds() {  // against the plain form, every lane and bin
+    for (int x = 0; x < R2; ++x)
+      for (int k = 0; k < R1; ++k) {
+        const int u = x + k * R2;
+        if (col(u) != col(x) + own_off(k)) return false;
+        if (col((N - u) % N) != off(k) - x + (x ? 0 : delta(cls(k)))) return false;
+      }
+    return true;
+  }
+};
+
 template <int N, int PK, bool HAS_ROW0>
 __device__ __forceinline__ void row_pass_xpow(cf* __restrict__ z, int line0, int lane, const cf* tw_row) {
   using P = PcTraits<N>;
@@ -221,12 +247,29 @@ __device__ __forceinline__ void row_pass_xpow(cf* __restrict__ z, int line0, int
       const int line = line0 + ord1<N>(q / R2), x = q % R2;
       const int pline = (N - line) % N;
       const bool packed = HAS_ROW0 && line == 0;
+      // all 2 R1 reads first, then the batch (pc_common.hpp): the waits on the reads are progressive, as in every other stage.
+      // The partner's address is one per-lane base plus a compile-time offset (XpowPartner), not a zaddr per bin.
+      static_assert(R2 <= 8 && 8 % R2 == 0 && XpowPartner<N>::holds(), "stage-1 address offsets of the fused cross-power");
+      const int own = zaddr<N>(line, x), prow = zaddr<N>(pline, 0) - x;
+      const int pbase[3] = {prow + (x ? 0 : XpowPartner<N>::delta(0)), prow + (x ? 0 : XpowPartner<N>::delta(1)),
+                            prow + (x ? 0 : XpowPartner<N>::delta(2))};
+      cf zk[R1], zm[R1];
 #pragma unroll
       for (int k = 0; k < R1; ++k) {
-        const int u = x + k * R2, um = (N - u) % N;
-        const cf zk = lds_read(&z[zaddr<N>(line, u)]), zm = lds_read(&z[zaddr<N>(pline, um)]);
-        const cf C = cross_power<PK>(zk, zm, false);
-        v[b][k] = packed ? zk : cf{C.x, -C.y};
+        zk[k] = lds_read(&z[own + XpowPartner<N>::own_off(k)]);
+        zm[k] = lds_read(&z[pbase[XpowPartner<N>::cls(k)] + XpowPartner<N>::off(k)]);
+      }
+      // PK = 0 at N = 64: two batches of four (115 VGPRs) -- all eight bins' P', q and s live across one branch take 128, the last
+      // register of four workgroups per CU. N = 32, whose one wave sat at 126 before: 130 with batches of four or two, 127 with
+      // one bin per branch -- the reads are all in flight before the first of them either way (profiles/xpow_batch_static.txt).
+      constexpr int BS = PK == 1 ? R1 : (N == 32 ? 1 : 4);
+#pragma unroll
+      for (int h = 0; h < R1; h += BS) {
+        cross_power_batch<PK, BS>(zk + h, zm + h, v[b] + h);
+        if constexpr (HAS_ROW0) {
+#pragma unroll
+          for (int k = h; k < h + BS; ++k) v[b][k] = packed ? zk[k] : v[b][k];
+        }
       }
       butterfly<R1>(v[b]);
     }

@@ -91,11 +91,14 @@ __device__ __forceinline__ void col_pass_fused64(cf* __restrict__ z, int col0, i
     for (int k = 0; k < 8; ++k) prev[k] = v[k];
     return;
   }
+  {  // the lane's eight bins as one batch: one test and one (rare) branch for all of them (pc_common.hpp)
+    cf C[8];
+    cross_power_ab_batch<PK, 8, XPOW_SEQ>(v, prev, C);
 #pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    const cf C = cross_power_ab<PK>(v[k], prev[k], false);
-    prev[k] = v[k];
-    v[k] = {C.x, -C.y};
+    for (int k = 0; k < 8; ++k) {
+      prev[k] = v[k];
+      v[k] = {C[k].x, -C[k].y};
+    }
   }
   if (has_col0 && (lane & 7) == 0) {
 #pragma unroll
