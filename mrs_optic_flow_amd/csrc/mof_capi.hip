@@ -552,7 +552,8 @@ int mof_fft_create(const mof_fft_config* cfg, mof_fft_engine** out) try {
   if (!fft_route(*cfg, &e->plan, &e->route))  // (validate_fft has checked that a plan exists)
     return fail(MOF_ERR_UNSUPPORTED, "no plan for patch_size %d", cfg->patch_size);
   const FftRoute& r = e->route;
-  const std::vector<float> tw = mof::twiddle_table(r.m);
+  std::vector<float> tw = mof::twiddle_table(r.m);
+  mof::pc_append_twiddle_rows(tw, r.m);  // K1's packed rows behind the classic table (32 and 64; a no-op elsewhere)
   HIP_TRY(e->stream.create());
   HIP_TRY(mof::upload(e->d_twiddles, tw, e->stream));
   for (auto& frame : e->d_frames) {

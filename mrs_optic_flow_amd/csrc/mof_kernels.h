@@ -109,6 +109,9 @@ hipError_t launch_pc_half_sequence(const PcArgs& a, int m, int n, int n_pairs, i
 bool pc_patch_size_supported(int n);  // the hand-tuned instantiations: 32, 64, 120, 128
 hipError_t pc_configure(int patch_size);  // once per device before the first launch
 hipError_t launch_pc_field(const PcArgs& a, int patch_size, int n_pairs, hipStream_t stream);
+// launch_pc_field's a.twiddles at 32 and 64: twiddle_table(n) with the packed per-index rows appended (TwRows, pc_passes.hpp); other
+// sizes are left as they are. The classic table stays at offset 0 for every kernel that reads it.
+void pc_append_twiddle_rows(std::vector<float>& table, int n);
 // Frame sequences (pc_seq_kernel.hip; 64 x 64 patches): a.cur = frame 0, a.cur_stride = bytes between frames, pair k =
 // (frame k + 1, frame k) for k < n_pairs; one workgroup per patch position walks `run` consecutive pairs
 bool pc_sequence_supported(int patch_size);

@@ -7,6 +7,7 @@
 #include <stdint.h>
 
 #include "mof_kernels.h"
+#include "pc_argmax.hpp"
 
 namespace mof {
 namespace {
@@ -221,14 +222,7 @@ __device__ __forceinline__ cf lds_read(const cf* p) {
   return {t.x, t.y};
 }
 
-struct Best {
-  float v;
-  int idx;
-};
-__device__ __forceinline__ Best better(Best a, Best b) {
-  // first maximum in row-major order of the fft-shifted surface (cv::minMaxLoc)
-  return (b.v > a.v || (b.v == a.v && b.idx < a.idx)) ? b : a;
-}
+// (Best, better() and the value-first selection rule: pc_argmax.hpp, host-callable)
 
 // ---- cross-lane exchange on the VALU -------------------------------------------------------------------------------
 // lane_xor<OFF>(x) = the x of lane (lane ^ OFF), OFF in {32, 16, 8, 4, 2, 1}: what __shfl_xor(x, OFF, 64) returns, without
@@ -314,6 +308,25 @@ __device__ __forceinline__ Best wave_best(Best b) {
   b = wave_best_level<4>(b);
   b = wave_best_level<2>(b);
   return wave_best_level<1>(b);
+}
+
+// The value alone: every lane ends with the wave's maximum. One exchange and one v_max_f32 per level -- fmaxf is symmetric in its
+// operands where neither is NaN (the callers' values never are: they come out of fmaxf chains seeded with -inf), so the two swap levels
+// take the maximum of the swap's two results and need no select on the lane's half. +0 and -0 compare equal and either may come out:
+// the result is for comparing, not for storing.
+__device__ __forceinline__ float wave_max(float v) {
+  {
+    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+    v = fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
+  }
+  {
+    const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+    v = fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
+  }
+  v = fmaxf(v, lane_xor<8>(v));
+  v = fmaxf(v, lane_xor<4>(v));
+  v = fmaxf(v, lane_xor<2>(v));
+  return fmaxf(v, lane_xor<1>(v));
 }
 
 // cv::cvtColor(.., CV_RGB2GRAY) on 8-bit data (fixed point, yuv_shift 14): gray = (c0*R2Y + c1*G2Y + c2*B2Y + 2^13) >> 14

@@ -72,6 +72,9 @@ __global__ void __launch_bounds__(PcTraits<N>::T) pc_field_kernel(PcArgs a) {
   constexpr bool PERSIST = P::PERSIST;
   constexpr bool FWD3 = N == 64 && DS == 1;                  // the three-stage forward transform (pc_passes3.hpp)
   constexpr bool RAW = (N == 128 || N == 64) && DS == 1;     // raw pixel staging (pc_passes.hpp)
+  // arg-max by value first (below). One patch per workgroup and more than one wave: a single wave (N = 32) always holds the maximum,
+  // so nothing would leave its path; the persistent form's second barrier already has a job (it protects the tile)
+  constexpr bool VALUE_FIRST = !PERSIST && P::WAVES > 1;
   (void)patches;
   // (x0, y0) of a patch are in the units of the correlated image: full-res pixels, or quarter-res when DS = 4
   auto patch_base = [&](int p, const uint8_t* frames, size_t frame_stride) -> const uint8_t* {
@@ -94,6 +97,10 @@ __global__ void __launch_bounds__(PcTraits<N>::T) pc_field_kernel(PcArgs a) {
   cf tw_row[R2 - 1], tw_col[R2 - 1];
   {
     const int xr = lane0 % R1, xc = lane0 / (64 / R1);
+    if constexpr (TwRows<N>::USE) {  // one packed row each (TwRows, pc_passes.hpp)
+      tw_row_load<R2>(a.twiddles + TwRows<N>::ROWS_AT + 2 * R2 * xr, tw_row);
+      tw_row_load<R2>(a.twiddles + TwRows<N>::ROWS_AT + 2 * R2 * xc, tw_col);
+    } else
 #pragma unroll
     for (int k = 1; k < R2; ++k) {
       tw_row[k - 1] = {a.twiddles[2 * (k * xr)], a.twiddles[2 * (k * xr) + 1]};
@@ -286,10 +293,33 @@ __global__ void __launch_bounds__(PcTraits<N>::T) pc_field_kernel(PcArgs a) {
   if (wave < P::WI) row_pass<N, P::LI>(z, wave * P::LI, lane, tw_row);
   }  // FUSE_XPOW
   __syncthreads();
-  Best best = {-__builtin_huge_valf(), 0x7fffffff};
+  Best best = argmax_neutral();
+  if constexpr (VALUE_FIRST) {
+    // The value first, the index only where the value matched (the rule and why it gives the parent fold's Best: pc_argmax.hpp). Each
+    // lane keeps its 16 surface values; the wave's maximum goes to a float slot in the free part of `red`; behind the barrier every wave
+    // forms the workgroup's maximum gm from the WAVES slots. Only a wave that holds a lane with m == gm -- one wave, unless the maximum is
+    // attained in several -- walks the index chain and folds (value, index) pairs, all 64 lanes active (lane_xor's contract); the others
+    // store the neutral pair. The second barrier, which a one-patch workgroup did not need before, now orders red[] for wave 0.
+    static_assert(P::WI == P::WAVES, "every wave runs the inverse column pass");
+    float* red_max = reinterpret_cast<float*>(red + 16);  // red[0 .. WAVES-1] pairs; [16, 32) free; the constant-patch codes from 32
+    cf sv[InvPlan<N>::PER * R2];
+    const float m = col_pass_inv<N, PK, false>(z, wave * P::LI, lane, tw_col, a.search_radius, sv).v;
+    const float wm = wave_max(m);
+    if (lane == 0) red_max[wave] = wm;
+    __syncthreads();
+    float gm = red_max[0];
+#pragma unroll
+    for (int w = 1; w < P::WAVES; ++w) gm = fmaxf(gm, red_max[w]);
+    if (__builtin_amdgcn_ballot_w64(m == gm) != 0ull) {
+      asm volatile("");  // (keeps the rare branch a branch, as for the constant-patch codes above)
+      best = wave_best(argmax_entry(m, gm, col_pass_inv_index<N>(sv, m, wave * P::LI, lane)));
+    }
+    if (lane == 0) red[wave] = best;
+  } else {
   if (wave < P::WI) best = col_pass_inv<N, PK>(z, wave * P::LI, lane, tw_col, a.search_radius);
   best = wave_best(best);
   if (lane == 0) red[wave] = best;
+  }
   __syncthreads();
 
   // ---- 5x5 weighted centroid in double + validity gate  (:1337-1383, :1838-1856), wave 0. The window is read
@@ -306,8 +336,9 @@ __global__ void __launch_bounds__(PcTraits<N>::T) pc_field_kernel(PcArgs a) {
     });
     degenerate = const_codes_degenerate<P::WAVES>(my_code, lane);
   }
-  // (only the persistent form needs it; the one-patch forms without it were never measured: docs/history/retired_switches.md)
-  __syncthreads();
+  // (only the persistent form needs it: the value-first forms have spent their second barrier above and nothing follows that it could
+  // protect; N = 32 keeps it, never measured without: docs/history/retired_switches.md)
+  if constexpr (!VALUE_FIRST) __syncthreads();
   if (wave == 0)
     centroid_gate_store<N, PK>(best, wval, lane, a.max_px_speed_sq, a.out + 2 * (size_t)p, a.quality ? a.quality + 2 * (size_t)p : nullptr, degenerate,
                                degenerate ? *reinterpret_cast<const float*>(const_code + 16) : 0.f);
@@ -371,5 +402,26 @@ hipError_t launch_pc_field(const PcArgs& a, int patch_size, int n_pairs, hipStre
 }
 
 bool pc_patch_size_supported(int n) { return n == 32 || n == 64 || n == 128 || n == 120; }
+
+template <int N>
+static void append_rows_n(std::vector<float>& t) {
+  using R = TwRows<N>;
+  t.resize(R::FLOATS);
+  auto copy = [&](size_t at, int k) {  // entry `at` of the appended part <- W_N^k of the classic table, the very floats
+    t[at] = t[2 * (size_t)k];
+    t[at + 1] = t[2 * (size_t)k + 1];
+  };
+  for (int x = 0; x < R::R1; ++x)
+    for (int k = 0; k < R::R2; ++k) copy(R::ROWS_AT + 2 * (size_t)(x * R::R2 + k), k * x);
+  if constexpr (N == 64)
+    for (int i = 0; i < 16; ++i)
+      for (int k = 0; k < 4; ++k) copy(R::FWD3_AT + 2 * (size_t)(i * 4 + k), k * i);
+}
+
+void pc_append_twiddle_rows(std::vector<float>& table, int n) {
+  if (table.size() != 2 * (size_t)n) return;  // (not a classic table of that size)
+  if (n == 32) append_rows_n<32>(table);
+  else if (n == 64) append_rows_n<64>(table);
+}
 
 }  // namespace mof

@@ -73,6 +73,36 @@ struct PcTraits {
   static_assert(R1 * R2 == N && T % 64 == 0 && 64 % R1 == 0 && 64 % R2 == 0, "bad plan");
 };
 
+// ---- the twiddles of a lane from packed per-index rows -------------------------------------------------------------------------
+// PcArgs::twiddles of K1 is the classic table W_N^k, k < N, with two blocks behind it (pc_append_twiddle_rows, pc_kernel.hip; every
+// kernel that reads the classic table finds it at offset 0):
+//   block 1  for x = 0..R1-1 the row W_N^{k x}, k = 0..R2-1: the second Stockham stage's twiddles of the lane with x = lane % R1 (row
+//            passes) or lane / (64 / R1) (column passes);
+//   block 2  (N = 64) for i = 0..15 the row W_64^{k i}, k = 0..3: the three-stage forward transform's (pc_passes3.hpp).
+// k x <= (R2 - 1)(R1 - 1) < N and k i <= 45: no wrap, every entry is a copy of the classic table's. A lane reads its row with 16-byte
+// loads off ONE address instead of gathering R2 - 1 (or 3) entries at 2 k x, each with its own multiply and 64-bit address.
+template <int N>
+struct TwRows {
+  static constexpr int R1 = Cfg<N>::R1, R2 = Cfg<N>::R2;
+  static constexpr int ROWS_AT = 2 * N;                                 // in floats
+  static constexpr int FWD3_AT = ROWS_AT + 2 * R1 * R2;
+  static constexpr int FLOATS = FWD3_AT + (N == 64 ? 2 * 16 * 4 : 0);  // the whole table
+  // N = 128 keeps the classic table and its gathers: with the rows (and the mirror bases below) its four full-resolution forms spill
+  // two to four VGPRs to scratch (profiles/k1_index_path_static.txt)
+  static constexpr bool USE = N <= 64;
+  static_assert((R1 - 1) * (R2 - 1) < N && R2 % 2 == 0, "rows are copies of the classic table, whole 16-byte pieces");
+};
+// tw[k - 1] = row[k], k = 1..R-1, of a 16-byte-aligned row of R complex values
+template <int R>
+__device__ __forceinline__ void tw_row_load(const float* __restrict__ row, cf* tw) {
+  typedef float f4 __attribute__((ext_vector_type(4)));
+  f4 q[R / 2];
+#pragma unroll
+  for (int j = 0; j < R / 2; ++j) q[j] = reinterpret_cast<const f4*>(row)[j];
+#pragma unroll
+  for (int k = 1; k < R; ++k) tw[k - 1] = (k & 1) ? cf{q[k / 2].z, q[k / 2].w} : cf{q[k / 2].x, q[k / 2].y};
+}
+
 // z(r, c): skewed tile address in complex units
 template <int N>
 __device__ __forceinline__ int zaddr(int r, int c) {
@@ -365,8 +395,49 @@ __device__ __forceinline__ void col_pass_fwd(cf* __restrict__ z, int col0, int l
 // columns ride one complex transform: E[v] = F1[v][x1] + i F1[v][x2]; Re/Im of its transform are the
 // correlation surface at columns x1 / x2. Output: z(y, x1) = (c[y][x1], c[y][x1 + N/2]); returns the
 // lane's best (value, shifted index).
-template <int N, int PK>
-__device__ __forceinline__ Best col_pass_inv(cf* __restrict__ z, int col0, int lane, const cf* tw_col, int search_radius) {
+//
+// Stage 1's mirror rows. For k > R1/2 (and k = R1/2 where x > 0) a lane reads row N - x - k R2, x < R2 <= 8. N - k R2 is a multiple of R2,
+// so for x > 0 those rows share one block of the row skew (8 (r >> 3) at N = 64, 8 (r >> 5) at 128, none at 32) and the address is
+// off(k) - x PITCH + column; the lanes with x == 0 sit one skew step (8) further where N - k R2 starts a block (cls(k) = 1). Two per-lane
+// bases at the most, formed once; every read then is a base plus a compile-time offset in the read's offset field (as XpowPartner above).
+template <int N>
+struct InvMirror {
+  static constexpr int R1 = Cfg<N>::R1, R2 = Cfg<N>::R2, PITCH = Cfg<N>::PITCH, STEP = 8;
+  static constexpr bool USE = N <= 64;  // (N = 128 keeps the plain form: see TwRows::USE)
+  static constexpr int rskew(int r) { return N == 128 ? 8 * (r >> 5) : (N == 64 ? 8 * (r >> 3) : 0); }
+  static constexpr int off(int k) { return (N - k * R2) * PITCH + rskew(N - k * R2 - 1); }
+  static constexpr int cls(int k) { return rskew(N - k * R2) != rskew(N - k * R2 - 1) ? 1 : 0; }
+  static constexpr bool holds() {  // against the plain form (zaddr's row part), every lane and mirror row
+    for (int x = 0; x < R2; ++x)
+      for (int k = R1 / 2; k < R1; ++k) {
+        if (k == R1 / 2 && x == 0) continue;  // the packed row 0
+        const int r = N - x - k * R2;
+        if (r * PITCH + rskew(r) != off(k) - x * PITCH + (x == 0 && cls(k) == 1 ? STEP : 0)) return false;
+        if (rskew(N - k * R2) - rskew(N - k * R2 - 1) != (cls(k) ? STEP : 0)) return false;
+      }
+    return true;
+  }
+};
+
+template <int N>
+struct InvPlan {
+  static constexpr int PER = PcTraits<N>::LI * PcTraits<N>::R1 / 64;  // stage-2 butterflies of a lane: PER x R2 complex = 16 column pairs' values
+};
+
+// one value pair of a lane, rows y of columns col | col + H: the smallest shifted index so far among the values that attain the lane's maximum m
+template <int N>
+__device__ __forceinline__ int inv_index_step(int mi, cf v, float m, int y, int col) {
+  constexpr int H = N / 2;
+  const int base = ((y + H) % N) * N + col;
+  mi = argmax_first_index(mi, v.x, m, base + H);  // column col      -> shifted col + H
+  return argmax_first_index(mi, v.y, m, base);    // column col + H  -> shifted col
+}
+
+// INDEX = true: returns the lane's best (value, shifted index). INDEX = false (the value-first arg-max of pc_kernel.hip): the index chain
+// is left out -- the lane's maximum comes back with the neutral index -- and the lane's PER x R2 value pairs are handed out in `keep`
+// for col_pass_inv_index below.
+template <int N, int PK, bool INDEX = true>
+__device__ __forceinline__ Best col_pass_inv(cf* __restrict__ z, int col0, int lane, const cf* tw_col, int search_radius, cf* keep = nullptr) {
   using P = PcTraits<N>;
   constexpr int R1 = P::R1, R2 = P::R2, LI = P::LI, H = N / 2;
   {  // stage 1
@@ -380,6 +451,28 @@ __device__ __forceinline__ Best col_pass_inv(cf* __restrict__ z, int col0, int l
       // per k, except for the lanes with x == 0 at k = 0 (r = 0) and k = R1/2 (r = H), which read the packed row 0
       static_assert(R1 % 2 == 0 && 64 / CW == R2, "row classes below assume x < R2 and an even R1");
       const bool x0 = x == 0;
+      if constexpr (InvMirror<N>::USE) {
+        static_assert(R2 <= 8 && 8 % R2 == 0 && H % (1 << P::SK) == 0 && InvMirror<N>::holds(), "stage-1 address offsets of the mirror rows");
+        constexpr int HOFF = H + (H >> P::SK);  // column col + H of the same row
+        const int ccol = col + (col >> P::SK), mrow = ccol - x * P::PITCH;
+        const int mbase[2] = {mrow, mrow + (x0 ? InvMirror<N>::STEP : 0)};
+#pragma unroll
+        for (int k = 0; k < R1; ++k) {
+          int at = zaddr<N>(x + k * R2, col);
+          if (k >= R1 / 2) at = mbase[InvMirror<N>::cls(k)] + InvMirror<N>::off(k);
+          if (k == R1 / 2) at = x0 ? ccol : at;  // the packed row 0
+          const cf a = lds_read(&z[at]), c = lds_read(&z[at + HOFF]);
+          cf e;
+          if (k < R1 / 2) {
+            e = {a.x - c.y, a.y + c.x};
+            if (k == 0 && x0) e = {a.x, c.x};
+          } else {
+            e = {a.x + c.y, c.x - a.y};
+            if (k == R1 / 2 && x0) e = {a.y, c.y};
+          }
+          v[b][k] = e;
+        }
+      } else {
 #pragma unroll
       for (int k = 0; k < R1; ++k) {
         const int r = x + k * R2;  // 0..N-1
@@ -395,6 +488,7 @@ __device__ __forceinline__ Best col_pass_inv(cf* __restrict__ z, int col0, int l
         }
         v[b][k] = e;
       }
+      }
       butterfly<R1>(v[b]);
     }
     wave_sync();
@@ -408,7 +502,7 @@ __device__ __forceinline__ Best col_pass_inv(cf* __restrict__ z, int col0, int l
   }
   Best best = {-__builtin_huge_valf(), 0x7fffffff};
   {  // stage 2 + arg-max from registers (fftShift :1297-1305, minMaxLoc :1539)
-    constexpr int PER = LI * R1 / 64, CW = 64 / R1;
+    constexpr int PER = InvPlan<N>::PER, CW = 64 / R1;
     cf v[PER][R2];
 #pragma unroll
     for (int b = 0; b < PER; ++b) {
@@ -445,14 +539,31 @@ __device__ __forceinline__ Best col_pass_inv(cf* __restrict__ z, int col0, int l
       for (int k = 0; k < R2; ++k) {
         const int y = x + k * R1;
         z[zaddr<N>(y, col)] = v[b][k];
-        const int base = ((y + H) % N) * N + col;
-        mi = min(mi, v[b][k].x == m ? base + H : 0x7fffffff);  // column col      -> shifted col + H
-        mi = min(mi, v[b][k].y == m ? base : 0x7fffffff);      // column col + H  -> shifted col
+        if constexpr (INDEX) {  // (inv_index_step, spelled as it always was here: through the helper N = 128 schedules differently)
+          const int base = ((y + H) % N) * N + col;
+          mi = min(mi, v[b][k].x == m ? base + H : 0x7fffffff);  // column col      -> shifted col + H
+          mi = min(mi, v[b][k].y == m ? base : 0x7fffffff);      // column col + H  -> shifted col
+        }
+        else keep[b * R2 + k] = v[b][k];
       }
     }
     best = Best{m, mi};
   }
   return best;
+}
+
+// the index chain on the value pairs col_pass_inv<N, PK, false> handed out: the smallest shifted index among the lane's values that attain
+// its maximum m (0x7fffffff: none does -- every one of them is NaN)
+template <int N>
+__device__ __forceinline__ int col_pass_inv_index(const cf* keep, float m, int col0, int lane) {
+  using P = PcTraits<N>;
+  constexpr int R1 = P::R1, R2 = P::R2, PER = InvPlan<N>::PER, CW = 64 / R1;
+  int mi = 0x7fffffff;
+#pragma unroll
+  for (int b = 0; b < PER; ++b)
+#pragma unroll
+    for (int k = 0; k < R2; ++k) mi = inv_index_step<N>(mi, keep[b * R2 + k], m, lane / CW + k * R1, col0 + lane % CW + CW * b);
+  return mi;
 }
 
 }  // namespace mof

@@ -22,11 +22,10 @@ struct Fwd3Tw {
   cf wr[3], wc[3];  // W64^{n2 k1}, n2 = 1..3 (k1 = 4 wave + lane % 4);  W64^{m2 l1}, l1 = 1..3 (m2 = lane / 4)
   __device__ __forceinline__ void load(const float* __restrict__ table, int wave, int lane) {
     const int k1 = 4 * wave + (lane & 3), m2 = lane >> 2;
-#pragma unroll
-    for (int i = 1; i < 4; ++i) {
-      wr[i - 1] = {table[2 * (i * k1)], table[2 * (i * k1) + 1]};
-      wc[i - 1] = {table[2 * (i * m2)], table[2 * (i * m2) + 1]};
-    }
+    // the rows W64^{k k1} and W64^{k m2}, k = 0..3, of the table's second block (TwRows, pc_passes.hpp): two 16-byte loads each
+    static_assert(TwRows<64>::USE, "the packed rows are behind the classic table");
+    tw_row_load<4>(table + TwRows<64>::FWD3_AT + 8 * k1, wr);
+    tw_row_load<4>(table + TwRows<64>::FWD3_AT + 8 * m2, wc);
   }
 };
 

@@ -1,4 +1,4 @@
-// Self-test of the cross-lane helpers of pc_common.hpp (lane_xor, wave_best, wave_sum3): ONE launch of ONE wave that
+// Self-test of the cross-lane helpers of pc_common.hpp (lane_xor, wave_best, wave_max, wave_sum3): ONE launch of ONE wave that
 // compares them with __shfl_xor and with serial scans, and counts the mismatches. Not part of the public interface
 // (not in mof.h): tests/test_gpu_wave_ops.py calls it through ctypes.
 #include <hip/hip_runtime.h>
@@ -52,6 +52,23 @@ __device__ __forceinline__ int check_best(float v, int lane, Best* lds) {
   return bad + (!same_bits(neu.v, old.v)) + (neu.idx != old.idx);
 }
 
+// wave_max (the value-only fold of the value-first arg-max) against fmaxf folded serially over lanes 0 .. 63 and against the
+// __shfl_xor butterfly, every lane holding the result. Values as the kernels feed it: never NaN. Compared as VALUES (==), which is
+// how the kernel uses it: where +0 and -0 are both the maximum either may come out.
+__device__ __forceinline__ int check_max(float v, int lane, Best* lds) {
+  lds[lane] = Best{v, lane};
+  wave_sync();
+  float ref = lds[0].v;
+#pragma unroll 1
+  for (int l = 1; l < 64; ++l) ref = fmaxf(ref, lds[l].v);
+  wave_sync();
+  float old = v;
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) old = fmaxf(old, __shfl_xor(old, off, 64));
+  const float got = wave_max(v);
+  return !(got == ref) + !(got == old);
+}
+
 // wave_sum3 against the __shfl_xor butterfly it replaces, bit for bit, on `n` non-zero lanes of mixed magnitude and sign
 template <int TOP>
 __device__ __forceinline__ int check_sum3(int n, int lane) {
@@ -85,6 +102,12 @@ __global__ __launch_bounds__(64) void wave_ops_selftest_kernel(int* mismatches) 
     bad += check_best(nan, lane, lds);
     bad += wave_best(better(Best{ninf, 0x7fffffff}, Best{nan, lane})).idx != 0x7fffffff;
   }
+  bad += check_max((float)((lane * 37) % 64) - 20.5f, lane, lds);                // distinct values, the maximum in each half in turn
+  bad += check_max((float)(((lane + 32) * 37) % 64) - 20.5f, lane, lds);
+  bad += check_max(lane == 40 || lane == 3 ? 7.f : (float)(lane % 5), lane, lds);  // a tie across the 32-lane halves
+  bad += check_max(lane == 17 ? 0.f : (lane == 50 ? -0.f : -1.f - (float)lane), lane, lds);  // +0 and -0 are the maximum
+  bad += check_max(ninf, lane, lds);                                             // all -inf
+  bad += check_max(lane == 63 ? -3.e38f : ninf, lane, lds);                      // one finite value in the last lane
   bad += check_sum3<32>(25, lane) + check_sum3<32>(49, lane) + check_sum3<16>(25, lane);
   if (bad) atomicAdd(mismatches, bad);
 }
