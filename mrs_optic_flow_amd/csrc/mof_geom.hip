@@ -135,7 +135,8 @@ __device__ __forceinline__ void geom_wave_sync() {
 // (-ffp-contract=off on both sides). All lanes return the same H.
 // ws: tab[n][18], A[81], V[81], M[72], g[8] doubles in LDS.
 constexpr int kFitTab = 18;
-constexpr int kWaveFitPoints = 256;  // 36 KB of per-point rows: every BASELINE grid (c4: 16 x 16)
+constexpr int kWaveFitPoints = 256;  // 36 KB of per-point rows: every BASELINE grid (c4: 16 x 16). The 256 / 257 boundary is watched by
+                                     // tests/test_gpu_geometry_paths.py::test_wave_fit_equals_lane_fit_bit_for_bit
 __device__ bool homography_fit_wave(const double* a, const double* b, const unsigned char* mask, int n, double* H, double* ws,
                                     int lane) {
   double* tab = ws;
