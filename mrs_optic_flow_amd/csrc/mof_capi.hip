@@ -89,38 +89,12 @@ int parked_count() {
 }
 }  // namespace mof
 
-namespace {
+namespace mof {
 
-constexpr auto& fail = mof::capi_fail;
-
-using mof::BusyGuard;
-
-// Which kernels an engine launches, decided once at create (fft_route)
-struct FftRoute {
-  enum Family { TUNED, PLANNED, LARGE };
-  enum Video { PAIRS, SEQ, SEQ_HALF, HALF_SEQ };
-  Family family = TUNED;    // what every launch can run: the hand-tuned K1 of the patch size, the planned LDS kernel
-                            // (pc_kernel_generic.hip), or -- padded patch too large for a CU -- the planned pipeline through HBM (pc_large_kernel.hip)
-  int m = 0;                // transform size: the patch size (TUNED) or the size cv::phaseCorrelate pads it to
-  int half_m = 0;           // > 0: full-resolution pair launches run the fused half-tile kernel of this size instead (pc_half_kernel.hip;
-                            //      cv::phaseCorrelate model only)
-  Video video = PAIRS;      // a video: the pair form on consecutive frames, K1s (pc_seq_kernel.hip), pc_seq_half.hip, or the half-tile
-  int video_m = 0;          // kernel's sequence form at transform size video_m
-  bool large_tuned = false; // LARGE, full resolution: the estimator's tuned K5s / K6s / K7 instead of L5 / L6 / L7
-  bool odd_tail = false;    // ... on a size whose Nyquist bins are not exact (the rows kernel's exact sums stand in)
-  bool large_video = false; // ... and a video transforms every frame once per pass
-};
-
-// The MOF_FFT_* knobs that select kernels (README), read once per process
-struct FftKnobs {
-  int half;  // MOF_FFT_HALF: -1 unset
-  bool force_planned, force_large, seq_pairs, seq_half128, half_seq_off, large_tuned, large_video;
-};
-
-// The route of a configuration (validated by validate_fft); *plan receives the plan of the planned families. False: no plan.
-bool fft_route(const mof_fft_config& c, mof::PcPlan* plan, FftRoute* r) {
+// The knobs, read at the first create of the process
+const FftKnobs& fft_knobs() {
   static const FftKnobs k = [] {
-    FftKnobs r{};
+    FftKnobs r;
     const char* v;
     r.half = (v = getenv("MOF_FFT_HALF")) ? atoi(v) : -1;
     r.force_planned = getenv("MOF_FFT_FORCE_PLANNED") != nullptr;
@@ -130,33 +104,46 @@ bool fft_route(const mof_fft_config& c, mof::PcPlan* plan, FftRoute* r) {
     r.half_seq_off = (v = getenv("MOF_FFT_HALF_SEQ")) && atoi(v) == 0;
     r.large_tuned = !(v = getenv("MOF_FFT_LARGE_TUNED")) || atoi(v) != 0;
     r.large_video = !(v = getenv("MOF_FFT_LARGE_VIDEO")) || atoi(v) != 0;
+    if ((v = getenv("MOF_FFT_SEQ_RUN")) && atoi(v) >= 1) r.seq_run = atoi(v);
+    if ((v = getenv("MOF_FFT_LARGE_PASS")) && atoi(v) > 0) r.large_pass = atoi(v);
+    r.planned_static = !(v = getenv("MOF_PLANNED_STATIC")) || atoi(v) != 0;
     return r;
   }();
-  const bool ocv = c.peak_model == MOF_PEAK_OPENCV;
+  return k;
+}
+
+// The planned transform sizes where the fused half-tile kernel (K1h) is the default: it beats the full-tile planned kernel on the box at
+// 60, 96, 100 (p60 1.10 -> 1.38 M, p96 757 -> 855 k pairs/s, profiles/r05_half_vs_planned_bench_ab.txt, r05_half_vs_planned_rates.txt),
+// at 72, 90 (+3 % on pairs, and the video form: profiles/r05_half_vs_planned_final.txt) and at 120 -- patches of 109 .. 119 pixels pad
+// to 120 and follow N = 120 itself (the planned kernel at 120: 869 k against 1.30 M pairs/s). On patches padded to 64 it loses 4 % (p62).
+static bool half_default_planned(int m) {
+  for (int s : {60, 72, 90, 96, 100, 120})
+    if (m == s) return true;
+  return false;
+}
+
+bool fft_route(int patch_size, int peak_model, const FftKnobs& k, PcPlan* plan, FftRoute* r) {
+  const bool ocv = peak_model == MOF_PEAK_OPENCV;
   *r = FftRoute{};
-  if (mof::pc_patch_size_supported(c.patch_size) && !k.force_planned && !k.force_large)
+  if (pc_patch_size_supported(patch_size) && !k.force_planned && !k.force_large)
     r->family = FftRoute::TUNED;
-  else if (!(k.force_large && ocv) && mof::pc_build_plan(c.patch_size, plan))  // (MOF_FFT_FORCE_LARGE with MOF_PEAK_OCL: the planned kernel)
+  else if (!(k.force_large && ocv) && pc_build_plan(patch_size, plan))  // (MOF_FFT_FORCE_LARGE with MOF_PEAK_OCL: the planned kernel)
     r->family = FftRoute::PLANNED;
-  else if (mof::pc_build_line_plan(c.patch_size, plan))
+  else if (pc_build_line_plan(patch_size, plan))
     r->family = FftRoute::LARGE;
   else
     return false;
   const bool tuned = r->family == FftRoute::TUNED, planned = r->family == FftRoute::PLANNED;
-  const int m = r->m = tuned ? c.patch_size : plan->m;
+  const int m = r->m = tuned ? patch_size : plan->m;
   // The fused half-tile kernel: the default for large patches whose half tile fits a CU (even padded size <= 192); MOF_FFT_HALF=0 keeps
   // them on the pipeline through HBM scratch, MOF_FFT_HALF=1 also routes the tuned / planned sizes it is instantiated for through it.
   // r05: N = 120 -- the reference's default samplePointSize -- takes it by default too: two workgroups per CU and every phase on all
-  // waves beat the tuned one-workgroup kernel there (1.14 M against 1.10 M pairs/s same-box, profiles/r05_half_raw_pairsrc_ab.txt).
-  // ... and the planned sizes where it beats the full-tile planned kernel on the box (transform sizes 60, 96, 100: p60 1.10 -> 1.38 M,
-  // p96 757 -> 855 k pairs/s, profiles/r05_half_vs_planned_bench_ab.txt, r05_half_vs_planned_rates.txt; 72, 90: +3 % on pairs, and the
-  // video form: profiles/r05_half_vs_planned_final.txt; on patches padded to 64 it loses 4 %, p62); the tuned N = 64 / 128 pair kernels
-  // stay faster than it and keep their sizes. Patches of 109 .. 119 pixels pad to 120 and follow N = 120 itself (the planned kernel at
-  // 120: 869 k against 1.30 M pairs/s). Long-range launches stay on the family's kernel (launch_field).
+  // waves beat the tuned one-workgroup kernel there (1.14 M against 1.10 M pairs/s same-box, profiles/r05_half_raw_pairsrc_ab.txt),
+  // and so do the planned sizes of half_default_planned; the tuned N = 64 / 128 pair kernels stay faster than it and keep their sizes.
+  // Long-range launches stay on the family's kernel (launch_field).
   const bool half_ok = ocv && k.half != 0 && !k.force_large && !k.force_planned;
-  if (half_ok && mof::pc_half_supported(m) &&
-      (r->family == FftRoute::LARGE || k.half == 1 || (tuned && m == 120) ||
-       (planned && (m == 60 || m == 72 || m == 90 || m == 96 || m == 100 || m == 120))))
+  if (half_ok && pc_half_supported(m) &&
+      (r->family == FftRoute::LARGE || k.half == 1 || (tuned && m == 120) || (planned && half_default_planned(m))))
     r->half_m = m;
   // The video form. The half-tile kernel's sequence form: every size it serves by default but 162 (MOF_FFT_HALF_SEQ=0 keeps the pair form);
   // 128 x 128 patches, whose pair form stays on the tuned kernel -- there it beats the older half-tile sequence kernel (pc_seq_half.hip: one
@@ -164,14 +151,17 @@ bool fft_route(const mof_fft_config& c, mof::PcPlan* plan, FftRoute* r) {
   // the video form wins (50, 54, 108: pc_half_kernel.hip, MOF_HALF_SEQ_SIZES).
   int kh_m = r->half_m;
   if (kh_m == 0 && tuned && m == 128 && !k.seq_half128) kh_m = 128;
-  if (kh_m == 0 && planned && half_ok && !mof::pc_half_supported(m)) kh_m = m;
-  if (kh_m > 0 && ocv && !k.seq_pairs && !k.half_seq_off && mof::pc_half_sequence_supported(kh_m)) {
+  if (kh_m == 0 && planned && half_ok && !pc_half_supported(m)) kh_m = m;
+  if (kh_m > 0 && ocv && !k.seq_pairs && !k.half_seq_off && pc_half_sequence_supported(kh_m)) {
     r->video = FftRoute::HALF_SEQ;
     r->video_m = kh_m;
-  } else if (tuned && !k.seq_pairs && mof::pc_sequence_half_supported(m)) {
+    r->min_run = 4;  // (the launchers' own run lengths are at least 4 / 2; pc_seq_half.hip takes 16)
+  } else if (tuned && !k.seq_pairs && pc_sequence_half_supported(m)) {
     r->video = FftRoute::SEQ_HALF;
-  } else if (tuned && !k.seq_pairs && mof::pc_sequence_supported(m)) {
+    r->min_run = 16;
+  } else if (tuned && !k.seq_pairs && pc_sequence_supported(m)) {
     r->video = FftRoute::SEQ;
+    r->min_run = 2;
   }
   if (r->family == FftRoute::LARGE) {
     // r06: the tuned transform sizes from 200 on (sr_transform_size_tuned; 96 .. 192 keep L5 / L6 / L7 under MOF_FFT_HALF=0 and
@@ -180,12 +170,25 @@ bool fft_route(const mof_fft_config& c, mof::PcPlan* plan, FftRoute* r) {
     // fallback among them, FftMethod.cpp:1709-1716) run them 2.5 x faster than the planned kernels, same Zh / Dt / candidate formats.
     bool exact = true;
     // MOF_PEAK_OCL (never padded) keeps L5 - L8, whose PK = 1 forms carry its model (the tuned K6s / K7 have cv::phaseCorrelate's only)
-    r->large_tuned = ocv && k.large_tuned && m >= 200 && mof::sr_transform_size_tuned(m, &exact);
+    r->large_tuned = ocv && k.large_tuned && m >= 200 && sr_transform_size_tuned(m, &exact);
     r->odd_tail = r->large_tuned && !exact;
     r->large_video = r->large_tuned && k.large_video;
   }
+  r->variant = r->half_m > 0 ? "planned-half" : (r->family == FftRoute::LARGE ? "planned-large" : (planned ? "planned" : "stockham"));
+  r->seq_run = k.seq_run;
+  r->large_pass = k.large_pass;
+  r->planned_static = k.planned_static;
   return true;
 }
+
+}  // namespace mof
+
+namespace {
+
+constexpr auto& fail = mof::capi_fail;
+
+using mof::BusyGuard;
+using mof::FftRoute;
 
 }  // namespace
 
@@ -241,8 +244,7 @@ static hipError_t large_alloc(mof_fft_engine* e, int cap) {
 // Frame pairs per pass of the large-patch pipeline: as many as keep the scratch (three Zh-sized planes per patch pair) under
 // ~1.5 GB, at least one (MOF_FFT_LARGE_PASS overrides, sweeps)
 static int large_pass_pairs(const mof_fft_engine* e, int patches) {
-  static const int forced = [] { const char* v = getenv("MOF_FFT_LARGE_PASS"); return v ? atoi(v) : 0; }();
-  if (forced > 0) return forced;
+  if (e->route.large_pass > 0) return e->route.large_pass;
   const size_t per_pair = (size_t)3 * patches * mof::pcl_zh_floats(e->plan) * sizeof(float);
   const size_t n = ((size_t)3 << 29) / (per_pair ? per_pair : 1);
   return n < 1 ? 1 : (n > 4096 ? 4096 : (int)n);
@@ -354,9 +356,20 @@ static int launch_field(mof_fft_engine* e, const mof::PcArgs& a, int n_pairs, hi
     return MOF_OK;
   }
   if (r.family == FftRoute::LARGE) return launch_large(e, a, n_pairs, stream);
-  HIP_TRY(r.family == FftRoute::PLANNED ? mof::launch_pc_generic(a, e->plan, n_pairs, stream)
+  HIP_TRY(r.family == FftRoute::PLANNED ? mof::launch_pc_generic(a, e->plan, r.planned_static, n_pairs, stream)
                                         : mof::launch_pc_field(a, e->cfg.patch_size, n_pairs, stream));
   return MOF_OK;
+}
+// once per engine, before its first launch: the dynamic-LDS limits of the kernels launch_field and fft_sequence can launch on route r
+// (a video's half-tile form runs at half_m whenever that is set); the large-patch pipeline's kernels need none
+static hipError_t configure_route(const FftRoute& r) {
+  hipError_t err = hipSuccess;
+  if (r.half_m > 0 || r.video == FftRoute::HALF_SEQ) err = mof::pc_configure_half(r.half_m > 0 ? r.half_m : r.video_m);
+  if (err == hipSuccess && r.family == FftRoute::PLANNED) err = mof::pc_configure_generic();
+  if (err == hipSuccess && r.family == FftRoute::TUNED) err = mof::pc_configure(r.m);
+  if (err == hipSuccess && r.video == FftRoute::SEQ) err = mof::pc_configure_sequence();
+  if (err == hipSuccess && r.video == FftRoute::SEQ_HALF) err = mof::pc_configure_sequence_half(r.m);
+  return err;
 }
 #define FIELD_TRY(expr)       \
   do {                        \
@@ -494,23 +507,19 @@ static int validate_fft(const mof_fft_config* c) {
       c->origin_y < 0 || c->stride_x < 0 || c->stride_y < 0)
     return fail(MOF_ERR_BAD_ARG, "bad FFT geometry");
   if (c->patch_size < 2) return fail(MOF_ERR_BAD_ARG, "patch_size %d: a patch needs at least 2 x 2 pixels", c->patch_size);
-  if (!mof::pc_patch_size_supported(c->patch_size)) {
-    // any other samplePointSize (FftMethod.cpp:1680-1720 takes it from a ROS parameter): the planned kernel on the size
-    // cv::phaseCorrelate pads to, M = getOptimalDFTSize(N)
-    mof::PcPlan plan;
-    if (!mof::pc_build_plan(c->patch_size, &plan)) {
-      // the padded patch does not fit one CU's LDS (M > 135): the planned pipeline through HBM scratch (pc_large_kernel.hip), both
-      // peak models
-      if (!mof::pc_build_line_plan(c->patch_size, &plan))
-        return fail(MOF_ERR_UNSUPPORTED, "patch_size %d pads to %d: beyond the planned transforms (<= 960)", c->patch_size,
-                    mof::pc_optimal_dft_size(c->patch_size));
-    }
-    // useOCL=true plans radix-{2,3,4,5,8} passes for the patch size itself and never pads (FftMethod.cpp:481-539, :787-816):
-    // sizes with another prime factor have no OpenCL plan in the reference either; its CCS packing assumes an even size
-    if (c->peak_model == MOF_PEAK_OCL && (plan.m != plan.n || (plan.n & 1)))
-      return fail(MOF_ERR_UNSUPPORTED, "peak_model MOF_PEAK_OCL needs an even patch_size of the form 2^a 3^b 5^c, up to 960 (the "
-                  "reference's OpenCL branch cannot plan %d either)", c->patch_size);
-  }
+  // Whether a plan exists does not depend on the knobs: the default route answers. A size without a tuned kernel (any samplePointSize:
+  // FftMethod.cpp:1680-1720 takes it from a ROS parameter) runs on the size cv::phaseCorrelate pads to, M = getOptimalDFTSize(N) -- the
+  // planned kernel or, where the padded patch does not fit one CU's LDS (M > 135), the planned pipeline through HBM scratch
+  mof::PcPlan plan;
+  FftRoute route;
+  if (!mof::fft_route(c->patch_size, c->peak_model, mof::FftKnobs{}, &plan, &route))
+    return fail(MOF_ERR_UNSUPPORTED, "patch_size %d pads to %d: beyond the planned transforms (<= 960)", c->patch_size,
+                mof::pc_optimal_dft_size(c->patch_size));
+  // useOCL=true plans radix-{2,3,4,5,8} passes for the patch size itself and never pads (FftMethod.cpp:481-539, :787-816):
+  // sizes with another prime factor have no OpenCL plan in the reference either; its CCS packing assumes an even size
+  if (route.family != FftRoute::TUNED && c->peak_model == MOF_PEAK_OCL && (plan.m != plan.n || (plan.n & 1)))
+    return fail(MOF_ERR_UNSUPPORTED, "peak_model MOF_PEAK_OCL needs an even patch_size of the form 2^a 3^b 5^c, up to 960 (the "
+                "reference's OpenCL branch cannot plan %d either)", c->patch_size);
   if (c->origin_x + (long)(c->grid_x - 1) * c->stride_x + c->patch_size > c->frame_width ||
       c->origin_y + (long)(c->grid_y - 1) * c->stride_y + c->patch_size > c->frame_height)
     return fail(MOF_ERR_BAD_ARG, "patch grid leaves the frame");
@@ -549,7 +558,7 @@ int mof_fft_create(const mof_fft_config* cfg, mof_fft_engine** out) try {
   if (!e) return fail(MOF_ERR_NO_MEMORY, "out of host memory");
   e->cfg = *cfg;
   e->frame_bytes = (size_t)cfg->frame_width * cfg->frame_height;
-  if (!fft_route(*cfg, &e->plan, &e->route))  // (validate_fft has checked that a plan exists)
+  if (!mof::fft_route(cfg->patch_size, cfg->peak_model, mof::fft_knobs(), &e->plan, &e->route))  // (validate_fft has checked that a plan exists)
     return fail(MOF_ERR_UNSUPPORTED, "no plan for patch_size %d", cfg->patch_size);
   const FftRoute& r = e->route;
   std::vector<float> tw = mof::twiddle_table(r.m);
@@ -561,18 +570,11 @@ int mof_fft_create(const mof_fft_config* cfg, mof_fft_engine** out) try {
     HIP_TRY(mof::fill_on(e->stream, frame, 0, e->frame_bytes));
   }
   HIP_TRY(mof::alloc_all(e->d_out, res, e->h_out, res, e->d_quality, res, e->h_quality, res, e->h_stage, e->frame_bytes));
-  // the kernels the route can launch (a video's half-tile form runs at half_m whenever that is set)
-  if (r.half_m > 0 || r.video == FftRoute::HALF_SEQ) HIP_TRY(mof::pc_configure_half(r.half_m > 0 ? r.half_m : r.video_m));
+  HIP_TRY(configure_route(r));
   if (r.family == FftRoute::LARGE) {
     HIP_TRY(e->fence.create());
     HIP_TRY(large_alloc(e.get(), cfg->grid_x * cfg->grid_y));  // one frame pair; a batch grows it to a whole pass
-  } else if (r.family == FftRoute::PLANNED) {
-    HIP_TRY(mof::pc_configure_generic());
-  } else {
-    HIP_TRY(mof::pc_configure(r.m));
   }
-  if (r.video == FftRoute::SEQ) HIP_TRY(mof::pc_configure_sequence());
-  if (r.video == FftRoute::SEQ_HALF) HIP_TRY(mof::pc_configure_sequence_half(r.m));
   *out = e.release();
   return MOF_OK;
 } catch (const std::bad_alloc&) {
@@ -580,11 +582,7 @@ int mof_fft_create(const mof_fft_config* cfg, mof_fft_engine** out) try {
 }
 
 const char* mof_fft_kernel_variant(const mof_fft_engine* e) {
-  if (!e) return "";
-  const FftRoute& r = e->route;
-  return r.half_m > 0 ? "planned-half"
-                      : (r.family == FftRoute::LARGE ? "planned-large"
-                                                     : (r.family == FftRoute::PLANNED ? "planned" : "stockham"));
+  return e ? e->route.variant : "";
 }
 
 void mof_fft_destroy(mof_fft_engine* e) {
@@ -812,11 +810,11 @@ static int fft_sequence(mof_fft_engine* e, const uint8_t* d_frames, size_t frame
     FIELD_TRY(launch_field(e, a, n_pairs, (hipStream_t)stream));
     return gate_end(e, a.out, a.quality, n_patches, (hipStream_t)stream, own_q);
   }
-  // MOF_FFT_SEQ_RUN: pairs a workgroup walks in time (0: the launchers pick the run length; pc_seq_half.hip takes 16)
-  static const int run_knob = [] { const char* v = getenv("MOF_FFT_SEQ_RUN"); const int r = v ? atoi(v) : 0; return r >= 1 ? r : 0; }();
+  // pairs a workgroup walks in time (MOF_FFT_SEQ_RUN; 0: the launchers pick the run length; pc_seq_half.hip takes 16)
+  const int run_knob = r.seq_run;
   // the run index rides gridDim.z (at most 65535 per launch): a very long video goes out in several launches
   const size_t per_pair = (size_t)e->cfg.grid_x * e->cfg.grid_y * 2;
-  const int max_pairs = 65535 * (run_knob ? run_knob : (r.video == FftRoute::HALF_SEQ ? 4 : (r.video == FftRoute::SEQ ? 2 : 16)));  // (the launchers' own run lengths are at least 4 / 2)
+  const int max_pairs = 65535 * (run_knob ? run_knob : r.min_run);
   for (int k0 = 0; k0 < n_pairs; k0 += max_pairs) {
     const int nk = n_pairs - k0 < max_pairs ? n_pairs - k0 : max_pairs;
     mof::PcArgs c = a;

@@ -51,7 +51,8 @@ int pc_optimal_dft_size(int n);                          // cv::getOptimalDFTSiz
 int pc_radix_chain(int m, int* radix, int max_stages);   // number of stages, -1 if m is not 5-smooth
 bool pc_build_plan(int n, PcPlan* out);                  // false: n needs the large-patch pipeline (or is < 2)
 hipError_t pc_configure_generic();
-hipError_t launch_pc_generic(const PcArgs& a, const PcPlan& plan, int n_pairs, hipStream_t stream);
+// use_static (FftRoute::planned_static): the compile-time plan of the transform size where there is one; false: the run-time plan
+hipError_t launch_pc_generic(const PcArgs& a, const PcPlan& plan, bool use_static, int n_pairs, hipStream_t stream);
 
 // ---- images too large for a CU (padded side m > 135): the planned pipeline through HBM scratch (pc_large_kernel.hip) ----
 bool pc_build_line_plan(int n, PcPlan* out);  // n, m, radix chain only (no LDS tile); false for n < 2 or m > 960
@@ -222,6 +223,46 @@ std::vector<SrTileBox> sr_tile_boxes(const std::vector<SrMapEntry>& map, int res
 
 bool sr_always_tuned(int res);             // 240, 256, 480: on the tuned transforms whatever MOF_SR_TUNED_ALL says
 bool sr_transform_size_tuned(int m, bool* exact_nyquist);  // the tuned transforms K5s / K6s / K7 exist for transform size m (sr_common.hpp: MOF_SR_TUNED_SIZES)
+
+// The MOF_FFT_* knobs of the FFT engine and MOF_PLANNED_STATIC (README), read once per process (mof_capi.hip: fft_knobs)
+struct FftKnobs {
+  int half = -1;               // MOF_FFT_HALF: -1 unset
+  bool force_planned = false;  // MOF_FFT_FORCE_PLANNED, MOF_FFT_FORCE_LARGE, MOF_FFT_SEQ_PAIRS, MOF_FFT_SEQ_HALF128: set, whatever the value
+  bool force_large = false;
+  bool seq_pairs = false;
+  bool seq_half128 = false;
+  bool half_seq_off = false;   // MOF_FFT_HALF_SEQ=0
+  bool large_tuned = true;     // MOF_FFT_LARGE_TUNED=0, MOF_FFT_LARGE_VIDEO=0 clear them
+  bool large_video = true;
+  int seq_run = 0;             // MOF_FFT_SEQ_RUN >= 1: pairs a workgroup of a video kernel walks in time; 0: the launchers pick
+  int large_pass = 0;          // MOF_FFT_LARGE_PASS > 0: frame pairs per pass of the large-patch scratch; 0: from the scratch's size
+  bool planned_static = true;  // MOF_PLANNED_STATIC=0: the planned kernel on its run-time plan also where a compile-time one exists
+};
+// Which kernels an FFT engine launches, decided once at create (fft_route)
+struct FftRoute {
+  enum Family { TUNED, PLANNED, LARGE };
+  enum Video { PAIRS, SEQ, SEQ_HALF, HALF_SEQ };
+  Family family = TUNED;    // what every launch can run: the hand-tuned K1 of the patch size, the planned LDS kernel
+                            // (pc_kernel_generic.hip), or -- padded patch too large for a CU -- the planned pipeline through HBM (pc_large_kernel.hip)
+  int m = 0;                // transform size: the patch size (TUNED) or the size cv::phaseCorrelate pads it to
+  int half_m = 0;           // > 0: full-resolution pair launches run the fused half-tile kernel of this size instead (pc_half_kernel.hip;
+                            //      cv::phaseCorrelate model only)
+  Video video = PAIRS;      // a video: the pair form on consecutive frames, K1s (pc_seq_kernel.hip), pc_seq_half.hip, or the half-tile
+  int video_m = 0;          // kernel's sequence form at transform size video_m
+  bool large_tuned = false; // LARGE, full resolution: the estimator's tuned K5s / K6s / K7 instead of L5 / L6 / L7
+  bool odd_tail = false;    // ... on a size whose Nyquist bins are not exact (the rows kernel's exact sums stand in)
+  bool large_video = false; // ... and a video transforms every frame once per pass
+  const char* variant = ""; // mof_fft_kernel_variant: "stockham", "planned", "planned-large", or "planned-half" wherever half_m > 0
+  int min_run = 0;          // the least run length the video form's launcher picks on its own (HALF_SEQ 4, SEQ 2, SEQ_HALF 16; PAIRS 0):
+                            // with the 65535 runs of a launch, the pairs a launch can take
+  int seq_run = 0;          // FftKnobs::seq_run, large_pass, planned_static as the launches read them
+  int large_pass = 0;
+  bool planned_static = true;
+};
+// Pure host code (no HIP call, no environment): the route of a patch size >= 2 under a peak model; *plan receives the plan of the planned
+// families. False: the patch pads beyond the planned transforms (> 960).
+bool fft_route(int patch_size, int peak_model, const FftKnobs& k, PcPlan* plan, FftRoute* r);
+const FftKnobs& fft_knobs();
 
 // The MOF_SR_* knobs of the estimator's engine (README), read once per process (mof_sr.hip: sr_knobs)
 struct SrKnobs {

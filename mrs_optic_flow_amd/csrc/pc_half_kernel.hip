@@ -787,43 +787,55 @@ hipError_t configure_half_size() {
   });
 }
 
+// a run-time padded size to its compile-time one -- f(pc_const<M>{}) -- over each of the two lists; hipErrorInvalidValue for a size the
+// list does not hold. Everything below is built on these two: a new size is one entry of its list.
+template <class F>
+hipError_t dispatch_half_pair_size(int m, F&& f) {
+  switch (m) {
+#define X(M) \
+  case M: return f(pc_const<M>{});
+    MOF_HALF_SIZES(X)
+#undef X
+    default: return hipErrorInvalidValue;
+  }
+}
+template <class F>
+hipError_t dispatch_half_video_only_size(int m, F&& f) {
+  switch (m) {
+#define X(M) \
+  case M: return f(pc_const<M>{});
+    MOF_HALF_SEQ_SIZES(X)
+#undef X
+    default: return hipErrorInvalidValue;
+  }
+}
+// ... and over both: a size is in one list at the most
+template <class F>
+hipError_t dispatch_half_size(int m, F&& f) {
+  return pc_half_supported(m) ? dispatch_half_pair_size(m, f) : dispatch_half_video_only_size(m, f);
+}
+
 }  // namespace
 
 bool pc_half_supported(int m) {
-  switch (m) {
-#define X(M) case M:
-    MOF_HALF_SIZES(X)
-#undef X
-    return true;
-    default: return false;
-  }
+  return dispatch_half_pair_size(m, [](auto) { return hipSuccess; }) == hipSuccess;
 }
 
 int pc_half_workgroups_per_cu(int m) {
-  switch (m) {
-#define X(M) case M: return HalfPlanOf<M>::HP.wgs_per_cu;
-    MOF_HALF_SIZES(X)
-    MOF_HALF_SEQ_SIZES(X)
-#undef X
-    default: return 0;
-  }
+  int wgs = 0;
+  (void)dispatch_half_size(m, [&wgs](auto ms) {
+    wgs = HalfPlanOf<ms>::HP.wgs_per_cu;
+    return hipSuccess;
+  });
+  return wgs;
 }
 
 // raises the dynamic-LDS limit of the ONE padded size `m` an engine will launch (pair form and, where it exists, video form; both
 // channel counts) on the calling thread's current device -- not of all ~60 instantiations: that loaded every code object at every
 // engine create, on every device of a shard group
 hipError_t pc_configure_half(int m) {
-  switch (m) {
-#define X(M) \
-  case M: return configure_half_size<M, true>();
-    MOF_HALF_SIZES(X)
-#undef X
-#define X(M) \
-  case M: return configure_half_size<M, false>();
-    MOF_HALF_SEQ_SIZES(X)
-#undef X
-    default: return hipErrorInvalidValue;
-  }
+  return pc_half_supported(m) ? dispatch_half_pair_size(m, [](auto ms) { return configure_half_size<ms, true>(); })
+                              : dispatch_half_video_only_size(m, [](auto ms) { return configure_half_size<ms, false>(); });
 }
 
 // a.downscale must be 1 and a.peak_model 0 (the caller keeps the other front ends on their pipelines); m = the padded size, n the patch
@@ -831,28 +843,17 @@ hipError_t launch_pc_half(const PcArgs& a_in, int m, int n, int n_pairs, hipStre
   if (a_in.downscale != 1 || a_in.peak_model != 0 || (a_in.channels != 1 && a_in.channels != 3) || n > m || n < 2) return hipErrorInvalidValue;
   return pc_split_pairs(a_in, n_pairs, [&](const PcArgs& c, int nk) {  // the pair index rides gridDim.z
     const dim3 g((unsigned)c.grid_x, (unsigned)c.grid_y, (unsigned)nk);
-    switch (m) {
-#define X(M)                                                                                                                             \
-  case M:                                                                                                                                \
-    return pc_dispatch_form<PC_FORMS_CH>(c, [&](auto, auto ch, auto) {                                                                   \
-      hipLaunchKernelGGL((pc_half_kernel<ch, M>), g, dim3((unsigned)HalfPlanOf<M>::T), (size_t)HalfPlanOf<M>::HP.lds_bytes, stream, c, n, nk, 1); \
-      return hipGetLastError();                                                                                                          \
+    return dispatch_half_pair_size(m, [&](auto ms) {
+      return pc_dispatch_form<PC_FORMS_CH>(c, [&](auto, auto ch, auto) {
+        hipLaunchKernelGGL((pc_half_kernel<ch, ms>), g, dim3((unsigned)HalfPlanOf<ms>::T), (size_t)HalfPlanOf<ms>::HP.lds_bytes, stream, c, n, nk, 1);
+        return hipGetLastError();
+      });
     });
-      MOF_HALF_SIZES(X)
-#undef X
-      default: return hipErrorInvalidValue;
-    }
   });
 }
 
 bool pc_half_sequence_supported(int m) {
-  switch (m) {
-#define X(M) case M:
-    MOF_HALF_SEQ_SIZES(X)
-#undef X
-    return true;
-    default: return pc_half_supported(m) && half_seq_size(m);
-  }
+  return dispatch_half_size(m, [](auto ms) { return half_seq_size(ms) ? hipSuccess : hipErrorInvalidValue; }) == hipSuccess;
 }
 
 // the video form: a.cur = frame 0 of the launch's first pair, frame f at a.cur + f * a.cur_stride; n_pairs pairs in runs of `run`
@@ -876,21 +877,15 @@ hipError_t launch_pc_half_sequence(const PcArgs& a, int m, int n, int n_pairs, i
   PcArgs c = a;
   c.total = n_pairs * a.grid_x * a.grid_y;
   const dim3 g((unsigned)c.grid_x, (unsigned)c.grid_y, (unsigned)n_runs);
-  switch (m) {
-#define X(M)                                                                                                                               \
-  case M:                                                                                                                                  \
-    if constexpr (half_seq_size(M))                                                                                                        \
-      return pc_dispatch_form<PC_FORMS_CH>(c, [&](auto, auto ch, auto) {                                                                   \
-        hipLaunchKernelGGL((pc_half_kernel<ch, M, true>), g, dim3((unsigned)HalfPlanOf<M>::T), (size_t)HalfPlanOf<M>::HP.lds_bytes, stream, c, n, n_pairs, run); \
-        return hipGetLastError();                                                                                                          \
-      });                                                                                                                                  \
-    else                                                                                                                                   \
+  return dispatch_half_size(m, [&](auto ms) {
+    if constexpr (half_seq_size(ms))
+      return pc_dispatch_form<PC_FORMS_CH>(c, [&](auto, auto ch, auto) {
+        hipLaunchKernelGGL((pc_half_kernel<ch, ms, true>), g, dim3((unsigned)HalfPlanOf<ms>::T), (size_t)HalfPlanOf<ms>::HP.lds_bytes, stream, c, n, n_pairs, run);
+        return hipGetLastError();
+      });
+    else
       return hipErrorInvalidValue;
-    MOF_HALF_SIZES(X)
-    MOF_HALF_SEQ_SIZES(X)
-#undef X
-    default: return hipErrorInvalidValue;
-  }
+  });
 }
 
 }  // namespace mof

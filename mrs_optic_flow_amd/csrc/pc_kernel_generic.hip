@@ -431,20 +431,21 @@ static hipError_t configure_generic_plan() {
   return pc_each_form<generic_forms<MS>>([](auto ds, auto ch, auto pk) { return pc_raise_lds(&pc_generic_kernel<ds, ch, pk, MS>, 160 * 1024); });
 }
 
+// the run-time plan, then every listed size through the dispatch the launch uses
 hipError_t pc_configure_generic() {
   hipError_t e = configure_generic_plan<0>();
-#define X(M) \
-  if (e == hipSuccess) e = configure_generic_plan<M>();
-  MOF_STATIC_SIZES(X)
-#undef X
+  for (int m = 1; m <= 135 && e == hipSuccess; ++m)  // (135: the largest tile of one CU, mof_kernels.h)
+    e = dispatch_static_size(m, [](auto ms) {
+      if constexpr (decltype(ms)::value != 0) return configure_generic_plan<decltype(ms)::value>();
+      return hipSuccess;
+    });
   return e;
 }
 
-hipError_t launch_pc_generic(const PcArgs& a_in, const PcPlan& pl, int n_pairs, hipStream_t stream) {
+// use_static = false (MOF_PLANNED_STATIC=0): the run-time plan also where a compile-time instantiation exists (A/B and the tests of that form)
+hipError_t launch_pc_generic(const PcArgs& a_in, const PcPlan& pl, bool use_static, int n_pairs, hipStream_t stream) {
   if (a_in.downscale == 4 && a_in.channels == 3) return hipErrorInvalidValue;
   if (pl.threads < 64 || pl.threads > 1024 || pl.lds_bytes > 160 * 1024) return hipErrorInvalidValue;
-  // MOF_PLANNED_STATIC=0: the run-time plan also where a compile-time instantiation exists (A/B and the tests of that form)
-  static const bool use_static = [] { const char* v = getenv("MOF_PLANNED_STATIC"); return !v || atoi(v) != 0; }();
   // gray and BGR8 frames (the latter promise the gray path's bits, include/mof.h) and the long-range mode (FftMethod.cpp:1905-2007; r06:
   // lr60 / lr96 ran the run-time-plan kernel at a third of the gray compile-time-plan rate) take the compile-time plan of the transform
   // size where there is one; the OpenCL model runs on run-time plans

@@ -7,11 +7,18 @@
 //   * the geometry tail's host forms (getRT / get2DT and their stages),
 //   * the estimator's create-time route (sr_route) for every even resolution against tests/golden/sr_route_table.txt, recorded from the
 //     code before SrRoute existed, and the one list of tuned transform sizes seen through each of its three users,
+//   * the FFT engine's create-time route (fft_route) for both peak models, every patch size 2 .. 1000 and every recorded knob setting
+//     against tests/golden/fft_route_table.txt, recorded from the code before fft_route was a pure function; what the route carries
+//     for its users; and the half-tile kernel's two size lists seen through each of their users,
 //   * the engines' resource owners (csrc/dev_mem.hpp) and the scratch-growth guard (csrc/capi_graph.hpp) with stub callables.
 // Where a device IS present the create() calls succeed and the engines are destroyed again.
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
+#include <map>
+#include <string>
 #include <type_traits>
 #include <utility>
 #include <vector>
@@ -194,6 +201,125 @@ int main() {
       listed += tuned;
     }
     CHECK(listed == 50);
+  }
+  // ---- the FFT engine's route, decided without a device: every (knob setting, peak model, patch size) of the recorded table ----
+  {
+    struct Row {
+      bool ok = false;
+      char fam[16] = "", video[16] = "";
+      int m = 0, half_m = 0, video_m = 0, large_tuned = 0, odd_tail = 0, large_video = 0;
+      bool same(const Row& o) const {
+        return ok == o.ok && !std::strcmp(fam, o.fam) && !std::strcmp(video, o.video) && m == o.m && half_m == o.half_m && video_m == o.video_m &&
+               large_tuned == o.large_tuned && odd_tail == o.odd_tail && large_video == o.large_video;
+      }
+    };
+    struct Section { std::string label; mof::FftKnobs k; std::map<std::pair<int, int>, Row> rows; };
+    std::vector<Section> sections;
+    std::FILE* f = std::fopen(MOF_GOLDEN_DIR "/fft_route_table.txt", "r");
+    CHECK(f != nullptr);
+    char line[512];
+    int rows = 0;
+    while (std::fgets(line, sizeof line, f)) {
+      if (line[0] == '#') continue;
+      if (std::strncmp(line, "knobs ", 6) == 0) {
+        // the knobs of a label, by the rules fft_knobs() reads the environment with
+        Section s;
+        s.label = std::string(line + 6, std::strcspn(line + 6, "\n"));
+        for (size_t at = 0; s.label != "default" && at < s.label.size();) {
+          const size_t eq = s.label.find('=', at), end = std::min(s.label.find(',', at), s.label.size());
+          CHECK(eq != std::string::npos && eq < end);
+          const std::string name = s.label.substr(at, eq - at);
+          const int v = std::atoi(s.label.c_str() + eq + 1);
+          if (name == "MOF_FFT_HALF") s.k.half = v;
+          else if (name == "MOF_FFT_FORCE_PLANNED") s.k.force_planned = true;
+          else if (name == "MOF_FFT_FORCE_LARGE") s.k.force_large = true;
+          else if (name == "MOF_FFT_SEQ_PAIRS") s.k.seq_pairs = true;
+          else if (name == "MOF_FFT_SEQ_HALF128") s.k.seq_half128 = true;
+          else if (name == "MOF_FFT_HALF_SEQ") s.k.half_seq_off = v == 0;
+          else if (name == "MOF_FFT_LARGE_TUNED") s.k.large_tuned = v != 0;
+          else if (name == "MOF_FFT_LARGE_VIDEO") s.k.large_video = v != 0;
+          else if (name == "MOF_FFT_SEQ_RUN") s.k.seq_run = v >= 1 ? v : 0;
+          else if (name == "MOF_FFT_LARGE_PASS") s.k.large_pass = v > 0 ? v : 0;
+          else if (name == "MOF_PLANNED_STATIC") s.k.planned_static = v != 0;
+          else CHECK(!"a knob the driver does not know");
+          at = end + 1;
+        }
+        sections.push_back(s);
+        continue;
+      }
+      CHECK(!sections.empty());
+      Row r;
+      int model, n;
+      const int got = std::sscanf(line, "%d %d %15s %d %d %15s %d %d %d %d", &model, &n, r.fam, &r.m, &r.half_m, r.video, &r.video_m, &r.large_tuned,
+                                  &r.odd_tail, &r.large_video);
+      CHECK((got == 3 && std::strcmp(r.fam, "unsupported") == 0) || got == 10);
+      r.ok = got == 10;
+      CHECK((model == 0 || model == 1) && n >= 2 && n <= 1000 && sections.back().rows.emplace(std::make_pair(model, n), r).second);
+      ++rows;
+    }
+    std::fclose(f);
+    CHECK(sections.size() == 15 && sections[0].label == "default" && sections[0].rows.size() == 2 * 999 && rows == 6097);
+    static const char* const families[] = {"TUNED", "PLANNED", "LARGE"};
+    static const char* const videos[] = {"PAIRS", "SEQ", "SEQ_HALF", "HALF_SEQ"};
+    static const int min_runs[] = {0, 2, 16, 4};
+    int supported[2] = {0, 0};
+    for (const Section& s : sections)
+      for (int model = 0; model <= 1; ++model)
+        for (int n = 2; n <= 1000; ++n) {
+          const auto key = std::make_pair(model, n);
+          const auto own = s.rows.find(key);
+          const Row& want = own != s.rows.end() ? own->second : sections[0].rows.at(key);  // (no row under a label: the default's)
+          CHECK(&s == &sections[0] || own == s.rows.end() || !want.same(sections[0].rows.at(key)));  // (listed: it differs)
+          mof::PcPlan plan{};
+          mof::FftRoute r;
+          const bool ok = mof::fft_route(n, model, s.k, &plan, &r);
+          if (&s == &sections[0]) {
+            // `unsupported` is what create answers: no plan, or a size the OpenCL model cannot plan (a status that no knob changes)
+            mof_fft_config c;
+            mof_fft_engine* e = nullptr;
+            CHECK(mof_fft_config_reference(&c, 480, 120, 80.0) == MOF_OK);
+            c.frame_width = c.frame_height = c.stride_x = c.stride_y = c.patch_size = n;
+            c.grid_x = c.grid_y = 1;
+            c.peak_model = model;
+            const int rc = mof_fft_create(&c, &e);
+            CHECK(want.ok ? (rc == MOF_OK || rc == MOF_ERR_NO_DEVICE) : (rc == MOF_ERR_UNSUPPORTED && e == nullptr));
+            if (rc == MOF_OK) mof_fft_destroy(e);
+            supported[model] += want.ok;
+          }
+          if (!want.ok) {
+            CHECK(model == MOF_PEAK_OCL || !ok);
+            continue;
+          }
+          CHECK(ok && std::strcmp(want.fam, families[r.family]) == 0 && r.m == want.m && r.half_m == want.half_m);
+          CHECK(std::strcmp(want.video, videos[r.video]) == 0 && r.video_m == want.video_m);
+          CHECK(r.large_tuned == (want.large_tuned != 0) && r.odd_tail == (want.odd_tail != 0) && r.large_video == (want.large_video != 0));
+          CHECK(r.family == mof::FftRoute::TUNED || (plan.n == n && plan.m == want.m));
+          // what the route carries for its users follows the route and the knobs
+          const char* variant = r.half_m > 0 ? "planned-half" : r.family == mof::FftRoute::LARGE ? "planned-large" : r.family == mof::FftRoute::PLANNED ? "planned" : "stockham";
+          CHECK(std::strcmp(r.variant, variant) == 0 && r.min_run == min_runs[r.video]);
+          CHECK(r.seq_run == s.k.seq_run && r.large_pass == s.k.large_pass && r.planned_static == s.k.planned_static);
+        }
+    CHECK(supported[0] == 959 && supported[1] == 65);
+    for (int n = 2; n <= 960; ++n) {
+      mof::FftKnobs k;
+      mof::PcPlan plan{};
+      mof::FftRoute r;
+      CHECK(mof::fft_route(n, MOF_PEAK_OPENCV, k, &plan, &r) && r.seq_run == 0 && r.large_pass == 0 && r.planned_static);
+      k.seq_run = 7;
+      k.large_pass = 5;
+      k.planned_static = false;
+      CHECK(mof::fft_route(n, MOF_PEAK_OPENCV, k, &plan, &r) && r.seq_run == 7 && r.large_pass == 5 && !r.planned_static);
+    }
+    // the half-tile kernel's two size lists, whoever is asked
+    int pair = 0, video = 0, planned = 0;
+    for (int m = 2; m <= 1000; ++m) {
+      const bool p = mof::pc_half_supported(m), v = mof::pc_half_sequence_supported(m), w = mof::pc_half_workgroups_per_cu(m) > 0;
+      CHECK(w == (p || v) && (p || !v || m == 50 || m == 54 || m == 108) && (v || !p || m == 162));
+      pair += p;
+      video += v;
+      planned += w;
+    }
+    CHECK(pair == 14 && video == 16 && planned == 17);
   }
   // ---- geometry tail, host forms ----
   {

@@ -1,6 +1,6 @@
 """GPU tests of the per-patch correlation quality on the kernel forms a knob selects and on forced pass / run / chunk boundaries.
 
-The MOF_FFT_* knobs are read once per process (mof_capi.hip fft_route, launch_large, fft_sequence; host_pipe.hpp), so every form runs
+The MOF_FFT_* knobs are read once per process (mof_capi.hip fft_knobs, behind fft_route; host_pipe.hpp), so every form runs
 in ONE child process with the environment set -- the convention of test_gpu_kernel_forms.py and test_gpu_generic.py. The child runs
 the route tests of test_gpu_fft_quality.py (the f64 oracle at 360 d, quality_cases.py; the shifts' bits with and without the quality
 output), which take their batches and the kernel_variant or bit relation they expect from MOF_QUALITY_PAIRS / _LONG_RANGE / _VIDEOS:

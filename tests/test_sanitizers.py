@@ -1,7 +1,8 @@
 """Sanitizer builds of the host side: AddressSanitizer + UndefinedBehaviorSanitizer over
 (1) the CPU oracle's whole C surface and (2) the product library's host code -- C-ABI argument / geometry validation,
 every entry point on a null engine, the scale/rotation estimator's host-built remap tables (compared with the oracle's
-inside the driver), the estimator's create-time route for every even resolution against tests/golden/sr_route_table.txt
+inside the driver), the estimator's create-time route for every even resolution against tests/golden/sr_route_table.txt,
+the FFT engine's for both peak models, every patch size and every recorded knob setting against tests/golden/fft_route_table.txt,
 and the geometry tail's host forms -- run WITHOUT a device (GPU sanitizers are not available on this
 pool; device code is compiled as usual, -Xarch_host keeps the instrumentation on the host pass). tests/san/Makefile."""
 import os
