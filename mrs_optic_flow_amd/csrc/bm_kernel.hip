@@ -553,21 +553,18 @@ static void scan16_plan(const BmArgs& a, int* bpw, int* waves_per_row, int* stri
 constexpr size_t SCAN16_Q_LDS = 64 * sizeof(uint32_t);  // the Q form's second reduce array
 
 template <int R>
-static hipError_t launch_scan16(const BmArgs& a, const BmQArgs* q, int n_pairs, hipStream_t stream) {
-  int bpw, wpr, sd;
-  size_t lds;
-  scan16_plan<R>(a, &bpw, &wpr, &sd, &lds);
-  if (lds > 64 * 1024) return hipErrorInvalidValue;
-  const dim3 grid((unsigned)n_pairs * a.grid_y * wpr);
+static hipError_t launch_scan16(const BmArgs& a, const BmQArgs* q, const BmRoute& r, int n_pairs, hipStream_t stream) {
+  const dim3 grid((unsigned)n_pairs * a.grid_y * r.waves_per_row);
   if (q) {
-    lds += SCAN16_Q_LDS;
+    const size_t lds = r.lds + SCAN16_Q_LDS;
+    // (per launch: an instantiation's LDS follows the geometry, and engines of different geometries share instantiations)
     if (lds > 64 * 1024) {
       hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&bm_scan16_kernel<R, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
       if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL((bm_scan16_kernel<R, true>), grid, dim3(64), lds, stream, a, sd, bpw, wpr, *q);
+    hipLaunchKernelGGL((bm_scan16_kernel<R, true>), grid, dim3(64), lds, stream, a, r.strip_dwords, r.bpw, r.waves_per_row, *q);
   } else {
-    hipLaunchKernelGGL((bm_scan16_kernel<R, false>), grid, dim3(64), lds, stream, a, sd, bpw, wpr, BmNoQ{});
+    hipLaunchKernelGGL((bm_scan16_kernel<R, false>), grid, dim3(64), r.lds, stream, a, r.strip_dwords, r.bpw, r.waves_per_row, BmNoQ{});
   }
   return hipGetLastError();
 }
@@ -674,17 +671,10 @@ hipError_t launch_bm_refine_sad(const uint8_t* A, const uint8_t* B, int W2, int 
 constexpr size_t BM_LDS_MAX = 160 * 1024;  // LDS of one CU on gfx950
 constexpr int BM_XB_MAX = 3;
 
-// Launch shape of the generic scan for one geometry.
-struct BmPlan {
-  int xb = 0, g = 8, bpw = 0, wpd = 0, slot_dwords = 0, threads = 0;
-  size_t lds = 0;
-  double cost = 1e30;  // modelled issue cycles per useful v_qsad (16 = the instruction's own rate)
+// Launch shape of the generic scan for one geometry: a form of the route and its blocks per lane (0: no block's window fits)
+struct BmPlan : BmRoute::Form {
+  int xb = 0;
 };
-
-static int bm_env_int(const char* name) {
-  const char* e = getenv(name);
-  return e ? atoi(e) : 0;
-}
 
 // LDS cycles of one window ds_read_b32 of a wave (two 32-lane groups, 32 banks; (ds_read_b32: 2 cycles conflict-free)
 static double bm_window_read_cycles(int D, int XGL, int xb, int wpd, int slot, int items) {
@@ -701,9 +691,9 @@ static double bm_window_read_cycles(int D, int XGL, int xb, int wpd, int slot, i
   return groups ? 2.0 * total / groups : 2.0;
 }
 
-static BmPlan bm_plan_search(int block, int radius, int grid_x) {
+// The search walks a few hundred candidates with a bank simulation each (~0.1-1 ms of host time): once per engine, at create (bm_route)
+static BmPlan bm_plan_search(int block, int radius, int grid_x, int forced_xb, int forced_bpw) {
   const int D = 2 * radius + 1, XG = (D + 3) / 4, WW = block + 2 * radius, CPD = block / 4;
-  const int forced_xb = bm_env_int("MOF_BM_XB"), forced_bpw = bm_env_int("MOF_BM_BPW");
   BmPlan best;
   for (int xb = 1; xb <= BM_XB_MAX; ++xb) {
     if (forced_xb && xb != forced_xb) continue;
@@ -746,27 +736,6 @@ static BmPlan bm_plan_search(int block, int radius, int grid_x) {
   return best;
 }
 
-// The search walks a few hundred candidates with a bank simulation each (~0.1-1 ms of host time): the last plan of each
-// thread is kept, an engine asks for the same geometry on every launch.
-static BmPlan bm_plan(int block, int radius, int grid_x) {
-  struct Key {
-    int block, radius, grid_x;
-  };
-  static thread_local Key key{-1, -1, -1};
-  static thread_local BmPlan plan;
-  if (key.block != block || key.radius != radius || key.grid_x != grid_x) {
-    plan = bm_plan_search(block, radius, grid_x);
-    key = Key{block, radius, grid_x};
-  }
-  return plan;
-}
-
-// Block sizes up to 128 (the reference's default sample_point_size is 120, config/default.yaml:32) and radii up to 48
-// (its own limit is 2r + 1 <= 50, FastSpacedBMMethod.cl:1), as long as one block's window fits the LDS.
-bool bm_config_supported(int block, int radius) {
-  return block >= 4 && block <= 128 && (block % 4) == 0 && radius >= 1 && radius <= 48 && bm_plan(block, radius, 0).xb > 0;
-}
-
 // The Q form's plan: the searched plan with 4 more bytes per slot (the per-block maximum), one block fewer per workgroup where that would
 // pass the LDS (bpw = 1 always fits: a slot is a multiple of 8 bytes, so 8 k + 12 <= 160 KB implies 8 k + 16 <= 160 KB).
 static BmPlan bm_plan_q(BmPlan p, int radius) {
@@ -781,7 +750,8 @@ static BmPlan bm_plan_q(BmPlan p, int radius) {
 }
 
 template <int XB, int G, bool Q>
-static hipError_t launch_bm_generic(const BmArgs& a, BmQ<Q> q, int n_pairs, const BmPlan& p, hipStream_t stream) {
+static hipError_t launch_bm_generic(const BmArgs& a, BmQ<Q> q, int n_pairs, const BmRoute::Form& p, hipStream_t stream) {
+  // (per launch: an instantiation's LDS follows the geometry, and engines of different geometries share instantiations)
   if (p.lds > 64 * 1024) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&bm_scan_kernel<XB, G, Q>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
     if (e != hipSuccess) return e;
@@ -793,8 +763,8 @@ static hipError_t launch_bm_generic(const BmArgs& a, BmQ<Q> q, int n_pairs, cons
 }
 
 template <int XB, bool Q>
-static hipError_t launch_bm_generic_g(const BmArgs& a, BmQ<Q> q, int n_pairs, const BmPlan& p, hipStream_t stream) {
-  switch (p.g) {
+static hipError_t launch_bm_generic_g(const BmArgs& a, BmQ<Q> q, int n_pairs, int g, const BmRoute::Form& p, hipStream_t stream) {
+  switch (g) {
     case 6: return launch_bm_generic<XB, 6, Q>(a, q, n_pairs, p, stream);
     case 7: return launch_bm_generic<XB, 7, Q>(a, q, n_pairs, p, stream);
     case 10: return launch_bm_generic<XB, 10, Q>(a, q, n_pairs, p, stream);
@@ -803,54 +773,86 @@ static hipError_t launch_bm_generic_g(const BmArgs& a, BmQ<Q> q, int n_pairs, co
 }
 
 template <bool Q>
-static hipError_t launch_bm_generic_xb(const BmArgs& a, BmQ<Q> q, int n_pairs, const BmPlan& p, hipStream_t stream) {
-  switch (p.xb) {
-    case 1: return launch_bm_generic_g<1, Q>(a, q, n_pairs, p, stream);
-    case 2: return launch_bm_generic_g<2, Q>(a, q, n_pairs, p, stream);
-    default: return launch_bm_generic_g<3, Q>(a, q, n_pairs, p, stream);
+static hipError_t launch_bm_generic_xb(const BmArgs& a, BmQ<Q> q, int n_pairs, const BmRoute& r, hipStream_t stream) {
+  const BmRoute::Form& p = Q ? r.q : r.plain;
+  switch (r.xb) {
+    case 1: return launch_bm_generic_g<1, Q>(a, q, n_pairs, r.g, p, stream);
+    case 2: return launch_bm_generic_g<2, Q>(a, q, n_pairs, r.g, p, stream);
+    default: return launch_bm_generic_g<3, Q>(a, q, n_pairs, r.g, p, stream);
   }
 }
 
-// Q form iff a quality pointer was given or the gate is armed; with neither, the launch of the engine without them
-hipError_t launch_bm_scan(const BmArgs& a, const BmQArgs& qa, int n_pairs, hipStream_t stream) {
-  const bool Q = qa.quality != nullptr || bm_gate_armed(qa);
-  if (fast16_ok(a) && !getenv("MOF_BM_GENERIC")) {
-    hipError_t err = hipErrorInvalidValue;
-    scan16_dispatch(a.radius, [&](auto r) { err = launch_scan16<decltype(r)::value>(a, Q ? &qa : nullptr, n_pairs, stream); });
-    return err;
+const BmKnobs& bm_knobs() {
+  static const BmKnobs k = [] {
+    BmKnobs r;
+    const char* v;
+    r.generic = getenv("MOF_BM_GENERIC") != nullptr;
+    if ((v = getenv("MOF_BM_XB"))) r.xb = atoi(v);
+    if ((v = getenv("MOF_BM_BPW"))) r.bpw = atoi(v);
+    if ((v = getenv("MOF_BM_G"))) r.g = atoi(v);
+    r.verbose = getenv("MOF_BM_VERBOSE") != nullptr;
+    return r;
+  }();
+  return k;
+}
+
+bool bm_route(int block, int step, int radius, int grid_x, const BmKnobs& k, BmRoute* r) {
+  *r = BmRoute{};
+  r->verbose = k.verbose;
+  BmArgs a{};
+  a.block = block, a.step = step, a.radius = radius, a.grid_x = grid_x, a.grid_y = 1;
+  if (grid_x > 0 && !k.generic && fast16_ok(a)) {
+    r->scan16 = true;
+    scan16_dispatch(radius, [&](auto rr) { scan16_plan<decltype(rr)::value>(a, &r->bpw, &r->waves_per_row, &r->strip_dwords, &r->lds); });
+    return true;
   }
-  BmPlan p = bm_plan(a.block, a.radius, a.grid_x);
-  if (p.xb == 0) return hipErrorInvalidValue;
-  if (Q) p = bm_plan_q(p, a.radius);
+  const BmPlan p = bm_plan_search(block, radius, grid_x, k.xb, k.bpw);
+  if (p.xb == 0) return false;
+  r->xb = p.xb;
+  r->plain = p;
+  r->q = bm_plan_q(p, radius);
   // row chunk: the length in {10, 8, 6, 7} that leaves the shortest ragged tail, longer on ties
-  const int CPD = a.block / 4, cand[4] = {10, 8, 6, 7};
+  const int CPD = block / 4, cand[4] = {10, 8, 6, 7};
   int best_tail = 1 << 30;
   for (int g : cand) {
     if (g > CPD && CPD >= 6) continue;
     const int tail = CPD % g;
-    if (tail < best_tail) best_tail = tail, p.g = g;
+    if (tail < best_tail) best_tail = tail, r->g = g;
   }
-  if (const int fg = bm_env_int("MOF_BM_G")) p.g = fg;
-  if (getenv("MOF_BM_VERBOSE"))
-    fprintf(stderr, "mof: block scan plan xb %d g %d bpw %d wpd %d threads %d lds %zu cost %.1f\n", p.xb, p.g, p.bpw, p.wpd, p.threads, p.lds, p.cost);
-  return Q ? launch_bm_generic_xb<true>(a, qa, n_pairs, p, stream) : launch_bm_generic_xb<false>(a, BmNoQ{}, n_pairs, p, stream);
+  if (k.g) r->g = k.g;
+  return true;
 }
 
-// the launch shape launch_bm_scan would use, without a device (host tests of the LDS arithmetic): {scan16, blocks per workgroup, threads, LDS bytes}
-bool bm_scan_plan(int block, int step, int radius, int grid_x, bool quality, int out[4]) {
-  BmArgs a{};
-  a.block = block, a.step = step, a.radius = radius, a.grid_x = grid_x, a.grid_y = 1;
-  if (grid_x > 0 && fast16_ok(a) && !getenv("MOF_BM_GENERIC")) {
-    int bpw = 0, wpr = 0, sd = 0;
-    size_t lds = 0;
-    scan16_dispatch(radius, [&](auto r) { scan16_plan<decltype(r)::value>(a, &bpw, &wpr, &sd, &lds); });
-    out[0] = 1, out[1] = bpw, out[2] = 64, out[3] = (int)(lds + (quality ? SCAN16_Q_LDS : 0));
-    return true;
+// Q form iff a quality pointer was given or the gate is armed; with neither, the launch of the engine without them
+hipError_t launch_bm_scan(const BmArgs& a, const BmQArgs& qa, const BmRoute& r, int n_pairs, hipStream_t stream) {
+  const bool Q = qa.quality != nullptr || bm_gate_armed(qa);
+  if (r.scan16) {
+    hipError_t err = hipErrorInvalidValue;
+    scan16_dispatch(a.radius, [&](auto rr) { err = launch_scan16<decltype(rr)::value>(a, Q ? &qa : nullptr, r, n_pairs, stream); });
+    return err;
   }
-  BmPlan p = bm_plan_search(block, radius, grid_x);
-  if (p.xb == 0) return false;
-  if (quality) p = bm_plan_q(p, radius);
-  out[0] = 0, out[1] = p.bpw, out[2] = p.threads, out[3] = (int)p.lds;
+  if (r.xb == 0) return hipErrorInvalidValue;
+  if (r.verbose) {
+    const BmRoute::Form& p = Q ? r.q : r.plain;
+    fprintf(stderr, "mof: block scan plan xb %d g %d bpw %d wpd %d threads %d lds %zu cost %.1f\n", r.xb, r.g, p.bpw, p.wpd, p.threads, p.lds, p.cost);
+  }
+  return Q ? launch_bm_generic_xb<true>(a, qa, n_pairs, r, stream) : launch_bm_generic_xb<false>(a, BmNoQ{}, n_pairs, r, stream);
+}
+
+// Block sizes up to 128 (the reference's default sample_point_size is 120, config/default.yaml:32) and radii up to 48
+// (its own limit is 2r + 1 <= 50, FastSpacedBMMethod.cl:1), as long as one block's window fits the LDS: the generic search at any width
+bool bm_config_supported(int block, int radius) {
+  BmRoute r;
+  return block >= 4 && block <= 128 && (block % 4) == 0 && radius >= 1 && radius <= 48 && bm_route(block, 0, radius, 0, bm_knobs(), &r);
+}
+
+// the launch shape of a route, without a device (host tests of the LDS arithmetic): {scan16, blocks per workgroup, threads, LDS bytes}
+bool bm_scan_plan(int block, int step, int radius, int grid_x, bool quality, int out[4]) {
+  BmRoute r;
+  if (!bm_route(block, step, radius, grid_x, bm_knobs(), &r)) return false;
+  const BmRoute::Form& p = quality ? r.q : r.plain;
+  if (r.scan16) out[0] = 1, out[1] = r.bpw, out[2] = 64, out[3] = (int)(r.lds + (quality ? SCAN16_Q_LDS : 0));
+  else out[0] = 0, out[1] = p.bpw, out[2] = p.threads, out[3] = (int)p.lds;
   return true;
 }
 

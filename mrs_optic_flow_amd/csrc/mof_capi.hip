@@ -429,6 +429,7 @@ struct mof_bm_engine {
   mof::PinnedMem<uint32_t> h_q;
   // the match gate (mof_bm_set_gate): kernel arguments, no buffer -- block-matching batches keep "never pin"
   uint32_t max_min_sad = 0xffffffffu, min_sad_range = 0u;
+  mof::BmRoute route;  // which scan every launch runs and its shape (bm_route)
   mof::PinnedMem<uint8_t> h_stage;
   // BlockMethod::Refine scratch (allocated on first use): the two 2x images, nine SADs
   mof::DevMem<uint8_t> d_up[2];
@@ -1005,6 +1006,8 @@ int mof_bm_create(const mof_bm_config* cfg, mof_bm_engine** out) {
   std::unique_ptr<mof_bm_engine, BmDestroyNow> e(new (std::nothrow) mof_bm_engine());
   if (!e) return fail(MOF_ERR_NO_MEMORY, "out of host memory");
   e->cfg = *cfg;
+  if (!mof::bm_route(cfg->block_size, cfg->step_size, cfg->scan_radius, cfg->grid_x, mof::bm_knobs(), &e->route))
+    return fail(MOF_ERR_UNSUPPORTED, "block_size %d / scan_radius %d: no scan plan", cfg->block_size, cfg->scan_radius);
   e->frame_bytes = (size_t)cfg->frame_width * cfg->frame_height;
   const size_t nb = (size_t)cfg->grid_x * cfg->grid_y;
   HIP_TRY(e->stream.create());
@@ -1094,7 +1097,7 @@ int mof_bm_process_q(mof_bm_engine* e, const uint8_t* frame, size_t pitch, int8_
   mof::BmArgs a = bm_args(e, e->d_frames[cur_slot], 0, e->d_frames[e->prev_slot], 0, (size_t)e->cfg.frame_width,
                           e->d_dx, e->d_dy, e->d_mode);
   const mof::BmQArgs q = bm_qargs(e, quality ? e->d_q.get() : nullptr);
-  HIP_TRY(mof::launch_bm_scan(a, q, 1, e->stream));
+  HIP_TRY(mof::launch_bm_scan(a, q, e->route, 1, e->stream));
   HIP_TRY(mof::launch_bm_mode(a, q, n_invalid ? reinterpret_cast<int32_t*>(e->d_q + 3 * nb) : nullptr, 1, e->stream));
   HIP_TRY(hipMemcpyAsync(e->h_res, e->d_dx, nb, hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(hipMemcpyAsync(e->h_res + nb, e->d_dy, nb, hipMemcpyDeviceToHost, e->stream));
@@ -1183,7 +1186,7 @@ static int bm_batch(mof_bm_engine* e, const uint8_t* d_cur, size_t cur_stride, c
   hipStream_t s = (hipStream_t)stream;  // (a captured block-matching batch reads no engine-owned memory: no pin)
   mof::BmArgs a = bm_args(e, d_cur, cur_stride, d_prev, prev_stride, pitch, d_dx, d_dy, d_mode, channels);
   const mof::BmQArgs q = bm_qargs(e, d_quality);
-  HIP_TRY(mof::launch_bm_scan(a, q, n_pairs, s));
+  HIP_TRY(mof::launch_bm_scan(a, q, e->route, n_pairs, s));
   HIP_TRY(mof::launch_bm_mode(a, q, d_n_invalid, n_pairs, s));
   return MOF_OK;
 }

@@ -152,9 +152,38 @@ struct BmQArgs {
 constexpr int BM_INVALID = -128;  // MOF_BM_INVALID: outside every scan range (radius <= 48)
 inline bool bm_gate_armed(const BmQArgs& q) { return q.max_min_sad != 0xffffffffu || q.min_sad_range != 0u; }
 
+// The MOF_BM_* knobs of the scans (README), read once per process (bm_kernel.hip: bm_knobs). A default-constructed value: nothing set
+struct BmKnobs {
+  bool generic = false;   // MOF_BM_GENERIC set, whatever the value: 16 x 16 blocks on the generic scan too
+  int xb = 0, bpw = 0;    // MOF_BM_XB / MOF_BM_BPW != 0: the plan search held to that many blocks per lane / per workgroup
+  int g = 0;              // MOF_BM_G != 0: the row chunk, over the one chosen from the block size
+  bool verbose = false;   // MOF_BM_VERBOSE set: the plan line on stderr at every launch of the generic scan
+};
+// Everything a launch of the scan needs beside its arguments, decided once at create (bm_route)
+struct BmRoute {
+  bool scan16 = false;    // the 16 x 16 scan (block 16, step % 4 == 0, even radius <= 16, strip within 64 KB); else the generic scan
+  // scan16: blocks per wave, waves per block row, dwords per strip row, dynamic LDS of the plain form (the Q form: one more reduce array)
+  int bpw = 0, waves_per_row = 0, strip_dwords = 0;
+  size_t lds = 0;
+  // the generic scan: blocks per lane, row chunk (instantiated: 6, 7, 10, anything else as 8), and the launch shape without / with quality
+  int xb = 0, g = 8;
+  struct Form {
+    int bpw = 0, wpd = 0, slot_dwords = 0, threads = 0;
+    size_t lds = 0;
+    double cost = 1e30;   // modelled issue cycles per useful v_qsad (16 = the instruction's own rate)
+  } plain, q;
+  bool verbose = false;   // BmKnobs::verbose as the launches read it
+};
+// Pure host code (no HIP call, no environment, no static state): the route of a geometry; grid_x = 0: any width (one block per workgroup,
+// never scan16). False: no block's window fits the LDS.
+bool bm_route(int block, int step, int radius, int grid_x, const BmKnobs& k, BmRoute* r);
+const BmKnobs& bm_knobs();
+
+// the two below: projections of bm_route under bm_knobs()
 bool bm_config_supported(int block, int radius);
 bool bm_scan_plan(int block, int step, int radius, int grid_x, bool quality, int out[4]);
-hipError_t launch_bm_scan(const BmArgs& a, const BmQArgs& q, int n_pairs, hipStream_t stream);
+// the Q form iff q holds a quality pointer or an armed gate; r: bm_route of a's geometry
+hipError_t launch_bm_scan(const BmArgs& a, const BmQArgs& q, const BmRoute& r, int n_pairs, hipStream_t stream);
 hipError_t launch_bm_mode(const BmArgs& a, const BmQArgs& q, int32_t* n_invalid, int n_pairs, hipStream_t stream);
 // BlockMethod::Refine building blocks (K9 2x resize, K10 nine cut-out SADs)
 hipError_t launch_bm_resize2x(const uint8_t* src, size_t pitch, int w, int h, uint8_t* dst, hipStream_t stream);
@@ -271,6 +300,13 @@ struct SrKnobs {
   int seq_run = 0;        // MOF_SR_SEQ_RUN in 1 .. 4096: the fixed run of K6s; 0: chosen per pass
   int chunk = 0;          // MOF_SR_CHUNK: pairs per pass over mof_sr_config.batch_chunk (a value outside 1 .. 4096: the default); 0: unset
   int overlap = -1;       // MOF_SR_OVERLAP: 0 / 1 over mof_sr_config.pipeline_lanes; -1: unset
+  // the log-polar remap (K4), A/B runs and the tests of each form
+  bool lp_global = false; // MOF_SR_LP_GLOBAL != 0: the per-pixel kernel (weights fetched from L2) for every batch
+  bool lp_staged = true;  // MOF_SR_LP_STAGED=0: no LDS-staged source boxes, the table-in-LDS kernel instead
+  bool lp_super = true;   // MOF_SR_LP_SUPER=0: staged per wave also where a 16 x 16 super-tile's box would fit
+  bool lp_xcd = true;     // MOF_SR_LP_XCD=0: workgroups in plain order, not grouped by XCD
+  bool lp_long_ring = false;  // MOF_SR_LP_RING=16: the 16-deep staging ring also for maps whose boxes fit the 12-deep one
+  int lp_ipw = 0;         // MOF_SR_LP_IPW > 0: images per wave of the staged kernel; 0: from the batch size
 };
 // Which kernels an estimator launches and how large its buffers are, decided once at create (sr_route)
 struct SrRoute {
@@ -288,7 +324,34 @@ struct SrRoute {
 // resolution pads beyond the planned transforms.
 bool sr_route(int resolution, const SrKnobs& k, PcPlan* plan, SrRoute* r);
 int sr_candidates(int res);
-hipError_t launch_sr_logpolar(const SrLpArgs& a, int interp /*2 cubic, 4 lanczos4*/, int n_images, hipStream_t stream);
+// Which remap kernel an estimator's batches take under one interpolation, decided once at create (sr_lp_route) from the map's boxes
+struct SrLpRoute {
+  // PIXEL: one gather per destination pixel, weights from L2; TABLE: the weight table in LDS; WAVE / SUPER: tile-stationary with the
+  // source box of an 8 x 8 tile (one wave) / a 16 x 16 super-tile (four waves) staged in LDS
+  enum Form { PIXEL, TABLE, WAVE, SUPER };
+  Form form = PIXEL;
+  int interp = 2;         // 2 cubic, 4 Lanczos4
+  int res = 0;
+  int ring = 0;           // WAVE / SUPER: depth of the staging ring, 12 or 16
+  size_t lds = 0;         // WAVE / SUPER: dynamic LDS of a workgroup
+  int ipw = 0;            // SrKnobs::lp_ipw, lp_xcd as the plans read them
+  bool xcd = true;
+};
+// What one call launches (sr_lp_plan)
+struct SrLpPlan {
+  SrLpRoute::Form form = SrLpRoute::PIXEL;  // the form this batch takes: fewer than four staged images fall to TABLE, fewer than four images to PIXEL
+  int n_st = 0;           // images of that launch: all of them, or all but the last where last_pixel
+  bool last_pixel = false;  // WAVE / SUPER on a layout that is not whole dwords: the last image takes the per-pixel kernel (it has nothing behind it)
+  int ipw = 0, xcd_groups = 0;  // WAVE / SUPER: images per wave; image groups the workgroups are ordered by XCD over (0: plain order)
+  long grid = 0;          // workgroups (PIXEL: per image; TABLE: before the cap at the device's CU count)
+};
+// Pure host code (no HIP call, no environment, no static state). box_dwords_max / sbox_dwords_max: the largest per-tile / per-super-tile box
+// of the map under this interpolation's footprint (sr_tile_boxes); has_sboxes: the super-tile boxes exist (res % 16 == 0)
+SrLpRoute sr_lp_route(int res, int box_dwords_max, int sbox_dwords_max, bool has_sboxes, int interp, const SrKnobs& k);
+// dword_layout: row pitch and image stride of the source are whole dwords
+SrLpPlan sr_lp_plan(const SrLpRoute& r, int n_images, bool dword_layout);
+// a.boxes, a.wplanes [, a.sboxes] as r was made from
+hipError_t launch_sr_logpolar(const SrLpArgs& a, const SrLpRoute& r, int n_images, hipStream_t stream);
 // K7 + K8 alone (uses a.Dt, a.cand, a.twiddles, a.M, a.out)
 hipError_t launch_sr_peak(const SrPcArgs& a, int res, int n_pairs, hipStream_t stream);
 // Sequence pipeline (sr_seq_kernel.hip). Zh = the row half-spectra of ONE log-polar image, doubled and transposed:

@@ -52,6 +52,12 @@ const mof::SrKnobs& sr_knobs() {
     if ((v = getenv("MOF_SR_SEQ_RUN")) && atoi(v) >= 1 && atoi(v) <= 4096) r.seq_run = atoi(v);
     if ((v = getenv("MOF_SR_CHUNK"))) r.chunk = atoi(v) >= 1 && atoi(v) <= 4096 ? atoi(v) : kChunkDefault;
     if ((v = getenv("MOF_SR_OVERLAP"))) r.overlap = atoi(v) != 0;
+    r.lp_global = (v = getenv("MOF_SR_LP_GLOBAL")) && atoi(v) != 0;
+    r.lp_staged = !(v = getenv("MOF_SR_LP_STAGED")) || atoi(v) != 0;
+    r.lp_super = !((v = getenv("MOF_SR_LP_SUPER")) && atoi(v) == 0);
+    r.lp_xcd = !((v = getenv("MOF_SR_LP_XCD")) && atoi(v) == 0);
+    r.lp_long_ring = (v = getenv("MOF_SR_LP_RING")) && atoi(v) == 16;
+    if ((v = getenv("MOF_SR_LP_IPW"))) r.lp_ipw = atoi(v);
     return r;
   }();
   return k;
@@ -310,6 +316,7 @@ struct mof_sr_engine {
   bool first = true;             // :31
   double min_response = 0.0;     // mof_sr_set_min_response: 0 = the reference's gate alone
   SrRoute route;                 // which transforms every launch runs (sr_route)
+  mof::SrLpRoute lp_route[2];    // which remap kernel a batch takes (sr_lp_route): cubic, Lanczos4
   mof::PcPlan plan{};            // route.family TUNED_PAD / PLANNED: the line plan of the padded size route.m
   std::atomic<bool> busy{false};
   std::atomic<bool> graph_pinned{false};  // a batch call was captured into a HIP graph
@@ -521,6 +528,8 @@ int mof_sr_create(const mof_sr_config* cfg, mof_sr_engine** out) try {
   e->lds_per_wave[1] = lds_l;
   HIP_TRY(mof::upload(e->d_boxes[0], bc, e->stream));
   HIP_TRY(mof::upload(e->d_boxes[1], bl, e->stream));
+  for (int k = 0; k < 2; ++k)
+    e->lp_route[k] = mof::sr_lp_route(res, e->lds_per_wave[k] / 4, (k == 0 ? slds_c : slds_l) / 4, !sbc.empty(), k == 0 ? 2 : 4, sr_knobs());
   if (!sbc.empty()) {
     e->sbox_dwords[0] = slds_c / 4;
     e->sbox_dwords[1] = slds_l / 4;
@@ -570,15 +579,24 @@ int mof_sr_set_min_response(mof_sr_engine* e, double min_response) {
 
 double mof_sr_min_response(const mof_sr_engine* e) { return e ? e->min_response : 0.0; }
 
-static void lp_tables(const mof_sr_engine* e, int interp, mof::SrLpArgs* lp) {
+// The engine's half of a remap's arguments under one interpolation (2 cubic, 4 Lanczos4): the map and the tables lp_route[k] was made
+// from. The caller sets src / dst, the strides, pitch and zero_invalid.
+static mof::SrLpArgs lp_args(const mof_sr_engine* e, int interp) {
   const int k = interp == 2 ? 0 : 1;
-  lp->weights = k == 0 ? e->d_w_cubic : e->d_w_lanczos;
-  lp->wplanes = e->d_wp[k];
-  lp->sboxes = e->d_sboxes[k];
-  lp->sbox_dwords_max = e->sbox_dwords[k];
-  lp->boxes = e->d_boxes[k];
-  lp->lds_per_wave = e->lds_per_wave[k];
-  lp->box_dwords_max = e->lds_per_wave[k] / 4;
+  mof::SrLpArgs lp{};
+  lp.map = e->d_map;
+  lp.res = e->cfg.resolution;
+  lp.weights = k == 0 ? e->d_w_cubic : e->d_w_lanczos;
+  lp.wplanes = e->d_wp[k];
+  lp.sboxes = e->d_sboxes[k];
+  lp.sbox_dwords_max = e->sbox_dwords[k];
+  lp.boxes = e->d_boxes[k];
+  lp.lds_per_wave = e->lds_per_wave[k];
+  lp.box_dwords_max = e->lds_per_wave[k] / 4;
+  return lp;
+}
+static hipError_t remap(const mof_sr_engine* e, const mof::SrLpArgs& lp, int interp, int n_images, hipStream_t s) {
+  return mof::launch_sr_logpolar(lp, e->lp_route[interp == 2 ? 0 : 1], n_images, s);
 }
 
 static mof::SrPcArgs pc_args(const mof_sr_engine* e, double* out, double* quality) {
@@ -622,17 +640,12 @@ int mof_sr_process_q(mof_sr_engine* e, const uint8_t* frame, size_t pitch, doubl
   const size_t nn = (size_t)res * res, zh_bytes = e->route.zh_floats * sizeof(float);
   for (int y = 0; y < res; ++y) std::memcpy(e->h_stage + (size_t)y * res, frame + (size_t)y * pitch, (size_t)res);
   HIP_TRY(hipMemcpyAsync(e->d_frame, e->h_stage, nn, hipMemcpyHostToDevice, e->stream));
-  mof::SrLpArgs lp{};
+  const int interp = e->first ? 2 : 4;  // INTER_CUBIC for the very first frame (:45), INTER_LANCZOS4 from then on (:112)
+  mof::SrLpArgs lp = lp_args(e, interp);
   lp.src = e->d_frame;
-  lp.src_stride = 0;
   lp.pitch = (size_t)res;
   lp.dst = e->d_temp_im;
-  lp.dst_stride = 0;
-  lp.map = e->d_map;
-  lp.res = res;
-  const int interp = e->first ? 2 : 4;  // INTER_CUBIC for the very first frame (:45), INTER_LANCZOS4 from then on (:112)
-  lp_tables(e, interp, &lp);
-  HIP_TRY(mof::launch_sr_logpolar(lp, interp, 1, e->stream));
+  HIP_TRY(remap(e, lp, interp, 1, e->stream));
   HIP_TRY(e->fence.acquire(e->stream));
   // tempIm.convertTo(CV_32FC1) (:47, :115) + the row half of the forward DFT of cv::phaseCorrelate (:117): K5s
   HIP_TRY(rows_real(e, e->d_temp_im, 0, e->d_Zt, 0, 1, e->stream));
@@ -706,21 +719,22 @@ int mof_sr_process_sequence_device_q(mof_sr_engine* e, const uint8_t* d_frames, 
   bool first = e->first;
   int gated_total = 0;
   const int rc = [&]() -> int {
-    mof::SrLpArgs lp{};
-    lp.zero_invalid = 1;  // tempIm starts as zeros (:27) and transparent pixels never change: write the zeros here
-    lp.pitch = pitch;
-    lp.map = e->d_map;
-    lp.res = res;
-    lp.src_stride = frame_stride;
-    lp.dst_stride = nn;
+    // tempIm starts as zeros (:27) and transparent pixels never change: write the zeros here (zero_invalid)
+    auto frames = [&](int interp, int first_frame, uint8_t* dst) {
+      mof::SrLpArgs lp = lp_args(e, interp);
+      lp.zero_invalid = 1;
+      lp.pitch = pitch;
+      lp.src = d_frames + (size_t)first_frame * frame_stride;
+      lp.src_stride = frame_stride;
+      lp.dst = dst;
+      lp.dst_stride = nn;
+      return lp;
+    };
     int done = 0;
     int carry = -1;  // slot of the previous pass whose spectra are `prev` for the next frame (-1: the engine's state)
     while (done < n_frames) {
       if (first) {  // the very first frame: INTER_CUBIC (:45), becomes prev (:48), returns (1, 0) (:74)
-        lp.src = d_frames + (size_t)done * frame_stride;
-        lp.dst = e->d_lp;
-        lp_tables(e, 2, &lp);
-        HIP_TRY(mof::launch_sr_logpolar(lp, 2, 1, s));
+        HIP_TRY(remap(e, frames(2, done, e->d_lp), 2, 1, s));
         HIP_TRY(rows_real(e, e->d_lp, nn, zh, zhf, 1, s));
         HIP_TRY(mof::launch_sr_identity(d_out + 4 * (size_t)done, d_quality ? d_quality + 2 * (size_t)done : nullptr, s));
         first = false;  // :73
@@ -733,10 +747,7 @@ int mof_sr_process_sequence_device_q(mof_sr_engine* e, const uint8_t* d_frames, 
       const int m = n_frames - done < C ? n_frames - done : C;
       carry = 0;
       if (m > 0) {
-        lp.src = d_frames + (size_t)done * frame_stride;
-        lp.dst = e->d_lp + nn;
-        lp_tables(e, 4, &lp);
-        HIP_TRY(mof::launch_sr_logpolar(lp, 4, m, s));  // INTER_LANCZOS4, :112 -- every frame once
+        HIP_TRY(remap(e, frames(4, done, e->d_lp + nn), 4, m, s));  // INTER_LANCZOS4, :112 -- every frame once
         HIP_TRY(rows_real(e, e->d_lp + nn, nn, zh + zhf, zhf, m, s));
         HIP_TRY(cols_seq(e, zh, zh + zhf, zhf, m, seq_run_for(e, m), s));
         // the pass's quality: the caller's array, or -- where the host walks the response gate below and needs it all the same -- the engine's
@@ -873,22 +884,18 @@ int mof_sr_process_batch_device_q(mof_sr_engine* e, const uint8_t* d_cur, size_t
     // (:112) onto the same zero-initialised tempIm; the transparent pixels are the same for both maps, so both
     // remaps simply write zeros there (zero_invalid) and the scratch needs no clearing pass
     if (two_lanes && chunk_no >= 2) HIP_TRY(hipStreamWaitEvent(sr, e->ev_fft[b], 0));  // buffer b is free again
-    mof::SrLpArgs lp{};
-    lp.zero_invalid = 1;
-    lp.pitch = pitch;
-    lp.map = e->d_map;
-    lp.res = res;
-    lp.dst_stride = 2 * nn;
-    lp.src = d_prev + (size_t)k0 * prev_stride;
-    lp.src_stride = prev_stride;
-    lp.dst = lp_buf + nn;
-    lp_tables(e, 2, &lp);
-    HIP_TRY(mof::launch_sr_logpolar(lp, 2, n, sr));
-    lp.src = d_cur + (size_t)k0 * cur_stride;
-    lp.src_stride = cur_stride;
-    lp.dst = lp_buf;
-    lp_tables(e, 4, &lp);
-    HIP_TRY(mof::launch_sr_logpolar(lp, 4, n, sr));
+    auto side = [&](int interp, const uint8_t* src, size_t stride, uint8_t* dst) {
+      mof::SrLpArgs lp = lp_args(e, interp);
+      lp.zero_invalid = 1;
+      lp.pitch = pitch;
+      lp.src = src + (size_t)k0 * stride;
+      lp.src_stride = stride;
+      lp.dst = dst;
+      lp.dst_stride = 2 * nn;
+      return lp;
+    };
+    HIP_TRY(remap(e, side(2, d_prev, prev_stride, lp_buf + nn), 2, n, sr));
+    HIP_TRY(remap(e, side(4, d_cur, cur_stride, lp_buf), 4, n, sr));
     if (two_lanes) {
       HIP_TRY(hipEventRecord(e->ev_lp[b], sr));
       HIP_TRY(hipStreamWaitEvent(s, e->ev_lp[b], 0));  // also the join: every remap precedes a wait on the caller's stream
@@ -916,17 +923,14 @@ int mof_sr_logpolar_batch_device(mof_sr_engine* e, const uint8_t* d_src, size_t 
   BusyGuard g(e->busy);
   if (!g.owned) return mof::capi_fail(MOF_ERR_BUSY, "engine busy");
   HIP_TRY(hipSetDevice(e->cfg.device));
-  mof::SrLpArgs lp{};
+  mof::SrLpArgs lp = lp_args(e, interpolation);
   lp.src = d_src;
   lp.src_stride = src_stride;
   lp.pitch = pitch;
   lp.dst = d_dst;
   lp.dst_stride = (size_t)res * res;
-  lp.map = e->d_map;
-  lp.res = res;
-  lp_tables(e, interpolation, &lp);
   if (mof::stream_capturing((hipStream_t)stream)) e->graph_pinned.store(true);  // the map and the tables are the engine's
-  HIP_TRY(mof::launch_sr_logpolar(lp, interpolation, n_images, (hipStream_t)stream));  // touches no engine scratch
+  HIP_TRY(remap(e, lp, interpolation, n_images, (hipStream_t)stream));  // touches no engine scratch
   return MOF_OK;
 }
 

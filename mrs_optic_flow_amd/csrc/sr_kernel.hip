@@ -574,86 +574,118 @@ bool sr_transform_size_tuned(int m, bool* exact_nyquist) {
 }
 bool sr_always_tuned(int res) { return res == 240 || res == 256 || res == 480; }  // (these stay tuned under MOF_SR_TUNED_ALL=0)
 
+// `work`: 16-tile units of the batch (SrLpPlan::grid); the CU count is asked per call (the devices of a shard group need not be alike)
 template <int K>
-static hipError_t launch_lp_lds(const SrLpArgs& a, int n_images, hipStream_t stream) {
+static hipError_t launch_lp_lds(const SrLpArgs& a, int n_images, long work, hipStream_t stream) {
   const int cus = pc_cu_count();
   hipError_t e = pc_raise_lds(&sr_logpolar_lds_kernel<K>, LpLds<K>::BYTES);
   if (e != hipSuccess) return e;
-  const int tiles = (a.res + 7) / 8;
-  const long total = (long)n_images * tiles * tiles;
-  const unsigned blocks = (unsigned)((total + 15) / 16 < cus ? (total + 15) / 16 : cus);
+  const unsigned blocks = (unsigned)(work < cus ? work : cus);
   hipLaunchKernelGGL(sr_logpolar_lds_kernel<K>, dim3(blocks), dim3(1024), LpLds<K>::BYTES, stream, a, n_images);
   return hipGetLastError();
 }
 
-hipError_t launch_sr_logpolar(const SrLpArgs& a, int interp, int n_images, hipStream_t stream) {
-  // MOF_SR_LP_GLOBAL=1: the first formulation (weights fetched from L2 per pixel), kept for A/B measurements; it also
-  // serves single images, where staging the table would cost more than it saves
-  static const bool global_w = [] { const char* e = getenv("MOF_SR_LP_GLOBAL"); return e && atoi(e) != 0; }();
-  // batches whose rows and frames keep one dword alignment: tile-stationary kernel with LDS-staged source boxes
-  // (MOF_SR_LP_STAGED=0 falls back to the table-in-LDS formulation, kept for A/B runs and unaligned layouts)
-  static const bool staged_on = [] { const char* e = getenv("MOF_SR_LP_STAGED"); return !e || atoi(e) != 0; }();
+// The create-time half: which form the map's boxes allow. PIXEL (MOF_SR_LP_GLOBAL=1) is the first formulation, kept for A/B measurements;
+// TABLE (MOF_SR_LP_STAGED=0, or a box beyond the staging ring) the table-in-LDS one; else the tile-stationary kernel with LDS-staged source
+// boxes: per 16 x 16 super-tile (four waves share a box) where the map's largest one fits the staging ring (256 x NR dwords), per wave otherwise.
+SrLpRoute sr_lp_route(int res, int box_dwords_max, int sbox_dwords_max, bool has_sboxes, int interp, const SrKnobs& k) {
   constexpr int NR = 16;
-  // (r06) layouts whose rows / frames are not whole dwords apart are staged from unaligned dwords: the last dword of the LAST row of an image may
-  // then reach up to three bytes past that image -- into the next one, harmless, except behind the last image of the caller's buffer. So the
-  // last image of such a batch takes the per-pixel kernel (`finish`), the others the staged one.
-  const bool dword_layout = ((a.pitch | a.src_stride) & 3) == 0;
-  const int n_st = dword_layout ? n_images : n_images - 1;  // images of the staged launch
-  auto finish = [&]() -> hipError_t {
-    if (n_st < n_images) {
-      SrLpArgs last = a;
-      last.src = a.src + (size_t)n_st * a.src_stride;
-      last.dst = a.dst + (size_t)n_st * a.dst_stride;
-      const dim3 grid1((unsigned)(((a.res + 31) / 32) * ((a.res + 7) / 8)), 1u);
-      if (interp == 2) hipLaunchKernelGGL(sr_logpolar_kernel<4>, grid1, dim3(256), 0, stream, last);
-      else hipLaunchKernelGGL(sr_logpolar_kernel<8>, grid1, dim3(256), 0, stream, last);
-    }
-    return hipGetLastError();
-  };
-  if (staged_on && !global_w && n_st >= 4 && a.boxes && a.wplanes && a.box_dwords_max <= 64 * NR) {
-    const int tiles = (a.res + 7) / 8, n_tiles = tiles * tiles;
+  constexpr int NRS = 12;  // the shorter ring where every box of the map fits it (480^2, M = 49.9: 2472 dwords of 3072)
+  SrLpRoute r;
+  r.interp = interp;
+  r.res = res;
+  r.ipw = k.lp_ipw;
+  r.xcd = k.lp_xcd;
+  if (k.lp_global) return r;
+  r.form = SrLpRoute::TABLE;
+  if (!k.lp_staged || box_dwords_max > 64 * NR) return r;
+  if (k.lp_super && has_sboxes && res % 16 == 0 && sbox_dwords_max <= 256 * NR) {
+    r.form = SrLpRoute::SUPER;
+    r.ring = !k.lp_long_ring && sbox_dwords_max <= 256 * NRS ? NRS : NR;
+    r.lds = sizeof(uint32_t) * (size_t)2 * 4 * lp_box_capacity((sbox_dwords_max + 3) / 4) + 512;  // two boxes + two output tiles
+  } else {
+    r.form = SrLpRoute::WAVE;
+    r.ring = NR;
+    r.lds = (size_t)4 * 2 * sizeof(uint32_t) * lp_box_capacity(box_dwords_max);
+  }
+  return r;
+}
+
+static unsigned lp_pixel_grid(int res) { return (unsigned)(((res + 31) / 32) * ((res + 7) / 8)); }
+
+// The per-call half. (r06) layouts whose rows / frames are not whole dwords apart are staged from unaligned dwords: the last dword of the LAST
+// row of an image may then reach up to three bytes past that image -- into the next one, harmless, except behind the last image of the caller's
+// buffer. So the last image of such a batch takes the per-pixel kernel, the others the staged one. Single images take the per-pixel kernel
+// too: staging the table would cost more than it saves.
+SrLpPlan sr_lp_plan(const SrLpRoute& r, int n_images, bool dword_layout) {
+  SrLpPlan p;
+  const int tiles = (r.res + 7) / 8, n_tiles = tiles * tiles;
+  const int n_st = dword_layout ? n_images : n_images - 1;  // images of a staged launch
+  if ((r.form == SrLpRoute::WAVE || r.form == SrLpRoute::SUPER) && n_st >= 4) {
+    p.form = r.form;
+    p.n_st = n_st;
+    p.last_pixel = n_st < n_images;
     // images per wave: long runs amortise the per-tile set-up; short ones keep the images that the resident waves
     // share within the L2 (MOF_SR_LP_IPW: diagnostic override)
-    static const int forced_ipw = [] { const char* e = getenv("MOF_SR_LP_IPW"); return e ? atoi(e) : 0; }();
-    const int ipw = forced_ipw > 0 ? forced_ipw : (n_st >= 128 ? 32 : (n_st >= 64 ? 16 : (n_st >= 16 ? 8 : 4)));
-    const int groups = (n_st + ipw - 1) / ipw;
-    static const bool xcd_off = [] { const char* e = getenv("MOF_SR_LP_XCD"); return e && atoi(e) == 0; }();
-    const int nq = (n_tiles + 3) / 4;
-    const int xcd_groups = (groups >= 8 && !xcd_off) ? groups : 0;  // fewer than 8 groups would leave XCDs idle
-    const unsigned blocks = xcd_groups ? (unsigned)(8 * ((groups + 7) / 8) * nq) : (unsigned)(((long)n_tiles * groups + 3) / 4);
-    // shared box per 16 x 16 super-tile (four waves) where the map's largest one fits the staging ring (256 x NR dwords)
-    static const bool super_off = [] { const char* e = getenv("MOF_SR_LP_SUPER"); return e && atoi(e) == 0; }();
-    if (!super_off && a.sboxes && a.res % 16 == 0 && a.sbox_dwords_max <= 256 * NR) {
+    p.ipw = r.ipw > 0 ? r.ipw : (n_st >= 128 ? 32 : (n_st >= 64 ? 16 : (n_st >= 16 ? 8 : 4)));
+    const int groups = (n_st + p.ipw - 1) / p.ipw;
+    p.xcd_groups = (groups >= 8 && r.xcd) ? groups : 0;  // fewer than 8 groups would leave XCDs idle
+    if (r.form == SrLpRoute::SUPER) {
       const int n_super = (tiles / 2) * (tiles / 2);
-      const unsigned sblocks = xcd_groups ? (unsigned)(8 * ((groups + 7) / 8) * n_super) : (unsigned)((long)n_super * groups);
-      const size_t slds = sizeof(uint32_t) * (size_t)2 * 4 * lp_box_capacity((a.sbox_dwords_max + 3) / 4) + 512;  // two boxes + two output tiles
-      constexpr int NRS = 12;  // the shorter ring where every box of the map fits it (480^2, M = 49.9: 2472 dwords of 3072)
-      // (MOF_SR_LP_RING=16 keeps the 16-deep form for maps that fit the short one: A/B runs and the tests of that form)
-      static const bool long_ring = [] { const char* e = getenv("MOF_SR_LP_RING"); return e && atoi(e) == 16; }();
-      const bool short_ring = !long_ring && a.sbox_dwords_max <= 256 * NRS;
-      if (interp == 2 && short_ring)
-        hipLaunchKernelGGL((sr_logpolar_staged_kernel<4, NRS, true>), dim3(sblocks), dim3(256), slds, stream, a, n_st, ipw, xcd_groups);
-      else if (interp == 2)
-        hipLaunchKernelGGL((sr_logpolar_staged_kernel<4, NR, true>), dim3(sblocks), dim3(256), slds, stream, a, n_st, ipw, xcd_groups);
-      else if (short_ring)
-        hipLaunchKernelGGL((sr_logpolar_staged_kernel<8, NRS, true>), dim3(sblocks), dim3(256), slds, stream, a, n_st, ipw, xcd_groups);
-      else
-        hipLaunchKernelGGL((sr_logpolar_staged_kernel<8, NR, true>), dim3(sblocks), dim3(256), slds, stream, a, n_st, ipw, xcd_groups);
-      return finish();
+      p.grid = p.xcd_groups ? (long)(8 * ((groups + 7) / 8) * n_super) : (long)n_super * groups;
+    } else {
+      const int nq = (n_tiles + 3) / 4;
+      p.grid = p.xcd_groups ? (long)(8 * ((groups + 7) / 8) * nq) : ((long)n_tiles * groups + 3) / 4;
     }
-    const size_t lds = (size_t)4 * 2 * sizeof(uint32_t) * lp_box_capacity(a.box_dwords_max);
-    if (interp == 2)
-      hipLaunchKernelGGL((sr_logpolar_staged_kernel<4, NR, false>), dim3(blocks), dim3(256), lds, stream, a, n_st, ipw, xcd_groups);
-    else
-      hipLaunchKernelGGL((sr_logpolar_staged_kernel<8, NR, false>), dim3(blocks), dim3(256), lds, stream, a, n_st, ipw, xcd_groups);
-    return finish();
+  } else if (r.form != SrLpRoute::PIXEL && n_images >= 4) {
+    p.form = SrLpRoute::TABLE;
+    p.n_st = n_images;
+    p.grid = ((long)n_images * n_tiles + 15) / 16;
+  } else {
+    p.n_st = n_images;
+    p.grid = lp_pixel_grid(r.res);
   }
-  if (!global_w && n_images >= 4) return interp == 2 ? launch_lp_lds<4>(a, n_images, stream) : launch_lp_lds<8>(a, n_images, stream);
-  const dim3 grid((unsigned)(((a.res + 31) / 32) * ((a.res + 7) / 8)), (unsigned)n_images);
-  if (interp == 2)
-    hipLaunchKernelGGL(sr_logpolar_kernel<4>, grid, dim3(256), 0, stream, a);
-  else
-    hipLaunchKernelGGL(sr_logpolar_kernel<8>, grid, dim3(256), 0, stream, a);
+  return p;
+}
+
+hipError_t launch_sr_logpolar(const SrLpArgs& a, const SrLpRoute& r, int n_images, hipStream_t stream) {
+  const SrLpPlan p = sr_lp_plan(r, n_images, ((a.pitch | a.src_stride) & 3) == 0);
+  const bool cubic = r.interp == 2;
+  auto pixel = [&](const SrLpArgs& args, int n) {
+    const dim3 grid(lp_pixel_grid(r.res), (unsigned)n);
+    if (cubic) hipLaunchKernelGGL(sr_logpolar_kernel<4>, grid, dim3(256), 0, stream, args);
+    else hipLaunchKernelGGL(sr_logpolar_kernel<8>, grid, dim3(256), 0, stream, args);
+  };
+  const dim3 grid((unsigned)p.grid);
+  switch (p.form) {
+    case SrLpRoute::SUPER:
+      if (cubic && r.ring == 12)
+        hipLaunchKernelGGL((sr_logpolar_staged_kernel<4, 12, true>), grid, dim3(256), r.lds, stream, a, p.n_st, p.ipw, p.xcd_groups);
+      else if (cubic)
+        hipLaunchKernelGGL((sr_logpolar_staged_kernel<4, 16, true>), grid, dim3(256), r.lds, stream, a, p.n_st, p.ipw, p.xcd_groups);
+      else if (r.ring == 12)
+        hipLaunchKernelGGL((sr_logpolar_staged_kernel<8, 12, true>), grid, dim3(256), r.lds, stream, a, p.n_st, p.ipw, p.xcd_groups);
+      else
+        hipLaunchKernelGGL((sr_logpolar_staged_kernel<8, 16, true>), grid, dim3(256), r.lds, stream, a, p.n_st, p.ipw, p.xcd_groups);
+      break;
+    case SrLpRoute::WAVE:
+      if (cubic)
+        hipLaunchKernelGGL((sr_logpolar_staged_kernel<4, 16, false>), grid, dim3(256), r.lds, stream, a, p.n_st, p.ipw, p.xcd_groups);
+      else
+        hipLaunchKernelGGL((sr_logpolar_staged_kernel<8, 16, false>), grid, dim3(256), r.lds, stream, a, p.n_st, p.ipw, p.xcd_groups);
+      break;
+    case SrLpRoute::TABLE:
+      return cubic ? launch_lp_lds<4>(a, n_images, p.grid, stream) : launch_lp_lds<8>(a, n_images, p.grid, stream);
+    case SrLpRoute::PIXEL:
+      pixel(a, n_images);
+      break;
+  }
+  if (p.last_pixel) {
+    SrLpArgs last = a;
+    last.src = a.src + (size_t)p.n_st * a.src_stride;
+    last.dst = a.dst + (size_t)p.n_st * a.dst_stride;
+    pixel(last, 1);
+  }
   return hipGetLastError();
 }
 

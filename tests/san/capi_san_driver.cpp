@@ -10,6 +10,9 @@
 //   * the FFT engine's create-time route (fft_route) for both peak models, every patch size 2 .. 1000 and every recorded knob setting
 //     against tests/golden/fft_route_table.txt, recorded from the code before fft_route was a pure function; what the route carries
 //     for its users; and the half-tile kernel's two size lists seen through each of their users,
+//   * the block matchers' route (bm_route) and the log-polar remap's route and per-call plan (sr_lp_route, sr_lp_plan) against
+//     tests/golden/bm_route_table.txt and sr_lp_route_table.txt, recorded from the launchers before the routes existed, and
+//     mof_bm_scan_plan as the projection of the route,
 //   * the engines' resource owners (csrc/dev_mem.hpp) and the scratch-growth guard (csrc/capi_graph.hpp) with stub callables.
 // Where a device IS present the create() calls succeed and the engines are destroyed again.
 #include <algorithm>
@@ -320,6 +323,186 @@ int main() {
       planned += w;
     }
     CHECK(pair == 14 && video == 16 && planned == 17);
+  }
+  // ---- the block matchers' route, decided without a device: every (knob setting, geometry) of the recorded table, every field ----
+  {
+    std::FILE* f = std::fopen(MOF_GOLDEN_DIR "/bm_route_table.txt", "r");
+    CHECK(f != nullptr);
+    auto project = [](const mof::BmRoute& r, bool quality, int out[4]) {
+      const mof::BmRoute::Form& p = quality ? r.q : r.plain;
+      if (r.scan16) out[0] = 1, out[1] = r.bpw, out[2] = 64, out[3] = (int)r.lds + (quality ? 256 : 0);
+      else out[0] = 0, out[1] = p.bpw, out[2] = p.threads, out[3] = (int)p.lds;
+    };
+    mof::BmKnobs k;
+    bool is_default = false;
+    int sections = 0, rows = 0, kinds[4] = {0, 0, 0, 0};
+    char line[256];
+    while (std::fgets(line, sizeof line, f)) {
+      if (line[0] == '#') continue;
+      if (std::strncmp(line, "knobs ", 6) == 0) {
+        const std::string label(line + 6, std::strcspn(line + 6, "\n"));
+        const size_t eq = label.find('=');
+        const int v = eq == std::string::npos ? 0 : std::atoi(label.c_str() + eq + 1);
+        k = mof::BmKnobs{};
+        is_default = label == "default";
+        if (is_default) {}
+        else if (label.rfind("MOF_BM_GENERIC=", 0) == 0) k.generic = true;
+        else if (label.rfind("MOF_BM_XB=", 0) == 0) k.xb = v;
+        else if (label.rfind("MOF_BM_BPW=", 0) == 0) k.bpw = v;
+        else if (label.rfind("MOF_BM_G=", 0) == 0) k.g = v;
+        else CHECK(!"a knob the driver does not know");
+        ++sections;
+        continue;
+      }
+      int b, s, r, gx, at = 0;
+      char kind;
+      CHECK(sections > 0 && std::sscanf(line, "%d %d %d %d %c%n", &b, &s, &r, &gx, &kind, &at) == 5);
+      const char* rest = line + at;
+      mof::BmRoute rt;
+      const bool ok = mof::bm_route(b, s, r, gx, k, &rt);
+      int plain[4] = {-1, -1, -1, -1}, q[4] = {-1, -1, -1, -1};
+      if (ok) project(rt, false, plain), project(rt, true, q);
+      if (kind == 'N') {
+        CHECK(!ok);
+        ++kinds[0];
+      } else if (kind == 'S') {
+        int bpw, wpr, sd;
+        size_t lds, ldsq;
+        CHECK(std::sscanf(rest, "%d %d %d %zu %zu", &bpw, &wpr, &sd, &lds, &ldsq) == 5);
+        CHECK(ok && rt.scan16 && gx > 0 && rt.bpw == bpw && rt.waves_per_row == wpr && rt.strip_dwords == sd && rt.lds == lds && ldsq == lds + 256);
+        CHECK(q[3] == (int)ldsq && !k.generic);
+        ++kinds[1];
+      } else if (kind == 'G') {
+        int xb, G, bpw, wpd, slot, thr, grid, bpwq, thrq, gridq;
+        size_t lds, ldsq;
+        char cost[32], mine[32];
+        CHECK(std::sscanf(rest, "%d %d %d %d %d %d %zu %d %31s %d %d %zu %d", &xb, &G, &bpw, &wpd, &slot, &thr, &lds, &grid, cost, &bpwq, &thrq, &ldsq, &gridq) == 13);
+        CHECK(ok && !rt.scan16 && rt.xb == xb && (rt.g == 6 || rt.g == 7 || rt.g == 10 ? rt.g : 8) == G && (k.g == 0 || rt.g == k.g));
+        CHECK(rt.plain.bpw == bpw && rt.plain.wpd == wpd && rt.plain.slot_dwords == slot && rt.plain.threads == thr && rt.plain.lds == lds);
+        CHECK(rt.q.bpw == bpwq && rt.q.wpd == wpd && rt.q.slot_dwords == slot && rt.q.threads == thrq && rt.q.lds == ldsq && rt.q.cost == rt.plain.cost);
+        CHECK((gx + bpw - 1) / bpw == grid && (gx + bpwq - 1) / bpwq == gridq);
+        std::snprintf(mine, sizeof mine, "%.9g", rt.plain.cost);
+        CHECK(std::strcmp(mine, cost) == 0);
+        ++kinds[2];
+      } else {
+        int o[4], oq[4];
+        CHECK(kind == 'P' && gx == 0 && std::sscanf(rest, "%d %d %d %d %d %d %d %d", &o[0], &o[1], &o[2], &o[3], &oq[0], &oq[1], &oq[2], &oq[3]) == 8);
+        CHECK(ok && !rt.scan16 && std::memcmp(o, plain, sizeof o) == 0 && std::memcmp(oq, q, sizeof oq) == 0);
+        ++kinds[3];
+      }
+      CHECK(rt.verbose == false);
+      if (is_default) {
+        // what mof_bm_scan_plan reports is the route's projection (this process runs with no MOF_BM_* set); no plan: create's refusal
+        int got[4] = {-1, -1, -1, -1};
+        const int rc = mof_bm_scan_plan(b, s, r, gx, 0, got);
+        CHECK(ok ? (rc == MOF_OK && std::memcmp(got, plain, sizeof got) == 0) : rc == MOF_ERR_BAD_ARG);
+        CHECK(mof_bm_scan_plan(b, s, r, gx, 1, got) == rc && (!ok || std::memcmp(got, q, sizeof got) == 0));
+      }
+      ++rows;
+    }
+    std::fclose(f);
+    CHECK(sections == 9 && rows == 2845 && kinds[0] == 160 && kinds[1] == 247 && kinds[2] == 2422 && kinds[3] == 16);
+    // the one plan family that fills the LDS: with two groups of x-shifts per lane 7 blocks take 163 828 bytes, the quality form takes 6
+    for (int gx : {7, 13, 14, 28}) {
+      mof::BmKnobs k2;
+      k2.xb = 2;
+      mof::BmRoute rt;
+      CHECK(mof::bm_route(100, 0, 4, gx, k2, &rt) && !rt.scan16 && rt.xb == 2);
+      CHECK(rt.plain.bpw == 7 && rt.plain.threads == 128 && rt.plain.lds == 163828 && rt.plain.lds + 4 * 7 > 160 * 1024);
+      CHECK(rt.q.bpw == 6 && rt.q.threads == 128 && rt.q.lds == (163828 - 12 * 7) / 7 * 6 + 16 * 6 && rt.q.lds <= 160 * 1024);
+    }
+    mof::BmKnobs kv;
+    kv.verbose = true;
+    mof::BmRoute rv;
+    CHECK(mof::bm_route(32, 0, 8, 8, kv, &rv) && rv.verbose);
+  }
+  // ---- the log-polar remap's route and plan, decided without a device: every row of the recorded table ----
+  {
+    std::FILE* f = std::fopen(MOF_GOLDEN_DIR "/sr_lp_route_table.txt", "r");
+    CHECK(f != nullptr);
+    static const char* const forms[] = {"PIXEL", "TABLE", "WAVE", "SUPER"};
+    static const int ns[] = {1, 3, 4, 5, 15, 16, 63, 64, 127, 128, 1024};
+    mof::SrKnobs k;
+    bool is_default = false;
+    int sections = 0, rows = 0, boxes_checked = 0;
+    char line[256];
+    while (std::fgets(line, sizeof line, f)) {
+      if (line[0] == '#') continue;
+      if (std::strncmp(line, "knobs ", 6) == 0) {
+        // the knobs of a label, by the rules sr_knobs() reads the environment with
+        const std::string label(line + 6, std::strcspn(line + 6, "\n"));
+        const size_t eq = label.find('=');
+        const int v = eq == std::string::npos ? 0 : std::atoi(label.c_str() + eq + 1);
+        k = mof::SrKnobs{};
+        is_default = label == "default";
+        if (is_default) {}
+        else if (label.rfind("MOF_SR_LP_GLOBAL=", 0) == 0) k.lp_global = v != 0;
+        else if (label.rfind("MOF_SR_LP_STAGED=", 0) == 0) k.lp_staged = v != 0;
+        else if (label.rfind("MOF_SR_LP_SUPER=", 0) == 0) k.lp_super = v != 0;
+        else if (label.rfind("MOF_SR_LP_RING=", 0) == 0) k.lp_long_ring = v == 16;
+        else if (label.rfind("MOF_SR_LP_XCD=", 0) == 0) k.lp_xcd = v != 0;
+        else if (label.rfind("MOF_SR_LP_IPW=", 0) == 0) k.lp_ipw = v;
+        else CHECK(!"a knob the driver does not know");
+        ++sections;
+        continue;
+      }
+      int res, interp, boxdw, sboxdw, has_sb, ring;
+      double M;
+      size_t lds;
+      char form[16];
+      unsigned long long want = 0;
+      CHECK(sections > 0 && std::sscanf(line, "%d %lf %d %d %d %d %15s %d %zu %llx", &res, &M, &interp, &boxdw, &sboxdw, &has_sb, form, &ring, &lds, &want) == 10);
+      if (is_default && (res <= 64 || res == 240 || res == 480)) {
+        // the recorded box sizes are what create computes
+        int bytes = 0;
+        const std::vector<mof::SrMapEntry> map = mof::sr_logpolar_map(res, M, 0);
+        mof::sr_tile_boxes(map, res, interp == 2 ? 4 : 8, &bytes, 8);
+        CHECK(bytes / 4 == boxdw && has_sb == (res % 16 == 0));
+        if (has_sb) {
+          mof::sr_tile_boxes(map, res, interp == 2 ? 4 : 8, &bytes, 16);
+          CHECK(bytes / 4 == sboxdw);
+        }
+        ++boxes_checked;
+      }
+      const mof::SrLpRoute r = mof::sr_lp_route(res, boxdw, sboxdw, has_sb != 0, interp, k);
+      CHECK(std::strcmp(forms[r.form], form) == 0 && r.ring == ring && r.lds == lds && r.res == res && r.interp == interp);
+      CHECK(r.ipw == k.lp_ipw && r.xcd == k.lp_xcd);
+      const unsigned pixel_grid = (unsigned)(((res + 31) / 32) * ((res + 7) / 8));
+      std::string text;
+      for (int n : ns)
+        for (int aligned = 1; aligned >= 0; --aligned) {
+          const mof::SrLpPlan p = mof::sr_lp_plan(r, n, aligned != 0);
+          char buf[160];
+          std::snprintf(buf, sizeof buf, "n%d a%d:", n, aligned);
+          text += buf;
+          if (p.form == mof::SrLpRoute::SUPER || p.form == mof::SrLpRoute::WAVE) {
+            CHECK(p.form == r.form && p.n_st == (aligned ? n : n - 1) && p.last_pixel == !aligned);
+            std::snprintf(buf, sizeof buf, " %c%d g%u l%zu n%d i%d x%d", p.form == mof::SrLpRoute::SUPER ? 'S' : 'W', r.ring, (unsigned)p.grid, r.lds, p.n_st, p.ipw,
+                          p.xcd_groups);
+            text += buf;
+            if (p.last_pixel) {
+              std::snprintf(buf, sizeof buf, " P g%u,1 s%d", pixel_grid, p.n_st);
+              text += buf;
+            }
+          } else if (p.form == mof::SrLpRoute::TABLE) {
+            CHECK(p.n_st == n && !p.last_pixel);
+            std::snprintf(buf, sizeof buf, " T g%u n%d", (unsigned)(p.grid < 256 ? p.grid : 256), n);  // (recorded with 256 CUs)
+            text += buf;
+          } else {
+            CHECK(p.n_st == n && !p.last_pixel && p.grid == (long)pixel_grid);
+            std::snprintf(buf, sizeof buf, " P g%u,%d s0", pixel_grid, n);
+            text += buf;
+          }
+          text += ";";
+        }
+      unsigned long long h = 1469598103934665603ull;
+      for (unsigned char c : text) h = (h ^ c) * 1099511628211ull;
+      if (h != want) std::fprintf(stderr, "remap plan of res %d M %g interp %d differs from the record: %s\n", res, M, interp, text.c_str());
+      CHECK(h == want);
+      ++rows;
+    }
+    std::fclose(f);
+    CHECK(sections == 7 && rows == 2836 && boxes_checked > 100);
   }
   // ---- geometry tail, host forms ----
   {

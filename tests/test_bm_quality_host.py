@@ -120,12 +120,30 @@ def test_quality_plan_lds_for_every_supported_geometry():
     assert supported > 1000 and smaller == 0, (supported, smaller)
 
 
-def test_quality_plan_takes_one_block_fewer_where_the_lds_is_full(monkeypatch):
+_LDS_FULL_SCRIPT = """
+import ctypes as C, sys
+sys.path.insert(0, {root!r})
+from mrs_optic_flow_amd import _capi
+lib = _capi.load()
+LDS_MAX = 160 * 1024
+def _plan(block, step, radius, grid_x, q):
+    out = (C.c_int * 4)()
+    rc = lib.mof_bm_scan_plan(block, step, radius, grid_x, q, out)
+    return None if rc != _capi.MOF_OK else tuple(out)
+for grid_x in (7, 13, 14, 28):
+    plain, q = _plan(100, 0, 4, grid_x, 0), _plan(100, 0, 4, grid_x, 1)
+    assert plain == (0, 7, 128, 163828) and plain[3] + 4 * plain[1] > LDS_MAX, plain
+    assert q[0] == 0 and q[1] == 6 and q[2] == 128 and q[3] == (163828 - 12 * 7) // 7 * 6 + 16 * 6 <= LDS_MAX, q
+print("lds full ok")
+"""
+
+
+def test_quality_plan_takes_one_block_fewer_where_the_lds_is_full():
     """The one plan family that reaches the limit (found by sweeping grid_x = 0 .. 64 under MOF_BM_XB = 1, 2, 3): block 100, radius 4 with two
-    groups of x-shifts per lane holds 7 blocks in 163 828 bytes; 28 more would pass 163 840, so the quality form launches 6"""
-    lib = _capi.load()
-    monkeypatch.setenv("MOF_BM_XB", "2")
-    for grid_x in (7, 13, 14, 28):
-        plain, q = _plan(lib, 100, 0, 4, grid_x, 0), _plan(lib, 100, 0, 4, grid_x, 1)
-        assert plain == (0, 7, 128, 163828) and plain[3] + 4 * plain[1] > LDS_MAX
-        assert q[0] == 0 and q[1] == 6 and q[2] == 128 and q[3] == (163828 - 12 * 7) // 7 * 6 + 16 * 6 <= LDS_MAX, q
+    groups of x-shifts per lane holds 7 blocks in 163 828 bytes; 28 more would pass 163 840, so the quality form launches 6. The knob is read
+    once per process, so the four geometries are asked in a child process that starts with it set."""
+    import subprocess
+    import sys
+    r = subprocess.run([sys.executable, "-c", _LDS_FULL_SCRIPT.format(root=ROOT)], capture_output=True, text=True, timeout=120,
+                       env=dict(os.environ, MOF_BM_XB="2"))
+    assert r.returncode == 0 and "lds full ok" in r.stdout, (r.stdout[-1500:], r.stderr[-1500:])

@@ -398,7 +398,7 @@ print("generic16 ok", checked)
 
 
 def test_block_16_on_the_generic_scan_with_saturated_sads(gpu):
-    """MOF_BM_GENERIC=1 sends 16 x 16 blocks through the generic scan (the knob is read in the launch path): the saturated cases of the
+    """MOF_BM_GENERIC=1 sends 16 x 16 blocks through the generic scan (the knob is read once per process): the saturated cases of the
     16 x 16 geometries once more in a child process with the knob set; MOF_BM_VERBOSE shows that the generic form really ran."""
     import subprocess
     import sys
