@@ -259,6 +259,70 @@ int mof_fft_process_batch_host_q(mof_fft_engine* e, const uint8_t* cur, size_t c
 int mof_fft_set_min_response(mof_fft_engine* e, double min_response);
 double mof_fft_min_response(const mof_fft_engine* e);
 
+/* Predicted-shift window offsets and a coarse-to-fine entry (no reference counterpart). A patch of side N cannot measure a shift
+ * beyond N / 2: past it the correlation peak wraps and the patch returns a finite, wrong shift that passes the validity rule. The
+ * reference answers with a mode switch (long_range_mode: quarter-scale frames, four times the range at a quarter of the resolution).
+ * Here the previous frame's patch window is read at a PREDICTED displacement, so that the correlation sees only the residual -- what
+ * PIV codes call a window offset. The prediction may come from the long-range pass (the coarse-to-fine entries below), from an IMU, or
+ * from the previous frame's flow.
+ *
+ * Sign is the reference's: positive means content moved right or down from prev to cur.
+ *
+ * - Prediction. Patch q of pair k has top-left (x0, y0), side n = patch_size, in frames of W x H. Its prediction is p = (p_x, p_y),
+ *   two int32.
+ * - Applied prediction. a is p clamped so that the previous window stays inside the frame:
+ *     a_x = min(max(p_x, x0 - (W - n)), x0)
+ *     a_y = min(max(p_y, y0 - (H - n)), y0)
+ *   The clamp is done without overflow for any int32 input.
+ *   The previous patch window is read at (x0 - a_x, y0 - a_y). The current window stays at (x0, y0).
+ * - Residual. r is exactly what the engine's existing kernels return for that pair of windows. This includes their NaN rule and, if
+ *   armed, the min_response gate.
+ * - Total. d = (a_x + r_x, a_y + r_y). It becomes (NaN, NaN) if r is NaN or if d_x^2 + d_y^2 > max_px_speed^2.
+ * - Other outputs. Quality outputs (response, peak) describe the residual's correlation surface. n_invalid counts NaN totals.
+ * - Zero prediction. With p = 0 everywhere, every output bit equals the plain entry's.
+ *   (A component of a that is 0 keeps the residual's bits -- the sign of a zero residual too --, and a patch with a = (0, 0) is not
+ *   gated a second time.)
+ *
+ * Coarse-to-fine, for the reference tiling only (the conditions of the long-range mode above):
+ * - The coarse pass is the existing long-range pass (gx_lr = grid_x / 4, gy_lr = grid_y / 4, integer-held gate).
+ * - Fine patch (i, j) takes the long-range patch (min(i/4, gx_lr - 1), min(j/4, gy_lr - 1)).
+ * - Its prediction is p = (rint(4 s_x), rint(4 s_y)), rounded in fp64, half to even.
+ * - A patch whose long-range shift is NaN gets (0, 0).
+ * - An armed response gate acts on both passes. A gated coarse patch predicts 0.
+ *
+ * How it runs (csrc/pc_offset_kernel.hip): a gather kernel copies every patch's displaced previous window into an engine-owned scratch
+ * frame at the patch's own place -- same pitch, frame stride H * pitch --, the engine's unchanged kernels run with prev = scratch, and a
+ * one-lane-per-patch kernel behind them (and behind the response gate) forms the total. The scratch follows the rules of the gate's
+ * buffer: it grows with the first call that needs more, never inside a graph capture (MOF_ERR_BAD_ARG) and never while a captured graph
+ * pins the engine (MOF_ERR_BUSY). mof_fft_reserve_pred(e, n_pairs) grows, ahead of a capture, everything a window-offset call of n_pairs
+ * pairs of DENSE frames (pitch = frame_width) needs -- this scratch, the large-patch pipeline's, the gate's buffer if the gate is armed
+ * at that moment; frames with a larger pitch: run one batch before capturing. A batch larger than ~1.5 GB of frames goes out in passes.
+ *
+ * d_pred_xy, d_applied_xy: int32 [pair][patch][2] (x, y); d_applied_xy may be null. d_out_xy, d_quality (nullable) as on
+ * mof_fft_process_batch_device_q. d_coarse_xy (nullable): the long-range shifts, [pair][mof_fft_long_range_patches][2] doubles in
+ * quarter-resolution pixels, after the gates. All asynchronous on `stream` and capturable.
+ * mof_fft_process_coarse_to_fine is the stateful form with processImage's frame chain: the first frame is correlated with itself,
+ * then previous <- current always (it shares the chain with mof_fft_process; mof_fft_reset restarts it).
+ *
+ * Limits, nothing is launched and no output is touched: MOF_ERR_UNSUPPORTED for a layout whose patches overlap (stride < patch_size
+ * on an axis with more than one patch: overlapping windows cannot share one displaced frame), for MOF_PEAK_OCL, and for
+ * coarse-to-fine off the reference tiling; MOF_ERR_BAD_ARG for null pointers or pitch < frame_width. Gray frames only; no sequence
+ * form (a displaced window cannot reuse the previous spectrum) and no shard-group form.
+ *
+ * The two definitions as pure host functions, no device needed: mof_fft_pred_clamp -- a of patch `patch` (index i + j * grid_x) of
+ * layout cfg for prediction (px, py); MOF_ERR_BAD_ARG if the patch is outside the grid or leaves the frame -- and
+ * mof_fft_pred_from_coarse -- p of a long-range shift (sx, sy). */
+int mof_fft_pred_clamp(const mof_fft_config* cfg, int patch, int32_t px, int32_t py, int32_t* ax, int32_t* ay);
+int mof_fft_pred_from_coarse(double sx, double sy, int32_t* px, int32_t* py);
+int mof_fft_reserve_pred(mof_fft_engine* e, int n_pairs);
+int mof_fft_process_batch_device_pred(mof_fft_engine* e, const uint8_t* d_cur, size_t cur_stride, const uint8_t* d_prev, size_t prev_stride,
+                                      size_t pitch, int n_pairs, const int32_t* d_pred_xy, double* d_out_xy, double* d_quality,
+                                      int32_t* d_applied_xy, void* stream);
+int mof_fft_process_coarse_to_fine_batch_device(mof_fft_engine* e, const uint8_t* d_cur, size_t cur_stride, const uint8_t* d_prev,
+                                                size_t prev_stride, size_t pitch, int n_pairs, double* d_out_xy, double* d_quality,
+                                                int32_t* d_applied_xy, double* d_coarse_xy, void* stream);
+int mof_fft_process_coarse_to_fine(mof_fft_engine* e, const uint8_t* frame, size_t pitch, double* out_xy, double* quality, int* n_invalid);
+
 /* Pinned (page-locked) host memory for callers that do not link HIP themselves: hipHostMalloc / hipHostFree / hipHostRegister /
  * hipHostUnregister behind the C ABI. Frames handed to the *_batch_host entries from such memory skip the staging copy. */
 int mof_host_alloc(size_t bytes, void** out);

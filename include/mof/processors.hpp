@@ -149,6 +149,39 @@ class FftMethod {
                   "mof_fft_process_sequence_device_q");
   }
 
+  // Predicted-shift window offsets (include/mof.h; no reference counterpart): every patch's previous window is read at its prediction
+  // d_pred_xy (int32 [pair][patch][2]), the outputs are totals = applied prediction + residual. d_quality, d_applied_xy may be null.
+  void processBatchDevicePred(const uint8_t* d_cur, size_t cur_stride, const uint8_t* d_prev, size_t prev_stride, size_t pitch, int n_pairs,
+                              const int32_t* d_pred_xy, double* d_out_xy, double* d_quality = nullptr, int32_t* d_applied_xy = nullptr,
+                              void* stream = nullptr) {
+    detail::check(mof_fft_process_batch_device_pred(engine_, d_cur, cur_stride, d_prev, prev_stride, pitch, n_pairs, d_pred_xy, d_out_xy,
+                                                    d_quality, d_applied_xy, stream), "mof_fft_process_batch_device_pred");
+  }
+  // ... with the predictions taken from the long-range pass: one call in place of the node's long_range_mode switch (reference tiling
+  // only). d_coarse_xy (nullable): the long-range shifts, quarter-pixels.
+  void processCoarseToFineBatchDevice(const uint8_t* d_cur, size_t cur_stride, const uint8_t* d_prev, size_t prev_stride, size_t pitch,
+                                      int n_pairs, double* d_out_xy, double* d_quality = nullptr, int32_t* d_applied_xy = nullptr,
+                                      double* d_coarse_xy = nullptr, void* stream = nullptr) {
+    detail::check(mof_fft_process_coarse_to_fine_batch_device(engine_, d_cur, cur_stride, d_prev, prev_stride, pitch, n_pairs, d_out_xy,
+                                                              d_quality, d_applied_xy, d_coarse_xy, stream),
+                  "mof_fft_process_coarse_to_fine_batch_device");
+  }
+  // ... and on processImage's frame chain (shared with processImage): sqNum^2 full-resolution vectors whose range is the long-range mode's
+  std::vector<Point2d> processImageCoarseToFine(ImageView imCurr) {
+    if (imCurr.rows != cfg_.frame_height || imCurr.cols != cfg_.frame_width)
+      throw std::runtime_error("processImageCoarseToFine: frame size does not match the engine geometry");
+    std::vector<Point2d> speeds((size_t)cfg_.grid_x * cfg_.grid_y);
+    std::vector<PatchQuality> quality(speeds.size());
+    const int rc = mof_fft_process_coarse_to_fine(engine_, imCurr.data, imCurr.step, reinterpret_cast<double*>(speeds.data()),
+                                                  reinterpret_cast<double*>(quality.data()), &last_invalid_);
+    if (rc == MOF_ERR_BUSY) return {};
+    detail::check(rc, "mof_fft_process_coarse_to_fine");
+    last_quality_.swap(quality);
+    return speeds;
+  }
+  // what a window-offset call of n_pairs pairs of dense frames needs, grown ahead of a graph capture
+  void reservePred(int n_pairs) { detail::check(mof_fft_reserve_pred(engine_, n_pairs), "mof_fft_reserve_pred"); }
+
   // A video in HOST memory (a replayed camera log): frame i at frames + i * frame_stride, rows `pitch` bytes apart. Returns the vectors the
   // processImage calls of frames 1 .. n - 1 would return, pair-major ((n_frames - 1) * sqNum^2 entries). The frames go up once each on a
   // copy stream while the previous chunk is computed (mof_fft_process_batch_host; frames in pinned memory -- mof_host_alloc /

@@ -95,6 +95,12 @@ SYMBOLS = {
     "mof_fft_process_batch_host_q": (_I, [_VP, _VP, _SZ, _VP, _SZ, _SZ, _I, _VP, _VP]),
     "mof_fft_set_min_response": (_I, [_VP, C.c_double]),
     "mof_fft_min_response": (C.c_double, [_VP]),
+    "mof_fft_pred_clamp": (_I, [C.POINTER(FftConfig), _I, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "mof_fft_pred_from_coarse": (_I, [C.c_double, C.c_double, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "mof_fft_reserve_pred": (_I, [_VP, _I]),
+    "mof_fft_process_batch_device_pred": (_I, [_VP, _VP, _SZ, _VP, _SZ, _SZ, _I, _VP, _VP, _VP, _VP, _VP]),
+    "mof_fft_process_coarse_to_fine_batch_device": (_I, [_VP, _VP, _SZ, _VP, _SZ, _SZ, _I, _VP, _VP, _VP, _VP, _VP]),
+    "mof_fft_process_coarse_to_fine": (_I, [_VP, _VP, _SZ, _VP, _VP, C.POINTER(_I)]),
     "mof_shard_fft_set_min_response": (_I, [_VP, C.c_double]),
     "mof_shard_fft_min_response": (C.c_double, [_VP]),
     "mof_host_alloc": (_I, [_SZ, C.POINTER(_VP)]),

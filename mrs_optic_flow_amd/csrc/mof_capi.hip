@@ -27,6 +27,8 @@
 // The response gate's kernel and its launcher (mof::launch_pc_response_gate): no translation unit of its own -- this file is its only
 // caller and held no device code before, so the gate adds one code object to the library and changes none.
 #include "pc_gate_kernel.hip"
+// ... and so are the kernels of the predicted-shift window offsets (launch_pc_offset_gather / _finish, launch_pc_pred_from_coarse)
+#include "pc_offset_kernel.hip"
 
 namespace {
 thread_local char g_err[512] = "";
@@ -199,6 +201,7 @@ struct mof_fft_engine {
   mof::Stream stream;
   mof::ScratchFence fence;                // cross-stream ordering of the large-patch scratch
   mof::ScratchFence gate_fence;           // ... and of the response gate's quality buffer (d_gate_q; created with it)
+  mof::ScratchFence pred_fence;           // ... and of the window-offset scratch (d_pred_*; created with it)
   mof::DevMem<float> d_twiddles;
   mof::DevMem<uint8_t> d_frames[2];       // [cur_slot], [1-cur_slot] = previous
   int prev_slot = 0;
@@ -222,6 +225,14 @@ struct mof_fft_engine {
   std::atomic<double> min_response{0.0};  // (mof_fft_min_response reads it without the busy flag)
   mof::DevMem<double> d_gate_q;
   size_t gate_cap = 0;
+  // predicted-shift window offsets (mof_fft_process_batch_device_pred, the coarse-to-fine entries): the displaced previous windows of one
+  // pass of frame pairs (pred_bytes, at the caller's pitch), and per pair of a call the predictions and applied predictions the caller
+  // did not bring plus the long-range shifts (pred_pairs). Made by the first call, grown as the gate's buffer is.
+  mof::DevMem<uint8_t> d_pred_frames;
+  size_t pred_bytes = 0;
+  mof::DevMem<int32_t> d_pred_xy, d_pred_applied;
+  mof::DevMem<double> d_pred_coarse;
+  int pred_pairs = 0;
   std::atomic<bool> busy{false};
   std::atomic<bool> graph_pinned{false};  // a batch call was captured into a HIP graph (capi_graph.hpp)
   std::mutex host_mu;                     // mof_fft_process_batch_host: upload / run / download pipeline (host_pipe.hpp), made by its first call
@@ -250,16 +261,21 @@ static int large_pass_pairs(const mof_fft_engine* e, int patches) {
   return n < 1 ? 1 : (n > 4096 ? 4096 : (int)n);
 }
 
+// the scratch of a call of n_pairs frame pairs of `patches` patches on stream s: a whole pass at most (launch_large, mof_fft_reserve_pred)
+static int large_reserve(mof_fft_engine* e, int patches, int n_pairs, hipStream_t s) {
+  const int pass_max = large_pass_pairs(e, patches);
+  const int want_pairs = n_pairs < pass_max ? n_pairs : pass_max;
+  return mof::grow_scratch(e->graph_pinned.load(), e->fence, {e->stream}, mof::stream_capturing(s), "the large-patch scratch (patch pairs)",
+                           e->cap, (long)want_pairs * patches, (long)e->cfg.grid_x * e->cfg.grid_y,
+                           [e](long cap) { return large_alloc(e, (int)cap); });
+}
+
 // The large-patch pipeline on n_pairs frame pairs (a.grid_* patches each; a.downscale / a.channels as K1): passes of whole frame
 // pairs through the engine's scratch. Returns a MOF status.
 static int launch_large(mof_fft_engine* e, const mof::PcArgs& a, int n_pairs, hipStream_t s) {
   const int patches = a.grid_x * a.grid_y;
-  const int pass_max = large_pass_pairs(e, patches);
-  const int want_pairs = n_pairs < pass_max ? n_pairs : pass_max;
   {
-    const int rc = mof::grow_scratch(e->graph_pinned.load(), e->fence, {e->stream}, mof::stream_capturing(s), "the large-patch scratch (patch pairs)",
-                                     e->cap, (long)want_pairs * patches, (long)e->cfg.grid_x * e->cfg.grid_y,
-                                     [e](long cap) { return large_alloc(e, (int)cap); });
+    const int rc = large_reserve(e, patches, n_pairs, s);
     if (rc != MOF_OK) return rc;
   }
   HIP_TRY(e->fence.acquire(s));
@@ -540,6 +556,7 @@ static void fft_destroy_now(void* p) {
   if (e->stream) (void)hipStreamSynchronize(e->stream);
   e->fence.wait_idle();
   e->gate_fence.wait_idle();
+  e->pred_fence.wait_idle();
   delete e;
 }
 struct FftDestroyNow {
@@ -783,6 +800,241 @@ int mof_fft_process_long_range_batch_device(mof_fft_engine* e, const uint8_t* d_
                                             const uint8_t* d_prev, size_t prev_stride, size_t pitch, int n_pairs,
                                             double* d_out_xy, void* stream) {
   return fft_batch(e, d_cur, cur_stride, d_prev, prev_stride, pitch, n_pairs, d_out_xy, nullptr, stream, 1, true);
+}
+
+/* ---- predicted-shift window offsets (include/mof.h) ----------------------------------------- */
+
+int mof_fft_pred_clamp(const mof_fft_config* cfg, int patch, int32_t px, int32_t py, int32_t* ax, int32_t* ay) {
+  if (!cfg || !ax || !ay) return fail(MOF_ERR_BAD_ARG, "mof_fft_pred_clamp: null pointer");
+  const mof_fft_config& c = *cfg;
+  if (c.grid_x < 1 || c.grid_y < 1 || patch < 0 || patch >= (long)c.grid_x * c.grid_y)
+    return fail(MOF_ERR_BAD_ARG, "mof_fft_pred_clamp: patch %d outside the %d x %d grid", patch, c.grid_x, c.grid_y);
+  const long x0 = c.origin_x + (long)(patch % c.grid_x) * c.stride_x, y0 = c.origin_y + (long)(patch / c.grid_x) * c.stride_y;
+  if (c.patch_size < 1 || c.origin_x < 0 || c.origin_y < 0 || c.stride_x < 0 || c.stride_y < 0 || x0 + c.patch_size > c.frame_width ||
+      y0 + c.patch_size > c.frame_height)
+    return fail(MOF_ERR_BAD_ARG, "mof_fft_pred_clamp: the patch leaves the frame");
+  *ax = mof::pred_clamp_axis(px, (int)x0, c.frame_width, c.patch_size);
+  *ay = mof::pred_clamp_axis(py, (int)y0, c.frame_height, c.patch_size);
+  return MOF_OK;
+}
+
+int mof_fft_pred_from_coarse(double sx, double sy, int32_t* px, int32_t* py) {
+  if (!px || !py) return fail(MOF_ERR_BAD_ARG, "mof_fft_pred_from_coarse: null pointer");
+  mof::pred_from_coarse(sx, sy, px, py);
+  return MOF_OK;
+}
+
+// Frame pairs per pass of the window gather: as many as keep the scratch frames under the large-patch pipeline's bound (~1.5 GB), at least one
+static int pred_pass_pairs(const mof_fft_engine* e, size_t pitch) {
+  const size_t per_pair = (size_t)e->cfg.frame_height * pitch;
+  const size_t n = ((size_t)3 << 29) / per_pair;
+  return n < 1 ? 1 : (n > 0x7fffffffull ? 0x7fffffff : (int)n);
+}
+
+// The window-offset scratch for a call of n_pairs pairs at `pitch` on stream s: the frames of one pass, zero-filled when they are made, and
+// the per-pair side buffers. Both by the rules of every engine-owned scratch (grow_scratch), ordered by pred_fence.
+static int pred_reserve(mof_fft_engine* e, size_t pitch, int n_pairs, hipStream_t s) {
+  const int pass = pred_pass_pairs(e, pitch);
+  const size_t want_bytes = (size_t)(n_pairs < pass ? n_pairs : pass) * e->cfg.frame_height * pitch;
+  const bool pinned = e->graph_pinned.load(), capturing = mof::stream_capturing(s);
+  int rc = mof::grow_scratch(pinned, e->pred_fence, {e->stream}, capturing, "the window-offset scratch (bytes of displaced frames)",
+                             (long)e->pred_bytes, (long)want_bytes, 0, [e](long bytes) {
+                               mof::RelaxedCapture relaxed;
+                               e->pred_bytes = 0;
+                               e->d_pred_frames.reset();
+                               if (bytes == 0) return hipSuccess;
+                               if (!e->pred_fence.ev) {
+                                 const hipError_t err = e->pred_fence.create();
+                                 if (err != hipSuccess) return err;
+                               }
+                               hipError_t err = e->d_pred_frames.alloc((size_t)bytes);
+                               if (err == hipSuccess) err = mof::fill_on(e->stream, e->d_pred_frames, 0, (size_t)bytes);
+                               if (err == hipSuccess) e->pred_bytes = (size_t)bytes;
+                               return err;
+                             });
+  if (rc != MOF_OK) return rc;
+  return mof::grow_scratch(pinned, e->pred_fence, {e->stream}, capturing, "the window-offset scratch (pairs of predictions)", e->pred_pairs,
+                           n_pairs, 0, [e](long pairs) {
+                             mof::RelaxedCapture relaxed;
+                             e->pred_pairs = 0;
+                             const size_t n = (size_t)pairs * e->cfg.grid_x * e->cfg.grid_y;
+                             const hipError_t err = mof::alloc_all(e->d_pred_xy, 2 * n, e->d_pred_applied, 2 * n, e->d_pred_coarse, 2 * (n / 16 + (size_t)pairs));
+                             if (err == hipSuccess) e->pred_pairs = (int)pairs;
+                             return err;
+                           });
+}
+
+// what the window-offset entries share: arguments, then the limits of the feature, each with its own message. *empty: nothing to do.
+static int pred_check(const mof_fft_engine* e, const void* d_cur, const void* d_prev, size_t pitch, int n_pairs, const void* d_out_xy,
+                      bool* empty) {
+  *empty = false;
+  if (!e) return fail(MOF_ERR_NOT_INIT, "null engine");
+  if (n_pairs == 0) {
+    *empty = true;  // an empty batch carries no pointers to check
+    return MOF_OK;
+  }
+  if (!d_cur || !d_prev || !d_out_xy || n_pairs < 0) return fail(MOF_ERR_BAD_ARG, "bad batch arguments (null pointer or negative count)");
+  if (pitch < (size_t)e->cfg.frame_width) return fail(MOF_ERR_BAD_ARG, "pitch %zu is smaller than the frame width %d", pitch, e->cfg.frame_width);
+  if ((unsigned long long)n_pairs * (unsigned long long)(e->cfg.grid_x * e->cfg.grid_y) > 0x7fffffffull)
+    return fail(MOF_ERR_BAD_ARG, "batch too large for one launch");
+  const mof_fft_config& c = e->cfg;
+  if ((c.grid_x > 1 && c.stride_x < c.patch_size) || (c.grid_y > 1 && c.stride_y < c.patch_size))
+    return fail(MOF_ERR_UNSUPPORTED, "window offsets need patches that do not overlap (stride >= patch_size on both axes): overlapping "
+                "windows cannot share one displaced frame");
+  if (c.peak_model != MOF_PEAK_OPENCV) return fail(MOF_ERR_UNSUPPORTED, "window offsets are not defined for peak_model MOF_PEAK_OCL");
+  return MOF_OK;
+}
+
+// The window-offset pipeline on stream s (busy flag held, device current, pred_check passed). d_pred_xy == nullptr: coarse-to-fine --
+// the long-range pass first, the predictions from its shifts. Returns a MOF status.
+static int pred_run(mof_fft_engine* e, const uint8_t* d_cur, size_t cur_stride, const uint8_t* d_prev, size_t prev_stride, size_t pitch,
+                    int n_pairs, const int32_t* d_pred_xy, double* d_out_xy, double* d_quality, int32_t* d_applied_xy, double* d_coarse_xy,
+                    hipStream_t s) {
+  const bool coarse = d_pred_xy == nullptr;
+  const int patches = e->cfg.grid_x * e->cfg.grid_y;
+  const size_t n_patches = (size_t)n_pairs * patches;
+  mof::PcArgs a = fft_args(e, d_cur, cur_stride, d_prev, prev_stride, pitch, d_out_xy, d_quality);
+  mof::PcArgs lr = a;
+  if (coarse) {
+    const int rc = long_range_args(e, &lr);
+    if (rc) return rc;
+  }
+  FIELD_TRY(pred_reserve(e, pitch, n_pairs, s));
+  bool own_q = false;
+  FIELD_TRY(gate_begin(e, n_patches, s, &a.quality, &own_q));
+  if (mof::stream_capturing(s)) e->graph_pinned.store(true);
+  HIP_TRY(e->pred_fence.acquire(s));
+  if (coarse) {
+    // the long-range shifts; armed, the gate acts on them too (their responses pass through the fine pass's quality buffer, which the
+    // fine pass then overwrites), and a gated patch -- NaN -- predicts 0
+    const size_t n_lr = (size_t)n_pairs * lr.grid_x * lr.grid_y;
+    lr.out = d_coarse_xy ? d_coarse_xy : e->d_pred_coarse.get();
+    lr.quality = e->min_response > 0.0 ? a.quality : nullptr;
+    FIELD_TRY(launch_field(e, lr, n_pairs, s));
+    if (lr.quality) HIP_TRY(mof::launch_pc_response_gate(lr.out, lr.quality, n_lr, e->min_response, s));
+    HIP_TRY(mof::launch_pc_pred_from_coarse(lr.out, e->d_pred_xy, a.grid_x, a.grid_y, n_pairs, s));
+    d_pred_xy = e->d_pred_xy;
+  }
+  int32_t* applied = d_applied_xy ? d_applied_xy : e->d_pred_applied.get();
+  const size_t frame = (size_t)e->cfg.frame_height * pitch;
+  const int pass = (int)(e->pred_bytes / frame);  // (>= 1: pred_reserve)
+  for (int k0 = 0; k0 < n_pairs; k0 += pass) {
+    const int np = n_pairs - k0 < pass ? n_pairs - k0 : pass;
+    const size_t q0 = (size_t)k0 * patches;
+    mof::PcOffsetArgs g{};
+    g.prev = d_prev + (size_t)k0 * prev_stride;
+    g.prev_stride = prev_stride;
+    g.scratch = e->d_pred_frames;
+    g.pitch = pitch;
+    g.frame_w = e->cfg.frame_width;
+    g.frame_h = e->cfg.frame_height;
+    g.n = e->cfg.patch_size;
+    g.grid_x = a.grid_x;
+    g.grid_y = a.grid_y;
+    g.origin_x = a.origin_x;
+    g.origin_y = a.origin_y;
+    g.stride_x = a.stride_x;
+    g.stride_y = a.stride_y;
+    g.pred = d_pred_xy + 2 * q0;
+    g.applied = applied + 2 * q0;
+    HIP_TRY(mof::launch_pc_offset_gather(g, np, s));
+    mof::PcArgs f = a;
+    f.cur = d_cur + (size_t)k0 * cur_stride;
+    f.prev = e->d_pred_frames;
+    f.prev_stride = frame;
+    f.out = a.out + 2 * q0;
+    f.quality = a.quality ? a.quality + 2 * q0 : nullptr;
+    FIELD_TRY(launch_field(e, f, np, s));
+  }
+  FIELD_TRY(gate_end(e, a.out, a.quality, n_patches, s, own_q));
+  HIP_TRY(mof::launch_pc_offset_finish(a.out, applied, n_patches, a.max_px_speed_sq, s));
+  HIP_TRY(e->pred_fence.release(s));
+  return MOF_OK;
+}
+
+int mof_fft_reserve_pred(mof_fft_engine* e, int n_pairs) {
+  if (!e) return fail(MOF_ERR_NOT_INIT, "null engine");
+  if (n_pairs < 0) return fail(MOF_ERR_BAD_ARG, "n_pairs must be >= 0");
+  const int patches = e->cfg.grid_x * e->cfg.grid_y;
+  if ((unsigned long long)n_pairs * (unsigned long long)patches > 0x7fffffffull) return fail(MOF_ERR_BAD_ARG, "batch too large for one launch");
+  BusyGuard g(e->busy);
+  if (!g.owned) return fail(MOF_ERR_BUSY, "engine busy");
+  if (n_pairs == 0) return MOF_OK;
+  HIP_TRY(hipSetDevice(e->cfg.device));
+  // everything a window-offset call of n_pairs pairs of dense frames (pitch = frame_width) may have to grow: its own scratch, the
+  // large-patch pipeline's for one pass, the gate's buffer where the gate is armed now
+  const size_t pitch = (size_t)e->cfg.frame_width;
+  FIELD_TRY(pred_reserve(e, pitch, n_pairs, e->stream));
+  if (e->route.family == FftRoute::LARGE) {
+    const int pass = pred_pass_pairs(e, pitch);
+    FIELD_TRY(large_reserve(e, patches, n_pairs < pass ? n_pairs : pass, e->stream));
+  }
+  double* q = nullptr;
+  bool own_q = false;
+  return gate_begin(e, (size_t)n_pairs * patches, e->stream, &q, &own_q);
+}
+
+int mof_fft_process_batch_device_pred(mof_fft_engine* e, const uint8_t* d_cur, size_t cur_stride, const uint8_t* d_prev, size_t prev_stride,
+                                      size_t pitch, int n_pairs, const int32_t* d_pred_xy, double* d_out_xy, double* d_quality,
+                                      int32_t* d_applied_xy, void* stream) {
+  bool empty = false;
+  const int rc = pred_check(e, d_cur, d_prev, pitch, n_pairs, d_out_xy, &empty);
+  if (rc != MOF_OK || empty) return rc;
+  if (!d_pred_xy) return fail(MOF_ERR_BAD_ARG, "null predictions");
+  BusyGuard g(e->busy);
+  if (!g.owned) return fail(MOF_ERR_BUSY, "engine busy");
+  HIP_TRY(hipSetDevice(e->cfg.device));
+  return pred_run(e, d_cur, cur_stride, d_prev, prev_stride, pitch, n_pairs, d_pred_xy, d_out_xy, d_quality, d_applied_xy, nullptr,
+                  (hipStream_t)stream);
+}
+
+int mof_fft_process_coarse_to_fine_batch_device(mof_fft_engine* e, const uint8_t* d_cur, size_t cur_stride, const uint8_t* d_prev,
+                                                size_t prev_stride, size_t pitch, int n_pairs, double* d_out_xy, double* d_quality,
+                                                int32_t* d_applied_xy, double* d_coarse_xy, void* stream) {
+  bool empty = false;
+  int rc = pred_check(e, d_cur, d_prev, pitch, n_pairs, d_out_xy, &empty);
+  if (rc != MOF_OK || empty) return rc;
+  mof::PcArgs lr{};
+  rc = long_range_args(e, &lr);  // (coarse-to-fine off the reference tiling: MOF_ERR_UNSUPPORTED, before anything is enqueued)
+  if (rc) return rc;
+  BusyGuard g(e->busy);
+  if (!g.owned) return fail(MOF_ERR_BUSY, "engine busy");
+  HIP_TRY(hipSetDevice(e->cfg.device));
+  return pred_run(e, d_cur, cur_stride, d_prev, prev_stride, pitch, n_pairs, nullptr, d_out_xy, d_quality, d_applied_xy, d_coarse_xy,
+                  (hipStream_t)stream);
+}
+
+// processImage's frame chain around the coarse-to-fine pipeline: the first frame against itself, previous <- current always
+int mof_fft_process_coarse_to_fine(mof_fft_engine* e, const uint8_t* frame, size_t pitch, double* out_xy, double* quality, int* n_invalid) {
+  bool empty = false;
+  int rc = pred_check(e, frame, frame, pitch, 1, out_xy, &empty);
+  if (rc != MOF_OK) return rc;
+  mof::PcArgs lr{};
+  rc = long_range_args(e, &lr);
+  if (rc) return rc;
+  BusyGuard g(e->busy);
+  if (!g.owned) return fail(MOF_ERR_BUSY, "engine busy");
+  HIP_TRY(hipSetDevice(e->cfg.device));
+  const int cur_slot = 1 - e->prev_slot;
+  HIP_TRY(upload_frame(e, cur_slot, frame, pitch));
+  const uint8_t* prev = e->first ? e->d_frames[cur_slot] : e->d_frames[e->prev_slot];
+  FIELD_TRY(pred_run(e, e->d_frames[cur_slot], 0, prev, 0, (size_t)e->cfg.frame_width, 1, nullptr, e->d_out, quality ? e->d_quality.get() : nullptr,
+                     nullptr, nullptr, e->stream));
+  const size_t res = (size_t)e->cfg.grid_x * e->cfg.grid_y * 2;
+  HIP_TRY(hipMemcpyAsync(e->h_out, e->d_out, res * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+  if (quality) HIP_TRY(hipMemcpyAsync(e->h_quality, e->d_quality, res * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  if (quality) std::memcpy(quality, e->h_quality, res * sizeof(double));
+  int bad = 0;
+  for (size_t i = 0; i < res; i += 2) {
+    out_xy[i] = e->h_out[i];
+    out_xy[i + 1] = e->h_out[i + 1];
+    if (std::isnan(e->h_out[i])) ++bad;
+  }
+  if (n_invalid) *n_invalid = bad;
+  e->prev_slot = cur_slot;
+  e->first = false;
+  return MOF_OK;
 }
 
 // A video: pair k = (frame k + 1, frame k), in the route's video form (fft_route); the pair form runs the engine's pair kernels on

@@ -129,6 +129,43 @@ hipError_t launch_pc_field_120(const PcArgs& a, int n_pairs, hipStream_t stream)
 // at out[2 i], every other patch is left as it is
 hipError_t launch_pc_response_gate(double* out, const double* quality, size_t n_patches, double min_response, hipStream_t stream);
 
+// ---- predicted-shift window offsets (pc_offset_kernel.hip; include/mof.h, "Predicted-shift window offsets") ----
+// The two definitions, shared by the kernels and the pure host helpers (mof_fft_pred_clamp, mof_fft_pred_from_coarse).
+// Applied prediction on one axis: p clamped into [x0 - (w - n), x0], so that the previous window [x0 - a, x0 - a + n) stays inside
+// [0, w). 0 <= x0 <= w - n, so neither bound overflows and p is only compared.
+__host__ __device__ inline int32_t pred_clamp_axis(int32_t p, int x0, int w, int n) {
+  const int32_t lo = x0 - (w - n), hi = x0;
+  return p < lo ? lo : (p > hi ? hi : p);
+}
+// Prediction from a long-range shift (quarter-pixels): rint(4 s) in fp64, half to even; a NaN shift predicts (0, 0)
+__host__ __device__ inline int32_t pred_round4(double s) {
+  double v = __builtin_rint(4.0 * s);
+  v = v < -2147483648.0 ? -2147483648.0 : (v > 2147483647.0 ? 2147483647.0 : v);
+  return (int32_t)v;
+}
+__host__ __device__ inline void pred_from_coarse(double sx, double sy, int32_t* px, int32_t* py) {
+  const bool nan = sx != sx || sy != sy;
+  *px = nan ? 0 : pred_round4(sx);
+  *py = nan ? 0 : pred_round4(sy);
+}
+struct PcOffsetArgs {
+  const uint8_t* prev;   // device, pair k at prev + k * prev_stride
+  size_t prev_stride;
+  uint8_t* scratch;      // device, pair k at scratch + k * frame_h * pitch: the window of patch (x0, y0) lands AT (x0, y0)
+  size_t pitch;          // of both
+  int frame_w, frame_h, n;
+  int grid_x, grid_y, origin_x, origin_y, stride_x, stride_y;
+  const int32_t* pred;   // device, [pair][patch][2]
+  int32_t* applied;      // device, [pair][patch][2]: written
+};
+// Window gather: the n x n bytes of prev at (x0 - a_x, y0 - a_y) into scratch at (x0, y0), a = the clamped pred, for every patch of n_pairs pairs
+hipError_t launch_pc_offset_gather(const PcOffsetArgs& a, int n_pairs, hipStream_t stream);
+// Finish, behind the field's kernels and the response gate: out[i] = applied[i] + out[i] per component (a zero component keeps the residual's
+// bits), (NaN, NaN) where the residual is NaN or |total|^2 > max_px_speed_sq; a patch with applied = (0, 0) is left as it is
+hipError_t launch_pc_offset_finish(double* out, const int32_t* applied, size_t n_patches, double max_px_speed_sq, hipStream_t stream);
+// Prediction of fine patch (i, j) from the long-range patch (min(i / 4, gx_lr - 1), min(j / 4, gy_lr - 1)) of its pair
+hipError_t launch_pc_pred_from_coarse(const double* coarse, int32_t* pred, int grid_x, int grid_y, int n_pairs, hipStream_t stream);
+
 // ---- K2/K3: SAD block scan + histogram mode -------------------------------------------------
 struct BmArgs {
   const uint8_t* cur;

@@ -261,6 +261,85 @@ class FftMethod:
                                                                 _stream_ptr(s)))
         return out
 
+    # -- predicted-shift window offsets (include/mof.h) -------------------------------------------
+    def reserve_pred(self, n_pairs: int) -> None:
+        """Grows, ahead of a graph capture, what a window-offset call of ``n_pairs`` pairs of dense frames needs (mof_fft_reserve_pred)."""
+        check(self._lib.mof_fft_reserve_pred(self._h, int(n_pairs)))
+
+    def pred_clamp(self, patch: int, px: int, py: int) -> tuple[int, int]:
+        """The applied prediction of patch ``patch`` (index i + j * grid_x) for prediction (px, py): mof_fft_pred_clamp, pure host."""
+        ax, ay = C.c_int32(0), C.c_int32(0)
+        check(self._lib.mof_fft_pred_clamp(C.byref(self.cfg), int(patch), int(px), int(py), C.byref(ax), C.byref(ay)))
+        return ax.value, ay.value
+
+    def _pred_outputs(self, cur, return_quality, return_applied):
+        import torch
+
+        n = cur.shape[0]
+        out = torch.empty((n, self.n_patches, 2), dtype=torch.float64, device=cur.device)
+        quality = self._quality_like(out) if return_quality else None
+        applied = torch.empty((n, self.n_patches, 2), dtype=torch.int32, device=cur.device) if return_applied else None
+        return out, quality, applied
+
+    def process_batch_device_pred(self, cur, prev, pred, return_quality=False, return_applied=False, stream=None):
+        """process_batch_device with the previous window of every patch read at a predicted displacement: ``pred`` is a torch int32
+        tensor [n, patches, 2] of (x, y) predictions on the engine's device. Returns the total shifts [n, patches, 2] (applied
+        prediction + residual; include/mof.h, "Predicted-shift window offsets"), then ``quality`` and the int32 ``applied`` tensor
+        if asked for, in that order. Asynchronous."""
+        import torch
+
+        _check_device_batch(cur, prev, (self.cfg.frame_height, self.cfg.frame_width), self.cfg.device)
+        n = cur.shape[0]
+        if not (isinstance(pred, torch.Tensor) and pred.dtype == torch.int32 and pred.is_cuda and pred.device == cur.device
+                and pred.is_contiguous() and tuple(pred.shape) == (n, self.n_patches, 2)):
+            raise ValueError("pred must be a dense int32 tensor [n, patches, 2] on the engine's device")
+        out, quality, applied = self._pred_outputs(cur, return_quality, return_applied)
+        s = stream if stream is not None else torch.cuda.current_stream(cur.device)
+        _pin_if_capturing(self, s)
+        check(self._lib.mof_fft_process_batch_device_pred(
+            self._h, cur.data_ptr(), cur.stride(0), prev.data_ptr(), prev.stride(0), cur.stride(1), n, pred.data_ptr(), out.data_ptr(),
+            quality.data_ptr() if return_quality else None, applied.data_ptr() if return_applied else None, _stream_ptr(s)))
+        res = (out,) + ((quality,) if return_quality else ()) + ((applied,) if return_applied else ())
+        return res[0] if len(res) == 1 else res
+
+    def process_coarse_to_fine_batch_device(self, cur, prev, return_quality=False, return_applied=False, return_coarse=False, stream=None):
+        """The long-range pass, its shifts as predictions, the full-resolution pass on the offset windows -- one call in place of the
+        node's long_range_mode switch (reference tiling only). Returns the total shifts, then ``quality``, ``applied`` and the
+        long-range shifts ``coarse`` ([n, long-range patches, 2], quarter-pixels) if asked for, in that order. Asynchronous."""
+        import torch
+
+        _check_device_batch(cur, prev, (self.cfg.frame_height, self.cfg.frame_width), self.cfg.device)
+        n = cur.shape[0]
+        out, quality, applied = self._pred_outputs(cur, return_quality, return_applied)
+        coarse = None
+        if return_coarse:
+            n_lr = self._lib.mof_fft_long_range_patches(self._h)
+            if n_lr < 0:
+                check(n_lr)
+            coarse = torch.empty((n, n_lr, 2), dtype=torch.float64, device=cur.device)
+        s = stream if stream is not None else torch.cuda.current_stream(cur.device)
+        _pin_if_capturing(self, s)
+        check(self._lib.mof_fft_process_coarse_to_fine_batch_device(
+            self._h, cur.data_ptr(), cur.stride(0), prev.data_ptr(), prev.stride(0), cur.stride(1), n, out.data_ptr(),
+            quality.data_ptr() if return_quality else None, applied.data_ptr() if return_applied else None,
+            coarse.data_ptr() if return_coarse else None, _stream_ptr(s)))
+        res = (out,) + tuple(t for t in (quality, applied, coarse) if t is not None)
+        return res[0] if len(res) == 1 else res
+
+    def process_image_coarse_to_fine(self, frame) -> np.ndarray:
+        """processImage's frame chain on the coarse-to-fine pipeline: [patches, 2] total shifts, NaN = invalid; the first frame is
+        correlated with itself. ``last_invalid`` / ``last_quality`` as after processImage."""
+        f = _np_u8(frame)
+        self._check_shape(f)
+        out = np.empty((self.n_patches, 2), np.float64)
+        quality = np.empty((self.n_patches, 2), np.float64)
+        ninv = C.c_int(0)
+        check(self._lib.mof_fft_process_coarse_to_fine(self._h, f.ctypes.data, f.strides[0], out.ctypes.data, quality.ctypes.data,
+                                                       C.byref(ninv)))
+        self.last_invalid = ninv.value
+        self.last_quality = quality
+        return out
+
     # -- batched --------------------------------------------------------------------------------
     def process_batch_host(self, cur: np.ndarray, prev: np.ndarray, return_quality=False):
         cur, prev, cs, ps, pitch = _host_batch_views(cur, prev)
