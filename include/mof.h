@@ -290,7 +290,7 @@ double mof_fft_min_response(const mof_fft_engine* e);
  * - A patch whose long-range shift is NaN gets (0, 0).
  * - An armed response gate acts on both passes. A gated coarse patch predicts 0.
  *
- * How it runs (csrc/pc_offset_kernel.hip): a gather kernel copies every patch's displaced previous window into an engine-owned scratch
+ * How it runs, the GATHER route -- MOF_PRED_ROUTE_GATHER, every engine's default (csrc/pc_offset_kernel.hip): a gather kernel copies every patch's displaced previous window into an engine-owned scratch
  * frame at the patch's own place -- same pitch, frame stride H * pitch --, the engine's unchanged kernels run with prev = scratch, and a
  * one-lane-per-patch kernel behind them (and behind the response gate) forms the total. The scratch follows the rules of the gate's
  * buffer: it grows with the first call that needs more, never inside a graph capture (MOF_ERR_BAD_ARG) and never while a captured graph
@@ -305,9 +305,34 @@ double mof_fft_min_response(const mof_fft_engine* e);
  * then previous <- current always (it shares the chain with mof_fft_process; mof_fft_reset restarts it).
  *
  * Limits, nothing is launched and no output is touched: MOF_ERR_UNSUPPORTED for a layout whose patches overlap (stride < patch_size
- * on an axis with more than one patch: overlapping windows cannot share one displaced frame), for MOF_PEAK_OCL, and for
- * coarse-to-fine off the reference tiling; MOF_ERR_BAD_ARG for null pointers or pitch < frame_width. Gray frames only; no sequence
- * form (a displaced window cannot reuse the previous spectrum) and no shard-group form.
+ * on an axis with more than one patch: overlapping windows cannot share one displaced frame) -- on the gather route --, for MOF_PEAK_OCL,
+ * and for coarse-to-fine off the reference tiling; MOF_ERR_BAD_ARG for null pointers or pitch < frame_width. Gray frames only on the
+ * gather route; no sequence form (a displaced window cannot reuse the previous spectrum) and no shard-group form.
+ *
+ * The FUSED route -- MOF_PRED_ROUTE_FUSED, chosen per engine with mof_fft_set_pred_route. The field kernel itself reads every previous
+ * patch window at its applied prediction: a clamp kernel stores a (one lane per patch), and the workgroup of patch q moves the base
+ * address of its previous patch by -(a_y * pitch + channels * a_x) -- two scalar loads and scalar arithmetic, no window is
+ * materialised. Every definition above holds word for word, and on a layout both routes accept every output bit is the same. What
+ * changes on it:
+ * - A layout whose patches overlap is accepted by all three entries (coarse to fine still needs the reference tiling, which never
+ *   overlaps: there only the fine pass reads differently).
+ * - mof_fft_process_batch_device_pred_bgr: the arguments of mof_fft_process_batch_device_pred on interleaved BGR8 frames, pitch in bytes
+ *   (>= 3 * frame_width), CV_RGB2GRAY fused into the load as on mof_fft_process_batch_device_bgr: the bits of the gray entry on the
+ *   converted frames. On the gather route it returns MOF_ERR_UNSUPPORTED and launches nothing. No BGR8 coarse to fine (the long-range
+ *   pass has no BGR8 form).
+ * - No displaced-frame scratch is allocated or touched and a batch of any size is one pass; mof_fft_reserve_pred grows the per-pair side
+ *   buffers and the gate's buffer only. The capture rules are the same.
+ * - MOF_PEAK_OCL stays MOF_ERR_UNSUPPORTED.
+ * The fused form exists on K1 (patch sizes 32, 64, 128) and on the half-tile kernel (kernel variant "planned-half": 120, 60 / 72 / 90 /
+ * 96 / 100 and every patch that pads to an even size in 136 .. 192). On the planned LDS kernel, the large-patch pipeline and the 15 x 8
+ * kernel at 120 that only MOF_FFT_HALF=0 reaches, mof_fft_set_pred_route(e, MOF_PRED_ROUTE_FUSED) returns MOF_ERR_UNSUPPORTED and the
+ * engine keeps the gather, whose cost is within a device copy there (README, "Shifts beyond half a patch").
+ * mof_fft_set_pred_route: MOF_ERR_BAD_ARG for any other route value, MOF_ERR_NOT_INIT for a null engine, MOF_ERR_BUSY while a call is in
+ * flight or a captured graph pins the engine (the rule of mof_fft_set_min_response); on every error the route is unchanged. Switching
+ * back and forth between calls is allowed and frees nothing. mof_fft_pred_route returns the current route (GATHER for a null engine).
+ * mof_fft_pred_route_supported(cfg, route): 1 or 0 for the default kernel route of cfg's patch_size and peak_model (no MOF_FFT_* knob
+ * set), MOF_ERR_BAD_ARG for a null cfg or an unknown route; pure host code, no device needed.
+ * The route's two constants and four functions are declared in include/mof_pred_route.h, which this header includes at its end.
  *
  * The two definitions as pure host functions, no device needed: mof_fft_pred_clamp -- a of patch `patch` (index i + j * grid_x) of
  * layout cfg for prediction (px, py); MOF_ERR_BAD_ARG if the patch is outside the grid or leaves the frame -- and
@@ -768,4 +793,5 @@ int mof_geom_get_2dt_batch_device(const double* d_shifts_xy, const mof_geom_layo
 #ifdef __cplusplus
 }
 #endif
+#include "mof_pred_route.h"
 #endif /* MOF_H */

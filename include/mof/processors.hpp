@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "../mof.h"
+#include "pred_route.hpp"
 
 namespace mof {
 
@@ -156,6 +157,18 @@ class FftMethod {
                               void* stream = nullptr) {
     detail::check(mof_fft_process_batch_device_pred(engine_, d_cur, cur_stride, d_prev, prev_stride, pitch, n_pairs, d_pred_xy, d_out_xy,
                                                     d_quality, d_applied_xy, stream), "mof_fft_process_batch_device_pred");
+  }
+  // How the displaced windows are read: MOF_PRED_ROUTE_GATHER (the default, through a scratch frame) or MOF_PRED_ROUTE_FUSED (inside the
+  // field kernel: overlapping layouts and BGR8 frames too, no scratch). Throws where the engine's kernels have no fused form
+  // (MOF_ERR_UNSUPPORTED) and while a captured graph pins the engine (MOF_ERR_BUSY); the route is then unchanged.
+  void setPredRoute(int route) { detail::check(detail::fftSetPredRoute(engine_, route), "mof_fft_set_pred_route"); }
+  int predRoute() const { return detail::fftPredRoute(engine_); }
+  // processBatchDevicePred on interleaved BGR8 frames (pitch in bytes, >= 3 * frame width): the fused route only
+  void processBatchDevicePredBgr(const uint8_t* d_cur, size_t cur_stride, const uint8_t* d_prev, size_t prev_stride, size_t pitch,
+                                 int n_pairs, const int32_t* d_pred_xy, double* d_out_xy, double* d_quality = nullptr,
+                                 int32_t* d_applied_xy = nullptr, void* stream = nullptr) {
+    detail::check(detail::fftProcessBatchDevicePredBgr(engine_, d_cur, cur_stride, d_prev, prev_stride, pitch, n_pairs, d_pred_xy,
+                                                        d_out_xy, d_quality, d_applied_xy, stream), "mof_fft_process_batch_device_pred_bgr");
   }
   // ... with the predictions taken from the long-range pass: one call in place of the node's long_range_mode switch (reference tiling
   // only). d_coarse_xy (nullable): the long-range shifts, quarter-pixels.

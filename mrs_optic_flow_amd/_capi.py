@@ -179,6 +179,14 @@ SYMBOLS = {
     "mof_geom_get_2dt_batch_device": (_I, [_VP, _VP, _VP, _VP, _I, _VP, _VP]),
 }
 
+# include/mof_pred_route.h (the companion header include/mof.h ends with): a table of its own, bound by load() like SYMBOLS
+PRED_ROUTE_SYMBOLS = {
+    "mof_fft_set_pred_route": (_I, [_VP, _I]),
+    "mof_fft_pred_route": (_I, [_VP]),
+    "mof_fft_pred_route_supported": (_I, [C.POINTER(FftConfig), _I]),
+    "mof_fft_process_batch_device_pred_bgr": (_I, [_VP, _VP, _SZ, _VP, _SZ, _SZ, _I, _VP, _VP, _VP, _VP, _VP]),
+}
+
 _lib = None
 
 
@@ -202,7 +210,7 @@ def load():
             lib = C.CDLL(LIB_PATH)
         except OSError as exc:  # pragma: no cover - depends on the host
             raise MofLibraryError(f"cannot load {LIB_PATH}: {exc}") from exc
-        for name, (res, args) in SYMBOLS.items():
+        for name, (res, args) in list(SYMBOLS.items()) + list(PRED_ROUTE_SYMBOLS.items()):
             fn = getattr(lib, name)  # AttributeError if the library does not export it
             fn.restype = res
             fn.argtypes = args

@@ -233,6 +233,9 @@ struct mof_fft_engine {
   mof::DevMem<int32_t> d_pred_xy, d_pred_applied;
   mof::DevMem<double> d_pred_coarse;
   int pred_pairs = 0;
+  // how the window-offset entries read the displaced windows (mof_fft_set_pred_route): MOF_PRED_ROUTE_GATHER through d_pred_frames, or
+  // MOF_PRED_ROUTE_FUSED inside the field kernel (PcArgs::prev_off) -- no d_pred_frames, overlapping layouts and BGR8 frames served
+  std::atomic<int> pred_route{MOF_PRED_ROUTE_GATHER};  // (mof_fft_pred_route reads it without the busy flag)
   std::atomic<bool> busy{false};
   std::atomic<bool> graph_pinned{false};  // a batch call was captured into a HIP graph (capi_graph.hpp)
   std::mutex host_mu;                     // mof_fft_process_batch_host: upload / run / download pipeline (host_pipe.hpp), made by its first call
@@ -367,6 +370,8 @@ static int launch_large(mof_fft_engine* e, const mof::PcArgs& a, int n_pairs, hi
 // too large for a CU -- the planned pipeline through HBM scratch. Returns a MOF status.
 static int launch_field(mof_fft_engine* e, const mof::PcArgs& a, int n_pairs, hipStream_t stream) {
   const FftRoute& r = e->route;
+  if (a.prev_off && !(a.downscale == 1 && mof::fft_pred_fused_supported(r, a.peak_model)))  // (mof_fft_set_pred_route keeps this from happening)
+    return fail(MOF_ERR_UNSUPPORTED, "this engine's kernels have no fused window-offset form");
   if (r.half_m > 0 && a.downscale == 1) {  // (no scratch, nothing engine-owned but the twiddles)
     HIP_TRY(mof::launch_pc_half(a, r.half_m, e->cfg.patch_size, n_pairs, stream));
     return MOF_OK;
@@ -835,7 +840,9 @@ static int pred_pass_pairs(const mof_fft_engine* e, size_t pitch) {
 // the per-pair side buffers. Both by the rules of every engine-owned scratch (grow_scratch), ordered by pred_fence.
 static int pred_reserve(mof_fft_engine* e, size_t pitch, int n_pairs, hipStream_t s) {
   const int pass = pred_pass_pairs(e, pitch);
-  const size_t want_bytes = (size_t)(n_pairs < pass ? n_pairs : pass) * e->cfg.frame_height * pitch;
+  // (the fused route materialises no window: no displaced frames, the side buffers alone)
+  const bool fused = e->pred_route.load() == MOF_PRED_ROUTE_FUSED;
+  const size_t want_bytes = fused ? 0 : (size_t)(n_pairs < pass ? n_pairs : pass) * e->cfg.frame_height * pitch;
   const bool pinned = e->graph_pinned.load(), capturing = mof::stream_capturing(s);
   int rc = mof::grow_scratch(pinned, e->pred_fence, {e->stream}, capturing, "the window-offset scratch (bytes of displaced frames)",
                              (long)e->pred_bytes, (long)want_bytes, 0, [e](long bytes) {
@@ -857,6 +864,10 @@ static int pred_reserve(mof_fft_engine* e, size_t pitch, int n_pairs, hipStream_
                            n_pairs, 0, [e](long pairs) {
                              mof::RelaxedCapture relaxed;
                              e->pred_pairs = 0;
+                             if (pairs > 0 && !e->pred_fence.ev) {  // (an engine that only ever ran fused makes the fence here)
+                               const hipError_t err = e->pred_fence.create();
+                               if (err != hipSuccess) return err;
+                             }
                              const size_t n = (size_t)pairs * e->cfg.grid_x * e->cfg.grid_y;
                              const hipError_t err = mof::alloc_all(e->d_pred_xy, 2 * n, e->d_pred_applied, 2 * n, e->d_pred_coarse, 2 * (n / 16 + (size_t)pairs));
                              if (err == hipSuccess) e->pred_pairs = (int)pairs;
@@ -866,7 +877,7 @@ static int pred_reserve(mof_fft_engine* e, size_t pitch, int n_pairs, hipStream_
 
 // what the window-offset entries share: arguments, then the limits of the feature, each with its own message. *empty: nothing to do.
 static int pred_check(const mof_fft_engine* e, const void* d_cur, const void* d_prev, size_t pitch, int n_pairs, const void* d_out_xy,
-                      bool* empty) {
+                      bool* empty, int channels = 1) {
   *empty = false;
   if (!e) return fail(MOF_ERR_NOT_INIT, "null engine");
   if (n_pairs == 0) {
@@ -874,11 +885,16 @@ static int pred_check(const mof_fft_engine* e, const void* d_cur, const void* d_
     return MOF_OK;
   }
   if (!d_cur || !d_prev || !d_out_xy || n_pairs < 0) return fail(MOF_ERR_BAD_ARG, "bad batch arguments (null pointer or negative count)");
-  if (pitch < (size_t)e->cfg.frame_width) return fail(MOF_ERR_BAD_ARG, "pitch %zu is smaller than the frame width %d", pitch, e->cfg.frame_width);
+  if (pitch < (size_t)channels * (size_t)e->cfg.frame_width)
+    return fail(MOF_ERR_BAD_ARG, "pitch %zu is smaller than the frame width %d (x %d channels)", pitch, e->cfg.frame_width, channels);
   if ((unsigned long long)n_pairs * (unsigned long long)(e->cfg.grid_x * e->cfg.grid_y) > 0x7fffffffull)
     return fail(MOF_ERR_BAD_ARG, "batch too large for one launch");
   const mof_fft_config& c = e->cfg;
-  if ((c.grid_x > 1 && c.stride_x < c.patch_size) || (c.grid_y > 1 && c.stride_y < c.patch_size))
+  const bool fused = e->pred_route.load() == MOF_PRED_ROUTE_FUSED;  // (only set where the route has the form and the model is cv::phaseCorrelate's)
+  if (!fused && channels != 1)
+    return fail(MOF_ERR_UNSUPPORTED, "window offsets on BGR8 frames need the fused route (mof_fft_set_pred_route): the gather's scratch "
+                "frames are gray");
+  if (!fused && ((c.grid_x > 1 && c.stride_x < c.patch_size) || (c.grid_y > 1 && c.stride_y < c.patch_size)))
     return fail(MOF_ERR_UNSUPPORTED, "window offsets need patches that do not overlap (stride >= patch_size on both axes): overlapping "
                 "windows cannot share one displaced frame");
   if (c.peak_model != MOF_PEAK_OPENCV) return fail(MOF_ERR_UNSUPPORTED, "window offsets are not defined for peak_model MOF_PEAK_OCL");
@@ -889,12 +905,14 @@ static int pred_check(const mof_fft_engine* e, const void* d_cur, const void* d_
 // the long-range pass first, the predictions from its shifts. Returns a MOF status.
 static int pred_run(mof_fft_engine* e, const uint8_t* d_cur, size_t cur_stride, const uint8_t* d_prev, size_t prev_stride, size_t pitch,
                     int n_pairs, const int32_t* d_pred_xy, double* d_out_xy, double* d_quality, int32_t* d_applied_xy, double* d_coarse_xy,
-                    hipStream_t s) {
+                    hipStream_t s, int channels = 1) {
   const bool coarse = d_pred_xy == nullptr;
+  const bool fused = e->pred_route.load() == MOF_PRED_ROUTE_FUSED;
   const int patches = e->cfg.grid_x * e->cfg.grid_y;
   const size_t n_patches = (size_t)n_pairs * patches;
   mof::PcArgs a = fft_args(e, d_cur, cur_stride, d_prev, prev_stride, pitch, d_out_xy, d_quality);
-  mof::PcArgs lr = a;
+  mof::PcArgs lr = a;  // (gray: coarse to fine has no BGR8 form)
+  a.channels = channels;
   if (coarse) {
     const int rc = long_range_args(e, &lr);
     if (rc) return rc;
@@ -916,35 +934,47 @@ static int pred_run(mof_fft_engine* e, const uint8_t* d_cur, size_t cur_stride, 
     d_pred_xy = e->d_pred_xy;
   }
   int32_t* applied = d_applied_xy ? d_applied_xy : e->d_pred_applied.get();
-  const size_t frame = (size_t)e->cfg.frame_height * pitch;
-  const int pass = (int)(e->pred_bytes / frame);  // (>= 1: pred_reserve)
-  for (int k0 = 0; k0 < n_pairs; k0 += pass) {
-    const int np = n_pairs - k0 < pass ? n_pairs - k0 : pass;
-    const size_t q0 = (size_t)k0 * patches;
-    mof::PcOffsetArgs g{};
-    g.prev = d_prev + (size_t)k0 * prev_stride;
-    g.prev_stride = prev_stride;
-    g.scratch = e->d_pred_frames;
-    g.pitch = pitch;
-    g.frame_w = e->cfg.frame_width;
-    g.frame_h = e->cfg.frame_height;
-    g.n = e->cfg.patch_size;
-    g.grid_x = a.grid_x;
-    g.grid_y = a.grid_y;
-    g.origin_x = a.origin_x;
-    g.origin_y = a.origin_y;
-    g.stride_x = a.stride_x;
-    g.stride_y = a.stride_y;
-    g.pred = d_pred_xy + 2 * q0;
-    g.applied = applied + 2 * q0;
-    HIP_TRY(mof::launch_pc_offset_gather(g, np, s));
+  mof::PcOffsetArgs g{};
+  g.prev_stride = prev_stride;
+  g.pitch = pitch;
+  g.frame_w = e->cfg.frame_width;
+  g.frame_h = e->cfg.frame_height;
+  g.n = e->cfg.patch_size;
+  g.grid_x = a.grid_x;
+  g.grid_y = a.grid_y;
+  g.origin_x = a.origin_x;
+  g.origin_y = a.origin_y;
+  g.stride_x = a.stride_x;
+  g.stride_y = a.stride_y;
+  if (fused) {
+    // the clamp, then the field kernel on the caller's own previous frames, reading every patch at its applied prediction: no window is
+    // materialised, so the whole batch is one pass, and overlapping patches and BGR8 frames are frames like any other
+    g.pred = d_pred_xy;
+    g.applied = applied;
+    HIP_TRY(mof::launch_pc_offset_clamp(g, n_pairs, s));
     mof::PcArgs f = a;
-    f.cur = d_cur + (size_t)k0 * cur_stride;
-    f.prev = e->d_pred_frames;
-    f.prev_stride = frame;
-    f.out = a.out + 2 * q0;
-    f.quality = a.quality ? a.quality + 2 * q0 : nullptr;
-    FIELD_TRY(launch_field(e, f, np, s));
+    f.prev_off = applied;
+    FIELD_TRY(launch_field(e, f, n_pairs, s));
+  } else {
+    // the gather: passes of as many pairs as the scratch holds displaced frames for
+    const size_t frame = (size_t)e->cfg.frame_height * pitch;
+    const int pass = (int)(e->pred_bytes / frame);  // (>= 1: pred_reserve)
+    for (int k0 = 0; k0 < n_pairs; k0 += pass) {
+      const int np = n_pairs - k0 < pass ? n_pairs - k0 : pass;
+      const size_t q0 = (size_t)k0 * patches;
+      g.prev = d_prev + (size_t)k0 * prev_stride;
+      g.scratch = e->d_pred_frames;
+      g.pred = d_pred_xy + 2 * q0;
+      g.applied = applied + 2 * q0;
+      HIP_TRY(mof::launch_pc_offset_gather(g, np, s));
+      mof::PcArgs f = a;
+      f.cur = d_cur + (size_t)k0 * cur_stride;
+      f.prev = e->d_pred_frames;
+      f.prev_stride = frame;
+      f.out = a.out + 2 * q0;
+      f.quality = a.quality ? a.quality + 2 * q0 : nullptr;
+      FIELD_TRY(launch_field(e, f, np, s));
+    }
   }
   FIELD_TRY(gate_end(e, a.out, a.quality, n_patches, s, own_q));
   HIP_TRY(mof::launch_pc_offset_finish(a.out, applied, n_patches, a.max_px_speed_sq, s));
@@ -974,19 +1004,59 @@ int mof_fft_reserve_pred(mof_fft_engine* e, int n_pairs) {
   return gate_begin(e, (size_t)n_pairs * patches, e->stream, &q, &own_q);
 }
 
-int mof_fft_process_batch_device_pred(mof_fft_engine* e, const uint8_t* d_cur, size_t cur_stride, const uint8_t* d_prev, size_t prev_stride,
-                                      size_t pitch, int n_pairs, const int32_t* d_pred_xy, double* d_out_xy, double* d_quality,
-                                      int32_t* d_applied_xy, void* stream) {
+static int pred_batch(mof_fft_engine* e, const uint8_t* d_cur, size_t cur_stride, const uint8_t* d_prev, size_t prev_stride, size_t pitch,
+                      int n_pairs, const int32_t* d_pred_xy, double* d_out_xy, double* d_quality, int32_t* d_applied_xy, void* stream,
+                      int channels) {
   bool empty = false;
-  const int rc = pred_check(e, d_cur, d_prev, pitch, n_pairs, d_out_xy, &empty);
+  const int rc = pred_check(e, d_cur, d_prev, pitch, n_pairs, d_out_xy, &empty, channels);
   if (rc != MOF_OK || empty) return rc;
   if (!d_pred_xy) return fail(MOF_ERR_BAD_ARG, "null predictions");
   BusyGuard g(e->busy);
   if (!g.owned) return fail(MOF_ERR_BUSY, "engine busy");
+  // (the route pred_check saw cannot have changed: mof_fft_set_pred_route takes the busy flag, and an engine is driven by one thread)
   HIP_TRY(hipSetDevice(e->cfg.device));
   return pred_run(e, d_cur, cur_stride, d_prev, prev_stride, pitch, n_pairs, d_pred_xy, d_out_xy, d_quality, d_applied_xy, nullptr,
-                  (hipStream_t)stream);
+                  (hipStream_t)stream, channels);
 }
+
+int mof_fft_process_batch_device_pred(mof_fft_engine* e, const uint8_t* d_cur, size_t cur_stride, const uint8_t* d_prev, size_t prev_stride,
+                                      size_t pitch, int n_pairs, const int32_t* d_pred_xy, double* d_out_xy, double* d_quality,
+                                      int32_t* d_applied_xy, void* stream) {
+  return pred_batch(e, d_cur, cur_stride, d_prev, prev_stride, pitch, n_pairs, d_pred_xy, d_out_xy, d_quality, d_applied_xy, stream, 1);
+}
+
+int mof_fft_process_batch_device_pred_bgr(mof_fft_engine* e, const uint8_t* d_cur, size_t cur_stride, const uint8_t* d_prev,
+                                          size_t prev_stride, size_t pitch, int n_pairs, const int32_t* d_pred_xy, double* d_out_xy,
+                                          double* d_quality, int32_t* d_applied_xy, void* stream) {
+  return pred_batch(e, d_cur, cur_stride, d_prev, prev_stride, pitch, n_pairs, d_pred_xy, d_out_xy, d_quality, d_applied_xy, stream, 3);
+}
+
+int mof_fft_pred_route_supported(const mof_fft_config* cfg, int route) {
+  if (!cfg || (route != MOF_PRED_ROUTE_GATHER && route != MOF_PRED_ROUTE_FUSED))
+    return fail(MOF_ERR_BAD_ARG, "mof_fft_pred_route_supported: null config or unknown route %d", route);
+  if (route == MOF_PRED_ROUTE_GATHER) return 1;
+  mof::PcPlan plan;
+  FftRoute r;
+  if (cfg->patch_size < 2 || !mof::fft_route(cfg->patch_size, cfg->peak_model, mof::FftKnobs{}, &plan, &r)) return 0;
+  return mof::fft_pred_fused_supported(r, cfg->peak_model) ? 1 : 0;
+}
+
+int mof_fft_set_pred_route(mof_fft_engine* e, int route) {
+  if (!e) return fail(MOF_ERR_NOT_INIT, "null engine");
+  if (route != MOF_PRED_ROUTE_GATHER && route != MOF_PRED_ROUTE_FUSED)
+    return fail(MOF_ERR_BAD_ARG, "route must be MOF_PRED_ROUTE_GATHER or MOF_PRED_ROUTE_FUSED");
+  BusyGuard g(e->busy);
+  if (!g.owned) return fail(MOF_ERR_BUSY, "engine busy");
+  // a captured graph holds the kernels of the route it was captured on: its replays would not follow (the rule of mof_fft_set_min_response)
+  if (e->graph_pinned.load()) return fail(MOF_ERR_BUSY, "the route is baked into a captured graph: mof_fft_release_graphs first");
+  if (route == MOF_PRED_ROUTE_FUSED && !mof::fft_pred_fused_supported(e->route, e->cfg.peak_model))
+    return fail(MOF_ERR_UNSUPPORTED, "the fused route exists on K1 (patch sizes 32, 64, 128) and the half-tile kernel under "
+                "cv::phaseCorrelate's peak model; this engine runs '%s'", e->route.variant);
+  e->pred_route = route;  // (frees nothing: the gather's scratch stays for the way back)
+  return MOF_OK;
+}
+
+int mof_fft_pred_route(const mof_fft_engine* e) { return e ? e->pred_route.load() : MOF_PRED_ROUTE_GATHER; }
 
 int mof_fft_process_coarse_to_fine_batch_device(mof_fft_engine* e, const uint8_t* d_cur, size_t cur_stride, const uint8_t* d_prev,
                                                 size_t prev_stride, size_t pitch, int n_pairs, double* d_out_xy, double* d_quality,

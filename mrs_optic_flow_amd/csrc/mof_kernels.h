@@ -29,6 +29,9 @@ struct PcArgs {
   const float* twiddles;  // device, N (cos, -sin) pairs, computed in double on the host
   double* out;            // device, [pair][patch] (x, y)
   double* quality;        // device, nullable: [pair][patch] (response, peak) of the correlation surface (pc_common.hpp, quality_store)
+  const int32_t* prev_off;  // device, nullable: [pair][patch][2] APPLIED predictions (a_x, a_y) of the launch's first pair -- the fused
+                            // window-offset forms read the previous patch at (x0 - a_x, y0 - a_y) (pc_offset_clamp_kernel wrote them: the
+                            // clamp keeps the window inside the frame). Last member: every older kernel's argument offsets stay put.
 };
 
 // twiddles W_n^k = exp(-2 pi i k / n), k < n, as (re, im) float pairs (mof_capi.hip; both engines' d_twiddles)
@@ -102,6 +105,9 @@ bool pc_half_supported(int m);
 int pc_half_workgroups_per_cu(int m);
 hipError_t pc_configure_half(int m);
 hipError_t launch_pc_half(const PcArgs& a, int m, int n, int n_pairs, hipStream_t stream);
+// ... with a.prev_off set (pc_half_fused.hip, a translation unit of its own): the fused window-offset form of every pair size
+hipError_t pc_configure_half_fused(int m);
+hipError_t launch_pc_half_fused(const PcArgs& a, int m, int n, int n_pairs, hipStream_t stream);
 // ... on a video (r05): runs of `run` consecutive pairs per workgroup, a frame's spectrum kept in registers for the next pair; a.cur = the
 // launch's first frame, frame f at a.cur + f * a.cur_stride (as launch_pc_sequence)
 bool pc_half_sequence_supported(int m);
@@ -158,6 +164,8 @@ struct PcOffsetArgs {
   const int32_t* pred;   // device, [pair][patch][2]
   int32_t* applied;      // device, [pair][patch][2]: written
 };
+// The clamp alone (the fused route): applied[q] = clamp(pred[q]) for every patch of n_pairs pairs; a.prev / a.scratch are not read
+hipError_t launch_pc_offset_clamp(const PcOffsetArgs& a, int n_pairs, hipStream_t stream);
 // Window gather: the n x n bytes of prev at (x0 - a_x, y0 - a_y) into scratch at (x0, y0), a = the clamped pred, for every patch of n_pairs pairs
 hipError_t launch_pc_offset_gather(const PcOffsetArgs& a, int n_pairs, hipStream_t stream);
 // Finish, behind the field's kernels and the response gate: out[i] = applied[i] + out[i] per component (a zero component keeps the residual's
@@ -328,6 +336,12 @@ struct FftRoute {
 // Pure host code (no HIP call, no environment): the route of a patch size >= 2 under a peak model; *plan receives the plan of the planned
 // families. False: the patch pads beyond the planned transforms (> 960).
 bool fft_route(int patch_size, int peak_model, const FftKnobs& k, PcPlan* plan, FftRoute* r);
+// Pure: the pair kernel of route r has a fused window-offset form (a.prev_off read inside the field kernel) -- K1h at every pair size,
+// K1 at 32 / 64 / 128; not the 15 x 8 kernel at 120, the planned LDS kernel or the large-patch pipeline, and cv::phaseCorrelate's
+// peak model only
+inline bool fft_pred_fused_supported(const FftRoute& r, int peak_model) {
+  return peak_model == 0 && (r.half_m > 0 || (r.family == FftRoute::TUNED && r.m != 120));
+}
 const FftKnobs& fft_knobs();
 
 // The MOF_SR_* knobs of the estimator's engine (README), read once per process (mof_sr.hip: sr_knobs)

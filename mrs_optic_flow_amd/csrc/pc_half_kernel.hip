@@ -305,8 +305,11 @@ struct HalfXpowSink {
 // CURRENT image once, and its spectrum -- the forward column pass's last-stage outputs, already in the lanes' registers where the
 // cross-power meets the previous one -- simply stays there for the next pair (HalfXpowSink<true>): one image transform per pair instead of
 // two (a run re-transforms its first frame: 1 / run more).
-template <int CH, int MS, bool SEQ = false>
+// OFF (the fused window-offset form; pc_half_fused.hip instantiates it): the previous patch of linear index p is read at
+// (x0 - a_x, y0 - a_y), (a_x, a_y) = a.prev_off[2 p], [2 p + 1] -- its base address moves, nothing else does (as pc_kernel.hip's OFF).
+template <int CH, int MS, bool SEQ = false, bool OFF = false>
 __global__ void __launch_bounds__(HalfPlanOf<MS>::T, HalfPlanOf<MS>::WPE) pc_half_kernel(PcArgs a, int n, int n_pairs, int run) {
+  static_assert(!(OFF && SEQ), "a displaced window cannot reuse the previous spectrum");
   using SP = HalfPlanOf<MS>;
   constexpr HalfPlan HP = SP::HP;
   constexpr int M = MS, H = M / 2, P = HP.pitch, P2 = P / 2, T = SP::T, WAVES = HP.waves, LPW = HP.lpw;
@@ -334,6 +337,10 @@ __global__ void __launch_bounds__(HalfPlanOf<MS>::T, HalfPlanOf<MS>::WPE) pc_hal
   const uint8_t* cur = SEQ ? prev + a.cur_stride : a.cur + pair0 * a.cur_stride + poff;
   size_t p = (pair0 * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
   int pairs_left = SEQ ? ((size_t)n_pairs - pair0 < (size_t)run ? (int)((size_t)n_pairs - pair0) : run) : 1;
+  if constexpr (OFF) {  // signed, 64-bit: either component may be negative; inside the frame by the clamp kernel's clamp (pc_offset_kernel.hip)
+    const int64_t ax = a.prev_off[2 * p], ay = a.prev_off[2 * p + 1];
+    prev -= ay * (int64_t)a.pitch + (int64_t)CH * ax;
+  }
 
   if (tid < 2) flags[tid] = 0;
 #pragma unroll 1
@@ -817,6 +824,13 @@ hipError_t dispatch_half_size(int m, F&& f) {
 
 }  // namespace
 
+// (pc_half_fused.hip compiles this file's kernel and dispatch helpers into a translation unit of its own and brings its own host side)
+#ifndef MOF_HALF_KERNEL_ONLY
+// The fused window-offset forms live in pc_half_fused.hip. WEAK references: a program that links this file without that one (the host-side
+// builds that list the library's files by name) still links; in it a launch with a.prev_off set is an error, never another kernel.
+hipError_t pc_configure_half_fused(int m) __attribute__((weak));
+hipError_t launch_pc_half_fused(const PcArgs& a, int m, int n, int n_pairs, hipStream_t stream) __attribute__((weak));
+
 bool pc_half_supported(int m) {
   return dispatch_half_pair_size(m, [](auto) { return hipSuccess; }) == hipSuccess;
 }
@@ -834,13 +848,15 @@ int pc_half_workgroups_per_cu(int m) {
 // channel counts) on the calling thread's current device -- not of all ~60 instantiations: that loaded every code object at every
 // engine create, on every device of a shard group
 hipError_t pc_configure_half(int m) {
-  return pc_half_supported(m) ? dispatch_half_pair_size(m, [](auto ms) { return configure_half_size<ms, true>(); })
-                              : dispatch_half_video_only_size(m, [](auto ms) { return configure_half_size<ms, false>(); });
+  if (!pc_half_supported(m)) return dispatch_half_video_only_size(m, [](auto ms) { return configure_half_size<ms, false>(); });
+  const hipError_t e = dispatch_half_pair_size(m, [](auto ms) { return configure_half_size<ms, true>(); });
+  return e == hipSuccess && pc_configure_half_fused ? pc_configure_half_fused(m) : e;  // ... and the pair size's fused window-offset forms
 }
 
 // a.downscale must be 1 and a.peak_model 0 (the caller keeps the other front ends on their pipelines); m = the padded size, n the patch
 hipError_t launch_pc_half(const PcArgs& a_in, int m, int n, int n_pairs, hipStream_t stream) {
   if (a_in.downscale != 1 || a_in.peak_model != 0 || (a_in.channels != 1 && a_in.channels != 3) || n > m || n < 2) return hipErrorInvalidValue;
+  if (a_in.prev_off) return launch_pc_half_fused ? launch_pc_half_fused(a_in, m, n, n_pairs, stream) : hipErrorNotSupported;
   return pc_split_pairs(a_in, n_pairs, [&](const PcArgs& c, int nk) {  // the pair index rides gridDim.z
     const dim3 g((unsigned)c.grid_x, (unsigned)c.grid_y, (unsigned)nk);
     return dispatch_half_pair_size(m, [&](auto ms) {
@@ -887,5 +903,7 @@ hipError_t launch_pc_half_sequence(const PcArgs& a, int m, int n, int n_pairs, i
       return hipErrorInvalidValue;
   });
 }
+
+#endif  // MOF_HALF_KERNEL_ONLY
 
 }  // namespace mof

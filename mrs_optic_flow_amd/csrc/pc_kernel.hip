@@ -49,9 +49,14 @@ namespace mof {
 // CH = 3: the frames are interleaved BGR8 and the CV_RGB2GRAY conversion of the node's front end
 // (optic_flow.cpp:1622) is fused into the load, so raw camera frames are read from HBM exactly once.
 // PK = 1: the peak model of the reference's useOCL=true branch (cl/FftMethod.cl) instead of cv::phaseCorrelate's.
-template <int N, int DS, int CH, int PK>
+// OFF: the fused window-offset form (include/mof.h, "Predicted-shift window offsets"; full resolution, PK = 0 only) -- the previous
+// patch of linear index q is read at (x0 - a_x, y0 - a_y), (a_x, a_y) = a.prev_off[2 q], [2 q + 1]: a change of its base address, which
+// depends on the workgroup's patch index alone -- two scalar loads and scalar arithmetic, no VGPR, no LDS
+// (profiles/fft_pred_fused_static.txt). Everything else is the form it was made from, so are its bits on the same pixels.
+template <int N, int DS, int CH, int PK, bool OFF = false>
 __global__ void __launch_bounds__(PcTraits<N>::T) pc_field_kernel(PcArgs a) {
   static_assert(CH == 1 || (CH == 3 && DS == 1), "BGR front end only for the full-resolution path");
+  static_assert(!OFF || (DS == 1 && PK == 0), "window offsets: full resolution, cv::phaseCorrelate's peak model");
   using P = PcTraits<N>;
   constexpr int T = P::T, H = N / 2, R1 = P::R1, R2 = P::R2, LPW = P::LPW;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -92,6 +97,20 @@ __global__ void __launch_bounds__(PcTraits<N>::T) pc_field_kernel(PcArgs a) {
     const int px0 = a.origin_x + bx * a.stride_x, py0 = a.origin_y + by * a.stride_y;
     return frames + (size_t)pr * frame_stride + (size_t)(DS * py0) * a.pitch + (size_t)(CH * DS * px0);
   };
+  // the previous patch's base: OFF moves it by the applied prediction of patch q -- signed, 64-bit: either component may be negative.
+  // The clamp kernel wrote a.prev_off (pc_offset_kernel.hip), so the window stays inside the frame.
+  auto prev_base = [&](int q) -> const uint8_t* {
+    const uint8_t* base = patch_base(q, a.prev, a.prev_stride);
+    if constexpr (OFF) {
+      // (through the constant address space: nothing writes the applied predictions while the kernel runs, and saying so keeps the
+      // persistent loop's re-reads scalar loads -- behind the loop's own stores the compiler otherwise takes a vector load)
+      typedef const int32_t __attribute__((address_space(4))) * const_i32_ptr;
+      const const_i32_ptr off = (const_i32_ptr)a.prev_off;
+      const int64_t ax = off[2 * (size_t)q], ay = off[2 * (size_t)q + 1];
+      base -= ay * (int64_t)a.pitch + (int64_t)CH * ax;
+    }
+    return base;
+  };
 
   // twiddles of the second Stockham stage, W_N^{k x}: x = lane % R1 in row passes, lane / (64/R1) in column passes
   cf tw_row[R2 - 1], tw_col[R2 - 1];
@@ -116,7 +135,7 @@ __global__ void __launch_bounds__(PcTraits<N>::T) pc_field_kernel(PcArgs a) {
   int p = PERSIST ? (int)blockIdx.x : (int)((blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x);
   auto fetch16 = [&](int pp, uint32_t* c, uint32_t* q) {
     const uint8_t* cs = patch_base(pp, a.cur, a.cur_stride) + (size_t)lrow * a.pitch + CH * lcol;
-    const uint8_t* ps = patch_base(pp, a.prev, a.prev_stride) + (size_t)lrow * a.pitch + CH * lcol;
+    const uint8_t* ps = prev_base(pp) + (size_t)lrow * a.pitch + CH * lcol;
     if constexpr (CH == 1) {
       __builtin_memcpy(c, cs, 16);
       __builtin_memcpy(q, ps, 16);
@@ -348,7 +367,10 @@ __global__ void __launch_bounds__(PcTraits<N>::T) pc_field_kernel(PcArgs a) {
 template <int N>
 static hipError_t configure_n() {
   const size_t lds = PcTraits<N>::LDS_BYTES + pc_extra_lds();
-  return pc_each_form([&](auto ds, auto ch, auto pk) { return pc_raise_lds(&pc_field_kernel<N, ds, ch, pk>, lds); });
+  const hipError_t e = pc_each_form([&](auto ds, auto ch, auto pk) { return pc_raise_lds(&pc_field_kernel<N, ds, ch, pk>, lds); });
+  if (e != hipSuccess) return e;
+  // the fused window-offset forms: gray and BGR8, the enumeration launch_n dispatches them by
+  return pc_each_form<PC_FORMS_CH>([&](auto ds, auto ch, auto pk) { return pc_raise_lds(&pc_field_kernel<N, ds, ch, pk, true>, lds); });
 }
 
 template <int N>
@@ -365,6 +387,11 @@ static hipError_t launch_n(const PcArgs& a_in, int n_pairs, hipStream_t stream) 
   const dim3 b(Tr::T);
   const size_t lds = Tr::LDS_BYTES + pc_extra_lds();
   auto launch = [&](const PcArgs& aa, dim3 g) {
+    if (aa.prev_off)  // the fused window-offset form; hipErrorInvalidValue for the long-range mode and the OpenCL peak model
+      return pc_dispatch_form<PC_FORMS_CH>(aa, [&](auto ds, auto ch, auto pk) {
+        hipLaunchKernelGGL((pc_field_kernel<N, ds, ch, pk, true>), g, b, lds, stream, aa);
+        return hipGetLastError();
+      });
     return pc_dispatch_form(aa, [&](auto ds, auto ch, auto pk) {
       hipLaunchKernelGGL((pc_field_kernel<N, ds, ch, pk>), g, b, lds, stream, aa);
       return hipGetLastError();
@@ -396,7 +423,7 @@ hipError_t launch_pc_field(const PcArgs& a, int patch_size, int n_pairs, hipStre
     case 32: return launch_n<32>(a, n_pairs, stream);
     case 64: return launch_n<64>(a, n_pairs, stream);
     case 128: return launch_n<128>(a, n_pairs, stream);
-    case 120: return launch_pc_field_120(a, n_pairs, stream);
+    case 120: return a.prev_off ? hipErrorInvalidValue : launch_pc_field_120(a, n_pairs, stream);  // (the 15 x 8 kernel has no fused form)
     default: return hipErrorInvalidValue;
   }
 }

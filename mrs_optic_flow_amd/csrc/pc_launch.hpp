@@ -70,7 +70,7 @@ hipError_t pc_each_form(F&& f) {
 constexpr int PC_MAX_GRID_PAIRS = 65535;
 constexpr int PC_MAX_GRID_IMAGES = 65534;  // images of pairs: an even count keeps cur / prev together
 
-// launch(slice, nk) for every slice of at most 65535 pairs of a.cur / a.prev / a.out / a.quality, slice.total = its patches; ends at
+// launch(slice, nk) for every slice of at most 65535 pairs of a.cur / a.prev / a.out / a.quality / a.prev_off, slice.total = its patches; ends at
 // the first error
 template <class F>
 hipError_t pc_split_pairs(const PcArgs& a, int n_pairs, F&& launch) {
@@ -82,6 +82,7 @@ hipError_t pc_split_pairs(const PcArgs& a, int n_pairs, F&& launch) {
     c.prev = a.prev + (size_t)k0 * a.prev_stride;
     c.out = a.out + (size_t)k0 * patches * 2;
     if (a.quality) c.quality = a.quality + (size_t)k0 * patches * 2;
+    if (a.prev_off) c.prev_off = a.prev_off + (size_t)k0 * patches * 2;
     c.total = nk * patches;
     const hipError_t e = launch(c, nk);
     if (e != hipSuccess) return e;

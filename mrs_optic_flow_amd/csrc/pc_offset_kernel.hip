@@ -1,6 +1,7 @@
-// pc_offset_kernel.hip -- predicted-shift window offsets for the FFT engine (include/mof.h, "Predicted-shift window offsets"): three
-// small kernels AROUND the field's kernels, none of which changes -- the tuned kernels have no registers to spare (the reasoning of
-// pc_gate_kernel.hip), so the displaced previous window is materialised instead of being addressed from inside them.
+// pc_offset_kernel.hip -- predicted-shift window offsets for the FFT engine (include/mof.h, "Predicted-shift window offsets"): small
+// kernels AROUND the field's kernels. On the gather route (MOF_PRED_ROUTE_GATHER, the default) none of the field's kernels changes: the
+// displaced previous window is materialised (1.). On the fused route (MOF_PRED_ROUTE_FUSED) K1 and K1h read it themselves -- a change of
+// the previous patch's base address, scalar per workgroup (pc_kernel.hip, pc_half_kernel.hip: OFF) -- and only the clamp (1b.) runs first.
 //
 //  1. pc_offset_gather_kernel, before the field: one workgroup per (pair, patch). It clamps the patch's prediction p to the applied
 //     prediction a (pred_clamp_axis, mof_kernels.h), stores a, and copies the n x n bytes of prev at (x0 - a_x, y0 - a_y) into the
@@ -9,6 +10,7 @@
 //     alone: scalar loads and scalar arithmetic. The copy moves 16 bytes per lane and step: a load from the unaligned source (the
 //     form K1's fetch16 takes at origin (1, 1)) and a store of the same width; the last chunk of a row whose n is no multiple of
 //     16 starts at n - 16 and overlaps its neighbour with the same bytes. n < 16 copies bytes.
+//  1b. pc_offset_clamp_kernel (the fused route): one lane per patch, a = clamp(p) stored, no copy.
 //  2. pc_offset_finish_kernel, behind the field and the response gate: one lane per patch, total = a + residual, the speed gate on
 //     the total. Shaped like the gate kernel.
 //  3. pc_pred_from_coarse_kernel: one lane per fine patch, p = rint(4 s) of its long-range patch (pred_from_coarse, mof_kernels.h).
@@ -56,6 +58,20 @@ __global__ void __launch_bounds__(256) pc_offset_gather_kernel(PcOffsetArgs a, u
       dst[(size_t)row * a.pitch + col] = src[(size_t)row * a.pitch + col];
     }
   }
+}
+
+// the gather kernel's clamp without the copy (the fused route): one lane per patch. The fused field kernels read ONLY what this kernel
+// stored -- never a caller's raw prediction --: the clamp is what keeps their displaced loads inside the frame.
+__global__ void __launch_bounds__(256) pc_offset_clamp_kernel(PcOffsetArgs a, size_t n_patches) {
+  const size_t q = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (q >= n_patches) return;
+  const unsigned patches = (unsigned)(a.grid_x * a.grid_y);
+  const unsigned pt = (unsigned)(q % patches);
+  const int x0 = a.origin_x + (int)(pt % (unsigned)a.grid_x) * a.stride_x;
+  const int y0 = a.origin_y + (int)(pt / (unsigned)a.grid_x) * a.stride_y;
+  const offset_ixy p = *reinterpret_cast<const offset_ixy*>(a.pred + 2 * q);
+  *reinterpret_cast<offset_ixy*>(a.applied + 2 * q) =
+      offset_ixy{pred_clamp_axis(p.x, x0, a.frame_w, a.n), pred_clamp_axis(p.y, y0, a.frame_h, a.n)};
 }
 
 __global__ void __launch_bounds__(256) pc_offset_finish_kernel(double* __restrict__ out, const int32_t* __restrict__ applied, size_t n_patches,
@@ -112,6 +128,15 @@ hipError_t launch_pc_offset_gather(const PcOffsetArgs& a, int n_pairs, hipStream
     if (err != hipSuccess) return err;
   }
   return hipSuccess;
+}
+
+hipError_t launch_pc_offset_clamp(const PcOffsetArgs& a, int n_pairs, hipStream_t stream) {
+  const size_t n_patches = (size_t)n_pairs * (size_t)(a.grid_x * a.grid_y);
+  if (n_patches == 0) return hipSuccess;
+  unsigned blocks;
+  if (!a.pred || !a.applied || a.n < 2 || a.n > a.frame_w || a.n > a.frame_h || !lane_blocks(n_patches, &blocks)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(pc_offset_clamp_kernel, dim3(blocks), dim3(256), 0, stream, a, n_patches);
+  return hipGetLastError();
 }
 
 hipError_t launch_pc_offset_finish(double* out, const int32_t* applied, size_t n_patches, double max_px_speed_sq, hipStream_t stream) {

@@ -281,14 +281,47 @@ class FftMethod:
         applied = torch.empty((n, self.n_patches, 2), dtype=torch.int32, device=cur.device) if return_applied else None
         return out, quality, applied
 
+    PRED_ROUTES = {"gather": 0, "fused": 1}  # MOF_PRED_ROUTE_GATHER, MOF_PRED_ROUTE_FUSED
+
+    def set_pred_route(self, route: str) -> None:
+        """How the window-offset entries read the displaced previous windows (mof_fft_set_pred_route): "gather" (the default: through a
+        scratch frame) or "fused" (inside the field kernel: overlapping layouts and BGR8 frames too, no scratch). ValueError for another
+        name; MofError(MOF_ERR_UNSUPPORTED) where the engine's kernels have no fused form, MOF_ERR_BUSY while a captured graph pins the
+        engine -- the route is then unchanged."""
+        if route not in self.PRED_ROUTES:
+            raise ValueError(f"route must be one of {sorted(self.PRED_ROUTES)}, not {route!r}")
+        check(self._lib.mof_fft_set_pred_route(self._h, self.PRED_ROUTES[route]))
+
+    @property
+    def pred_route(self) -> str:
+        code = self._lib.mof_fft_pred_route(self._h)
+        return next(k for k, v in self.PRED_ROUTES.items() if v == code)
+
+    def pred_route_supported(self, route: str) -> bool:
+        """Whether this engine's layout has ``route`` on its default kernels (mof_fft_pred_route_supported, pure host)."""
+        if route not in self.PRED_ROUTES:
+            raise ValueError(f"route must be one of {sorted(self.PRED_ROUTES)}, not {route!r}")
+        rc = self._lib.mof_fft_pred_route_supported(C.byref(self.cfg), self.PRED_ROUTES[route])
+        if rc < 0:
+            check(rc)
+        return bool(rc)
+
     def process_batch_device_pred(self, cur, prev, pred, return_quality=False, return_applied=False, stream=None):
         """process_batch_device with the previous window of every patch read at a predicted displacement: ``pred`` is a torch int32
         tensor [n, patches, 2] of (x, y) predictions on the engine's device. Returns the total shifts [n, patches, 2] (applied
         prediction + residual; include/mof.h, "Predicted-shift window offsets"), then ``quality`` and the int32 ``applied`` tensor
         if asked for, in that order. Asynchronous."""
+        return self._process_batch_device_pred(cur, prev, pred, return_quality, return_applied, stream, 1)
+
+    def process_batch_device_pred_bgr(self, cur, prev, pred, return_quality=False, return_applied=False, stream=None):
+        """process_batch_device_pred on interleaved BGR8 frames [n, H, W, 3], CV_RGB2GRAY fused into the load: the bits of the gray
+        entry on the converted frames. The fused route only (set_pred_route): MofError(MOF_ERR_UNSUPPORTED) on the gather route."""
+        return self._process_batch_device_pred(cur, prev, pred, return_quality, return_applied, stream, 3)
+
+    def _process_batch_device_pred(self, cur, prev, pred, return_quality, return_applied, stream, channels):
         import torch
 
-        _check_device_batch(cur, prev, (self.cfg.frame_height, self.cfg.frame_width), self.cfg.device)
+        _check_device_batch(cur, prev, (self.cfg.frame_height, self.cfg.frame_width), self.cfg.device, channels=channels)
         n = cur.shape[0]
         if not (isinstance(pred, torch.Tensor) and pred.dtype == torch.int32 and pred.is_cuda and pred.device == cur.device
                 and pred.is_contiguous() and tuple(pred.shape) == (n, self.n_patches, 2)):
@@ -296,7 +329,8 @@ class FftMethod:
         out, quality, applied = self._pred_outputs(cur, return_quality, return_applied)
         s = stream if stream is not None else torch.cuda.current_stream(cur.device)
         _pin_if_capturing(self, s)
-        check(self._lib.mof_fft_process_batch_device_pred(
+        entry = self._lib.mof_fft_process_batch_device_pred if channels == 1 else self._lib.mof_fft_process_batch_device_pred_bgr
+        check(entry(
             self._h, cur.data_ptr(), cur.stride(0), prev.data_ptr(), prev.stride(0), cur.stride(1), n, pred.data_ptr(), out.data_ptr(),
             quality.data_ptr() if return_quality else None, applied.data_ptr() if return_applied else None, _stream_ptr(s)))
         res = (out,) + ((quality,) if return_quality else ()) + ((applied,) if return_applied else ())

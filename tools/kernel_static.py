@@ -5,7 +5,8 @@ kernel_code_entry_byte_offset (bytes 16 .. 23), the distance from the descriptor
 or leaves the code object.
 
   tools/kernel_static.py LIB             one line per kernel, sorted by name
-  tools/kernel_static.py compare A B     whether each whole gfx950 code object is byte-identical (by position, and by content: a new
+  tools/kernel_static.py compare A B [REGEX=REPL ...]
+                                         whether each whole gfx950 code object is byte-identical (by position, and by content: a new
                                          translation unit shifts the positions behind it), then the names only in A, the names only
                                          in B, and the fields (code included) that changed
 
@@ -83,7 +84,8 @@ def code_hashes(co, sections, symbols):
         if ndx in sec:
             off = sec[ndx][1] + addr - sec[ndx][0]
             sym[name] = co[off:off + size]
-    return {n: (hashlib.sha256(b + sym[n + ".kd"][:16] + bytes(8) + sym[n + ".kd"][24:]).hexdigest(), len(b)) for n, b in sym.items() if n + ".kd" in sym}
+    return {n: (hashlib.sha256(b + sym[n + ".kd"][:16] + bytes(8) + sym[n + ".kd"][24:]).hexdigest(), len(b), hashlib.sha256(b).hexdigest())
+            for n, b in sym.items() if n + ".kd" in sym}
 
 
 def record(lib):
@@ -101,7 +103,7 @@ def record(lib):
             for name, fields in kernels_of(subprocess.check_output([readelf, "--notes", path], text=True)).items():
                 if name not in code:
                     sys.exit(f"{lib}: no symbol or no descriptor {name}.kd found for kernel {name} (llvm-readelf --symbols)")
-                fields["code"], fields["code_bytes"] = code[name]
+                fields["code"], fields["code_bytes"], fields["text"] = code[name]
                 while name in rec:  # (kernels of unnamed namespaces in two translation units may share a name)
                     name += "'"
                 rec[name] = fields
@@ -125,7 +127,12 @@ def main(argv):
             print(f"{name}: {row(rec[name])}")
         print(f"kernels: {len(rec)}")
         return 0
-    if len(argv) == 4 and argv[1] == "compare":
+    if len(argv) >= 4 and argv[1] == "compare":
+        # compare A B [REGEX=REPLACEMENT ...]: the kernel names of both sides rewritten first (a template that gained a defaulted
+        # parameter names its old instantiations differently: 'kernel<(.*), false>=kernel<\\1>')
+        for rule in argv[4:]:
+            pat, _, repl = rule.partition("=")
+            print(f"names rewritten: {pat} -> {repl}")
         ca, cb = [[hashlib.sha256(co).hexdigest() for co in code_objects(lib)] for lib in (argv[2], argv[3])]
         same = sum(x == y for x, y in zip(ca, cb))
         print(f"gfx950 code objects: A {len(ca)}, B {len(cb)}; byte-identical {same}" + ("" if len(ca) != len(cb) else f", differing {len(ca) - same}"))
@@ -136,6 +143,9 @@ def main(argv):
         print(f"by content: {len(ca) - len(gone)} of A's {len(ca)} code objects are byte-identical in B; only in A {[x[:16] for x in gone]}, "
               f"only in B {[y[:16] for y in new]}")
         a, b = record(argv[2]), record(argv[3])
+        for rule in argv[4:]:
+            pat, _, repl = rule.partition("=")
+            a, b = ({re.sub(pat, repl, n): f for n, f in r.items()} for r in (a, b))
         only_a, only_b = sorted(set(a) - set(b)), sorted(set(b) - set(a))
         print(f"kernels: A {len(a)}, B {len(b)}; library {os.path.getsize(argv[2])} -> {os.path.getsize(argv[3])} bytes")
         print(f"only in A: {only_a}")
@@ -144,7 +154,8 @@ def main(argv):
         for name in sorted(set(a) & set(b)):
             diff = [f"{s} {a[name].get(k, 0)} -> {b[name].get(k, 0)}" for s, k in zip(SHORT, FIELDS) if a[name].get(k, 0) != b[name].get(k, 0)]
             if a[name]["code"] != b[name]["code"]:
-                diff.append(f"code {a[name]['code'][:16]} -> {b[name]['code'][:16]}")
+                # (same instruction bytes: only the descriptor differs -- e.g. kernarg_size after a member was appended to an argument struct)
+                diff.append(f"code {a[name]['code'][:16]} -> {b[name]['code'][:16]}" + (" (descriptor only: .text bytes identical)" if a[name]["text"] == b[name]["text"] else ""))
             if diff:
                 changed += 1
                 print(f"{name}: {', '.join(diff)}")

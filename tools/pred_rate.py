@@ -83,8 +83,9 @@ def plain_only(reps, names):
     from mrs_optic_flow_amd import _capi
 
     exported = ctypes.CDLL(_capi.LIB_PATH)
-    for symbol in [s for s in _capi.SYMBOLS if not hasattr(exported, s)]:
-        del _capi.SYMBOLS[symbol]
+    for table in (_capi.SYMBOLS, _capi.PRED_ROUTE_SYMBOLS):
+        for symbol in [s for s in table if not hasattr(exported, s)]:
+            del table[symbol]
     for name in names:
         g, fm, cur, prev = setup(name)
         ms, rounds = measure({"plain": lambda: fm.process_batch_device(cur, prev)}, reps)["plain"]
