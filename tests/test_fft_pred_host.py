@@ -2,6 +2,7 @@
 state the definitions, held to numpy (tests/pred_cases.py), the surfaces that must name the same entries, and -- on the CPU oracle -- the
 facts the GPU tests rely on: the residuals of their inputs have clear peaks, and the coarse-to-fine ground is the one the feature adds."""
 import ctypes as C
+import hashlib
 import os
 import re
 
@@ -10,6 +11,8 @@ import pytest
 
 import oracle_lib as O
 import pred_cases as PC
+import route_cases as R
+import tolerances
 from mrs_optic_flow_amd import _capi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -33,7 +36,7 @@ def _from_coarse(sx, sy):
     return rc, (px.value, py.value)
 
 
-@pytest.mark.parametrize("l", PC.LAYOUTS, ids=lambda l: l.name)
+@pytest.mark.parametrize("l", PC.LAYOUTS + PC.EDGE_LAYOUTS, ids=lambda l: l.name)
 def test_clamp_matches_numpy_on_every_border_case(l):
     """every patch of the layout x predictions at, one inside and one outside each clamp bound, 0, +-n and the int32 extremes"""
     cfg = _cfg(l)
@@ -166,3 +169,66 @@ def test_cpu_oracle_coarse_to_fine_ground(fs):
     assert worst <= 0.25 and skipped <= may_skip, (worst, skipped)
     print(f"frame {fs}: plain wrong on {int(wrong.sum())} of {PC.patches(l)}, prediction {pred[0, 0].tolist()}, worst free patch {worst:.3f} px, "
           f"{skipped} of {n_clamped} clamped patches without a clear peak")
+
+
+# sha256 (first 16 hex digits) of case(name).pred and .cur as they stood before the edge layouts scaled the recipe: the existing cases keep
+# their exact bytes
+CASE_BYTES = {
+    "k1_32": ("8528097a29f49158", "79683bac60f40fb4"), "k1_64": ("6228ecabccfba0c3", "b75eafe2f626874a"),
+    "n120": ("ef04cf11cbca1f7e", "00374b935aa6fd4a"), "persistent_128": ("ab34f257da4708c9", "4116cb084bd3ca53"),
+    "k1h_96": ("8c2de2ebd1d127fd", "e5a06506d8a71efc"), "k1h_160": ("d62cc160b61fa154", "e81c59b917e38d79"),
+    "planned_62": ("1dbb5dee0c059cb9", "e3728fd4188daa6f"), "large_200": ("b5f9de8fe845ce16", "63ff537882016641"),
+    "offset_32": ("5bc8b7ac5704e1a2", "531de39f6c325703"),
+}
+
+
+def test_existing_cases_keep_their_bytes():
+    assert set(CASE_BYTES) == {l.name for l in PC.LAYOUTS}
+    for name, want in CASE_BYTES.items():
+        c = PC.case(name)
+        assert c.pred.dtype == np.int32 and c.cur.dtype == np.uint8
+        assert (hashlib.sha256(c.pred.tobytes()).hexdigest()[:16], hashlib.sha256(c.cur.tobytes()).hexdigest()[:16]) == want, name
+
+
+def test_edge_layouts_stand_at_the_sizes_the_kernels_branch_on():
+    """the byte copy (n < 16), two overlapping 16-byte chunks per row (16 < n < 32), an odd tail column (odd n), the padded and odd
+    half-tile sizes of the fused form, the large pipeline's odd tail; the variant and the fused form by the recorded route table"""
+    assert [l.n for l in PC.EDGE_LAYOUTS] == [8, 15, 20, 31, 37, 57, 136, 162, 244]
+    table = R.default_table()
+    offset = 0
+    for l in PC.EDGE_LAYOUTS:
+        row = table[(R.PEAK_OPENCV, l.n)]
+        assert R.variant(row) == l.variant, (l.name, row)
+        assert (row[2] > 0) == (l.name in PC.EDGE_FUSED), (l.name, row)
+        assert min(l.grid) >= 2 and l.pitch >= l.w
+        x1, y1 = PC.origin_of(l, PC.patches(l) - 1)
+        assert x1 + l.n <= l.w and y1 + l.n <= l.h and l.w - (x1 + l.n) <= 2 and l.h - (y1 + l.n) <= 1  # the smallest frames
+        offset += l.origin == (1, 1) and min(l.stride) > l.n and l.pitch > l.w
+    assert offset >= 2
+    assert [table[(R.PEAK_OPENCV, n)][1] for n in (57, 136, 162, 244)] == [60, 144, 162, 250]  # the transform sizes: padded but for 162
+
+
+@pytest.mark.parametrize("l", PC.EDGE_LAYOUTS, ids=lambda l: l.name)
+def test_cpu_oracle_residuals_of_the_edge_cases(l):
+    """What the GPU tests rely on at the edge sizes: from 15 on every patch has a clear peak and the two oracles lie within 2e-5 px; at 8,
+    where the 5 x 5 window is most of the surface, at most a quarter of the patches lack a clear peak (left out of the oracle comparison,
+    never of the bit identities) and the others lie within 2e-5 px. The planted shift is max(1, n // 8), the predictions spread
+    max(1, n // 16) around it, and the clamp acts."""
+    c = PC.case(l.name)
+    w64, w32, clear = PC.residual_oracles(l.name)
+    assert np.abs(c.planted).max() == max(1, l.n // 8)
+    spread = max(1, l.n // 16)
+    assert np.abs(c.pred[0] - c.planted[0]).max() <= spread  # (pair 0: seeded only)
+    assert (c.applied != c.pred).any() and (c.applied[1] != c.pred[1]).any(axis=-1).sum() >= PC.patches(l) - 2
+    unclear = int((~clear).sum())
+    assert unclear <= PC.unclear_cap(l.name), (unclear, np.argwhere(~clear).tolist())
+    assert PC.unclear_cap(l.name) == (3 if l.n == 8 else 0)
+    dd = np.abs(w64 - w32).max(axis=-1)
+    assert np.isfinite(w64[clear]).all() and dd[clear].max() <= tolerances.F32_LIMITED_FROM
+    # the plain entry is valid on every patch of the frames and of the displaced frames (no |shift| > n / 2): the bit identities compare numbers
+    lay = PC.oracle_layout(l)
+    for k in range(PC.N_PAIRS):
+        assert not np.isnan(O.fft_process(c.cur[k], c.prev[k], lay, 64)[0]).any() and not np.isnan(O.fft_process(c.cur[k], c.disp[k], lay, 64)[0]).any(), k
+    want = c.planted[:, None, :] - c.applied  # (no closeness asserted: at these sizes the 5 x 5 centroid is biased by a pixel and more)
+    print(f"{l.name}: {unclear} of {clear.size} patches without a clear peak (cap {PC.unclear_cap(l.name)}); oracle distance on the others, worst {dd[clear].max():.2e} px; "
+          f"residuals up to {np.abs(want).max()} px")

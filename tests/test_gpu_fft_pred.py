@@ -18,7 +18,7 @@ from mrs_optic_flow_amd import FftMethod, MofError, _capi, release_captured, syn
 from mrs_optic_flow_amd.engine import PEAK_OCL
 
 pytestmark = pytest.mark.gpu
-NAMES = [l.name for l in PC.LAYOUTS]
+NAMES = [l.name for l in PC.LAYOUTS + PC.EDGE_LAYOUTS]  # (the edge layouts: the sizes the window-offset kernels branch on)
 
 
 def _np(a):
@@ -112,7 +112,7 @@ def test_offset_windows_have_the_bits_of_a_gathered_frame(gpu, name):
 @pytest.mark.parametrize("name", NAMES)
 def test_residuals_against_the_oracle(gpu, name):
     """got - applied against -O.phase_correlate(cur window, displaced prev window) at 64 and 32 bit, every patch, by the rule of
-    tests/tolerances.py alone"""
+    tests/tolerances.py alone (at n = 8 the patches without a clear peak are left out: at most pred_cases.unclear_cap, none elsewhere)"""
     c = PC.case(name)
     l = c.layout
     fm = _engine(l)
@@ -120,16 +120,19 @@ def test_residuals_against_the_oracle(gpu, name):
     got, applied = _np(got), _np(applied)
     assert np.array_equal(applied, c.applied)
     w64, w32, clear = PC.residual_oracles(name)
-    assert clear.all()
+    left_out = int((~clear).sum())
+    assert left_out <= PC.unclear_cap(name)  # (0 everywhere but at n = 8)
     worst = 0.0
     for k in range(PC.N_PAIRS):
         for p in range(PC.patches(l)):
+            if not clear[k, p]:
+                continue
             r = got[k, p] - applied[k, p]
             worst = max(worst, float(np.abs(r - w64[k, p]).max()))
             pinned = T.check_patch(r, w64[k, p], w32[k, p], f"pred/{name}/pair{k}", p, what="offset window",
                                    pixels=(PC.window(l, c.cur[k], p), PC.window(l, c.disp[k], p)))
             assert pinned, (name, k, p)
-    print(f"{name}: worst |residual - f64 oracle| = {worst:.3g} px over {PC.N_PAIRS * PC.patches(l)} patches")
+    print(f"{name}: worst |residual - f64 oracle| = {worst:.3g} px over {PC.N_PAIRS * PC.patches(l) - left_out} patches, {left_out} left out")
 
 
 # ---- 5. coarse to fine ----

@@ -16,7 +16,8 @@ from mrs_optic_flow_amd import FftMethod, MofError, _capi, release_captured
 from mrs_optic_flow_amd.engine import PEAK_OCL
 
 pytestmark = pytest.mark.gpu
-FUSED_LAYOUTS = ["k1_32", "k1_64", "n120", "persistent_128", "k1h_96", "k1h_160", "offset_32"]  # those of pred_cases.LAYOUTS with a fused form
+# those of pred_cases.LAYOUTS with a fused form, and of its edge layouts: the padded and odd half-tile sizes (57 -> 60, 136 -> 144, 162)
+FUSED_LAYOUTS = ["k1_32", "k1_64", "n120", "persistent_128", "k1h_96", "k1h_160", "offset_32"] + PC.EDGE_FUSED
 OVER = [l.name for l in F.OVER]
 
 
