@@ -451,7 +451,10 @@ int mof_bm_refine(mof_bm_engine* e, int fullpix_x, int fullpix_y, int passes, in
 
 /* Batched mode on DEVICE pointers. d_dx, d_dy: n_pairs*grid_x*grid_y int8; d_mode: n_pairs*8 int8
  * = {modeX, modeY, 2nd X, 2nd Y, 3rd X, 3rd Y, 0, 0} (the TestDepth=3 list of
- * FastSpacedBMMethod_OCL.cpp:97 per axis). Asynchronous on `stream`. */
+ * FastSpacedBMMethod_OCL.cpp:97 per axis). Asynchronous on `stream`.
+ * Known reference defect, repaired (F13): on a one-block grid the reference's Histogram_C1_D0 never sorts its Y histogram (it
+ * sorts Y in work-item 1, which a 1 x 1 launch does not have) and returns Y = (-r, -r+1, -r+2) whatever the block found. This
+ * library returns the sorted list on every grid, as the kernel evidently intends; every other output equals the reference's. */
 int mof_bm_process_batch_device(mof_bm_engine* e, const uint8_t* d_cur, size_t cur_stride, const uint8_t* d_prev,
                                 size_t prev_stride, size_t pitch, int n_pairs, int8_t* d_dx, int8_t* d_dy,
                                 int8_t* d_mode, void* stream);

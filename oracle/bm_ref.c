@@ -1,8 +1,12 @@
 /*
  * bm_ref.c -- CPU restatement of the reference's two block-matching paths
- * (integer stage). TEST INFRASTRUCTURE ONLY; PARITY UNPINNED (see oracle.h):
- * both classes are dead code in the reference and there are no
- * fixtures; this file follows their text.
+ * (integer stage). TEST INFRASTRUCTURE ONLY. Both classes are dead code in the
+ * reference and there are no fixtures; this file follows their text.
+ * PINNED for the FastSpacedBM half: oracle_bm_process_u8 with the low-contrast rule
+ * and oracle_bm_histogram_top equal the reference's own OpenCL text executed on the
+ * CPU, bit for bit (ref_bm_cl.c, tests/test_ref_cl_host.py), except that a one-block
+ * grid's Y list is sorted here and not there. BlockMethod.cpp
+ * needs OpenCV and stays UNPINNED (see oracle.h).
  *
  *   BlockMethod::processImage     /root/reference/src/BlockMethod.cpp:25-94
  *   OptFlow_C1_D0, Histogram_C1_D0 /root/reference/src/FastSpacedBMMethod.cl:4-84, :86-169

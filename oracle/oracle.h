@@ -15,6 +15,16 @@
  * external calls (dft/idft CCS packing, mulSpectrums, minMaxLoc, weightedCentroid).
  * It is cross-checked against an independent numpy twin (tests/twin.py) and
  * analytic known-answer cases, not against reference output.
+ *
+ * PINNED, the exception: the parts of the reference that are plain OpenCL C need neither OpenCV nor ROS to execute.
+ * OptFlow_C1_D0 and Histogram_C1_D0 (src/FastSpacedBMMethod.cl) and the arg-max / refine tail of the useOCL=true chain
+ * (minmaxloc, refine in cl/FftMethod.cl) are pinned to the reference's own OpenCL text, executed on the CPU by cl_host.h
+ * under the launch-wide-barrier reading (ref_bm_cl.c, ref_fft_peak.cpp -> oracle/_ref/, built where the reference
+ * checkout exists; tests/test_ref_cl_host.py; recorded outputs in tests/golden/ref_cl_*.npz). oracle_bm_process_u8 (with
+ * the low-contrast rule), oracle_bm_histogram_top and oracle_ocl_peak_f32 agree with it bit for bit, with one documented
+ * repair: on a one-block grid the text never sorts its Y histogram (note F13).
+ * Everything that needs OpenCV stays unpinned: cv::phaseCorrelate, logPolar, resize, cvtColor, BlockMethod.cpp, and the
+ * transforms and cross-power stage of the useOCL=true chain.
  */
 #ifndef MOF_ORACLE_H
 #define MOF_ORACLE_H
@@ -79,6 +89,11 @@ int oracle_phase_correlate_ocl_f32(const float* a, size_t a_stride, const float*
                                    int y0, int search_radius, double* out_xy, oracle_pc_diag* diag, float* surface);
 int oracle_phase_correlate_ocl_f64(const double* a, size_t a_stride, const double* b, size_t b_stride, int n, int x0,
                                    int y0, int search_radius, double* out_xy, oracle_pc_diag* diag, double* surface);
+/* The peak stage of that model alone -- arg-max (first maximum in row-major order) and the radius-3 refine -- on a finished
+ * n x n surface (fft-shifted and masked, tightly packed). out_xy is the same float result, widened. PINNED: tests hold the
+ * f32 form bit for bit to the reference's own minmaxloc / refine text executed on the CPU (cl_host.h, ref_fft_peak.cpp). */
+int oracle_ocl_peak_f32(const float* surface, int n, int x0, int y0, double* out_xy);
+int oracle_ocl_peak_f64(const double* surface, int n, int x0, int y0, double* out_xy);
 /* FftMethod::processImage with useOCL=true under that model (src/FftMethod.cpp:1824-1825, :1833, :1840-1856;
  * SEARCH_RADIUS 55, :820). Same layout/outputs as oracle_fft_process_u8. */
 int oracle_fft_process_ocl_u8(const uint8_t* cur, const uint8_t* prev, size_t pitch, const oracle_fft_layout* layout,

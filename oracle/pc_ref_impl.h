@@ -269,6 +269,56 @@ int FN(oracle_phase_correlate)(const R* a, size_t a_stride, const R* b, size_t b
   return 0;
 }
 
+/* The peak stage of the useOCL=true model on a finished n x n surface (fft-shifted, masked): arg-max then refine, as listed
+ * below. Factored out so that a surface can be fed to it directly (tests hold it to the reference's OpenCL text run on the
+ * CPU, bit for bit); oracle_phase_correlate_ocl_* ends in it. (x0, y0) is the patch origin in the frame. */
+typedef struct {
+  int px, py, xmin, xmax, ymin, ymax;
+  R best, sum;
+} FN(ocl_peak);
+
+static void FN(ocl_peak_stage)(const R* S, int n, int x0, int y0, double* out_xy, FN(ocl_peak)* pk) {
+  const int h = n / 2;
+  const R eps = (R)FLT_EPSILON;
+  int px = 0, py = 0;
+  R best = -(R)FLT_MAX;
+  for (int y = 0; y < n; ++y)
+    for (int x = 0; x < n; ++x)
+      if (best < S[(size_t)y * n + x]) {
+        best = S[(size_t)y * n + x];
+        px = x;
+        py = y;
+      }
+
+  const int radius = 3;
+  const int xmin = px - radius >= 0 ? px - radius : 0, xmax = px + radius < n ? px + radius : n - 1;
+  const int ymin = py - radius >= 0 ? py - radius : 0, ymax = py + radius < n ? py + radius : n - 1;
+  R cx = (R)0, cy = (R)0, sum = eps;
+  for (int y = ymin; y <= ymax; ++y)
+    for (int x = xmin; x <= xmax; ++x) {
+      const R v = S[(size_t)y * n + x];
+      if (v > (R)0) {
+        cx += (R)(x0 + x) * v;
+        cy += (R)(y0 + y) * v;
+        sum += v;
+      }
+    }
+  cx /= sum;
+  cy /= sum;
+  out_xy[0] = (double)(R)(cx - (R)(x0 + h));
+  out_xy[1] = (double)(R)(cy - (R)(y0 + h));
+  if (pk) {
+    pk->px = px; pk->py = py; pk->xmin = xmin; pk->xmax = xmax; pk->ymin = ymin; pk->ymax = ymax;
+    pk->best = best; pk->sum = sum;
+  }
+}
+
+int FN(oracle_ocl_peak)(const R* surface, int n, int x0, int y0, double* out_xy) {
+  if (!surface || !out_xy || n < 8 || (n & 1)) return -1;
+  FN(ocl_peak_stage)(surface, n, x0, y0, out_xy, NULL);
+  return 0;
+}
+
 /* ---------------------------------------------------------------------------------------------
  * The useOCL=true peak model, restated from /root/reference/cl/FftMethod.cl as
  * the maths its kernel chain intends (the kernel synchronises work-groups with barrier(), which
@@ -352,33 +402,10 @@ int FN(oracle_phase_correlate_ocl)(const R* a, size_t a_stride, const R* b, size
       S[(size_t)sy * n + sx] = masked ? (R)0 : C[(size_t)y * n + x].re * scale;
     }
 
-  int px = 0, py = 0;
-  R best = -(R)FLT_MAX;
-  for (int y = 0; y < n; ++y)
-    for (int x = 0; x < n; ++x)
-      if (best < S[(size_t)y * n + x]) {
-        best = S[(size_t)y * n + x];
-        px = x;
-        py = y;
-      }
-
-  const int radius = 3;
-  const int xmin = px - radius >= 0 ? px - radius : 0, xmax = px + radius < n ? px + radius : n - 1;
-  const int ymin = py - radius >= 0 ? py - radius : 0, ymax = py + radius < n ? py + radius : n - 1;
-  R cx = (R)0, cy = (R)0, sum = eps;
-  for (int y = ymin; y <= ymax; ++y)
-    for (int x = xmin; x <= xmax; ++x) {
-      const R v = S[(size_t)y * n + x];
-      if (v > (R)0) {
-        cx += (R)(x0 + x) * v;
-        cy += (R)(y0 + y) * v;
-        sum += v;
-      }
-    }
-  cx /= sum;
-  cy /= sum;
-  out_xy[0] = (double)(R)(cx - (R)(x0 + h));
-  out_xy[1] = (double)(R)(cy - (R)(y0 + h));
+  FN(ocl_peak) pk;
+  FN(ocl_peak_stage)(S, n, x0, y0, out_xy, &pk);
+  const int xmin = pk.xmin, xmax = pk.xmax, ymin = pk.ymin, ymax = pk.ymax, px = pk.px, py = pk.py;
+  const R best = pk.best, sum = pk.sum;
 
   if (diag) {
     double second = -HUGE_VAL;

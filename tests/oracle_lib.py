@@ -83,6 +83,10 @@ def lib():
                                                       C.c_int, C.c_int, C.c_void_p, C.POINTER(PcDiag), C.c_void_p]
         L.oracle_phase_correlate_ocl_f64.restype = C.c_int
         L.oracle_phase_correlate_ocl_f64.argtypes = L.oracle_phase_correlate_ocl_f32.argtypes
+        L.oracle_ocl_peak_f32.restype = C.c_int
+        L.oracle_ocl_peak_f32.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        L.oracle_ocl_peak_f64.restype = C.c_int
+        L.oracle_ocl_peak_f64.argtypes = L.oracle_ocl_peak_f32.argtypes
         L.oracle_fft_process_ocl_u8.restype = C.c_int
         L.oracle_fft_process_ocl_u8.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(FftLayout), C.c_int, C.c_int,
                                                 C.c_void_p, C.POINTER(C.c_int), C.c_void_p]
@@ -230,6 +234,20 @@ def phase_correlate_ocl(a: np.ndarray, b: np.ndarray, origin=(0, 0), search_radi
     if want_surface:
         return (out[0], out[1]), d, surf
     return (out[0], out[1]), d
+
+
+def ocl_peak(surface: np.ndarray, origin=(0, 0), precision: int = 32) -> np.ndarray:
+    """The peak stage (arg-max + radius-3 refine) of the useOCL=true model on a finished n x n surface -> the shift (x, y) as
+    the oracle returns it (float64; for precision 32 each is exactly a float32)."""
+    n = surface.shape[0]
+    assert surface.shape == (n, n)
+    s = np.ascontiguousarray(surface, dtype=np.float32 if precision == 32 else np.float64)
+    out = np.zeros(2, np.float64)
+    fn = lib().oracle_ocl_peak_f32 if precision == 32 else lib().oracle_ocl_peak_f64
+    rc = fn(_ptr(s), n, int(origin[0]), int(origin[1]), _ptr(out))
+    if rc:
+        raise ValueError(f"oracle_ocl_peak rc={rc}")
+    return out
 
 
 def fft_process_ocl(cur: np.ndarray, prev: np.ndarray, layout: FftLayout, search_radius: int = 55, precision: int = 32,
