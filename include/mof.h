@@ -16,7 +16,9 @@
  * with MOF_ERR_NO_DEVICE.
  *
  * Conventions
- *   - frames are 8-bit single-channel, row-major, `pitch` bytes per row;
+ *   - frames are 8-bit single-channel, row-major, `pitch` bytes per row; the FFT
+ *     engine's pair, long-range and window-offset entries take pitch < 2^24 (16 MiB)
+ *     and answer MOF_ERR_BAD_ARG beyond it;
  *   - FFT results are (x, y) pixel shifts, +x right, +y down, positive = image
  *     content moved that way from the previous to the current frame (the sign of
  *     `-cv::phaseCorrelate(cur, prev)`, FftMethod.cpp:1836); invalid patches are

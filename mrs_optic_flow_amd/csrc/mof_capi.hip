@@ -370,6 +370,8 @@ static int launch_large(mof_fft_engine* e, const mof::PcArgs& a, int n_pairs, hi
 // too large for a CU -- the planned pipeline through HBM scratch. Returns a MOF status.
 static int launch_field(mof_fft_engine* e, const mof::PcArgs& a, int n_pairs, hipStream_t stream) {
   const FftRoute& r = e->route;
+  // one bound for every entry and every kernel family (K1's one-patch forms need it: mof_kernels.h, PC_MAX_PITCH)
+  if (a.pitch >= mof::PC_MAX_PITCH) return fail(MOF_ERR_BAD_ARG, "row pitch of 16 MiB or more");
   if (a.prev_off && !(a.downscale == 1 && mof::fft_pred_fused_supported(r, a.peak_model)))  // (mof_fft_set_pred_route keeps this from happening)
     return fail(MOF_ERR_UNSUPPORTED, "this engine's kernels have no fused window-offset form");
   if (r.half_m > 0 && a.downscale == 1) {  // (no scratch, nothing engine-owned but the twiddles)

@@ -115,6 +115,11 @@ hipError_t launch_pc_half_sequence(const PcArgs& a, int m, int n, int n_pairs, i
 
 bool pc_patch_size_supported(int n);  // the hand-tuned instantiations: 32, 64, 120, 128
 hipError_t pc_configure(int patch_size);  // once per device before the first launch
+// PcArgs::pitch must stay below PC_MAX_PITCH (16 MiB per frame row): the one-patch forms of K1 address a lane's pixels as a scalar patch
+// base plus ONE 32-bit lane offset, row-in-patch * pitch + column bytes, formed with a 24-bit multiply (pc_kernel.hip, fetch16). Every
+// field launch of the FFT engine is held to it (mof_capi.hip, launch_field: MOF_ERR_BAD_ARG); launch_pc_field itself answers
+// hipErrorInvalidValue beyond it.
+constexpr size_t PC_MAX_PITCH = (size_t)1 << 24;
 hipError_t launch_pc_field(const PcArgs& a, int patch_size, int n_pairs, hipStream_t stream);
 // launch_pc_field's a.twiddles at 32 and 64: twiddle_table(n) with the packed per-index rows appended (TwRows, pc_passes.hpp); other
 // sizes are left as they are. The classic table stays at offset 0 for every kernel that reads it.

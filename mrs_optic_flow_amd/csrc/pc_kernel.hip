@@ -75,6 +75,9 @@ __global__ void __launch_bounds__(PcTraits<N>::T) pc_field_kernel(PcArgs a) {
   // than a static stride does, and the patch coordinates come from blockIdx without the integer divisions that
   // otherwise cost ~5 % of the kernel's VALU instructions.
   constexpr bool PERSIST = P::PERSIST;
+  // N = 32 (one wave per workgroup) keeps the parent's prologue with the persistent form: with the straight-line one it measured 3 % slower
+  // (profiles/k1_prologue_ab.txt). OLD_PROLOGUE: the loop, the laundering, the p < total guard, 64-bit lane addresses, const_track as it was.
+  constexpr bool OLD_PROLOGUE = PERSIST || N == 32;
   constexpr bool FWD3 = N == 64 && DS == 1;                  // the three-stage forward transform (pc_passes3.hpp)
   constexpr bool RAW = (N == 128 || N == 64) && DS == 1;     // raw pixel staging (pc_passes.hpp)
   // arg-max by value first (below). One patch per workgroup and more than one wave: a single wave (N = 32) always holds the maximum,
@@ -113,29 +116,43 @@ __global__ void __launch_bounds__(PcTraits<N>::T) pc_field_kernel(PcArgs a) {
   };
 
   // twiddles of the second Stockham stage, W_N^{k x}: x = lane % R1 in row passes, lane / (64/R1) in column passes
+  // (the persistent form gathers them here, first; the one-patch forms -- the ones with packed rows -- ask for theirs behind the two pixel
+  // loads, which are what they wait for)
+  static_assert(TwRows<N>::USE == !P::PERSIST, "packed twiddle rows: the one-patch forms");
   cf tw_row[R2 - 1], tw_col[R2 - 1];
-  {
+  Fwd3Tw tw3;
+  auto load_twiddle_rows = [&] {  // one packed row each (TwRows, pc_passes.hpp)
     const int xr = lane0 % R1, xc = lane0 / (64 / R1);
-    if constexpr (TwRows<N>::USE) {  // one packed row each (TwRows, pc_passes.hpp)
-      tw_row_load<R2>(a.twiddles + TwRows<N>::ROWS_AT + 2 * R2 * xr, tw_row);
-      tw_row_load<R2>(a.twiddles + TwRows<N>::ROWS_AT + 2 * R2 * xc, tw_col);
-    } else
+    tw_row_load<R2, N == 32>(a.twiddles + TwRows<N>::ROWS_AT + 2 * R2 * xr, tw_row);
+    tw_row_load<R2, N == 32>(a.twiddles + TwRows<N>::ROWS_AT + 2 * R2 * xc, tw_col);
+    if constexpr (FWD3) tw3.load(a.twiddles, wave0, lane0);
+  };
+  if constexpr (TwRows<N>::USE && OLD_PROLOGUE) load_twiddle_rows();
+  if constexpr (!TwRows<N>::USE) {
+    const int xr = lane0 % R1, xc = lane0 / (64 / R1);
 #pragma unroll
     for (int k = 1; k < R2; ++k) {
       tw_row[k - 1] = {a.twiddles[2 * (k * xr)], a.twiddles[2 * (k * xr) + 1]};
       tw_col[k - 1] = {a.twiddles[2 * (k * xc)], a.twiddles[2 * (k * xc) + 1]};
     }
   }
-
-  Fwd3Tw tw3;
-  if constexpr (FWD3) tw3.load(a.twiddles, wave0, lane0);
   // ---- persistent workgroup: patches p = blockIdx.x, + gridDim.x, ...; the 2 x 16 B of the NEXT patch are
   //      requested from HBM before the current one is transformed, so the ~2 us load latency is off the critical path
   uint32_t cw[4] = {0u, 0u, 0u, 0u}, pw[4] = {0u, 0u, 0u, 0u};
   int p = PERSIST ? (int)blockIdx.x : (int)((blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x);
   auto fetch16 = [&](int pp, uint32_t* c, uint32_t* q) {
-    const uint8_t* cs = patch_base(pp, a.cur, a.cur_stride) + (size_t)lrow * a.pitch + CH * lcol;
-    const uint8_t* ps = prev_base(pp) + (size_t)lrow * a.pitch + CH * lcol;
+    const uint8_t *cs, *ps;
+    if constexpr (OLD_PROLOGUE) {
+      cs = patch_base(pp, a.cur, a.cur_stride) + (size_t)lrow * a.pitch + CH * lcol;
+      ps = prev_base(pp) + (size_t)lrow * a.pitch + CH * lcol;
+    } else {
+      // The patch bases depend on the workgroup alone (scalar, 64-bit, signed under OFF); the lane's part lrow * pitch + CH * lcol is ONE
+      // 32-bit value for both images: lrow < 64 and pitch < 2^24 (PC_MAX_PITCH, refused by launch_pc_field beyond it) keep the 24-bit
+      // multiply exact and the sum below 2^30 + 144. Scalar base + 32-bit lane offset is an addressing mode of global_load.
+      const uint32_t lane_off = __umul24((uint32_t)lrow, (uint32_t)a.pitch) + (uint32_t)(CH * lcol);
+      cs = patch_base(pp, a.cur, a.cur_stride) + lane_off;
+      ps = prev_base(pp) + lane_off;
+    }
     if constexpr (CH == 1) {
       __builtin_memcpy(c, cs, 16);
       __builtin_memcpy(q, ps, 16);
@@ -144,18 +161,24 @@ __global__ void __launch_bounds__(PcTraits<N>::T) pc_field_kernel(PcArgs a) {
       gray16_from_bgr48(ps, q);
     }
   };
-  if (DS == 1 && p < a.total && ld_on) fetch16(p, cw, pw);
+  // (one-patch forms: launch_n launches exactly grid_x x grid_y x nk workgroups with total = nk x patches -- pc_split_pairs --, so p < total
+  // holds for every workgroup and is not asked: the pixel loads do not wait for a kernel-argument round trip and a branch)
+  if (DS == 1 && (!OLD_PROLOGUE || p < a.total) && ld_on) fetch16(p, cw, pw);
+  if constexpr (TwRows<N>::USE && !OLD_PROLOGUE) load_twiddle_rows();
   // Co-resident workgroups would otherwise run the same phase at the same time (all of them LDS-bound, then all
   // VALU-bound): delay the k-th workgroup of a CU by k quarter-patches so their phases interleave.
   if constexpr (PERSIST) {
     const int slot = (blockIdx.x / a.stagger_div) & 3;
     for (int i = 0; i < slot * a.stagger_units; ++i) __builtin_amdgcn_s_sleep(100);
   }
+  // The persistent form walks its patches. A one-patch form runs the body once, as straight-line code: p < total holds (above) and the
+  // body ends with a break -- no loop header, no test of a.total, no wait for the twiddle loads in front of it.
+  if constexpr (!OLD_PROLOGUE) __builtin_assume(p < a.total);
   for (; p < a.total; p += PERSIST ? (int)gridDim.x : a.total) {
   // The lane / wave indices are laundered once per patch: otherwise LICM hoists every LDS address of the body out
-  // of the persistent loop (+70 VGPRs), which costs a whole workgroup of occupancy per CU.
+  // of the persistent loop (+70 VGPRs), which costs a whole workgroup of occupancy per CU. (No loop, nothing to hoist out of.)
   int lane = lane0, wave = wave0;
-  asm volatile("" : "+v"(lane), "+v"(wave));
+  if constexpr (OLD_PROLOGUE) asm volatile("" : "+v"(lane), "+v"(wave));
   lane &= 63;             // give the value ranges back to the optimiser (they fold the skew and the
   wave &= P::WAVES - 1;   // Hermitian row cases at compile time)
   const int tid = wave * 64 + lane;
@@ -167,17 +190,26 @@ __global__ void __launch_bounds__(PcTraits<N>::T) pc_field_kernel(PcArgs a) {
       // pre-test: a textured patch has a lane whose first two dwords differ -- two compares and it is out
       const bool maybe_c = __builtin_amdgcn_ballot_w64(ld_on && cw[0] != cw[1]) == 0ull;
       const bool maybe_p = __builtin_amdgcn_ballot_w64(ld_on && pw[0] != pw[1]) == 0ull;
-      // (the empty asm keeps the compiler from if-converting the rare branch into unconditional instructions)
+      // (the empty asm keeps the compiler from if-converting the rare branch into unconditional instructions. That alone does not pin
+      // const_track's compare chain, whose inputs are pure: the one-patch forms hand it the words through an asm inside the branch, so
+      // the chain depends on something that exists only there. The persistent form is spelled as it was.)
+      auto track = [&](const uint32_t* w, uint32_t& f, uint32_t& d) {
+        uint32_t t[4] = {w[0], w[1], w[2], w[3]};
+        asm volatile("" : "+v"(t[0]), "+v"(t[1]), "+v"(t[2]), "+v"(t[3]));
+        const_track(t, 4, true, f, d);
+      };
       if (__builtin_expect(maybe_c, 0)) {
         asm volatile("");
         uint32_t f, d;
-        const_track(cw, 4, true, f, d);
+        if constexpr (OLD_PROLOGUE) const_track(cw, 4, true, f, d);
+        else track(cw, f, d);
         cc = wave_const_code(ld_on, f, d);
       }
       if (__builtin_expect(maybe_p, 0)) {
         asm volatile("");
         uint32_t f, d;
-        const_track(pw, 4, true, f, d);
+        if constexpr (OLD_PROLOGUE) const_track(pw, 4, true, f, d);
+        else track(pw, f, d);
         cp = wave_const_code(ld_on, f, d);
       }
     }
@@ -361,6 +393,7 @@ __global__ void __launch_bounds__(PcTraits<N>::T) pc_field_kernel(PcArgs a) {
   if (wave == 0)
     centroid_gate_store<N, PK>(best, wval, lane, a.max_px_speed_sq, a.out + 2 * (size_t)p, a.quality ? a.quality + 2 * (size_t)p : nullptr, degenerate,
                                degenerate ? *reinterpret_cast<const float*>(const_code + 16) : 0.f);
+  if constexpr (!OLD_PROLOGUE) break;  // one patch
   }  // persistent loop
 }
 
@@ -419,6 +452,7 @@ hipError_t pc_configure(int patch_size) {
 }
 
 hipError_t launch_pc_field(const PcArgs& a, int patch_size, int n_pairs, hipStream_t stream) {
+  if (a.pitch >= PC_MAX_PITCH) return hipErrorInvalidValue;  // (the 32-bit lane offsets of fetch16; mof_kernels.h)
   switch (patch_size) {
     case 32: return launch_n<32>(a, n_pairs, stream);
     case 64: return launch_n<64>(a, n_pairs, stream);

@@ -92,15 +92,30 @@ struct TwRows {
   static constexpr bool USE = N <= 64;
   static_assert((R1 - 1) * (R2 - 1) < N && R2 % 2 == 0, "rows are copies of the classic table, whole 16-byte pieces");
 };
-// tw[k - 1] = row[k], k = 1..R-1, of a 16-byte-aligned row of R complex values
-template <int R>
+// tw[k - 1] = row[k], k = 1..R-1, of a 16-byte-aligned row of R complex values. Entry 0 (= 1) is not read: an 8-byte load takes entry 1
+// and 16-byte loads the rest -- no register that is loaded and never used, which the allocator would hand to the first instructions of the
+// body, making them wait for the twiddle loads.
+// WHOLE = true: the row as a whole, entry 0 included (N = 32, which keeps the parent's prologue: pc_kernel.hip).
+template <int R, bool WHOLE = false>
 __device__ __forceinline__ void tw_row_load(const float* __restrict__ row, cf* tw) {
   typedef float f4 __attribute__((ext_vector_type(4)));
-  f4 q[R / 2];
+  if constexpr (WHOLE) {
+    f4 q[R / 2];
 #pragma unroll
-  for (int j = 0; j < R / 2; ++j) q[j] = reinterpret_cast<const f4*>(row)[j];
+    for (int j = 0; j < R / 2; ++j) q[j] = reinterpret_cast<const f4*>(row)[j];
 #pragma unroll
-  for (int k = 1; k < R; ++k) tw[k - 1] = (k & 1) ? cf{q[k / 2].z, q[k / 2].w} : cf{q[k / 2].x, q[k / 2].y};
+    for (int k = 1; k < R; ++k) tw[k - 1] = (k & 1) ? cf{q[k / 2].z, q[k / 2].w} : cf{q[k / 2].x, q[k / 2].y};
+    return;
+  }
+  // (entry 1 as two scalars, which the back end loads as one dwordx2: as a two-float VECTOR it meets the two-float vectors of lds_read
+  // in cmul, the products become a packed multiply and the real part's fused multiply-add a multiply and a subtract -- other bits)
+  const float first_x = row[2], first_y = row[3];
+  f4 q[R / 2 - 1];
+#pragma unroll
+  for (int j = 1; j < R / 2; ++j) q[j - 1] = reinterpret_cast<const f4*>(row)[j];
+  tw[0] = {first_x, first_y};
+#pragma unroll
+  for (int k = 2; k < R; ++k) tw[k - 1] = (k & 1) ? cf{q[k / 2 - 1].z, q[k / 2 - 1].w} : cf{q[k / 2 - 1].x, q[k / 2 - 1].y};
 }
 
 // z(r, c): skewed tile address in complex units

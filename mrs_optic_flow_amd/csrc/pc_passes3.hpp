@@ -39,8 +39,13 @@ __device__ __forceinline__ void fwd3_rows(cf* __restrict__ z, int wave, int lane
   cf v[16];
 #pragma unroll
   for (int n1 = 0; n1 < 16; ++n1) {
+    // Each byte is converted where it lies (v_cvt_f32_ubyte0 / ubyte1). The empty asm hides the floats' origin: otherwise the
+    // compiler forms the butterfly's first two levels on the integers, which costs a shift per high byte to get at it. Sums and
+    // differences of up to four bytes are exact either way: the same bits.
     const uint32_t cp = lds_read_u16(src + 8 * n1);
-    v[n1] = {(float)(cp & 0xffu), (float)(cp >> 8)};
+    float c = (float)(cp & 0xffu), p = (float)(cp >> 8);
+    asm("" : "+v"(c), "+v"(p));
+    v[n1] = {c, p};
   }
   butterfly<16>(v);
   wave_sync();  // the raw area lies inside the wave's own part of the intermediate layout: all of it is read by now
