@@ -58,8 +58,13 @@ int mof_device_count(void);
 
 /* HIP graphs. Every *_batch_device entry point can be captured into a HIP graph on the caller's stream (no allocation,
  * synchronisation or host read-back inside). A captured kernel node holds raw pointers to engine-owned device memory
- * (FftMethod: the twiddle table; the scale/rotation estimator: its whole pipeline scratch), so a call made while `stream`
- * is capturing PINS its engine:
+ * (FftMethod: the twiddle table, and -- 64 x 64 patches under MOF_PEAK_OPENCV -- the engine's peak records, which the field kernel
+ * writes and the finish kernel behind it reads; the scale/rotation estimator: its whole pipeline scratch), so a call made while
+ * `stream` is capturing PINS its engine. Engine-owned scratch that a captured call WRITES is shared by every call on that engine:
+ * eager calls on different streams are ordered by the library (an event behind each call's last kernel), but while `stream` is
+ * being captured no cross-stream dependency is taken or left, so replays of graphs that captured one engine, and eager calls on it
+ * beside a replay, must be ordered by the caller (one stream, or events) -- for the 64 x 64 FftMethod as for the estimator below.
+ * Pinning:
  *   - while pinned, the estimator's scratch never moves: a later batch that would need more pairs per pass than the
  *     scratch holds fails with MOF_ERR_BUSY instead of re-allocating under the graph (mof_sr_reserve the largest batch
  *     BEFORE capturing);

@@ -202,6 +202,7 @@ struct mof_fft_engine {
   mof::ScratchFence fence;                // cross-stream ordering of the large-patch scratch
   mof::ScratchFence gate_fence;           // ... and of the response gate's quality buffer (d_gate_q; created with it)
   mof::ScratchFence pred_fence;           // ... and of the window-offset scratch (d_pred_*; created with it)
+  mof::ScratchFence finish_fence;         // ... and of K1's peak records (d_finish; created with it)
   mof::DevMem<float> d_twiddles;
   mof::DevMem<uint8_t> d_frames[2];       // [cur_slot], [1-cur_slot] = previous
   int prev_slot = 0;
@@ -220,6 +221,10 @@ struct mof_fft_engine {
   mof::DevMem<float2> d_cand;
   mof::DevMem<int> d_flags;
   int cap = 0;
+  // K1 at 64 under cv::phaseCorrelate's peak model: the records between the field kernel and pc_finish_kernel, one launch piece's worth
+  // (mof_kernels.h, pc_finish_records). Made with the engine and never resized: no call grows it, inside a capture or outside.
+  mof::DevMem<uint32_t> d_finish;
+  int finish_records = 0;
   // the response gate (mof_fft_set_min_response; 0 = off): where a batched call brings no quality buffer the kernels store the response
   // the gate reads into d_gate_q, for gate_cap patches -- made and grown as the large-patch scratch is, ordered by a fence of its own
   std::atomic<double> min_response{0.0};  // (mof_fft_min_response reads it without the busy flag)
@@ -379,8 +384,16 @@ static int launch_field(mof_fft_engine* e, const mof::PcArgs& a, int n_pairs, hi
     return MOF_OK;
   }
   if (r.family == FftRoute::LARGE) return launch_large(e, a, n_pairs, stream);
-  HIP_TRY(r.family == FftRoute::PLANNED ? mof::launch_pc_generic(a, e->plan, r.planned_static, n_pairs, stream)
-                                        : mof::launch_pc_field(a, e->cfg.patch_size, n_pairs, stream));
+  if (r.family == FftRoute::PLANNED) {
+    HIP_TRY(mof::launch_pc_generic(a, e->plan, r.planned_static, n_pairs, stream));
+    return MOF_OK;
+  }
+  // the tuned kernels; K1 at 64 hands its peak records to its finish kernel through the engine's buffer, ordered across streams as the
+  // other engine-owned scratch is
+  const bool records = e->finish_records > 0;
+  if (records) HIP_TRY(e->finish_fence.acquire(stream));
+  HIP_TRY(mof::launch_pc_field(a, e->cfg.patch_size, n_pairs, stream, e->d_finish, e->finish_records));
+  if (records) HIP_TRY(e->finish_fence.release(stream));
   return MOF_OK;
 }
 // once per engine, before its first launch: the dynamic-LDS limits of the kernels launch_field and fft_sequence can launch on route r
@@ -564,6 +577,7 @@ static void fft_destroy_now(void* p) {
   e->fence.wait_idle();
   e->gate_fence.wait_idle();
   e->pred_fence.wait_idle();
+  e->finish_fence.wait_idle();
   delete e;
 }
 struct FftDestroyNow {
@@ -599,6 +613,15 @@ int mof_fft_create(const mof_fft_config* cfg, mof_fft_engine** out) try {
   if (r.family == FftRoute::LARGE) {
     HIP_TRY(e->fence.create());
     HIP_TRY(large_alloc(e.get(), cfg->grid_x * cfg->grid_y));  // one frame pair; a batch grows it to a whole pass
+  }
+  if (r.family == FftRoute::TUNED) {
+    // (the long-range mode has fewer patches per frame than the full-resolution grid, never more)
+    const int records = mof::pc_finish_records(cfg->patch_size, cfg->peak_model, cfg->grid_x * cfg->grid_y);
+    if (records > 0) {
+      HIP_TRY(e->finish_fence.create());
+      HIP_TRY(e->d_finish.alloc((size_t)records * mof::PC_FINISH_DWORDS));
+      e->finish_records = records;
+    }
   }
   *out = e.release();
   return MOF_OK;

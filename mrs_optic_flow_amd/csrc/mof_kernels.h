@@ -34,6 +34,17 @@ struct PcArgs {
                             // clamp keeps the window inside the frame). Last member: every older kernel's argument offsets stay put.
 };
 
+// K1 at 64 ends a patch with a 128-byte record; pc_finish_kernel, one lane per patch, turns a piece's records into shifts and quality.
+//   dwords 0 .. 24: the 5 x 5 window, lane l's centroid_window_value (0 outside the clamped window)
+//   25: the first maximum's value   26: its shifted index   27: 1 = one of the two patches is constant   28: C_dc (0 unless 27 is set)
+constexpr int PC_FINISH_DWORDS = 32;
+// the ONE spelling of which K1 forms end a patch with a record: the kernel's argument type, its tail and the engine's buffer follow it
+constexpr bool pc_field_records(int patch_size, int peak_model) { return patch_size == 64 && peak_model == 0; }
+// records the engine of a K1 route must own for launch_pc_field (0: that route writes none): one launch piece of whole frame pairs --
+// 65536 patches (8 MiB), or one frame pair's where a frame holds more. A fixed size, made with the engine: nothing grows at a call, so a
+// fresh engine's first batch can still be captured into a graph.
+int pc_finish_records(int patch_size, int peak_model, int patches);
+
 // twiddles W_n^k = exp(-2 pi i k / n), k < n, as (re, im) float pairs (mof_capi.hip; both engines' d_twiddles)
 std::vector<float> twiddle_table(int n);
 
@@ -120,7 +131,9 @@ hipError_t pc_configure(int patch_size);  // once per device before the first la
 // field launch of the FFT engine is held to it (mof_capi.hip, launch_field: MOF_ERR_BAD_ARG); launch_pc_field itself answers
 // hipErrorInvalidValue beyond it.
 constexpr size_t PC_MAX_PITCH = (size_t)1 << 24;
-hipError_t launch_pc_field(const PcArgs& a, int patch_size, int n_pairs, hipStream_t stream);
+// finish, finish_records: the engine's record buffer (device, PC_FINISH_DWORDS dwords per record) where pc_finish_records says the route
+// needs one -- a kernel argument of its own beside PcArgs, whose size every other kernel's code depends on
+hipError_t launch_pc_field(const PcArgs& a, int patch_size, int n_pairs, hipStream_t stream, uint32_t* finish = nullptr, int finish_records = 0);
 // launch_pc_field's a.twiddles at 32 and 64: twiddle_table(n) with the packed per-index rows appended (TwRows, pc_passes.hpp); other
 // sizes are left as they are. The classic table stays at offset 0 for every kernel that reads it.
 void pc_append_twiddle_rows(std::vector<float>& table, int n);

@@ -5,7 +5,9 @@
 // tile in LDS ("two-for-one" real transform), transformed, untangled into the two real spectra,
 // turned into the normalised cross-power spectrum, inverse-transformed exploiting its Hermitian
 // symmetry (half the work of a complex inverse), and reduced to (arg-max, 5x5 centroid): 16 B leave
-// the CU per patch. Nothing but the frames and the results touches HBM.
+// the CU per patch. Nothing but the frames and the results touches HBM. (N = 64 under cv::phaseCorrelate's peak model: 128 B leave the
+// CU, a record of the peak and its window, and pc_finish_kernel -- one lane per patch, at the end of this file's kernels -- runs the fp64
+// centroid and the gate for the whole launch.)
 //
 // Replaces, per patch, the reference's
 //   -cv::phaseCorrelate(cur(roi), prev(roi))              src/FftMethod.cpp:1836
@@ -36,6 +38,7 @@
 
 #include "mof_kernels.h"
 #include "pc_common.hpp"
+#include "pc_finish_tree.hpp"
 #include "pc_launch.hpp"
 
 #include "pc_passes.hpp"
@@ -53,8 +56,26 @@ namespace mof {
 // patch of linear index q is read at (x0 - a_x, y0 - a_y), (a_x, a_y) = a.prev_off[2 q], [2 q + 1]: a change of its base address, which
 // depends on the workgroup's patch index alone -- two scalar loads and scalar arithmetic, no VGPR, no LDS
 // (profiles/fft_pred_fused_static.txt). Everything else is the form it was made from, so are its bits on the same pixels.
-template <int N, int DS, int CH, int PK, bool OFF = false>
-__global__ void __launch_bounds__(PcTraits<N>::T) pc_field_kernel(PcArgs a) {
+// A: PcArgs, or PcArgsRecord for the forms that end a patch with a record (RECORD below: N = 64 under cv::phaseCorrelate's peak model). The
+// record buffer rides behind the PcArgs those forms take: PcArgs keeps its size, and with it every other kernel that takes one its code.
+struct PcArgsRecord : PcArgs {
+  uint32_t* finish;  // device, engine-owned: PC_FINISH_DWORDS dwords per patch of the launch (mof_kernels.h)
+};
+// One patch's record (mof_kernels.h, PC_FINISH_DWORDS), by the wave that ends the patch, every lane with the same `b` and `deg`:
+// wv = the lane's centroid_window_value; const_code + 16 = C_dc, read for a constant patch only, as the finish read it in K1
+__device__ __forceinline__ void pc_store_record(uint32_t* finish, int p, int lane, Best b, float wv, bool deg, const int* const_code) {
+  const float c_dc = deg ? *reinterpret_cast<const float*>(const_code + 16) : 0.f;
+  uint32_t v = __float_as_uint(wv);  // (0 in lanes 25 .. 63: outside the 5 x 5 window)
+  v = lane == 25 ? __float_as_uint(b.v) : v;
+  v = lane == 26 ? (uint32_t)b.idx : v;
+  v = lane == 27 ? (deg ? 1u : 0u) : v;
+  v = lane == 28 ? __float_as_uint(c_dc) : v;
+  if (lane < PC_FINISH_DWORDS) finish[(size_t)PC_FINISH_DWORDS * (size_t)p + lane] = v;
+}
+template <int N, int PK>
+using PcFieldArgs = std::conditional_t<pc_field_records(N, PK), PcArgsRecord, PcArgs>;
+template <int N, int DS, int CH, int PK, bool OFF = false, class A = PcFieldArgs<N, PK>>
+__global__ void __launch_bounds__(PcTraits<N>::T) pc_field_kernel(A a) {
   static_assert(CH == 1 || (CH == 3 && DS == 1), "BGR front end only for the full-resolution path");
   static_assert(!OFF || (DS == 1 && PK == 0), "window offsets: full resolution, cv::phaseCorrelate's peak model");
   using P = PcTraits<N>;
@@ -345,6 +366,11 @@ __global__ void __launch_bounds__(PcTraits<N>::T) pc_field_kernel(PcArgs a) {
   }  // FUSE_XPOW
   __syncthreads();
   Best best = argmax_neutral();
+  // RECORD (N = 64 under cv::phaseCorrelate's peak model): the wave that ends the patch does not run the fp64 finish -- three 64-lane
+  // sums, two divisions, the gate: a third of the one-wave section that holds the workgroup's LDS. It stores what the finish needs, 128
+  // bytes in one store (pc_store_record), and pc_finish_kernel below, one lane per patch, does the rest for the whole piece.
+  constexpr bool RECORD = pc_field_records(N, PK);
+  static_assert(RECORD == std::is_same_v<A, PcArgsRecord> && (!RECORD || VALUE_FIRST), "the record forms take PcArgsRecord and reduce the value first");
   if constexpr (VALUE_FIRST) {
     // The value first, the index only where the value matched (the rule and why it gives the parent fold's Best: pc_argmax.hpp). Each
     // lane keeps its 16 surface values; the wave's maximum goes to a float slot in the free part of `red`; behind the barrier every wave
@@ -361,6 +387,29 @@ __global__ void __launch_bounds__(PcTraits<N>::T) pc_field_kernel(PcArgs a) {
     float gm = red_max[0];
 #pragma unroll
     for (int w = 1; w < P::WAVES; ++w) gm = fmaxf(gm, red_max[w]);
+    if constexpr (PK == 0) {
+      // The wave that holds the maximum ends the patch. A slot equals gm exactly where its wave has a lane with m == gm (m <= the wave's
+      // slot <= gm), so every wave counts the same holders. ONE holder -- every surface but a flat, a periodic or an all-NaN one -- : its
+      // wave_best is already the workgroup's pair (the other waves would hand in the neutral pair, which loses to it: gm > -inf, or all four
+      // slots were equal), so it reads the codes and its window element and ends the patch itself, all 64 lanes active, and the other waves
+      // leave: no red[] store, no second barrier, and the one-wave tail falls on whichever SIMD holds the peak. The window read is ordered:
+      // every wave stored its part of the surface before the barrier above. Any other count takes the path below: wave 0 behind a second barrier.
+      int holders = 0;
+#pragma unroll
+      for (int w = 0; w < P::WAVES; ++w) holders += red_max[w] == gm ? 1 : 0;
+      if (__builtin_amdgcn_readfirstlane(holders) == 1) {
+        if (__builtin_amdgcn_ballot_w64(m == gm) == 0ull) return;
+        const int my_code = const_code[lane & 15];
+        best = wave_best(argmax_entry(m, gm, col_pass_inv_index<N>(sv, m, wave * P::LI, lane)));
+        const float wv = centroid_window_value<N, PK>(best, lane, [&](int ys, int xs) {
+          const int y = (ys + H) % N, x = (xs + H) % N;  // un-shifted position
+          const cf s = z[zaddr<N>(y, x % H)];
+          return x < H ? s.x : s.y;
+        });
+        pc_store_record(a.finish, p, lane, best, wv, const_codes_degenerate<P::WAVES>(my_code, lane), const_code);
+        return;
+      }
+    }
     if (__builtin_amdgcn_ballot_w64(m == gm) != 0ull) {
       asm volatile("");  // (keeps the rare branch a branch, as for the constant-patch codes above)
       best = wave_best(argmax_entry(m, gm, col_pass_inv_index<N>(sv, m, wave * P::LI, lane)));
@@ -390,24 +439,70 @@ __global__ void __launch_bounds__(PcTraits<N>::T) pc_field_kernel(PcArgs a) {
   // (only the persistent form needs it: the value-first forms have spent their second barrier above and nothing follows that it could
   // protect; N = 32 keeps it, never measured without: docs/history/retired_switches.md)
   if constexpr (!VALUE_FIRST) __syncthreads();
-  if (wave == 0)
+  if constexpr (RECORD) {
+    if (wave == 0) pc_store_record(a.finish, p, lane, best, wval, degenerate, const_code);
+  } else if (wave == 0)
     centroid_gate_store<N, PK>(best, wval, lane, a.max_px_speed_sq, a.out + 2 * (size_t)p, a.quality ? a.quality + 2 * (size_t)p : nullptr, degenerate,
                                degenerate ? *reinterpret_cast<const float*>(const_code + 16) : 0.f);
   if constexpr (!OLD_PROLOGUE) break;  // one patch
   }  // persistent loop
 }
 
-template <int N>
-static hipError_t configure_n() {
-  const size_t lds = PcTraits<N>::LDS_BYTES + pc_extra_lds();
-  const hipError_t e = pc_each_form([&](auto ds, auto ch, auto pk) { return pc_raise_lds(&pc_field_kernel<N, ds, ch, pk>, lds); });
-  if (e != hipSuccess) return e;
-  // the fused window-offset forms: gray and BGR8, the enumeration launch_n dispatches them by
-  return pc_each_form<PC_FORMS_CH>([&](auto ds, auto ch, auto pk) { return pc_raise_lds(&pc_field_kernel<N, ds, ch, pk, true>, lds); });
+// the kernel of form (N, ds, ch, pk, OFF) as configure_n and launch_n name it: f(kernel, takes_records)
+template <int N, bool OFF, class DS, class CH, class PK, class F>
+static hipError_t pc_field_form(DS, CH, PK, F&& f) {
+  return f(&pc_field_kernel<N, DS::value, CH::value, PK::value, OFF>, std::is_same<PcFieldArgs<N, PK::value>, PcArgsRecord>{});
+}
+
+// The fp64 finish of K1 at 64 (RECORD above), on the same stream behind the field kernel: ONE LANE PER PATCH (a wave per patch would keep
+// 65536 waves of c2 busy with one lane's work each). A lane reads its patch's record, forms the three leaves of the 64 lanes of the tail it
+// replaces exactly as centroid_gate_store does -- (double)xs * val, (double)ys * val, val, val = 0 beyond lane 24 --, adds them in
+// wave_sum3's pairing (pc_finish_tree.hpp: the products are a 24-bit value times a small integer, exact in fp64, so a contraction into a
+// fused multiply-add changes nothing) and runs peak_finish<0>, the function K1 ran: same operands, same bits.
+constexpr int PC_FINISH_T = 256;
+__global__ void __launch_bounds__(PC_FINISH_T) pc_finish_kernel(const uint32_t* __restrict__ records, int total, double max_px_speed_sq,
+                                                                double* __restrict__ out, double* __restrict__ quality) {
+  const int p = (int)blockIdx.x * PC_FINISH_T + (int)threadIdx.x;
+  if (p >= total) return;
+  uint32_t w[PC_FINISH_DWORDS];
+  const uint4* r = reinterpret_cast<const uint4*>(records + (size_t)PC_FINISH_DWORDS * (size_t)p);
+#pragma unroll
+  for (int q = 0; q < PC_FINISH_DWORDS / 4; ++q) {
+    const uint4 v = r[q];
+    w[4 * q] = v.x, w[4 * q + 1] = v.y, w[4 * q + 2] = v.z, w[4 * q + 3] = v.w;
+  }
+  const Best best{__uint_as_float(w[25]), (int)w[26]};
+  const bool degenerate = w[27] != 0u;
+  const Sum3 s = finish_tree([&](int l) {
+    int ys, xs;
+    peak_window<0>(best, l, 64, &ys, &xs);
+    const double val = (double)(l < 25 ? __uint_as_float(w[l]) : 0.f);
+    return Sum3{(double)xs * val, (double)ys * val, val};
+  });
+  peak_finish<0>(s.cx, s.cy, s.sum, best, 64, 64, degenerate, __uint_as_float(w[28]), max_px_speed_sq, out + 2 * (size_t)p,
+                 quality ? quality + 2 * (size_t)p : nullptr);
+}
+
+int pc_finish_records(int patch_size, int peak_model, int patches) {
+  if (!pc_field_records(patch_size, peak_model)) return 0;
+  return patches > 65536 ? patches : 65536;
 }
 
 template <int N>
-static hipError_t launch_n(const PcArgs& a_in, int n_pairs, hipStream_t stream) {
+static hipError_t configure_n() {
+  const size_t lds = PcTraits<N>::LDS_BYTES + pc_extra_lds();
+  const hipError_t e = pc_each_form([&](auto ds, auto ch, auto pk) {
+    return pc_field_form<N, false>(ds, ch, pk, [&](auto* kernel, auto) { return pc_raise_lds(kernel, lds); });
+  });
+  if (e != hipSuccess) return e;
+  // the fused window-offset forms: gray and BGR8, the enumeration launch_n dispatches them by
+  return pc_each_form<PC_FORMS_CH>([&](auto ds, auto ch, auto pk) {
+    return pc_field_form<N, true>(ds, ch, pk, [&](auto* kernel, auto) { return pc_raise_lds(kernel, lds); });
+  });
+}
+
+template <int N>
+static hipError_t launch_n(const PcArgs& a_in, int n_pairs, hipStream_t stream, uint32_t* finish, int finish_records) {
   using Tr = PcTraits<N>;
   PcArgs a = a_in;
   a.total = n_pairs * a.grid_x * a.grid_y;
@@ -419,16 +514,23 @@ static hipError_t launch_n(const PcArgs& a_in, int n_pairs, hipStream_t stream) 
   }
   const dim3 b(Tr::T);
   const size_t lds = Tr::LDS_BYTES + pc_extra_lds();
+  auto go = [&](const PcArgs& aa, dim3 g) {
+    return [&, g](auto* kernel, auto takes_records) {
+      if constexpr (decltype(takes_records)::value) {
+        PcArgsRecord ar;
+        static_cast<PcArgs&>(ar) = aa;
+        ar.finish = finish;
+        hipLaunchKernelGGL(kernel, g, b, lds, stream, ar);
+      } else {
+        hipLaunchKernelGGL(kernel, g, b, lds, stream, aa);
+      }
+      return hipGetLastError();
+    };
+  };
   auto launch = [&](const PcArgs& aa, dim3 g) {
     if (aa.prev_off)  // the fused window-offset form; hipErrorInvalidValue for the long-range mode and the OpenCL peak model
-      return pc_dispatch_form<PC_FORMS_CH>(aa, [&](auto ds, auto ch, auto pk) {
-        hipLaunchKernelGGL((pc_field_kernel<N, ds, ch, pk, true>), g, b, lds, stream, aa);
-        return hipGetLastError();
-      });
-    return pc_dispatch_form(aa, [&](auto ds, auto ch, auto pk) {
-      hipLaunchKernelGGL((pc_field_kernel<N, ds, ch, pk>), g, b, lds, stream, aa);
-      return hipGetLastError();
-    });
+      return pc_dispatch_form<PC_FORMS_CH>(aa, [&](auto ds, auto ch, auto pk) { return pc_field_form<N, true>(ds, ch, pk, go(aa, g)); });
+    return pc_dispatch_form(aa, [&](auto ds, auto ch, auto pk) { return pc_field_form<N, false>(ds, ch, pk, go(aa, g)); });
   };
   if constexpr (Tr::PERSIST) {
     // as many workgroups as are resident at once (LDS-limited), each loops over patches (c4: +9 % over one per patch)
@@ -437,7 +539,22 @@ static hipError_t launch_n(const PcArgs& a_in, int n_pairs, hipStream_t stream) 
     return launch(a, dim3((unsigned)(a.total < resident ? a.total : resident)));
   } else {
     // one workgroup per patch; the pair index rides gridDim.z
-    return pc_split_pairs(a, n_pairs, [&](const PcArgs& c, int nk) { return launch(c, dim3((unsigned)a.grid_x, (unsigned)a.grid_y, (unsigned)nk)); });
+    const int patches = a.grid_x * a.grid_y;
+    // K1 at 64 under cv::phaseCorrelate's peak model: every piece is the field kernel and then the finish kernel over the piece's records, its
+    // own out / quality offsets and the record buffer from its start again -- a piece holds no more patches than the buffer holds records
+    const bool record = pc_finish_records(N, a.peak_model, patches) > 0;
+    int piece = PC_MAX_GRID_PAIRS;
+    if (record) {
+      if (!finish || finish_records < patches) return hipErrorInvalidValue;
+      if (finish_records / patches < piece) piece = finish_records / patches;
+    }
+    return pc_split_pairs(a, n_pairs, [&](const PcArgs& c, int nk) {
+      const hipError_t e = launch(c, dim3((unsigned)a.grid_x, (unsigned)a.grid_y, (unsigned)nk));
+      if (e != hipSuccess || !record) return e;
+      hipLaunchKernelGGL(pc_finish_kernel, dim3((unsigned)((c.total + PC_FINISH_T - 1) / PC_FINISH_T)), dim3(PC_FINISH_T), 0, stream, finish,
+                         c.total, c.max_px_speed_sq, c.out, c.quality);
+      return hipGetLastError();
+    }, piece);
   }
 }
 
@@ -451,12 +568,12 @@ hipError_t pc_configure(int patch_size) {
   }
 }
 
-hipError_t launch_pc_field(const PcArgs& a, int patch_size, int n_pairs, hipStream_t stream) {
+hipError_t launch_pc_field(const PcArgs& a, int patch_size, int n_pairs, hipStream_t stream, uint32_t* finish, int finish_records) {
   if (a.pitch >= PC_MAX_PITCH) return hipErrorInvalidValue;  // (the 32-bit lane offsets of fetch16; mof_kernels.h)
   switch (patch_size) {
-    case 32: return launch_n<32>(a, n_pairs, stream);
-    case 64: return launch_n<64>(a, n_pairs, stream);
-    case 128: return launch_n<128>(a, n_pairs, stream);
+    case 32: return launch_n<32>(a, n_pairs, stream, finish, finish_records);
+    case 64: return launch_n<64>(a, n_pairs, stream, finish, finish_records);
+    case 128: return launch_n<128>(a, n_pairs, stream, finish, finish_records);
     case 120: return a.prev_off ? hipErrorInvalidValue : launch_pc_field_120(a, n_pairs, stream);  // (the 15 x 8 kernel has no fused form)
     default: return hipErrorInvalidValue;
   }

@@ -71,12 +71,12 @@ constexpr int PC_MAX_GRID_PAIRS = 65535;
 constexpr int PC_MAX_GRID_IMAGES = 65534;  // images of pairs: an even count keeps cur / prev together
 
 // launch(slice, nk) for every slice of at most 65535 pairs of a.cur / a.prev / a.out / a.quality / a.prev_off, slice.total = its patches; ends at
-// the first error
+// the first error. max_pairs: a smaller slice, where a launcher has another bound as well (K1 at 64: its record buffer)
 template <class F>
-hipError_t pc_split_pairs(const PcArgs& a, int n_pairs, F&& launch) {
+hipError_t pc_split_pairs(const PcArgs& a, int n_pairs, F&& launch, int max_pairs = PC_MAX_GRID_PAIRS) {
   const int patches = a.grid_x * a.grid_y;
-  for (int k0 = 0; k0 < n_pairs; k0 += PC_MAX_GRID_PAIRS) {
-    const int nk = n_pairs - k0 < PC_MAX_GRID_PAIRS ? n_pairs - k0 : PC_MAX_GRID_PAIRS;
+  for (int k0 = 0; k0 < n_pairs; k0 += max_pairs) {
+    const int nk = n_pairs - k0 < max_pairs ? n_pairs - k0 : max_pairs;
     PcArgs c = a;
     c.cur = a.cur + (size_t)k0 * a.cur_stride;
     c.prev = a.prev + (size_t)k0 * a.prev_stride;
