@@ -45,5 +45,19 @@ MOF_ARGMAX_FN int argmax_first_index(int mi, float cand, float m, int idx) {
 //   * ties at gm, inside a lane, across lanes and across waves, are all still in the fold with their own indices.
 MOF_ARGMAX_FN Best argmax_entry(float m, float gm, int mi) { return m == gm ? Best{m, mi} : argmax_neutral(); }
 
+// A lone lane. holders = the wave's ballot of m == gm, bit l for lane l. Where exactly ONE bit is set, the wave's fold of the entries above
+// -- in any order, the xor butterfly of wave_best among them -- ends in every lane with that lane's own (m, mi), so the wave may read the
+// pair out of lane argmax_lone_lane(holders) and skip the fold:
+//   * one bit means gm > -inf: with gm == -inf every lane has m == -inf == gm (m >= -inf, never NaN) and all 64 bits are set;
+//   * so the 63 other entries are the neutral pair {-inf, 0x7fffffff}, whose value lies strictly below m. better(H, neutral) and
+//     better(neutral, H) both return H, the holder's pair, by the value alone: the index is not asked and +0 / -0 do not meet, since
+//     a lane that held the other zero would compare equal to gm and set a second bit; better(neutral, neutral) is the neutral pair;
+//   * every lane of a butterfly level therefore carries H or the neutral pair, and a lane carries H after the level exactly where it or
+//     its partner did before: the set of lanes with H doubles at each of the six levels, from 1 to 64.
+// The pair handed over is the lane's own m -- its bits, not gm's. Any other count (two lanes of the wave tie, a +0 beside a -0, the flat
+// and the all-NaN surfaces) keeps the fold. tests/cpp/test_argmax_lone.cpp holds the rule to the butterfly.
+MOF_ARGMAX_FN bool argmax_lone_holder(unsigned long long holders) { return __builtin_popcountll(holders) == 1; }
+MOF_ARGMAX_FN int argmax_lone_lane(unsigned long long holders) { return __builtin_ctzll(holders); }  // (holders != 0)
+
 }  // namespace
 }  // namespace mof

@@ -72,6 +72,21 @@ __device__ __forceinline__ void pc_store_record(uint32_t* finish, int p, int lan
   v = lane == 28 ? __float_as_uint(c_dc) : v;
   if (lane < PC_FINISH_DWORDS) finish[(size_t)PC_FINISH_DWORDS * (size_t)p + lane] = v;
 }
+// The pair of a wave that holds the workgroup's maximum gm, record forms (N = 64): `holders` = the wave's ballot of m == gm, not zero; sv, m
+// as col_pass_inv<N, PK, false> left them. Every lane walks the index chain, all 64 lanes active.
+// Where ONE lane of the wave holds the maximum -- every textured patch -- that lane's own (m, mi) is read with two v_readlane behind one
+// s_ff1 of the ballot: wave_best's six levels would end with that pair in every lane (argmax_lone_holder, pc_argmax.hpp). Any other count
+// folds as before. The branch is wave-uniform, and the fold, now the rare side, is kept behind it.
+template <int N>
+__device__ __forceinline__ Best holder_pair(const cf* sv, float m, float gm, int col0, int lane, unsigned long long holders) {
+  const int mi = col_pass_inv_index<N>(sv, m, col0, lane);
+  if (__builtin_expect(!argmax_lone_holder(holders), 0)) {
+    asm volatile("");
+    return wave_best(argmax_entry(m, gm, mi));
+  }
+  const int l = argmax_lone_lane(holders);
+  return Best{__int_as_float(__builtin_amdgcn_readlane(__float_as_int(m), l)), __builtin_amdgcn_readlane(mi, l)};
+}
 template <int N, int PK>
 using PcFieldArgs = std::conditional_t<pc_field_records(N, PK), PcArgsRecord, PcArgs>;
 template <int N, int DS, int CH, int PK, bool OFF = false, class A = PcFieldArgs<N, PK>>
@@ -398,9 +413,10 @@ __global__ void __launch_bounds__(PcTraits<N>::T) pc_field_kernel(A a) {
 #pragma unroll
       for (int w = 0; w < P::WAVES; ++w) holders += red_max[w] == gm ? 1 : 0;
       if (__builtin_amdgcn_readfirstlane(holders) == 1) {
-        if (__builtin_amdgcn_ballot_w64(m == gm) == 0ull) return;
+        const unsigned long long mine = __builtin_amdgcn_ballot_w64(m == gm);  // this wave's lanes that hold it
+        if (mine == 0ull) return;
         const int my_code = const_code[lane & 15];
-        best = wave_best(argmax_entry(m, gm, col_pass_inv_index<N>(sv, m, wave * P::LI, lane)));
+        best = holder_pair<N>(sv, m, gm, wave * P::LI, lane, mine);
         const float wv = centroid_window_value<N, PK>(best, lane, [&](int ys, int xs) {
           const int y = (ys + H) % N, x = (xs + H) % N;  // un-shifted position
           const cf s = z[zaddr<N>(y, x % H)];
@@ -410,9 +426,10 @@ __global__ void __launch_bounds__(PcTraits<N>::T) pc_field_kernel(A a) {
         return;
       }
     }
-    if (__builtin_amdgcn_ballot_w64(m == gm) != 0ull) {
+    if (const unsigned long long mine = __builtin_amdgcn_ballot_w64(m == gm); mine != 0ull) {
       asm volatile("");  // (keeps the rare branch a branch, as for the constant-patch codes above)
-      best = wave_best(argmax_entry(m, gm, col_pass_inv_index<N>(sv, m, wave * P::LI, lane)));
+      if constexpr (RECORD) best = holder_pair<N>(sv, m, gm, wave * P::LI, lane, mine);
+      else best = wave_best(argmax_entry(m, gm, col_pass_inv_index<N>(sv, m, wave * P::LI, lane)));
     }
     if (lane == 0) red[wave] = best;
   } else {
